@@ -13,6 +13,11 @@ data-path collective (weak scaling); `value` = frames all ranks rendered / max-o
 The real mip360_bicycle_30000.ply is a GitHub release asset of the reference and is not available offline;
 the workload is the deterministic synthetic stand-in `synth_unbounded` (seed 2001) with the same splat count
 unless --ply points at the real file.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, warm up, time --steps frames, print the line.  --full adds
+every other leg (per-frame events, moving camera, stage times, camera batch, stage path, rooflines, forward+backward
+and training steps, file order, CPU baseline and oracle parity).  --dump-outputs DIR writes the image the timed path
+rendered in its last step to DIR/image.npy (float32, 3 x H x W; rank 0's view).
 """
 import argparse
 import json
@@ -120,6 +125,25 @@ def view_pose(k: int):
     return (R @ pos).tolist(), (R @ tgt).tolist(), up.tolist()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 2_000_000
+
+
+def dump_outputs(out_dir, img):
+    """--dump-outputs: what the timed path hands its caller, the rendered image (3 x H x W float32), as DIR/image.npy.  An image
+    beyond 64 MiB is written as a fixed sample instead: the pixels (DIR/image_sample.npy, 3 x n) at the flat indices
+    y * W + x of DIR/image_sample_pixels.npy (float64), drawn with seed 0."""
+    os.makedirs(out_dir, exist_ok=True)
+    a = img.detach().float().cpu().numpy()
+    if a.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), a)
+        return
+    flat = a.reshape(a.shape[0], -1)
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[1], size=min(DUMP_SAMPLE_PIXELS, flat.shape[1]), replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), np.ascontiguousarray(flat[:, idx]))
+    np.save(os.path.join(out_dir, "image_sample_pixels.npy"), idx.astype(np.float64))
+
+
 def algorithmic_bytes(P, V, L, G, W, H):
     """Per-frame algorithmic HBM bytes, SURVEY 8(d) / BASELINE.md 3 (n = radix passes over the live key bits)."""
     b = 32 + max(1, math.ceil(math.log2(max(G, 2))))
@@ -133,6 +157,12 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--splats", type=int, default=P_BICYCLE)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: every other leg (per-frame events, moving camera, stage times, camera batch, "
+                         "stage path, rooflines, forward+backward, training steps, file order, CPU baseline); the --no-* "
+                         "options, --half-sh, --lod and --c4 select among them")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps: write the image of the last timed step to DIR/image.npy (float32)")
     ap.add_argument("--res", type=str, default="1920x1080")
     ap.add_argument("--ply", type=str, default=os.environ.get("LCGS_BICYCLE_PLY", ""))
     ap.add_argument("--garden-ply", type=str, default=os.environ.get("LCGS_GARDEN_PLY", ""),
@@ -165,7 +195,10 @@ def parse_args():
     ap.add_argument("--collective", choices=("rccl", "torch"), default="rccl",
                     help="N > 1 gradient collective: the library's own RCCL path (lcgs_comm C ABI, default) or "
                          "torch.distributed's (cross-check)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full and (args.half_sh or args.lod > 0 or args.c4):
+        ap.error("--half-sh, --lod and --c4 add legs of --full: pass --full as well")
+    return args
 
 
 def leg_moving_camera(L, r, cam, img, args, rank, world, W, H, timed):
@@ -983,7 +1016,8 @@ def main():
     #  without backward state, by the pair count: the counters reported are those of the frames that are timed)
     n_rendered = r.forward(cam, img, sync=True)
     stats = r.frame_stats()
-    stats["renderer_entries"] = renderer_entries(torch, r, stats, W, H, dev)
+    if args.full:
+        stats["renderer_entries"] = renderer_entries(torch, r, stats, W, H, dev)
 
     def barrier():
         torch.cuda.synchronize(dev)
@@ -999,20 +1033,24 @@ def main():
         r.forward(cam, img, sync=False)
     barrier()
     elapsed = time.perf_counter() - t0
-    # SURVEY 8d's protocol beside the contract's: the median of >= 50 frames on hipEvent pairs -- one event behind every
-    # frame on the context's stream (torch's current stream here).  Its own loop, so that `value` above is not perturbed
-    # by the event packets; reported beside `value`, never instead of it.
-    n_ev = max(50, args.steps)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(n_ev + 1)]
-    marks[0].record()
-    for i in range(n_ev):
-        r.forward(cam, img, sync=False)
-        marks[i + 1].record()
-    barrier()
-    frame_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(n_ev))
-    per_frame = {"frames": n_ev, "median_ms": round(frame_ms[n_ev // 2], 4), "min_ms": round(frame_ms[0], 4),
-                 "p90_ms": round(frame_ms[(n_ev * 9) // 10], 4), "frames_per_s_at_median": round(1e3 / frame_ms[n_ev // 2], 1),
-                 "how": "hipEvent pairs between consecutive frames on the context's stream (SURVEY 8d)"}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, img)
+    per_frame = None
+    if args.full:
+        # SURVEY 8d's protocol beside the contract's: the median of >= 50 frames on hipEvent pairs -- one event behind every
+        # frame on the context's stream (torch's current stream here).  Its own loop, so that `value` above is not perturbed
+        # by the event packets; reported beside `value`, never instead of it.
+        n_ev = max(50, args.steps)
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(n_ev + 1)]
+        marks[0].record()
+        for i in range(n_ev):
+            r.forward(cam, img, sync=False)
+            marks[i + 1].record()
+        barrier()
+        frame_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(n_ev))
+        per_frame = {"frames": n_ev, "median_ms": round(frame_ms[n_ev // 2], 4), "min_ms": round(frame_ms[0], 4),
+                     "p90_ms": round(frame_ms[(n_ev * 9) // 10], 4), "frames_per_s_at_median": round(1e3 / frame_ms[n_ev // 2], 1),
+                     "how": "hipEvent pairs between consecutive frames on the context's stream (SURVEY 8d)"}
     if dist is not None:
         t = torch.tensor([elapsed], device=red_dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1021,6 +1059,21 @@ def main():
         early.cancel()
     ms_per_step = elapsed * 1e3 / args.steps
     value = world * args.steps / elapsed
+
+    out = {
+        "metric": "forward fps @1080p, mip360_bicycle", "value": round(value, 2), "unit": "frames/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": data,
+        "config": {"workload": workload, "resolution": f"{W}x{H}", "splats": P, "visible_splats": stats["num_visible"],
+                   "tile_pairs_reference": stats["num_rendered"], "tile_pairs_sorted": stats["num_pairs"], "views_per_gpu": 1,
+                   "parallelism": f"view-parallel x{world}"},
+    }
+    if not args.full:  # the headline alone: the line, then the process group's teardown
+        if rank == 0:
+            print(json.dumps(out), file=line_out, flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # N > 1 bookkeeping: every timed leg carries its ordinal and the rank's failure flag through the max-reduction, so a
     # rank that failed alone and moved on can never have its reduction paired with another leg's on its peers (the
@@ -1070,17 +1123,11 @@ def main():
     lod = leg_lod(r, cam, img, args, world, timed) if args.lod > 0 else None
 
     rf = rooflines(r, stats, acc, data, P, W, H, ms_per_step)
-    roofline, frame_views, V, Lref, Lp = rf["roofline"], rf["frame_views"], rf["V"], rf["Lref"], rf["Lp"]
+    roofline, frame_views, V, Lp = rf["roofline"], rf["frame_views"], rf["V"], rf["Lp"]
     pmc_all, pmc_source, same_workload, src_hash = rf["pmc_all"], rf["pmc_source"], rf["same_workload"], rf["src_hash"]
     sq_issue_kernels, sq_issue_src = rf["sq_issue_kernels"], rf["sq_issue_src"]
 
-    out = {
-        "metric": "forward fps @1080p, mip360_bicycle", "value": round(value, 2), "unit": "frames/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": data,
-        "config": {"workload": workload, "resolution": f"{W}x{H}", "splats": P, "visible_splats": V,
-                   "tile_pairs_reference": Lref, "tile_pairs_sorted": Lp, "views_per_gpu": 1,
-                   "parallelism": f"view-parallel x{world}"},
+    out.update({
         "roofline": roofline,
         "frame_roofline": {"peak": HBM_PEAK_GBS, "attainable_peak": HBM_ATTAINABLE_GBS,
                            "attainable_peak_source": "tools/microbench/fetch_calib.hip: plain 12- / 16-byte-per-lane read streams "
@@ -1089,7 +1136,7 @@ def main():
                            "unit": "GB/s", **frame_views},
         "per_frame_events": per_frame,
         "stages_ms": {k: round(v, 4) for k, v in acc.items()},
-    }
+    })
     if stage_path is not None:
         out["stage_path"] = stage_path
     if half_sh is not None:

@@ -1,8 +1,9 @@
 """Diagnostic (not a test, CPU only): splits the f32 gradient error of ill-conditioned soak draws into the part made by the sums over
 pixels (render-backward) and the part made by the per-splat algebra (preprocess-backward): python tests/debug/grad_decomposition.py
 (output kept in profiles/r04_gradient_error_survey.txt)"""
-import sys, ctypes as C, numpy as np
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+import os, sys, ctypes as C, numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import Oracle, _ptr
 from test_gpu_random_sweep import _draw
 o32,o64=Oracle("f32"),Oracle("f64")

@@ -68,3 +68,31 @@ def test_committed_default_bench_line_has_the_contract_fields():
         assert {"survey_model", "own_algorithmic"} <= set(fr) and fr["peak"] == 8000.0
         assert fr["own_algorithmic"]["bytes"] == sum(fr["own_algorithmic"]["per_stage_bytes"].values())
         assert "moving_camera" in d and "file_order" in d
+
+
+def test_legs_of_the_full_run_are_refused_without_full():
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--half-sh"],
+                         capture_output=True, text=True, timeout=300)
+    assert res.returncode == 2 and "--full" in res.stderr
+    assert not any(line.startswith("{") for line in res.stdout.splitlines())
+
+
+def test_dump_outputs_writes_the_image_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    import torch
+
+    img = torch.from_numpy(np.random.default_rng(3).random((3, 24, 32), dtype=np.float32))
+    bench.dump_outputs(str(tmp_path / "whole"), img)
+    assert os.listdir(tmp_path / "whole") == ["image.npy"]
+    got = np.load(tmp_path / "whole" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img.numpy())
+    # beyond the size limit: the same seeded pixels on every run, each with its flat index
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1024)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_PIXELS", 50)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), img)
+        assert sorted(os.listdir(tmp_path / d)) == ["image_sample.npy", "image_sample_pixels.npy"]
+    s, idx = np.load(tmp_path / "a" / "image_sample.npy"), np.load(tmp_path / "a" / "image_sample_pixels.npy")
+    assert s.shape == (3, 50) and s.dtype == np.float32 and idx.dtype == np.float64
+    assert np.array_equal(s, img.numpy().reshape(3, -1)[:, idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "image_sample_pixels.npy"))
+    assert np.array_equal(s, np.load(tmp_path / "b" / "image_sample.npy"))

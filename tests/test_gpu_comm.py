@@ -208,7 +208,7 @@ def test_bench_runs_every_multi_gpu_code_path_on_one_rank(collective):
     N > 1 branch of the file runs (the driver launches the real N = 2, 4, 8 on a whole node)."""
     env = dict(os.environ, LCGS_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--splats", "200000", "--res", "640x480", "--steps",
-                          "3", "--warmup", "1", "--no-cpu-baseline", "--no-stage-path", "--no-spatial", "--collective",
+                          "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-stage-path", "--no-spatial", "--collective",
                           collective], capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     line = [x for x in res.stdout.splitlines() if x.startswith("{")][-1]
@@ -231,7 +231,7 @@ def test_bench_still_prints_its_line_when_a_multi_gpu_leg_fails():
     env = dict(os.environ, LCGS_BENCH_FORCE_DIST="1", LCGS_BENCH_INJECT_LEG_FAILURE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT="29534")
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--splats", "100000", "--res", "320x240", "--steps",
-                          "2", "--warmup", "1", "--no-cpu-baseline", "--no-stage-path", "--no-batch"],
+                          "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-stage-path", "--no-batch"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [x for x in res.stdout.splitlines() if x.startswith("{")]
@@ -247,7 +247,7 @@ def test_bench_falls_back_to_torch_distributed_when_the_communicator_fails_its_s
     env = dict(os.environ, LCGS_BENCH_FORCE_DIST="1", LCGS_BENCH_INJECT_SELFTEST_FAILURE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT="29536")
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--splats", "100000", "--res", "320x240", "--steps",
-                          "2", "--warmup", "1", "--no-cpu-baseline", "--no-stage-path", "--no-batch", "--no-spatial"],
+                          "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-stage-path", "--no-batch", "--no-spatial"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([x for x in res.stdout.splitlines() if x.startswith("{")][-1])
@@ -265,7 +265,7 @@ def test_bench_with_two_ranks_on_one_gpu_through_the_torch_collective():
     env = dict(os.environ, LCGS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
                           "127.0.0.1", "--master-port", "29543", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--splats",
-                          "100000", "--res", "320x240", "--steps", "4", "--warmup", "1", "--no-cpu-baseline",
+                          "100000", "--res", "320x240", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline",
                           "--no-stage-path", "--no-spatial", "--leg-timeout", "300", "--collective", "torch"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -294,7 +294,7 @@ def test_bench_with_two_ranks_on_one_gpu():
     env = dict(os.environ, LCGS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
                           "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--splats",
-                          "200000", "--res", "640x480", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+                          "200000", "--res", "640x480", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline",
                           "--no-stage-path", "--no-spatial", "--leg-timeout", "300"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]

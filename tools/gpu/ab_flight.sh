@@ -4,7 +4,7 @@
 # Prints, per setting and repetition: in-order fps, camera batch fps, fwd+bwd Msplats/s, lcgs_fit_views (4 views) Msplats/s.
 cd $GRAFT_REPO_ROOT
 cp luisacomputegaussiansplatting_amd/liblcgs_hip.so /tmp/lcgs_shipped.so
-B="python bench.py --steps 60 --warmup 8 --no-cpu-baseline --no-train-step --no-stage-path --no-spatial"
+B="python bench.py --steps 60 --warmup 8 --full --no-cpu-baseline --no-train-step --no-stage-path --no-spatial"
 for rep in 1 2; do for v in "$@"; do
 lib=$(echo "$v" | grep -o 'LIB=[a-z0-9_]*' | cut -d= -f2)
 if [ -n "$lib" ]; then cp gpurun_in/liblcgs_$lib.so luisacomputegaussiansplatting_amd/liblcgs_hip.so; else cp /tmp/lcgs_shipped.so luisacomputegaussiansplatting_amd/liblcgs_hip.so; fi

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 V=$1; shift
-CMD="bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-batch --no-train-step --no-stage-path --no-spatial --no-moving-camera --no-backward"
+CMD="bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-batch --no-train-step --no-stage-path --no-spatial --no-moving-camera --no-backward"
 for val in "$@"; do
   export $V=$val
   rm -rf gpurun_out/pmcab_$val

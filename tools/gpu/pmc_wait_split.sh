@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 O=${1:-gpurun_out/prof}
-CMD=${2:-"bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-batch --no-train-step --no-stage-path --no-spatial --no-moving-camera"}
+CMD=${2:-"bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-batch --no-train-step --no-stage-path --no-spatial --no-moving-camera"}
 mkdir -p $O
 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/ws -- python3 $CMD > $O/ws.log 2>&1 || { tail -5 $O/ws.log; exit 1; }
 python3 profiles/pmc_summary.py $O/ws > $O/pmc_wait_split.txt

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Regenerates the judged profile artefacts of a round on the GPU box (run through gpurun from the repo root):
-#   gpurun_out/prof/bench_default.json  default `python bench.py` line
+#   <out>/bench_default.json            the `python bench.py --full` line
 #   gpurun_out/prof/kernel_stats.{csv,txt}  rocprofv3 --kernel-trace --stats of the bench command
 #   gpurun_out/prof/pmc_traffic.{json,txt}  FETCH_SIZE / WRITE_SIZE (separate passes), per launch
 #   gpurun_out/prof/pmc_sq.txt              SQ instruction counters, per launch
@@ -10,10 +10,10 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 O=gpurun_out/prof
 mkdir -p $O
-CMD="bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-batch --no-train-step --no-stage-path --no-spatial --no-moving-camera"
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
+CMD="bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-batch --no-train-step --no-stage-path --no-spatial --no-moving-camera"
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
 echo "bench done" && cut -c1-200 $O/bench_default.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-spatial > $O/stats.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-spatial > $O/stats.log 2>&1 || exit 1
 f=$(find $O/stats -name '*_kernel_stats.csv' | sort | tail -1)
 cp "$f" $O/kernel_stats.csv
 python3 profiles/summarize.py $O/stats > $O/kernel_stats.txt
