@@ -398,8 +398,12 @@ __global__ void __launch_bounds__(256, LCGS_BWD_WAVES) k_render_backward(CamPara
                 // exp(power): the hardware's v_exp_f32 (1 ulp; two instructions) since round 5, not the forward's DEFINED
                 // function (ten).  The forward needs that one for bit-identical images; here the tolerance is 1e-3 and what
                 // the two differ by -- ~1e-7 relative in alpha, an entry within that of alpha = 1/255 blended on one side
-                // only (its weight is <= T / 255) -- is far inside it: every gradient test, the f64 checks at full size and
-                // the soak's error distribution are unchanged.  render-backward 0.66-0.68 -> 0.63-0.64 ms, forward+backward
+                // only (its weight is <= T / 255) -- is far inside it in the norm.  Row by row, tests/gpu_util.py::check_gradient_rows
+                // holds every gradient row to its own bound, whose flip term counts each entry within a few 1e-6 of 1/255,
+                // 0.99 or power = 0 in full.  On a frame whose opacities are constructed to put o G within 2 ulp of both
+                // thresholds (tests/test_gpu_gradient_rows.py; the flip term fires on 2 613 rows there) one SH row lands
+                // at 1.000 of its bound -- what one near-threshold entry decided apart from the forward and counted in full
+                // looks like (not yet A/B'd against the defined exp) -- the others <= 0.79; ordinary frames <= 0.51.  render-backward 0.66-0.68 -> 0.63-0.64 ms, forward+backward
                 // +2.2 % in same-box A/B (profiles/r05_bwd_hw_exp_ab.txt; -DLCGS_BWD_DEFINED_EXP builds the old form).
 #ifdef LCGS_BWD_DEFINED_EXP
                 const float G     = blend_exp(power);

@@ -117,6 +117,11 @@ class Oracle:
     def get_threads(self) -> int:
         return int(self.lib.orc_get_threads())
 
+    def set_backward_bound(self, on: bool) -> None:
+        """orc_set_backward_bound: orc_render_backward writes the per-row sums A, F instead of gradients (see
+        render_backward_bound); off = the default walk, bit for bit"""
+        self.lib.orc_set_backward_bound(C.c_int(1 if on else 0))
+
     # ------------------------------------------------------------------ camera
     def lookat(self, pos, target, world_up, width=None, height=None, fov=None):
         cam = self.Camera()
@@ -374,6 +379,52 @@ class Oracle:
                                      _ptr(nc, C.c_uint32), self.rp(dL), self.rp(gm), self.rp(gc), self.rp(go), self.rp(gcol))
         return gm, gc, go, gcol
 
+    def render_backward_bound(self, width, height, bg, ranges, point_list, means_pix, conic, opacity, color, final_T,
+                              n_contrib, dL_dimg):
+        """the same walk as render_backward with orc_set_backward_bound on: per splat row, for each of the nine 2-D
+        gradient components (mean2d 2, conic 3, opacity 1, colour 3), the sums A (|term| x (1 + depth in the
+        recursion)) and F (|term| over decisions within rounding of their threshold, and what flipping them rescales).
+        Returns (A, F), each [n, 9] in that component order."""
+        n = self.arr(opacity).shape[0]
+        rng = np.ascontiguousarray(ranges, dtype=np.uint32)
+        pl = np.ascontiguousarray(point_list, dtype=np.uint32)
+        nc = np.ascontiguousarray(n_contrib, dtype=np.uint32)
+        mp, cn, op, col, fT, dL, bga = (self.arr(x) for x in (means_pix, conic, opacity, color, final_T, dL_dimg, bg))
+        bm, bc, bo, bcol = (np.zeros((n, 2 * k), self.dtype) for k in (2, 3, 1, 3))
+        self.set_backward_bound(True)
+        try:
+            self.lib.orc_render_backward(C.c_int(width), C.c_int(height), self.rp(bga), _ptr(rng, C.c_uint32),
+                                         _ptr(pl, C.c_uint32), self.rp(mp), self.rp(cn), self.rp(op), self.rp(col),
+                                         self.rp(fT), _ptr(nc, C.c_uint32), self.rp(dL), self.rp(bm), self.rp(bc),
+                                         self.rp(bo), self.rp(bcol))
+        finally:
+            self.set_backward_bound(False)
+        parts = [(bm, 2), (bc, 3), (bo, 1), (bcol, 3)]
+        A = np.concatenate([b[:, :k] for b, k in parts], axis=1).astype(np.float64)
+        F = np.concatenate([b[:, k:] for b, k in parts], axis=1).astype(np.float64)
+        return A, F
+
+    def forward_state(self, scene, cam, bg=(0.0, 0.0, 0.0), scale_modifier=1.0, sh_deg=3, lod_min_radius=0):
+        """orc_render's sequence through the stage entry points, keeping what the backward walks: dict(img, radii, color,
+        means (pixel), conic, ranges, point_list, final_T, n_contrib).  lod_min_radius: orc_set_lod_min_radius's rule."""
+        pos = self.arr(scene["pos"], (-1, 3))
+        P = pos.shape[0]
+        W, H = cam.width, cam.height
+        color = self.sh_process(np.array(cam.position[:]), pos, self.arr(scene["sh"], (P, -1)), deg=sh_deg)
+        m2, depth, cov = self.project(pos, scene["scale"], scene["rotq"], cam, scale_modifier=scale_modifier)
+        means, conic, tiles, radii = self.allocate_tiles(W, H, depth, m2, cov)
+        if lod_min_radius > 0:
+            small = radii < lod_min_radius
+            radii[small], tiles[small] = 0, 0
+        offsets = self.inclusive_sum(tiles)
+        keys, vals = self.copy_with_keys(W, H, means, offsets, radii, depth)
+        keys, vals = self.sort_pairs(keys, vals)
+        ranges = self.get_ranges(keys, ((W + 15) // 16) * ((H + 15) // 16))
+        opacity = self.arr(scene["opacity"], (P,))
+        img, final_T, n_contrib, _ = self.render_forward(W, H, bg, ranges, vals, means, conic, opacity, color)
+        return {"img": img, "radii": radii, "color": color, "means": means, "conic": conic, "opacity": opacity,
+                "ranges": ranges, "point_list": vals, "final_T": final_T, "n_contrib": n_contrib}
+
     def render_backward_full(self, scene, cam, dL_dimg, bg=(0.0, 0.0, 0.0), scale_modifier=1.0, sh_deg=3):
         pos = self.arr(scene["pos"], (-1, 3))
         P = pos.shape[0]
@@ -399,6 +450,45 @@ class Oracle:
         g["img"] = img
         g["num_rendered"] = int(L)
         return g
+
+
+GRAD_2D = ("mean2d_x", "mean2d_y", "conic_a", "conic_b", "conic_c", "opacity", "color_r", "color_g", "color_b")
+_J_IN = (0, 1, 2, 3, 4, 6, 7, 8)  # the eight of GRAD_2D that orc_preprocess_backward maps (opacity passes through)
+
+
+def abs_jacobian_apply(o64, scene, cam, radii, vecs, scale_modifier=1.0, sh_deg=3):
+    """sum_k |J[row, out, k]| v[row, k] for each v of `vecs` ([P, 9] in GRAD_2D order), J the per-row Jacobian of the
+    preprocess-backward (2-D gradients -> pos, scale, rotq, sh).  With the forward fixed orc_preprocess_backward is linear
+    in (dL/dmean2d, dL/dconic, dL/dcolor), so column k of every row's J is one run of the f64 build with component k set
+    to 1 on every row (8 runs); J itself ([P, 58, 8]) is never held.  Opacity passes through: |J| = 1.
+    Returns one dict attribute -> [P, n] per v."""
+    assert o64.precision == "f64"
+    P = np.asarray(radii).shape[0]
+    outs = [{"pos": np.zeros((P, 3)), "scale": np.zeros((P, 3)), "rotq": np.zeros((P, 4)),
+             "sh": np.zeros((P, np.asarray(scene["sh"]).reshape(P, -1).shape[1])), "opacity": v[:, 5].copy()} for v in vecs]
+    for k in _J_IN:
+        unit = np.zeros((P, 9))
+        unit[:, k] = 1.0
+        col = o64.preprocess_backward(scene, cam, radii, unit[:, 0:2], unit[:, 2:5], unit[:, 6:9],
+                                      scale_modifier=scale_modifier, sh_deg=sh_deg)
+        for v, out in zip(vecs, outs):
+            for name in ("pos", "scale", "rotq", "sh"):
+                out[name] += np.abs(col[name]) * v[:, k:k + 1]
+    return outs
+
+
+def gradient_row_terms(o32, o64, scene, cam, dL_dimg, bg=(0.0, 0.0, 0.0), scale_modifier=1.0, sh_deg=3, lod_min_radius=0):
+    """The two rounding budgets of tests/gpu_util.py::check_gradient_rows, per attribute and per element: (|J| A, |J| F).
+    A and F come from the f64 walk (orc_set_backward_bound) over the binary32 forward state of the f32 oracle -- the state
+    the kernels' own forward produces bit for bit -- so that its threshold windows describe binary32 re-evaluations of
+    those very inputs; J from abs_jacobian_apply.  cam: the f32 oracle's camera."""
+    st = o32.forward_state(scene, cam, bg=bg, scale_modifier=scale_modifier, sh_deg=sh_deg, lod_min_radius=lod_min_radius)
+    W, H = cam.width, cam.height
+    A, F = o64.render_backward_bound(W, H, np.asarray(bg, np.float32), st["ranges"], st["point_list"], st["means"],
+                                     st["conic"], st["opacity"], st["color"], st["final_T"], st["n_contrib"],
+                                     np.asarray(dL_dimg, np.float32))
+    JA, JF = abs_jacobian_apply(o64, scene, o64.convert_camera(cam), st["radii"], (A, F), scale_modifier, sh_deg)
+    return {"JA": JA, "JF": JF, "A": A, "F": F, "state": st}
 
 
 class Ref:

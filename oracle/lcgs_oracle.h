@@ -188,6 +188,12 @@ void orc_render_backward(int width, int height, const real bg[3],
                          const real* final_T, const uint32_t* n_contrib,
                          const real* dL_dimg,
                          real* dL_dmean2d, real* dL_dconic, real* dL_dopacity, real* dL_dcolor);
+/* Per-row rounding budget of the walk above (lcgs_oracle_bwd.c, tests/gpu_util.py::check_gradient_rows).  On: the next
+ * orc_render_backward calls write, in place of the gradients and into rows TWICE as wide (mean2d 4, conic 6, opacity 2,
+ * colour 6 per splat; zero-initialised), the row's sums A (|term| x (1 + depth in the recursion)) then F (|term| over
+ * near-threshold decisions and what their flip rescales).  Off (the default): unchanged, bit for bit. */
+void orc_set_backward_bound(int on);
+int  orc_get_backward_bound(void);
 
 /* preprocess-backward: 2-D grads -> dL/d{pos, scale, rotq, sh}.  dL_dopacity passes through. */
 void orc_preprocess_backward(int P, int sh_deg, const real* pos, const real* scale, const real* rotq,

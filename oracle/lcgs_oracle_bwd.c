@@ -38,6 +38,115 @@ static inline real b_dot3(const real a[3], const real b[3]) { return a[0] * b[0]
 
 extern int orc_g_smooth; /* lcgs_oracle.c: FD-validation aid, disables the two hard blend thresholds */
 
+static int orc_g_bwd_bound = 0;
+void orc_set_backward_bound(int on) { orc_g_bwd_bound = on ? 1 : 0; }
+int  orc_get_backward_bound(void) { return orc_g_bwd_bound; }
+
+/* Relative window around the walk's three decisions (o G vs 1/255, o G vs 0.99, power vs 0) inside which an evaluation
+ * of the same binary32 inputs may decide the other way.  The kernels re-evaluate `power` with the forward's expression
+ * (bit-identical to the f32 walk; <= ~3 u x Pabs from the exact value this walk computes on the same inputs, Pabs = the
+ * sum of |parts| of power) and G = exp2(power log2e) with the hardware's v_exp_f32: the argument's rounding moves G by
+ * |power| u, the instruction by <= 1 ulp (2 u relative), the forward's defined exp by <= 2.73 ulp; o G adds one rounding.
+ * Near alpha = 1/255 |power| <= ln 255 = 5.5 (o <= 1), so the sum is <= (4 Pabs + 9) u ~ 3.4e-6 relative;
+ * BWD_BOUND_EPS + 4 u Pabs covers it with room, and stays right where the parts of `power` cancel (Pabs >> |power|). */
+#define BWD_BOUND_EPS 4e-6
+#define BWD_BOUND_U   5.9604644775390625e-8 /* 2^-24 */
+
+/* orc_render_backward with orc_set_backward_bound(1): the same walk, but each output row is twice as wide (mean2d 4,
+ * conic 6, opacity 2, colour 6 reals per splat) and holds, for its k components, first k sums A, then k sums F:
+ *   A = sum over the row's terms of |term| (1 + d), d the entry's depth in the back-to-front recursion: the steps
+ *       T / (1 - alpha) that reached it (last - j of them), each weighted 1 + alpha (4 + Pabs) / (1 - alpha) -- alpha
+ *       carries ~(4 + Pabs) u of rounding (power, exp, o G), which 1 - alpha amplifies by alpha / (1 - alpha), up to 99x
+ *       below the 0.99 cap: what summation order and the drift of T can move the sum by, in units of u;
+ *   F = sum of |term| over the entries whose decision lies within the window above (counted in full, whether this walk
+ *       takes or skips them), plus every term in front of such an entry in the same pixel times 2 alpha of it (a flipped
+ *       entry rescales T and the colour behind by that factor): what a decision flip can move the sum by.
+ * |term| is the magnitude of a term with every part taken by absolute value (the sums inside dL/dalpha cancel; their
+ * rounding does not).  In the f64 build on widened binary32 inputs the result describes the binary32 walk of those inputs. */
+static void render_backward_bound(int width, int height, const real bg[3], const uint32_t* ranges,
+                                  const uint32_t* point_list, const real* means_2d, const real* conic, const real* opacity,
+                                  const real* color, const real* final_T, const uint32_t* n_contrib, const real* dL_dimg,
+                                  real* b_mean2d, real* b_conic, real* b_opacity, real* b_color)
+{
+    static const int first[4] = { 0, 2, 5, 6 }, width_k[4] = { 2, 3, 1, 3 };
+    const uint32_t   gx = ((uint32_t)width + BLOCK_X - 1u) / BLOCK_X;
+    const size_t     hw = (size_t)width * (size_t)height;
+    const double     lo_thr = (double)(RC(1.0f) / RC(255.0f)), hi_thr = (double)RC(0.99f);
+    for (int y = 0; y < height; ++y) {
+        for (int x = 0; x < width; ++x) {
+            const uint32_t tile  = ((uint32_t)y / BLOCK_Y) * gx + (uint32_t)x / BLOCK_X;
+            const uint32_t start = ranges[2 * (size_t)tile + 0];
+            const size_t   pix   = (size_t)x + (size_t)width * (size_t)y;
+            const uint32_t last  = n_contrib[pix];
+            if (last == 0u) continue;
+            const real   T_final = final_T[pix];
+            const real   dpix[3] = { dL_dimg[pix], dL_dimg[pix + hw], dL_dimg[pix + 2 * hw] };
+            const double bg_abs  = fabs((double)(bg[0] * dpix[0])) + fabs((double)(bg[1] * dpix[1])) +
+                                   fabs((double)(bg[2] * dpix[2]));
+            real         T = T_final;
+            real         accum[3] = { RC(0.0f), RC(0.0f), RC(0.0f) }, last_color[3] = { RC(0.0f), RC(0.0f), RC(0.0f) };
+            real         last_alpha = RC(0.0f);
+            double       phi = 0.0;   /* sum of 2 alpha over the flagged entries behind the current one */
+            double       depth = 0.0; /* the steps T / (1 - alpha) taken so far, weighted (see A above) */
+            for (uint32_t j = last; j-- > 0u;) {
+                const uint32_t id = point_list[start + j];
+                const real     dx = means_2d[2 * (size_t)id + 0] - (real)x;
+                const real     dy = means_2d[2 * (size_t)id + 1] - (real)y;
+                const real     ca = conic[3 * (size_t)id + 0], cb = conic[3 * (size_t)id + 1], cc = conic[3 * (size_t)id + 2];
+                const real     o  = opacity[id];
+                const real     power = RC(-0.5f) * (ca * dx * dx + cc * dy * dy) - cb * dx * dy;
+                const double   pabs  = 0.5 * (fabs((double)(ca * dx * dx)) + fabs((double)(cc * dy * dy))) +
+                                    fabs((double)(cb * dx * dy));
+                const double   win    = BWD_BOUND_EPS + 4.0 * BWD_BOUND_U * pabs;
+                const int      flip_p = fabs((double)power) <= win * pabs;
+                if (power > RC(0.0f) && !flip_p) continue;
+                const real G       = R_EXP(power > RC(0.0f) ? RC(0.0f) : power);
+                const real oG      = o * G;
+                const real alpha   = b_min(RC(0.99f), oG);
+                const int  flip_lo = fabs((double)oG - lo_thr) <= win * lo_thr;
+                const int  flip_hi = fabs((double)oG - hi_thr) <= win * hi_thr;
+                const int  taken   = power <= RC(0.0f) && !(alpha < RC(1.0f) / RC(255.0f));
+                const int  flagged = flip_p || flip_lo || flip_hi;
+                if (!taken && !flagged) continue;
+                /* the state this entry sees; a skipped (flagged) entry is evaluated as if taken, the state left alone */
+                const real Tn = T / (RC(1.0f) - alpha);
+                real       acc[3];
+                double     mag_d = 0.0;
+                for (int ch = 0; ch < 3; ++ch) {
+                    acc[ch] = last_alpha * last_color[ch] + (RC(1.0f) - last_alpha) * accum[ch];
+                    mag_d += (fabs((double)color[3 * (size_t)id + ch]) + fabs((double)acc[ch])) * fabs((double)dpix[ch]);
+                }
+                const double dalpha = (double)Tn * mag_d + (double)T_final / (1.0 - (double)alpha) * bg_abs;
+                const double gate   = (oG < RC(0.99f) || flip_hi) ? 1.0 : 0.0;
+                const double qG = gate * (double)G * dalpha, qoG = qG * fabs((double)o);
+                const double adx = fabs((double)dx), ady = fabs((double)dy), wT = (double)alpha * (double)Tn;
+                const double mag[9] = { qoG * (adx * fabs((double)ca) + ady * fabs((double)cb)),
+                                        qoG * (ady * fabs((double)cc) + adx * fabs((double)cb)),
+                                        0.5 * qoG * adx * adx, qoG * adx * ady, 0.5 * qoG * ady * ady, qG,
+                                        wT * fabs((double)dpix[0]), wT * fabs((double)dpix[1]), wT * fabs((double)dpix[2]) };
+                if (taken) depth += 1.0 + (double)alpha * (4.0 + pabs) / (1.0 - (double)alpha);
+                const double depth_w = taken ? 1.0 + depth : 0.0;
+                const double fw      = phi + (flagged ? 1.0 : 0.0);
+                real* const  rows[4] = { &b_mean2d[4 * (size_t)id], &b_conic[6 * (size_t)id], &b_opacity[2 * (size_t)id],
+                                         &b_color[6 * (size_t)id] };
+                for (int r = 0; r < 4; ++r)
+                    for (int k = 0; k < width_k[r]; ++k) {
+                        rows[r][k] += (real)(mag[first[r] + k] * depth_w);
+                        rows[r][width_k[r] + k] += (real)(mag[first[r] + k] * fw);
+                    }
+                if (flagged) phi += 2.0 * (double)alpha;
+                if (!taken) continue;
+                T = Tn;
+                for (int ch = 0; ch < 3; ++ch) {
+                    accum[ch]      = acc[ch];
+                    last_color[ch] = color[3 * (size_t)id + ch];
+                }
+                last_alpha = alpha;
+            }
+        }
+    }
+}
+
 /* ------------------------------------------------------------------ render backward
  * Walks each pixel's tile list from its last contributor back to the front (the forward of
  * gs_tile_splatter/shader.cpp:249-274 in reverse), re-deriving alpha and re-applying the forward's skips. */
@@ -46,6 +155,11 @@ void orc_render_backward(int width, int height, const real bg[3], const uint32_t
                          const real* final_T, const uint32_t* n_contrib, const real* dL_dimg, real* dL_dmean2d,
                          real* dL_dconic, real* dL_dopacity, real* dL_dcolor)
 {
+    if (orc_g_bwd_bound) {
+        render_backward_bound(width, height, bg, ranges, point_list, means_2d, conic, opacity, color, final_T, n_contrib,
+                              dL_dimg, dL_dmean2d, dL_dconic, dL_dopacity, dL_dcolor);
+        return;
+    }
     const uint32_t gx = ((uint32_t)width + BLOCK_X - 1u) / BLOCK_X;
     const size_t   hw = (size_t)width * (size_t)height;
     /* serial over pixels: the per-splat accumulation order is then fixed (a reproducible oracle) */
@@ -325,6 +439,7 @@ int64_t orc_render_backward_full(int P, int sh_deg, const real* pos, const real*
                                  real scale_modifier, const real* dL_dimg, real* img, real* dL_dpos,
                                  real* dL_dscale, real* dL_drotq, real* dL_dsh, real* dL_dopacity)
 {
+    if (orc_g_bwd_bound) return -1; /* its 2-D buffers are sized for gradients, not for the bound's wider rows */
     const int      W = cam->width, H = cam->height;
     const uint32_t gx = ((uint32_t)W + BLOCK_X - 1u) / BLOCK_X, gy = ((uint32_t)H + BLOCK_Y - 1u) / BLOCK_Y;
     const size_t   G = (size_t)gx * gy, hw = (size_t)W * H;

@@ -109,6 +109,27 @@ def assert_parity_vs_numerics_variants(gpu_img, scene, ocam, **render_kw):
     return rep
 
 
+def random_draw(seed):
+    """One seeded random frame (tests/test_gpu_random_sweep.py, tests/test_oracle_gradient_rows.py): (rng, scene, W, H, pose,
+    fov, bg, scale_modifier) -- sizes, resolutions that are not multiples of 16, fields of view, scale distributions (every
+    third draw anisotropic needles and a few giants), poses, backgrounds, scale modifiers."""
+    from conftest import make_scene
+
+    rng = np.random.default_rng(1000 + seed)
+    P = int(rng.integers(1, 4000))
+    W, H = int(rng.integers(17, 420)), int(rng.integers(17, 300))
+    scene = make_scene(rng, P, spread=float(rng.uniform(0.2, 1.5)),
+                       log_scale=(float(rng.uniform(-5.5, -2.0)), float(rng.uniform(0.2, 1.2))))
+    if seed % 3 == 0:  # anisotropic needles and a few giants
+        scene["scale"][:, 0] *= 8.0
+        scene["scale"][: max(1, P // 50)] *= 25.0
+    ang, elev, dist = rng.uniform(0, 2 * np.pi), rng.uniform(-0.6, 0.9), rng.uniform(0.3, 6.0)
+    pos = [dist * np.cos(ang) * np.cos(elev), dist * np.sin(ang) * np.cos(elev), 0.5 + dist * np.sin(elev)]
+    pose = (pos, [0.0, 0.0, 0.5], [0.0, 0.0, 1.0])
+    return rng, scene, W, H, pose, float(rng.uniform(20.0, 110.0)), tuple(rng.uniform(0, 1, 3).tolist()), \
+        float(rng.uniform(0.5, 1.5))
+
+
 GRAD_F32_FACTOR = 3.0   # see check_gradients
 GRAD_GIANT_BAR = 5e-3
 
@@ -153,3 +174,102 @@ def check_gradients(g, ref32, ref64, P, radii, tag, report=None, flat_bar=None):
         assert flat_bar is None or e <= flat_bar, f"{tag} {k}: {e:.2e} vs the f64 oracle, beyond the flat bar {flat_bar:.0e}"
         assert eg <= max(GRAD_GIANT_BAR, GRAD_F32_FACTOR * eg32), (
             f"{tag} {k}: rows of the {int(giant.sum())} giants {eg:.2e} vs f64 (f32 oracle on them: {eg32:.2e})")
+
+
+# ---------------------------------------------------------------------------------------------------------------- per row
+GRAD_ROW_K = 3.0      # x the f32 oracles' own error on the component (the larger of the two builds')
+GRAD_ROW_CU = 128.0   # x u x (|J| A): summation order, the drift of T, the hardware exp's error in every G
+GRAD_ROW_FLOOR = 1e-7  # x (|J| A): an absolute floor, not a tolerance
+U32 = 2.0 ** -24
+_ORACLES = {}
+
+
+def _oracles():
+    if not _ORACLES:
+        from oracle import Oracle
+
+        _ORACLES.update(f32=Oracle("f32"), f64=Oracle("f64"), f32c=Oracle("f32", contracted=True))
+    return _ORACLES["f32"], _ORACLES["f64"], _ORACLES["f32c"]
+
+
+def gradient_row_bound(scene, ocam, dL, bg=(0.0, 0.0, 0.0), scale_modifier=1.0, sh_deg=3, ref32=None, ref64=None, ref32c=None,
+                       cam64=None):
+    """(per attribute [P, n] bound B, ref64) of check_gradient_rows, for one view.  ref32 / ref64 / ref32c: the oracles'
+    render_backward_full of the same view when the caller has them (f32, f64, contracted f32); computed otherwise.
+    cam64: the f64 oracle's own camera (default: ocam widened)."""
+    from oracle import gradient_row_terms
+
+    o32, o64, o32c = _oracles()
+    ocam = o32.convert_camera(ocam)
+    kw = dict(bg=bg, scale_modifier=scale_modifier, sh_deg=sh_deg)
+    if ref32 is None:
+        ref32 = o32.render_backward_full(scene, ocam, dL, **kw)
+    if ref64 is None:
+        ref64 = o64.render_backward_full(scene, cam64 if cam64 is not None else o64.convert_camera(ocam), dL, **kw)
+    if ref32c is None:
+        ref32c = o32c.render_backward_full(scene, o32c.convert_camera(ocam), dL, **kw)
+    t = gradient_row_terms(o32, o64, scene, ocam, dL, **kw)
+    P = np.asarray(scene["pos"]).reshape(-1, 3).shape[0]
+    B = {}
+    for k in ("pos", "scale", "rotq", "sh", "opacity"):
+        b64 = ref64[k].astype(np.float64).reshape(P, -1)
+        noise = np.maximum(np.abs(ref32[k].astype(np.float64).reshape(P, -1) - b64),
+                           np.abs(ref32c[k].astype(np.float64).reshape(P, -1) - b64))
+        JA, JF = t["JA"][k].reshape(P, -1), t["JF"][k].reshape(P, -1)
+        B[k] = GRAD_ROW_K * noise + GRAD_ROW_CU * U32 * JA + JF + GRAD_ROW_FLOOR * JA
+    return B, ref64
+
+
+def gradient_row_ratios(got, B, ref64, rows=None):
+    """per attribute: (worst |a - b64| / B, its row, rows over the bound).  got: attribute -> array or tensor; rows: the
+    oracle rows that got's rows hold (compact gradients), default all."""
+    out = {}
+    for k, bound in B.items():
+        a = got[k]
+        a = (a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)).astype(np.float64)
+        b64 = ref64[k].astype(np.float64).reshape(bound.shape[0], -1)
+        if rows is not None:
+            b64, bound = b64[rows], bound[rows]
+        a = a.reshape(b64.shape[0], -1)
+        diff = np.abs(a - b64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.where(bound > 0, diff / bound, np.where(diff > 0, np.inf, 0.0))
+        r = np.where(np.isfinite(a), r, np.inf).max(axis=1)
+        i = int(np.argmax(r)) if r.size else 0
+        bad = np.nonzero(r > 1.0)[0]
+        out[k] = (float(r[i]) if r.size else 0.0, int(rows[i]) if rows is not None and r.size else i,
+                  (np.asarray(rows)[bad] if rows is not None else bad))
+    return out
+
+
+def check_gradient_rows(g, scene, ocam, dL, bg=(0.0, 0.0, 0.0), scale_modifier=1.0, tag="", sh_deg=3, ref32=None, ref64=None,
+                        ref32c=None, rows=None, bound=None, report=None, cam64=None):
+    """The kernels' gradients held ROW BY ROW, every component of every row, against the f64 oracle:
+
+        |a_i - b64_i| <= K max(|b32_i - b64_i|, |b32c_i - b64_i|) + c_u u (|J| A)_i + (|J| F)_i + 1e-7 (|J| A)_i
+
+    for every component i of every row.  b32 / b32c: the f32 oracle and its contracted-FMA build (two samples of binary32
+    noise, incl. the f32/f64 forward's own decisions -- the kernels' forward is the f32 oracle's bit for bit, so what it
+    moves, it moves for them too).  A, F: the render-backward
+    walk's rounding budget per 2-D component (oracle/lcgs_oracle_bwd.c, orc_set_backward_bound), F for decisions within
+    rounding of a threshold; |J|: the per-row Jacobian of the preprocess-backward (oracle.abs_jacobian_apply).  K, c_u:
+    GRAD_ROW_K, GRAD_ROW_CU, chosen once on the CPU (tests/test_oracle_gradient_rows.py).  A norm over all rows lets a
+    handful of wrong rows through; this does not.
+    g: attribute -> kernel gradients (tensors or arrays); rows: the oracle rows g holds (compact rows); bound: a
+    precomputed (B, ref64) of gradient_row_bound (sums of views: add the views' B, and their ref64).
+    report: a list -> nothing asserted, the worst ratios appended.  Returns attribute -> (worst ratio, its row)."""
+    import time
+
+    t0 = time.perf_counter()
+    B, r64 = bound if bound is not None else gradient_row_bound(scene, ocam, dL, bg, scale_modifier, sh_deg, ref32, ref64,
+                                                                ref32c, cam64)
+    res = gradient_row_ratios(g, B, r64, rows)
+    worst = {k: (v[0], v[1]) for k, v in res.items()}
+    if report is not None:
+        report.append({"tag": tag, **{k: v[0] for k, v in res.items()}})
+        return worst
+    print(f"[gradient rows vs f64] {tag}: worst diff/bound " + ", ".join(f"{k} {v[0]:.3f} (row {v[1]})" for k, v in res.items()) +
+          f"; {time.perf_counter() - t0:.2f} s")
+    for k, (w, i, bad) in res.items():
+        assert w <= 1.0, f"{tag} {k}: {len(bad)} rows over their bound, worst row {i} at {w:.2f} x (rows {bad[:12].tolist()})"
+    return worst

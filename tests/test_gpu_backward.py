@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from conftest import make_scene
-from gpu_util import DEV, dev, upload_scene
+from gpu_util import DEV, check_gradient_rows, dev, gradient_row_bound, upload_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -29,6 +29,13 @@ def _grads(lcgs, oracle, scene, W, H, bg=(0.1, 0.2, 0.3), scale_modifier=1.0, se
     return {k: v.cpu().numpy() for k, v in g.items()}, ref
 
 
+def _rows(oracle, got, ref, scene, W, H, bg=(0.1, 0.2, 0.3), scale_modifier=1.0, seed=0, tag=""):
+    """every row against the f64 oracle, to its own bound (gpu_util.check_gradient_rows), beside _check's norms"""
+    dL = np.random.default_rng(seed).normal(size=(3, H, W)).astype(np.float32)
+    check_gradient_rows(got, scene, oracle.lookat(*POSE, width=W, height=H), dL, bg=bg, scale_modifier=scale_modifier, ref32=ref,
+                        tag=tag)
+
+
 def _check(got, ref):
     for name in ("pos", "scale", "rotq", "sh", "opacity"):
         a, b = got[name].astype(np.float64), ref[name].astype(np.float64)
@@ -51,6 +58,7 @@ def test_backward_matches_oracle(lcgs, oracle, P, res):
         scene["pos"][:50] = rng.normal(0, 0.3, (50, 3)) + POSE[0]
     got, ref = _grads(lcgs, oracle, scene, res[0], res[1])
     _check(got, ref)
+    _rows(oracle, got, ref, scene, res[0], res[1], tag=f"P={P} {res[0]}x{res[1]}")
 
 
 def test_backward_culled_splats_get_exact_zeros(lcgs, oracle):
@@ -60,6 +68,7 @@ def test_backward_culled_splats_get_exact_zeros(lcgs, oracle):
     scene["opacity"][100:150] = 1e-4
     got, ref = _grads(lcgs, oracle, scene, 128, 96, scale_modifier=1.2)
     _check(got, ref)
+    _rows(oracle, got, ref, scene, 128, 96, scale_modifier=1.2, tag="culled")
     for name in ("pos", "scale", "rotq", "sh", "opacity"):
         assert np.all(got[name][:150] == 0), name
 
@@ -122,5 +131,10 @@ def test_backward_accumulate_sums_the_views_of_a_batch(lcgs, oracle):
         a = g[k].cpu().numpy().astype(np.float64).ravel()
         b = sum(ref[k].astype(np.float64).ravel() for ref in refs)
         assert np.linalg.norm(a - b) / np.linalg.norm(b) <= 1e-3, k
+    # per row: the bound of a sum of views is the sum of the views' bounds
+    bounds = [gradient_row_bound(scene, oracle.lookat(*p, width=W, height=H), dL, ref32=ref) for p, dL, ref in zip(poses, dLs, refs)]
+    B = {k: bounds[0][0][k] + bounds[1][0][k] for k in keys}
+    r64 = {k: bounds[0][1][k].astype(np.float64) + bounds[1][1][k].astype(np.float64) for k in keys}
+    check_gradient_rows(g, scene, None, None, bound=(B, r64), tag="two views accumulated")
     with pytest.raises(ValueError):
         r.backward(dev(dLs[0]), *[g[k] for k in keys], compact=True, accumulate=True)

@@ -5,27 +5,12 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import make_scene
-from gpu_util import (DEV, assert_image_parity, assert_parity_vs_libm_expf, assert_parity_vs_numerics_variants, check_gradients, dev,
-                      upload_scene)
+from gpu_util import (DEV, assert_image_parity, assert_parity_vs_libm_expf, assert_parity_vs_numerics_variants, check_gradient_rows,
+                      check_gradients, dev, random_draw, upload_scene)
 
 pytestmark = pytest.mark.gpu
 
-
-def _draw(seed):
-    rng = np.random.default_rng(1000 + seed)
-    P = int(rng.integers(1, 4000))
-    W, H = int(rng.integers(17, 420)), int(rng.integers(17, 300))
-    scene = make_scene(rng, P, spread=float(rng.uniform(0.2, 1.5)),
-                       log_scale=(float(rng.uniform(-5.5, -2.0)), float(rng.uniform(0.2, 1.2))))
-    if seed % 3 == 0:  # anisotropic needles and a few giants
-        scene["scale"][:, 0] *= 8.0
-        scene["scale"][: max(1, P // 50)] *= 25.0
-    ang, elev, dist = rng.uniform(0, 2 * np.pi), rng.uniform(-0.6, 0.9), rng.uniform(0.3, 6.0)
-    pos = [dist * np.cos(ang) * np.cos(elev), dist * np.sin(ang) * np.cos(elev), 0.5 + dist * np.sin(elev)]
-    pose = (pos, [0.0, 0.0, 0.5], [0.0, 0.0, 1.0])
-    return rng, scene, W, H, pose, float(rng.uniform(20.0, 110.0)), tuple(rng.uniform(0, 1, 3).tolist()), \
-        float(rng.uniform(0.5, 1.5))
+_draw = random_draw  # (shared with tests/test_oracle_gradient_rows.py)
 
 
 @pytest.mark.parametrize("seed", range(12))
@@ -76,4 +61,5 @@ def test_random_backward_frames(lcgs, oracle, oracle64, seed):
     ref64 = oracle64.render_backward_full(scene, oracle64.lookat(*pose, width=W, height=H, fov=fov), dL, bg=bg,
                                           scale_modifier=sm)
     radii = oracle.render(scene, ocam, bg=bg, scale_modifier=sm)["radii"]
-    check_gradients(g, ref32, ref64, P, radii, f"seed {seed}")  # every row, the f64 oracle: gpu_util.check_gradients
+    check_gradients(g, ref32, ref64, P, radii, f"seed {seed}")  # the norms over all rows: gpu_util.check_gradients
+    check_gradient_rows(g, scene, ocam, dL, bg=bg, scale_modifier=sm, ref32=ref32, ref64=ref64, tag=f"seed {seed}")  # each row

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from conftest import make_scene
-from gpu_util import DEV, assert_image_parity, dev
+from gpu_util import DEV, assert_image_parity, check_gradient_rows, dev
 
 pytestmark = pytest.mark.gpu
 POSE = ([-3, -0.5, 2.3], [0, 0, 0.5], [0, 0, 1])
@@ -37,6 +37,7 @@ def test_lower_sh_degrees_forward_and_backward(lcgs, oracle, deg):
     for k in g:
         a, b = g[k].cpu().numpy().astype(np.float64).ravel(), gref[k].astype(np.float64).ravel()
         assert np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30) <= 1e-3, (deg, k)
+    check_gradient_rows(g, scene, ocam, dL, bg=(0.1, 0.0, 0.2), sh_deg=deg, ref32=gref, tag=f"degree {deg}")
     if deg < 3:
         with pytest.raises(lcgs.LcgsError):
             r.use_half_sh(True)  # the f16 copy exists for degree 3 only

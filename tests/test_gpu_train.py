@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from conftest import make_scene
-from gpu_util import DEV
+from gpu_util import DEV, check_gradient_rows, gradient_row_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -120,7 +120,7 @@ def test_adam_visible_only_touches_survivors_only(lcgs):
         assert torch.equal(raw[k][vis], raw_d[k][vis]), k
 
 
-def test_compact_gradient_rows_and_their_optimiser_step(lcgs):
+def test_compact_gradient_rows_and_their_optimiser_step(lcgs, oracle):
     """lcgs_render_backward_compact: row r = the r-th on-screen splat (ascending index, lcgs_visible_rows), equal to
     that splat's row of the dense gradients, nothing else written; lcgs_adam_step(visible_only = 2) on those rows equals
     the on-screen-only step on the dense gradients bit for bit."""
@@ -160,6 +160,12 @@ def test_compact_gradient_rows_and_their_optimiser_step(lcgs):
         off = torch.ones(P, dtype=torch.bool, device=DEV)
         off[rows] = False
         assert (d[off] == 0).all(), k  # the dense variant: exact zeros elsewhere
+    # both against the f64 oracle row by row: compact row r is splat rows[r]'s row
+    bound = gradient_row_bound({k: act[k].cpu().numpy() for k in KEYS}, oracle.lookat([-3, -0.5, 2.3], [0, 0, 0.5], [0, 0, 1],
+                                                                                       width=W, height=H), dL.cpu().numpy())
+    check_gradient_rows(dense, None, None, None, bound=bound, tag="dense")
+    check_gradient_rows({k: comp[k].reshape(P, -1)[:V] for k in KEYS}, None, None, None, bound=bound,
+                        rows=rows.cpu().numpy(), tag="compact rows")
     # optimiser: compact rows (mode 2) vs the same gradients scattered to their splats (mode 1)
     scattered = {k: torch.zeros_like(raw[k]) for k in KEYS}
     for k in KEYS:
@@ -197,6 +203,8 @@ def test_autograd_binding_matches_oracle_backward(lcgs, oracle):
     for k in KEYS:
         a, b = t[k].grad.cpu().numpy().astype(np.float64), ref[k].astype(np.float64).reshape(t[k].shape)
         assert np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30) <= 1e-3, k
+    check_gradient_rows({k: t[k].grad for k in KEYS}, scene, oracle.lookat(*pose, width=W, height=H), dL.cpu().numpy(),
+                        bg=(0.1, 0.2, 0.3), ref32=ref, tag="autograd")
 
 
 def test_autograd_multi_view_loss_and_interleaved_use(lcgs, oracle):
@@ -219,6 +227,12 @@ def test_autograd_multi_view_loss_and_interleaved_use(lcgs, oracle):
         a = t[k].grad.cpu().numpy().astype(np.float64)
         b = sum(ref[k].astype(np.float64).reshape(t[k].shape) for ref in refs)
         assert np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30) <= 1e-3, k
+    # per row: the bound of a sum of views is the sum of the views' bounds
+    bounds = [gradient_row_bound(scene, oracle.lookat(*p, width=W, height=H), dL.cpu().numpy(), bg=(0.1, 0.2, 0.3), ref32=ref)
+              for p, dL, ref in zip(poses, dLs, refs)]
+    check_gradient_rows({k: t[k].grad for k in KEYS}, None, None, None, tag="autograd, two views",
+                        bound=({k: bounds[0][0][k] + bounds[1][0][k] for k in KEYS},
+                               {k: bounds[0][1][k].astype(np.float64) + bounds[1][1][k] for k in KEYS}))
 
 
 def test_adam_step_argument_checks(lcgs):
