@@ -249,6 +249,46 @@ LCGS_API lcgs_status lcgs_l2_loss_backward(lcgs_context* ctx, int width, int hei
 LCGS_API lcgs_status lcgs_fit_views(lcgs_context* ctx, int num_views, const lcgs_camera* cameras, const float bg_color[3],
                                     float scale_modifier, const float* const* d_targets, const lcgs_grads* grads, float* d_losses);
 
+/* ---- adaptive density control (no reference counterpart: doc/roadmap.md:4 only names training) -------------- */
+/* Per-splat statistics of the steps since the last rewrite, caller-owned, zeroed by the caller (lcgs_densify zeroes its outputs). */
+typedef struct lcgs_densify_stats {
+    float*    grad_accum; /* P: sum over frames of |dL/d(mean in NDC)| */
+    uint32_t* denom;      /* P: frames in which the row was on screen   */
+    int32_t*  max_radii;  /* P: largest screen radius seen (pixels)     */
+} lcgs_densify_stats;
+/* The context's last keep_state lcgs_render_forward and the backward that followed it (any variant): for every on-screen row,
+ * grad_accum += |(gx W/2, gy H/2)| of its pixel-space mean gradient, denom += 1, max_radii = max(., reference radius,
+ * gs_tile_splatter/shader.cpp:145-148).  Other rows untouched; the context's row order.  LCGS_ERR_STATE: no such frame, no
+ * backward on it yet, or a frame of lcgs_owner_render.  Only enqueues. */
+LCGS_API lcgs_status lcgs_densify_accumulate(lcgs_context* ctx, int num_gaussians, const lcgs_densify_stats* stats);
+typedef struct lcgs_densify_config {
+    float    grad_threshold;  /* 3DGS: 2e-4 */
+    float    percent_dense;   /* 3DGS: 0.01 */
+    float    scene_extent;
+    float    min_opacity;     /* 3DGS: 0.005 */
+    int      max_screen_size; /* pixels; 0 = no size pruning */
+    uint64_t seed;            /* built-in sampler, used when d_noise is NULL */
+} lcgs_densify_config;
+/* Out-of-place rewrite of raw / m / v (destinations must not alias sources; out_activated pos / sh may alias out_raw's).  Per
+ * source row, binary32: avg = denom ? grad_accum / denom : 0, smax = max exp(raw scale), op = sigmoid(raw opacity);
+ * prune = op < min_opacity || (max_screen_size > 0 && (max_radii > max_screen_size || smax > 0.1 scene_extent)) -> no row;
+ * else avg < grad_threshold -> the row, bit for bit; else smax <= percent_dense scene_extent -> the row + a copy of raw with
+ * zero moments (clone); else two children instead of the row (split): pos + R(q/|q|) (s * n_k), raw scale - ln 1.6, the rest
+ * copied, zero moments; n_k = d_noise[i][k][0..2], or (NULL) standard normals of a counter-based generator keyed by
+ * (seed, i, k).  Output rows in source order at the prefix sums of the emit counts; out_activated written for all of them;
+ * out_stats rows zero; d_src_row[r] (nullable) = source row of output row r.  Synchronises once (the new count).
+ * LCGS_ERR_CAPACITY: *new_num_gaussians = rows needed > capacity, no destination touched.  The scene binding is not changed. */
+LCGS_API lcgs_status lcgs_densify(lcgs_context* ctx, int num_gaussians, int sh_degree, const lcgs_densify_config* cfg,
+                                  const lcgs_densify_stats* stats, const lcgs_params* raw, const lcgs_params* m, const lcgs_params* v,
+                                  const lcgs_params* out_raw, const lcgs_params* out_m, const lcgs_params* out_v,
+                                  const lcgs_params* out_activated, const lcgs_densify_stats* out_stats, int64_t capacity,
+                                  const float* d_noise /* [P][2][3] or NULL */, uint32_t* d_src_row /* [capacity] or NULL */,
+                                  int64_t* new_num_gaussians);
+/* raw opacity = min(raw opacity, logit(max_opacity)), its moments zeroed, activated opacity rewritten; only the opacity
+ * members of the packs are read.  Only enqueues. */
+LCGS_API lcgs_status lcgs_opacity_reset(lcgs_context* ctx, int num_gaussians, float max_opacity /* 3DGS: 0.01 */, const lcgs_params* raw,
+                                        const lcgs_params* m, const lcgs_params* v, const lcgs_params* activated);
+
 /* ---- multi-GPU (no reference counterpart: one device, app/main.cpp:162-163) ------------------------ */
 /* One process per GPU, scene replicated, one view per GPU; RCCL is bound at run time (absent: LCGS_ERR_NO_DEVICE). */
 typedef struct lcgs_comm lcgs_comm;

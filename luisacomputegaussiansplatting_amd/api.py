@@ -135,6 +135,15 @@ class _AdamConfig(C.Structure):
                 ("eps", C.c_float), ("step", C.c_int), ("visible_only", C.c_int)]
 
 
+class _DensifyStats(C.Structure):
+    _fields_ = [("grad_accum", C.c_void_p), ("denom", C.c_void_p), ("max_radii", C.c_void_p)]
+
+
+class _DensifyConfig(C.Structure):
+    _fields_ = [("grad_threshold", C.c_float), ("percent_dense", C.c_float), ("scene_extent", C.c_float),
+                ("min_opacity", C.c_float), ("max_screen_size", C.c_int), ("seed", C.c_uint64)]
+
+
 class _SceneHost(C.Structure):
     _fields_ = [("num_gaussians", C.c_int), ("sh_degree", C.c_int), ("pos", C.POINTER(C.c_float)),
                 ("feature", C.POINTER(C.c_float)), ("opacity", C.POINTER(C.c_float)),
@@ -160,6 +169,7 @@ EXPORTED_SYMBOLS = [
     "lcgs_grads_allreduce", "lcgs_adam_step_sharded", "lcgs_comm_track_touched_rows", "lcgs_comm_get_stats",
     "lcgs_adam_step_sparse", "lcgs_sparse_touched_rows", "lcgs_sparse_message_words", "lcgs_sparse_pack",
     "lcgs_sparse_accumulate", "lcgs_scene_declare_static", "lcgs_owner_project", "lcgs_owner_project_views", "lcgs_owner_counts", "lcgs_owner_render", "lcgs_owner_render_backward", "lcgs_owner_backward",
+    "lcgs_densify_accumulate", "lcgs_densify", "lcgs_opacity_reset",
 ]
 
 
@@ -200,6 +210,11 @@ def load_library():
     lib.lcgs_sparse_message_words.argtypes = [C.c_int64, C.c_int]
     lib.lcgs_comm_shard_rows.argtypes = [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.lcgs_projection_matrix.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float)]
+    pp, ps = C.POINTER(_Params), C.POINTER(_DensifyStats)
+    lib.lcgs_densify_accumulate.argtypes = [C.c_void_p, C.c_int, ps]
+    lib.lcgs_densify.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DensifyConfig), ps, pp, pp, pp, pp, pp, pp, pp, ps,
+                                 C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.lcgs_opacity_reset.argtypes = [C.c_void_p, C.c_int, C.c_float, pp, pp, pp, pp]
     _lib = lib
     return lib
 
@@ -755,6 +770,47 @@ class Renderer:
         packs = [_Params(*[_ptr(d[k]) for k in keys]) for d in (raw, m, v, activated)]
         _check(load_library().lcgs_render_backward_adam(self.ctx._h, _ptr(dL_dimg), C.c_int(P), C.c_int(sh_degree),
                                                         C.byref(cfg), *[C.byref(p) for p in packs]))
+
+
+    # ---- adaptive density control
+    def densify_accumulate(self, stats: dict):
+        """lcgs_densify_accumulate: the last keep_state frame and its backward -> stats["grad_accum"] (float32), ["denom"]
+        (int32 bits of a uint32 count), ["max_radii"] (int32), device tensors of P entries, on-screen rows only."""
+        st = _DensifyStats(_ptr(stats["grad_accum"]), _ptr(stats["denom"]), _ptr(stats["max_radii"]))
+        _check(load_library().lcgs_densify_accumulate(self.ctx._h, C.c_int(int(stats["denom"].shape[0])), C.byref(st)))
+
+    def densify(self, stats: dict, raw: dict, m: dict, v: dict, out_raw: dict, out_m: dict, out_v: dict, out_activated: dict,
+                out_stats: dict, grad_threshold: float = 2e-4, percent_dense: float = 0.01, scene_extent: float = 1.0,
+                min_opacity: float = 0.005, max_screen_size: int = 0, seed: int = 0, noise=None, src_row=None,
+                sh_degree: int = 3, capacity: Optional[int] = None) -> int:
+        """lcgs_densify: clone / split / prune `raw` with its Adam moments into the out_* arrays (out of place, source order kept,
+        new rows beside their parents) -> the new row count.  Dicts as in adam_step; the out_* tensors hold `capacity` rows
+        (default: out_raw["opacity"]'s length).  noise: [P, 2, 3] normals for the split children, None: the built-in sampler
+        keyed by seed.  src_row: optional int32 [capacity], output row -> source row.  Raises LcgsError (status 5, .needed = rows)
+        when the rewrite does not fit; nothing is written then.  Rebind out_activated and render a synchronising frame next."""
+        keys = ("pos", "scale", "rotq", "sh", "opacity")
+        P = int(raw["opacity"].shape[0])
+        cap = int(out_raw["opacity"].shape[0]) if capacity is None else int(capacity)
+        cfg = _DensifyConfig(grad_threshold, percent_dense, scene_extent, min_opacity, int(max_screen_size), int(seed))
+        packs = [_Params(*[_ptr(d[k]) for k in keys]) for d in (raw, m, v, out_raw, out_m, out_v, out_activated)]
+        st = [_DensifyStats(_ptr(d["grad_accum"]), _ptr(d["denom"]), _ptr(d["max_radii"])) for d in (stats, out_stats)]
+        n = C.c_int64(0)
+        status = load_library().lcgs_densify(self.ctx._h, C.c_int(P), C.c_int(sh_degree), C.byref(cfg), C.byref(st[0]),
+                                             *[C.byref(p) for p in packs], C.byref(st[1]), C.c_int64(cap), _ptr(noise),
+                                             _ptr(src_row), C.byref(n))
+        if status != 0:
+            err = LcgsError(status, load_library().lcgs_last_error().decode(errors="replace"))
+            err.needed = int(n.value)
+            raise err
+        return int(n.value)
+
+    def opacity_reset(self, raw: dict, m: dict, v: dict, activated: dict, max_opacity: float = 0.01):
+        """lcgs_opacity_reset: raw opacity = min(raw opacity, logit(max_opacity)), its moments zeroed, activated opacity
+        rewritten.  Only the "opacity" entries of the dicts are needed."""
+        keys = ("pos", "scale", "rotq", "sh", "opacity")
+        P = int(raw["opacity"].shape[0])
+        packs = [_Params(*[_ptr(d.get(k)) for k in keys]) for d in (raw, m, v, activated)]
+        _check(load_library().lcgs_opacity_reset(self.ctx._h, C.c_int(P), C.c_float(max_opacity), *[C.byref(p) for p in packs]))
 
 
 def _adam_config(lr: dict, betas, eps: float, step: int, visible_only: int) -> _AdamConfig:

@@ -210,6 +210,7 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
     if (!compact && !fused && ctx->comm)
         LCGS_TRY(lcgs::comm_mark_touched(ctx->comm, ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), (int64_t)P,
                                          ctx->hint_V, accumulate, st));
+    ctx->g2d_backward_done = true; // the frame's 2-D gradient rows now hold a backward's sums (lcgs_densify_accumulate)
     LCGS_TRY(mark(ctx, "preprocess_backward"));
     LCGS_HIP_CHECK(hipGetLastError());
     if (ctx->profiling) {

@@ -1,0 +1,126 @@
+// abi_densify.cpp -- the C ABI, part 7: adaptive density control (csrc/kernels/densify.hip) -- the statistics of a step, the
+// out-of-place clone / split / prune rewrite of raw parameters and Adam moments, and the opacity reset.
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+
+#include "abi_internal.hpp"
+
+using namespace lcgs;
+using namespace lcgs::abi;
+
+extern "C" {
+
+lcgs_status lcgs_densify_accumulate(lcgs_context* ctx, int num_gaussians, const lcgs_densify_stats* stats)
+{
+    LCGS_REQUIRE(ctx && stats, "NULL argument");
+    LCGS_REQUIRE(stats->grad_accum && stats->denom && stats->max_radii, "NULL device pointer in the statistics");
+    if (!ctx->frame_state_valid() || !ctx->last.has_state) {
+        set_last_error("lcgs_densify_accumulate needs a preceding lcgs_render_forward(..., keep_state = 1) of this scene");
+        return LCGS_ERR_STATE;
+    }
+    if (ctx->owner_recs) { // an ownership-step frame: its rows are the received records', not this context's scene's
+        set_last_error("the last frame was drawn from received records (lcgs_owner_render): no statistics for it");
+        return LCGS_ERR_STATE;
+    }
+    if (!ctx->g2d_backward_done) {
+        set_last_error("lcgs_densify_accumulate needs a backward of the last frame (its 2-D gradient rows are only zeros until then)");
+        return LCGS_ERR_STATE;
+    }
+    LCGS_REQUIRE(num_gaussians == ctx->P, "num_gaussians must be the bound scene's");
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    const int64_t hint = ctx->hint_V > 0 ? std::min<int64_t>(ctx->hint_V, num_gaussians) : num_gaussians;
+    launch_densify_stats(hint, num_gaussians, ctx->last.cp, ctx->last.scale_modifier, ctx->pos, ctx->scale, ctx->rotq,
+                         ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), ctx->grads2d.as<float>(), stats->grad_accum,
+                         stats->denom, stats->max_radii, ctx->stream);
+    LCGS_HIP_CHECK(hipGetLastError());
+    return LCGS_OK;
+}
+
+lcgs_status lcgs_densify(lcgs_context* ctx, int num_gaussians, int sh_degree, const lcgs_densify_config* cfg,
+                         const lcgs_densify_stats* stats, const lcgs_params* raw, const lcgs_params* m, const lcgs_params* v,
+                         const lcgs_params* out_raw, const lcgs_params* out_m, const lcgs_params* out_v,
+                         const lcgs_params* out_activated, const lcgs_densify_stats* out_stats, int64_t capacity,
+                         const float* d_noise, uint32_t* d_src_row, int64_t* new_num_gaussians)
+{
+    LCGS_REQUIRE(ctx && cfg && stats && raw && m && v && out_raw && out_m && out_v && out_activated && out_stats &&
+                     new_num_gaussians,
+                 "NULL argument");
+    LCGS_REQUIRE(num_gaussians >= 0, "num_gaussians is negative");
+    LCGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "sh_degree must be in [0,3]");
+    LCGS_REQUIRE(capacity >= 0, "capacity is negative");
+    *new_num_gaussians = 0;
+    if (num_gaussians == 0) return LCGS_OK;
+    const lcgs_params* packs[7] = { raw, m, v, out_raw, out_m, out_v, out_activated };
+    for (const lcgs_params* p : packs)
+        LCGS_REQUIRE(p->pos && p->scale && p->rotq && p->sh && p->opacity, "NULL device pointer in a parameter pack");
+    for (const lcgs_params* p : packs)
+        LCGS_REQUIRE((reinterpret_cast<uintptr_t>(p->rotq) & 15) == 0, "rotq arrays must be 16-byte aligned");
+    LCGS_REQUIRE(stats->grad_accum && stats->denom && stats->max_radii && out_stats->grad_accum && out_stats->denom &&
+                     out_stats->max_radii,
+                 "NULL device pointer in the statistics");
+    LCGS_REQUIRE(out_raw->pos != raw->pos && out_m->pos != m->pos && out_v->pos != v->pos && out_stats->denom != stats->denom,
+                 "the rewrite is out of place: destinations must not alias sources");
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t   st = ctx->stream;
+    const int64_t P  = num_gaussians;
+    LCGS_TRY(ctx->dn_emit.ensure((size_t)P * 4));
+    LCGS_TRY(ctx->dn_incl.ensure((size_t)P * 4));
+    LCGS_TRY(ctx->dn_action.ensure((size_t)P));
+    LCGS_TRY(ctx->st_scan_temp.ensure(scan_temp_bytes(P)));
+    DensifyRule rule;
+    rule.grad_threshold  = cfg->grad_threshold;
+    rule.dense_extent    = cfg->percent_dense * cfg->scene_extent;
+    rule.huge_extent     = 0.1f * cfg->scene_extent;
+    rule.min_opacity     = cfg->min_opacity;
+    rule.max_screen_size = cfg->max_screen_size;
+    launch_densify_classify(P, rule, raw->scale, raw->opacity, stats->grad_accum, stats->denom, stats->max_radii,
+                            ctx->dn_emit.as<uint32_t>(), ctx->dn_action.as<uint8_t>(), st);
+    launch_inclusive_sum_u32(ctx->dn_emit.as<uint32_t>(), ctx->dn_incl.as<uint32_t>(), P, ctx->st_scan_temp.ptr, st);
+    // the call's one read-back: the new count, known before anything is scattered
+    uint32_t total = 0;
+    LCGS_HIP_CHECK(hipMemcpyAsync(&total, ctx->dn_incl.as<uint32_t>() + (P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    LCGS_HIP_CHECK(hipStreamSynchronize(st));
+    *new_num_gaussians = (int64_t)total;
+    if ((int64_t)total > capacity) {
+        set_last_error("lcgs_densify: the rewrite needs " + std::to_string(total) + " rows, the destination arrays hold " +
+                       std::to_string((long long)capacity));
+        return LCGS_ERR_CAPACITY;
+    }
+    if (total == 0) return LCGS_OK;
+    scene_arrays_written(ctx, out_activated->pos, out_activated->scale, out_activated->rotq); // (destinations a context renders)
+    auto pack = [](const lcgs_params* p) { return AdamArrays{ p->pos, p->scale, p->rotq, p->sh, p->opacity }; };
+    // ln 1.6 to binary32 (children are 1.6 x smaller: raw scale - ln 1.6), rounded once from the double value
+    const float split_drop = (float)log((double)1.6f);
+    launch_densify_scatter(P, (sh_degree + 1) * (sh_degree + 1) * 3, ctx->dn_action.as<uint8_t>(), ctx->dn_incl.as<uint32_t>(),
+                           pack(raw), pack(m), pack(v), pack(out_raw), pack(out_m), pack(out_v), pack(out_activated),
+                           split_drop, d_noise, cfg->seed, d_src_row, st);
+    LCGS_HIP_CHECK(hipMemsetAsync(out_stats->grad_accum, 0, (size_t)total * 4, st));
+    LCGS_HIP_CHECK(hipMemsetAsync(out_stats->denom, 0, (size_t)total * 4, st));
+    LCGS_HIP_CHECK(hipMemsetAsync(out_stats->max_radii, 0, (size_t)total * 4, st));
+    LCGS_HIP_CHECK(hipGetLastError());
+    return LCGS_OK;
+}
+
+lcgs_status lcgs_opacity_reset(lcgs_context* ctx, int num_gaussians, float max_opacity, const lcgs_params* raw,
+                               const lcgs_params* m, const lcgs_params* v, const lcgs_params* activated)
+{
+    LCGS_REQUIRE(ctx && raw && m && v && activated, "NULL argument");
+    LCGS_REQUIRE(num_gaussians >= 0, "num_gaussians is negative");
+    LCGS_REQUIRE(max_opacity > 0.0f && max_opacity < 1.0f, "max_opacity must be in (0,1)");
+    scene_arrays_written(ctx, activated->pos, activated->scale, activated->rotq);
+    if (num_gaussians == 0) return LCGS_OK;
+    LCGS_REQUIRE(raw->opacity && m->opacity && v->opacity && activated->opacity, "NULL opacity pointer in a parameter pack");
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    // logit(max_opacity) to binary32, rounded once from the double value
+    const float ceiling = (float)log((double)max_opacity / (1.0 - (double)max_opacity));
+    launch_opacity_reset(num_gaussians, ceiling, raw->opacity, m->opacity, v->opacity, activated->opacity, ctx->stream);
+    LCGS_HIP_CHECK(hipGetLastError());
+    return LCGS_OK;
+}
+
+} // extern "C"

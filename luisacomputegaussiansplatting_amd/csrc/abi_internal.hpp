@@ -7,6 +7,7 @@
 //   abi_frame.cpp     the fused frame: workspace, enqueue, lcgs_render_forward, camera batches, the sibling context
 //   abi_backward.cpp  lcgs_render_backward and its variants (compact rows, accumulate, fused Adam)
 //   abi_train.cpp     lcgs_adam_step, lcgs_fit_views
+//   abi_densify.cpp   adaptive density control: lcgs_densify_accumulate, lcgs_densify, lcgs_opacity_reset
 #pragma once
 
 #include "common.hpp"

@@ -153,6 +153,10 @@ struct lcgs_context {
     // does not start with a 40 us zero-fill; consumed by the first backward of that frame
     hipEvent_t  ev_g2d_zero = nullptr;
     bool        g2d_zeroed  = false;
+    // a backward has run on the last keep-state frame: until then its 2-D gradient rows are only zeros (lcgs_densify_accumulate)
+    bool        g2d_backward_done = false;
+    // lcgs_densify: emit counts, their inclusive sums, actions (one entry per source row)
+    DeviceBuffer dn_emit, dn_incl, dn_action;
     // lcgs_render_forward_batch: a sibling context (own workspace, own streams) that renders every other view, so
     // that one view's latency-bound sort chain overlaps the other's bandwidth- and VALU-bound kernels
     lcgs_context* twin         = nullptr;

@@ -238,10 +238,8 @@ LCGS_HD void ndc_from_view(const CamParams& cp, const float v[3], float ndc[2])
 
 // R_from_qvec (util/transform.hpp:188-212), q = (x,y,z,w); calc_cov (util/gaussian.hpp:15-28):
 // M = R * diag(s), Sigma = M * M^T.  Column-major: M[c][r] = R[c][r] * s[c].
-LCGS_HD void cov3d_from_scale_rot(const float s[3], float qx, float qy, float qz, float qw, float Sig[3][3] /*[c][r]*/)
+LCGS_HD void rot_from_quat(float x, float y, float z, float w, float R[3][3] /*[c][r]*/)
 {
-    float x = qx, y = qy, z = qz, w = qw;
-    float R[3][3];
     R[0][0] = 1.0f - 2.0f * y * y - 2.0f * z * z;
     R[0][1] = 2.0f * x * y + 2.0f * z * w;
     R[0][2] = 2.0f * x * z - 2.0f * y * w;
@@ -251,6 +249,12 @@ LCGS_HD void cov3d_from_scale_rot(const float s[3], float qx, float qy, float qz
     R[2][0] = 2.0f * x * z + 2.0f * y * w;
     R[2][1] = 2.0f * y * z - 2.0f * x * w;
     R[2][2] = 1.0f - 2.0f * x * x - 2.0f * y * y;
+}
+
+LCGS_HD void cov3d_from_scale_rot(const float s[3], float qx, float qy, float qz, float qw, float Sig[3][3] /*[c][r]*/)
+{
+    float R[3][3];
+    rot_from_quat(qx, qy, qz, qw, R);
     float M[3][3];
 #pragma unroll
     for (int c = 0; c < 3; ++c)

@@ -208,6 +208,27 @@ void launch_adam_step(int64_t P, int sh_floats, const uint32_t* row_list, const 
                       const AdamArrays& grad, const AdamArrays& raw, const AdamArrays& m, const AdamArrays& v,
                       const AdamArrays& act, const AdamRates& lr, float beta1, float beta2, float eps, int step,
                       hipStream_t stream, bool grad_compact = false);
+// ---- densify.hip : adaptive density control (statistics of a step, the clone / split / prune rewrite, opacity reset) ----
+// one thread per on-screen row of the last keep-state frame (count in d_counts[0], launch sized for v_hint rows): the
+// screen-space positional gradient (grads2d rows, pixel units -> NDC), the visit count and the largest reference radius
+void launch_densify_stats(int64_t v_hint, int64_t P, const CamParams& cp, float scale_modifier, const float* pos,
+                          const float* scale, const float* rotq, const uint32_t* vis_index, const uint32_t* d_counts,
+                          const float* grads2d, float* grad_accum, uint32_t* denom, int32_t* max_radii, hipStream_t stream);
+struct DensifyRule {
+    float   grad_threshold, dense_extent /* percent_dense x scene_extent */, huge_extent /* 0.1 x scene_extent */, min_opacity;
+    int32_t max_screen_size;
+};
+// emit[i] = output rows of source row i (0, 1, 2), action[i] = 0 prune, 1 keep, 2 clone, 3 split
+void launch_densify_classify(int64_t P, const DensifyRule& rule, const float* raw_scale, const float* raw_opacity,
+                             const float* grad_accum, const uint32_t* denom, const int32_t* max_radii, uint32_t* emit,
+                             uint8_t* action, hipStream_t stream);
+// incl = inclusive sums of emit.  o_act.pos / .sh may alias o_raw's.  noise: [P][2][3] or NULL (Philox keyed by seed, row, child)
+void launch_densify_scatter(int64_t P, int sh_floats, const uint8_t* action, const uint32_t* incl, const AdamArrays& raw,
+                            const AdamArrays& m, const AdamArrays& v, const AdamArrays& o_raw, const AdamArrays& o_m,
+                            const AdamArrays& o_v, const AdamArrays& o_act, float split_drop, const float* noise, uint64_t seed,
+                            uint32_t* src_row, hipStream_t stream);
+// raw = min(raw, ceiling), m = v = 0, act = sigmoid(raw)
+void launch_opacity_reset(int64_t P, float ceiling, float* raw, float* m, float* v, float* act, hipStream_t stream);
 // backward.hip: the per-splat half of the backward with the on-screen-only Adam update applied where the gradients are
 // formed (degree 3, frames that kept the colour Jacobian): no gradient rows are written at all
 void launch_preprocess_backward_adam(int64_t v_hint, const CamParams& cp, float scale_modifier, const float* pos,

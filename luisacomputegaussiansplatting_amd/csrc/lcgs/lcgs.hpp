@@ -253,6 +253,27 @@ public:
     {
         check(lcgs_visible_rows(m_dev->ctx(), d_rows, d_count));
     }
+    // adaptive density control (no reference counterpart): statistics of the last keep-state frame + backward; the out-of-place
+    // clone / split / prune rewrite -> the new row count (throws Error(LCGS_ERR_CAPACITY) when it does not fit); opacity reset
+    void densify_accumulate(int num_gaussians, const lcgs_densify_stats& stats)
+    {
+        check(lcgs_densify_accumulate(m_dev->ctx(), num_gaussians, &stats));
+    }
+    int64_t densify(int num_gaussians, const lcgs_densify_config& cfg, const lcgs_densify_stats& stats, const lcgs_params& raw,
+                    const lcgs_params& m, const lcgs_params& v, const lcgs_params& out_raw, const lcgs_params& out_m,
+                    const lcgs_params& out_v, const lcgs_params& out_activated, const lcgs_densify_stats& out_stats,
+                    int64_t capacity, const float* d_noise = nullptr, uint32_t* d_src_row = nullptr, int sh_degree = 3)
+    {
+        int64_t n = 0;
+        check(lcgs_densify(m_dev->ctx(), num_gaussians, sh_degree, &cfg, &stats, &raw, &m, &v, &out_raw, &out_m, &out_v,
+                           &out_activated, &out_stats, capacity, d_noise, d_src_row, &n));
+        return n;
+    }
+    void opacity_reset(int num_gaussians, const lcgs_params& raw, const lcgs_params& m, const lcgs_params& v,
+                       const lcgs_params& activated, float max_opacity = 0.01f)
+    {
+        check(lcgs_opacity_reset(m_dev->ctx(), num_gaussians, max_opacity, &raw, &m, &v, &activated));
+    }
     // Morton order at ingest: the context renders from its own re-ordered copy; d_perm[r] = old index of new splat r
     void reorder_spatial(uint32_t* d_perm = nullptr) { check(lcgs_scene_reorder_spatial(m_dev->ctx(), d_perm)); }
 
