@@ -116,6 +116,8 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
         return LCGS_ERR_STATE;
     }
     LCGS_REQUIRE((reinterpret_cast<uintptr_t>(grads->d_dL_drotq) & 15) == 0, "dL_drotq must be 16-byte aligned");
+    // (the render-backward walks per-tile lists, and lcgs_render_forward never puts a frame that keeps state on per-block ones)
+    LCGS_REQUIRE(ctx->last.cp.list_shift == 0u, "the kept frame lists its pairs per block: no backward walks those lists");
     hipStream_t  st   = ctx->stream;
     const size_t P    = (size_t)ctx->P;
     const size_t feat = (size_t)(ctx->sh_deg + 1) * (ctx->sh_deg + 1) * 3;
@@ -129,10 +131,9 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
     // share of the five arrays with fire-and-forget stores before they turn to their tile -- instead of 0.33 ms of memset
     // kernels on the auxiliary stream, a fork and a join: 1.741 -> 1.724 ms per step (most of what the fill costs the
     // VALU-bound kernel is the memory system's either way).
-    // (LCGS_BWD_FILL=aux keeps the memsets: the A/B hook; per-stage profiling keeps them too, in order, as "zero_grads".)
-    static const bool fill_on_aux = [] { const char* e = getenv("LCGS_BWD_FILL"); return e && e[0] == 'a'; }();
+    // (Per-stage profiling keeps the memsets, in order, as "zero_grads"; so do arrays too long for the kernel's 32-bit lengths.)
     const bool  dense_fill = !compact && !accumulate;
-    const bool  fill_in_kernel = dense_fill && !ctx->profiling && !fill_on_aux && P * feat < ((size_t)1 << 32); // (u32 lengths)
+    const bool  fill_in_kernel = dense_fill && !ctx->profiling && P * feat < ((size_t)1 << 32); // (u32 lengths)
     const bool  overlap = !ctx->profiling && dense_fill && !fill_in_kernel;
     hipStream_t zs      = overlap ? ctx->aux_stream : st;
     DenseFill   fill;
@@ -176,13 +177,7 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
     const int      k_bwd = ctx->persist_bwd_forced >= 0 ? ctx->persist_bwd_forced
                                                         : (ctx->frames_in_flight ? ctx->persist_bwd_in_flight : 0);
     const uint32_t bwd_wgs = (!ctx->profiling && k_bwd > 0) ? (uint32_t)(k_bwd * std::max(ctx->num_cus, 1)) : 0u;
-    // (a frame on per-block lists left every tile a list of its own for this walk: render.hip COMPACT)
-    const bool      own_lists = ctx->last.cp.list_shift != 0u;
-    const uint32_t* bw_ranges = own_lists ? ctx->keep_ranges.as<uint32_t>() : ctx->ranges;
-    const uint32_t* bw_list   = own_lists ? ctx->keep_list.as<uint32_t>() : ctx->pairv[ctx->last.list_buf].as<uint32_t>();
-    CamParams       bw_cp     = ctx->last.cp;
-    bw_cp.list_shift          = 0u;
-    launch_render_backward(bw_cp, ctx->last.bg, bw_ranges, bw_list,
+    launch_render_backward(ctx->last.cp, ctx->last.bg, ctx->ranges, ctx->pairv[ctx->last.list_buf].as<uint32_t>(),
                            ctx->recs.as<SplatRecord>(), ctx->final_T.as<float>(), ctx->n_contrib.as<uint32_t>(),
                            d_dL_dimg, ctx->grads2d.as<float>(), ctx->last_tile_order, st,
                            render_forward_writes_strip_masks() && ctx->bwd_use_masks ? ctx->strip_masks.as<uint8_t>() : nullptr,

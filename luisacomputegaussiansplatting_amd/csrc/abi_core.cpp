@@ -202,39 +202,20 @@ lcgs_status lcgs_create(int device_id, void* stream, lcgs_context** out_ctx)
     if (const char* e = getenv("LCGS_STAGE_SIDE_COPY")) ctx->stage_side_copy = e[0] != '0'; // A/B hook
     if (const char* e = getenv("LCGS_STAGE_MAILBOX")) ctx->stage_mailbox = e[0] != '0';      // A/B hook
     if (const char* e = getenv("LCGS_COARSE_LISTS")) ctx->coarse_mode = e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2); // A/B / test hook
-    if (const char* e = getenv("LCGS_COARSE_KEEP")) ctx->coarse_keep = e[0] != '0';                               // A/B / test hook
     if (const char* e = getenv("LCGS_BWD_USE_MASKS")) ctx->bwd_use_masks = e[0] != '0';      // test hook: the launcher's mask-less form
     if (const char* e = getenv("LCGS_STAGE_SORT")) ctx->stage_sort = e[0] == 'l' ? 1 : (e[0] == 's' ? 2 : 0); // test hook
     // The auxiliary stream has the LOWEST dispatch priority: its bandwidth-bound workgroups fill the gaps the main
     // stream's short, latency-bound kernels leave instead of competing with them.
     hipError_t se;
     {
-        int         lo = 0, hi = 0;
-        const char* m  = getenv("LCGS_AUX_PRIORITY"); // tuning hook: "low" (default), "same"
+        int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi); // lo = numerically greatest = lowest priority
-        const int prio = (m && m[0] == 's') ? 0 : lo;
-        se             = hipStreamCreateWithPriority(&ctx->aux_stream, hipStreamNonBlocking, prio);
+        se = hipStreamCreateWithPriority(&ctx->aux_stream, hipStreamNonBlocking, lo);
         if (se != hipSuccess) se = hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking);
     }
     for (hipEvent_t* ev : { &ctx->ev_fork, &ctx->ev_join, &ctx->ev_ranges, &ctx->ev_aux_done, &ctx->ev_render, &ctx->ev_counts,
                             &ctx->ev_g2d_zero })
         if (se == hipSuccess) se = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-    if (const char* e = getenv("LCGS_CHAIN_CUS")) {
-        // tuning hook: the sort chain on a stream masked to K CUs, record builder + renderer on the complement.  The K
-        // units are spread evenly over the 8 XCDs whichever way the driver numbers the mask bits (XCD-interleaved or
-        // XCD-major): XCD x gets the bits 32 x + ((x + j) % 8 + 8 (j % 4)), j < K / 8.
-        const int K = atoi(e), n = ctx->num_cus;
-        if (K >= 8 && K <= 64 && K % 8 == 0 && n == 256) {
-            uint32_t chain[8] = {}, rest[8];
-            for (int x = 0; x < 8; ++x)
-                for (int j = 0; j < K / 8; ++j) chain[x] |= 1u << ((x + j) % 8 + 8 * (j % 4));
-            for (int x = 0; x < 8; ++x) rest[x] = ~chain[x];
-            if (se == hipSuccess) se = hipExtStreamCreateWithCUMask(&ctx->chain_stream, 8, chain);
-            if (se == hipSuccess) se = hipExtStreamCreateWithCUMask(&ctx->render_stream, 8, rest);
-            for (hipEvent_t* ev : { &ctx->ev_begin, &ctx->ev_chain })
-                if (se == hipSuccess) se = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-        }
-    }
     if (se != hipSuccess) {
         lcgs_status s = hip_fail(se, "aux stream / events", __FILE__, __LINE__);
         (void)lcgs_destroy(ctx); // releases whichever of the stream / events were created
@@ -269,18 +250,11 @@ lcgs_status lcgs_destroy(lcgs_context* ctx)
         if (ev) (void)hipEventDestroy(ev);
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
-    for (hipStream_t s : { ctx->chain_stream, ctx->render_stream })
-        if (s) {
-            (void)hipStreamSynchronize(s);
-            (void)hipStreamDestroy(s);
-        }
-    for (hipEvent_t ev : { ctx->ev_begin, ctx->ev_chain })
-        if (ev) (void)hipEventDestroy(ev);
     DeviceBuffer* bufs[] = { &ctx->recs, &ctx->sortk[0], &ctx->sortk[1], &ctx->sortv[0], &ctx->sortv[1], &ctx->vis_index,
                              &ctx->rects, &ctx->rects_sorted, &ctx->cull_slab, &ctx->chunk_info, &ctx->chunk_base, &ctx->pairk[0], &ctx->pairk[1], &ctx->pairv[0],
                              &ctx->pairv[1], &ctx->zero_ws[0], &ctx->zero_ws[1], &ctx->zero_ws[2], &ctx->counts, &ctx->sort_ws,
                              &ctx->expand_ws, &ctx->final_T, &ctx->n_contrib, &ctx->list_idx, &ctx->grads2d, &ctx->tile_order[0], &ctx->tile_order[1], &ctx->st_keys_tmp,
-                             &ctx->st_vals_tmp, &ctx->st_sort_temp, &ctx->st_scan_temp, &ctx->st_scalar, &ctx->sh_half, &ctx->strip_masks, &ctx->keep_list, &ctx->keep_ranges, &ctx->shjac, &ctx->tie_ws, &ctx->fused_grads, &ctx->bwd_counter, &ctx->st_flags, &ctx->st_keys_exp, &ctx->st_vals_exp,
+                             &ctx->st_vals_tmp, &ctx->st_sort_temp, &ctx->st_scan_temp, &ctx->st_scalar, &ctx->sh_half, &ctx->strip_masks, &ctx->shjac, &ctx->tie_ws, &ctx->fused_grads, &ctx->bwd_counter, &ctx->st_flags, &ctx->st_keys_exp, &ctx->st_vals_exp,
                              &ctx->st_u32[0], &ctx->st_u32[1], &ctx->st_u32[2], &ctx->st_u32[3], &ctx->st_u32[4], &ctx->st_u32[5], &ctx->st_u32[6], &ctx->st_u32[7],
                              &ctx->cull_bound_buf, &ctx->verify_ws, &ctx->st_win, &ctx->st_win2, &ctx->st_offs, &ctx->dn_emit, &ctx->dn_incl, &ctx->dn_action };
     for (DeviceBuffer* b : bufs) b->release();

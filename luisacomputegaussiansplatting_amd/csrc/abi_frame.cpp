@@ -76,13 +76,7 @@ lcgs_status ensure_fused_workspace(lcgs_context* ctx, const CamParams& cp, bool 
     if (keep_state) {
         LCGS_TRY(ctx->final_T.ensure((size_t)cp.width * cp.height * 4));
         LCGS_TRY(ctx->n_contrib.ensure((size_t)cp.width * cp.height * 4));
-        // (per-block lists: every tile owns a segment that could hold its whole block's list -- 4 x the pairs, render.hip COMPACT)
-        const size_t list_slots = (size_t)ctx->pair_capacity * (cp.list_shift ? 4u : 1u);
-        LCGS_TRY(ctx->strip_masks.ensure(list_slots));
-        if (cp.list_shift) {
-            LCGS_TRY(ctx->keep_list.ensure(list_slots * 4));
-            LCGS_TRY(ctx->keep_ranges.ensure(G * 8));
-        }
+        LCGS_TRY(ctx->strip_masks.ensure((size_t)ctx->pair_capacity));
         LCGS_TRY(ctx->grads2d.ensure(grads2d_bytes((int64_t)P)));
         LCGS_TRY(ctx->shjac.ensure(P * 48));
         if (!ctx->bwd_counter.ptr) { // (allocated once; starts at zero whatever runs first)
@@ -106,7 +100,7 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
                             float* d_img, int32_t* d_radii, bool keep_state, const FrameParams* d_fp,
                             bool in_capture = false)
 {
-    const hipStream_t vis  = ctx->stream; // the stream whose order the caller sees
+    const hipStream_t st = ctx->stream; // the stream whose order the caller sees
     uint32_t*    d_counts = ctx->counts.as<uint32_t>();
     const int    P        = ctx->P;
     SplatRecord* recs     = ctx->recs.as<SplatRecord>();
@@ -118,15 +112,6 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
     // attributable; otherwise independent work moves to the auxiliary stream (see below).
     const bool overlap  = !ctx->profiling;
     const bool deferred = overlap && !in_capture;
-    // CU-partitioned streams (tuning hook): the sort chain on `st` = the chain stream, record builder + renderer on the
-    // render stream; the caller's stream only orders the frame (waits for what came before, is waited on by the end)
-    const bool  part = deferred && ctx->chain_stream != nullptr;
-    hipStream_t st   = part ? ctx->chain_stream : vis;
-    hipStream_t rst  = part ? ctx->render_stream : vis;
-    if (part) {
-        LCGS_HIP_CHECK(hipEventRecord(ctx->ev_begin, vis));
-        LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_begin, 0));
-    }
     // Zeroed per frame: the tile ranges (the reference zero-fills ranges too,
     // gs_tile_splatter/impl.cpp:147).  Normally the auxiliary stream cleared this frame's copy during the last frame.
     const int zb = deferred ? ctx->zero_cur : 0;
@@ -175,7 +160,7 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
     LCGS_TRY(mark(ctx, "depth_sort"));
     // Record building (SH fetch + colour: bandwidth-bound) is independent of the rest of the sort chain (latency-bound
     // short kernels): fork it onto the auxiliary stream so the two overlap; the renderer joins.
-    hipStream_t rec_stream = part ? rst : (overlap ? ctx->aux_stream : st);
+    hipStream_t rec_stream = overlap ? ctx->aux_stream : st;
     if (overlap) {
         // (in a capture the fork is recorded here, after the whole depth sort; otherwise the first pass's scatter
         //  dispatch carries it)
@@ -187,7 +172,7 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
                          ctx->use_half_sh ? ctx->sh_half.as<uint16_t>() : nullptr,
                          keep_state ? ctx->shjac.as<float4>() : nullptr);
     ctx->last_has_jac = keep_state && build_records_writes_jacobian(ctx->sh_deg, ctx->sh, ctx->use_half_sh);
-    if (overlap && !part) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->aux_stream));
+    if (overlap) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->aux_stream));
     // keep_state frames: the 2-D gradient rows the backward adds to are cleared by the RENDERER as a side job (render.hip):
     // no launch on the auxiliary stream, no cross-stream wait in front of the render-backward
     ctx->g2d_zeroed = false;
@@ -240,27 +225,19 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
         ctx->order_cur         = ob; // written before the next frame's record builder runs: its renderer waits for that
     }
 
-    if (part) { // the records are ahead of the renderer on its own stream; it waits for the chain
-        LCGS_HIP_CHECK(hipEventRecord(ctx->ev_chain, st));
-        LCGS_HIP_CHECK(hipStreamWaitEvent(rst, ctx->ev_chain, 0));
-    } else if (overlap) {
-        LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_join, 0)); // records are ready
-    }
+    if (overlap) LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_join, 0)); // records are ready
     // several frames in flight: a bounded, persistent grid (context.hpp) -- same image, free wave slots on every CU
     const int      k_persist = ctx->persist_forced >= 0 ? ctx->persist_forced : (ctx->frames_in_flight ? ctx->persist_in_flight : 0);
     const uint32_t persist_wgs = (deferred && k_persist > 0) ? (uint32_t)(k_persist * std::max(ctx->num_cus, 1)) : 0u;
     launch_render_forward_rec(cp, bg, ctx->ranges, ctx->pairv[where2].as<uint32_t>(), recs, d_img,
                               keep_state ? ctx->final_T.as<float>() : nullptr,
-                              keep_state ? ctx->n_contrib.as<uint32_t>() : nullptr, d_counts, d_fp, order_now, part ? rst : st,
+                              keep_state ? ctx->n_contrib.as<uint32_t>() : nullptr, d_counts, d_fp, order_now, st,
                               keep_state ? ctx->strip_masks.as<uint8_t>() : nullptr, deferred ? ctx->ev_render : nullptr,
                               ctx->work_counters, persist_wgs, g2d_in_render ? ctx->grads2d.as<float>() : nullptr,
-                              g2d_in_render ? ctx->bwd_counter.as<uint32_t>() : nullptr,
-                              keep_state && cp.list_shift ? ctx->keep_list.as<uint32_t>() : nullptr,
-                              keep_state && cp.list_shift ? ctx->keep_ranges.as<uint32_t>() : nullptr);
+                              g2d_in_render ? ctx->bwd_counter.as<uint32_t>() : nullptr);
     ctx->g2d_zeroed = g2d_in_render; // (consumed by the first backward of this frame; same stream: no event)
     ctx->last_tile_order = order_now;
     LCGS_TRY(mark(ctx, "render"));
-    if (part) LCGS_HIP_CHECK(hipStreamWaitEvent(vis, ctx->ev_render, 0)); // the caller's stream sees the finished frame
 
     if (deferred) {
         // the counter read-back leaves through the auxiliary stream: the next frame does not queue behind it
@@ -298,11 +275,8 @@ lcgs_status lcgs_render_forward(lcgs_context* ctx, const lcgs_camera* camera, co
     LCGS_REQUIRE(ctx->pos != nullptr, "no scene bound (call lcgs_scene_bind / lcgs_scene_upload first)");
     CamParams cp      = make_cam_params(*camera);
     cp.lod_min_radius = ctx->lod_min_radius;
-    // (frames that keep backward state stay per tile: letting them follow -- their renderer then writes per-tile lists for the
-    // backward while it stages, render.hip COMPACT -- was built in round 6 and lost 1.1 %: REJECTED.md; LCGS_COARSE_KEEP=1 is
-    // the A/B hook; the segments need 4 x the pair capacity in 32-bit positions)
-    cp.list_shift     = ((!keep_state || (ctx->coarse_keep && ctx->pair_capacity < (1u << 30))) &&
-                     (ctx->coarse_mode == 1 || (ctx->coarse_mode == 2 && ctx->coarse_on))) ? 1u : 0u;
+    // (frames that keep backward state stay per tile: letting them follow was built in round 6 and lost 1.1 % -- REJECTED.md)
+    cp.list_shift     = (!keep_state && (ctx->coarse_mode == 1 || (ctx->coarse_mode == 2 && ctx->coarse_on))) ? 1u : 0u;
     ctx->owner_recs   = nullptr; // (an ordinary frame: its backward is lcgs_render_backward again)
     ctx->g2d_backward_done = false; // (a new frame: nothing for lcgs_densify_accumulate to read until its backward ran)
     uint32_t        earlier_truncated = 0; // asynchronous frames before this one that overflowed the pair workspace
@@ -435,26 +409,17 @@ lcgs_status lcgs_render_forward_batch(lcgs_context* ctx, int num_views, const lc
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     ctx->note_foreign_writes();
     const bool two = num_views > 1 && !ctx->profiling && !ctx->use_graph && ctx->P > 0;
-    // frames in flight: 2 (measured best through round 3); LCGS_BATCH_IN_FLIGHT = 3 / 4 is a tuning hook (a chain of siblings)
-    static const int want = [] {
-        const char* e = getenv("LCGS_BATCH_IN_FLIGHT");
-        return e ? std::min(std::max(atoi(e), 2), 4) : 2;
-    }();
-    lcgs_context* ring[4] = { ctx, nullptr, nullptr, nullptr };
-    int           n_ring  = 1;
-    if (two)
-        for (; n_ring < std::min(want, num_views); ++n_ring) {
-            LCGS_TRY(prepare_twin(ring[n_ring - 1]));
-            ring[n_ring] = ring[n_ring - 1]->twin;
-        }
+    // (two frames in flight: measured best through round 3 -- three and four were slower, REJECTED.md)
+    if (two) LCGS_TRY(prepare_twin(ctx));
     InFlight in_flight(ctx, two);
     for (int i = 0; i < num_views; ++i) {
         LCGS_REQUIRE(d_imgs[i] != nullptr, "NULL image pointer in the batch");
-        LCGS_TRY(lcgs_render_forward(ring[i % n_ring], &cameras[i], bg_color, scale_modifier, d_imgs[i], nullptr, 0, nullptr));
+        LCGS_TRY(lcgs_render_forward((two && (i & 1)) ? ctx->twin : ctx, &cameras[i], bg_color, scale_modifier, d_imgs[i], nullptr, 0,
+                                     nullptr));
     }
-    for (int k = 0; k + 1 < n_ring; ++k) { // the caller's stream waits for every sibling's frames
-        LCGS_HIP_CHECK(hipEventRecord(ring[k]->ev_batch_join, ring[k]->twin_stream));
-        LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ring[k]->ev_batch_join, 0));
+    if (two) { // the caller's stream waits for the sibling's frames
+        LCGS_HIP_CHECK(hipEventRecord(ctx->ev_batch_join, ctx->twin_stream));
+        LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_batch_join, 0));
     }
     return LCGS_OK;
 }

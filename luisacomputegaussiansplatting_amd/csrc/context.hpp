@@ -92,8 +92,7 @@ struct lcgs_context {
     // workspace of the fused frame
     DeviceBuffer cull_slab, chunk_info, chunk_base; // the cull pass's per-chunk output (fused_forward.hip k_cull_compact)
     DeviceBuffer recs, sortk[2], sortv[2], vis_index, rects, rects_sorted, pairk[2], pairv[2], zero_ws[3], counts, sort_ws,
-        expand_ws, final_T, n_contrib, list_idx, grads2d, strip_masks, shjac, tie_ws, fused_grads, bwd_counter, keep_list,
-        keep_ranges; // (the last two: per-tile lists a keep-state frame on per-block lists writes for its backward)
+        expand_ws, final_T, n_contrib, list_idx, grads2d, strip_masks, shjac, tie_ws, fused_grads, bwd_counter;
     bool         last_has_jac = false; // the last keep_state frame stored the colour Jacobian (degree 3)
     // zero_ws holds what a frame needs zeroed: the tile ranges.  Three
     // copies rotate: while frame N runs, the auxiliary stream clears the copy of frame N + 2.  Two frames ahead, not
@@ -139,10 +138,6 @@ struct lcgs_context {
     int       persist_bwd_in_flight = 0, persist_bwd_forced = -1; // the same for the render-backward (LCGS_BWD_WGS_PER_CU)
     bool      frames_in_flight = false; // set around the calls of a batch
     uint32_t* work_counters = nullptr; // [0] forward renderer, [1] render-backward: inside the frame's zeroed block
-    // CU-partitioned streams (tuning hook LCGS_CHAIN_CUS=K, measured in round 4): the sort chain on a stream masked to K
-    // CUs, record builder + renderer on the complement
-    hipStream_t chain_stream = nullptr, render_stream = nullptr;
-    hipEvent_t  ev_begin = nullptr, ev_chain = nullptr;
     bool use_graph = false; // opt-in (LCGS_GRAPH=1): measured no gain on MI355X, the short kernels are GPU-latency-bound
     // second stream: work that is independent of the sort chain (record building; gradient zero-fill) overlaps it
     hipStream_t aux_stream = nullptr;
@@ -205,14 +200,13 @@ struct lcgs_context {
     int stage_mode = 0; // LCGS_STAGES_EXACT
     uint32_t stage_serial = 0;   // lcgs_tile_splat_forward's per-frame mark of the "unwritten pair slots" word
     bool stage_side_copy = true; // the unsorted pair buffers' copy beside the depth sort (A/B hook LCGS_STAGE_SIDE_COPY=0)
-    // Frames that keep no backward state may list their pairs per block of 2 x 2 tiles (CamParams::list_shift).  It pays from
+    // Frames that keep no backward state may list their pairs per block of 2 x 2 tiles (CamParams::list_shift; frames that
+    // keep it never do: that was built in round 6 and lost 1.1 % on forward+backward, REJECTED.md).  It pays from
     // ~3 M per-tile pairs up (-2 % at 0.2-0.9 M, 0 at 2.5 M, +2.5 % at 4-8 M, +6 % at 10 M, +15 % at 17 M: profiles/
     // r05_coarse_lists_ab.txt), so the default decides per context from the last synchronised frame's pair count, with hysteresis;
     // LCGS_COARSE_LISTS=0 / 1 force it off / on (A/B and test hook).
     int  coarse_mode     = 2;     // 0 never, 1 always, 2 by the pair count
     bool coarse_on       = false; // (mode 2) the current decision
-    bool coarse_keep     = false; // frames that keep backward state follow the decision too (render.hip COMPACT): built and
-                                  // measured in round 6, -1.1 % on forward+backward (REJECTED.md) -- off; LCGS_COARSE_KEEP=1: A/B hook
     double coarse_yield  = 0.6;   // pruned per-tile pairs / reference num_rendered, from this context's last per-tile frame
     bool bwd_use_masks   = true; // the render-backward walks the forward's kept strip bits (test hook LCGS_BWD_USE_MASKS=0: it repeats the strip tests)
     bool stage_mailbox   = true; // the splatter's scalars posted to pinned memory and polled (A/B hook LCGS_STAGE_MAILBOX=0: copy + sync)

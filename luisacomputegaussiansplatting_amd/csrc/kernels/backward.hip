@@ -128,16 +128,6 @@ constexpr uint32_t kSlab       = kRows * 16u;         // bytes per slab of s_row
 constexpr uint32_t kListStride = 264u;                // 256 entries + 3 of padding, a multiple of four (8-byte rows)
 constexpr int kG2D = 12; // floats per splat in the 2-D gradient buffer: mean(2) conic(3) opacity(1) rgb(3) pad(3)
 
-#ifdef LCGS_BWD_STATS // (measuring builds only, tools/gpu/bwd_stats.py: what the render-backward's waves actually walk)
-// [0] (entry, strip) pairs walked  [1] ... that pass the wave-level candidate test  [2] lanes that blend, summed
-// [3] strips with at least one walked entry  [4] staging rounds  [5] tiles  [6] list entries staged  [7] entries fetched
-// [8 + b] strips whose walked count n satisfies 2^(b-1) < n <= 2^b (b = 0: n <= 1 incl. 0 ... b = 15)
-__device__ unsigned long long g_bwd_stats[32];
-#define LCGS_STAT(i, n) (st_[(i)] += (n))
-#else
-#define LCGS_STAT(i, n)
-#endif
-
 // (six waves per SIMD: 80 VGPRs with 8 spilled registers per lane instead of 92 and five waves -- render-backward 0.71 ->
 //  0.67 ms, +1.6 % on the whole forward+backward step in same-box A/B runs; seven waves spill 19 and lose it again)
 // KNOWN: the forward kept every entry's strip bits (it always does when it keeps backward state; the other instantiation
@@ -146,9 +136,6 @@ __device__ unsigned long long g_bwd_stats[32];
 // forward is in flight (lcgs_fit_views) the cap leaves wave slots, registers and LDS free on every CU for its sort chain.
 #ifndef LCGS_BWD_WAVES
 #define LCGS_BWD_WAVES 6
-#endif
-#ifndef LCGS_BWD_KO // knock-out builds (tools/gpu/bwd_knockout.sh): 1 no reduction, 2 no evaluation, 3 no flush -- wrong results, timing only
-#define LCGS_BWD_KO 0
 #endif
 // fill: the dense per-splat gradient rows' zero-fill as a side job (launch.hpp DenseFill): slot s clears its share of the five
 // arrays' 16-byte-aligned interiors with fire-and-forget stores before it turns to its tile -- 1.45 GB through a memory
@@ -189,10 +176,6 @@ __global__ void __launch_bounds__(256, LCGS_BWD_WAVES) k_render_backward(CamPara
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t slots = tile_order ? cp.grid_x * cp.grid_y : render_grid_size(cp.grid_x, cp.grid_y);
     uint32_t       slot  = blockIdx.x;
-#ifdef LCGS_BWD_STATS
-    unsigned long long st_[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    uint32_t           sub_[13];
-#endif
   for (;;) { // (one pass unless PERSIST)
     if (PERSIST) {
         __syncthreads(); // the previous tile's last flush has read s_flush / s_grad; nobody still reads s_slot
@@ -231,9 +214,6 @@ __global__ void __launch_bounds__(256, LCGS_BWD_WAVES) k_render_backward(CamPara
         if (PERSIST) continue;
         return;
     }
-#ifdef LCGS_BWD_STATS
-    for (int i = 0; i < 13; ++i) sub_[i] = 0;
-#endif
     uint32_t tx, ty;
     if (tile_order) { // longest-list-first schedule of the forward (scheduling hint only)
         const uint32_t t = tile_order[slot];
@@ -315,9 +295,6 @@ __global__ void __launch_bounds__(256, LCGS_BWD_WAVES) k_render_backward(CamPara
             }
         }
         __syncthreads(); // previous round fully flushed
-        LCGS_STAT(4, wave == 0u ? 1u : 0u);
-        LCGS_STAT(6, (unsigned)__popcll(__ballot(have)));
-        LCGS_STAT(7, (unsigned)__popcll(__ballot(have && kmask != 0u)));
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const unsigned long long m = __ballot((kmask >> k) & 1u);
@@ -374,12 +351,6 @@ __global__ void __launch_bounds__(256, LCGS_BWD_WAVES) k_render_backward(CamPara
             //  opacity joins the other entry-uniform factors at the flush)
             auto evaluate = [&](const uint32_t idx, float v[6], uint32_t& row) {
                 const uint32_t pos = lo + idx; // 0-based list position (the null entry: >= hi, never below `last`)
-                LCGS_STAT(0, idx < 256u ? 1u : 0u);
-#if LCGS_BWD_KO == 2 // (measuring builds only: no evaluation -- the walk and the reduction alone)
-                for (int g = 0; g < 6; ++g) v[g] = pxf + (float)pos;
-                row = grad_base + idx * 4u;
-                return;
-#endif
                 uint32_t roff = idx * 16u; // (byte offset of the entry's row in every slab; pinned: one scalar-to-vector move)
                 asm("" : "+v"(roff));
                 const char*    rows = reinterpret_cast<const char*>(&s_rows[0][0]) + roff;
@@ -394,7 +365,6 @@ __global__ void __launch_bounds__(256, LCGS_BWD_WAVES) k_render_backward(CamPara
                 const bool  cand  = c_pos & c_neg & c_flr;
                 // (three ballots of plain compares are the compares' own lane masks; a ballot of the conjunction costs a
                 //  select and another compare -- two vector instructions per walked entry)
-                LCGS_STAT(1, 1u);
                 // exp(power): the hardware's v_exp_f32 (1 ulp; two instructions) since round 5, not the forward's DEFINED
                 // function (ten).  The forward needs that one for bit-identical images; here the tolerance is 1e-3 and what
                 // the two differ by -- ~1e-7 relative in alpha, an entry within that of alpha = 1/255 blended on one side
@@ -413,20 +383,6 @@ __global__ void __launch_bounds__(256, LCGS_BWD_WAVES) k_render_backward(CamPara
                 const float oG    = eb.y * G;
                 const float alpha = __builtin_fminf(0.99f, oG);
                 const bool  valid = cand & !(alpha < 1.0f / 255.0f);
-                LCGS_STAT(2, (unsigned)__popcll(__builtin_amdgcn_ballot_w64(valid)));
-#ifdef LCGS_BWD_STATS
-                {   // which sub-blocks of the wave's unit does this entry blend into?  (Lane groups as named for the 16x4 strip of
-                    // rounds 1-5a, lane = 16 * row + column; on the 8x8 quadrant the same lane groups are other pixel blocks.)
-                    const unsigned long long vb = __builtin_amdgcn_ballot_w64(valid);
-                    sub_[0] += (vb & 0x00FF00FF00FF00FFull) != 0, sub_[1] += (vb & 0xFF00FF00FF00FF00ull) != 0; // 8x4 halves
-                    sub_[2] += (vb & 0x00000000FFFFFFFFull) != 0, sub_[3] += (vb & 0xFFFFFFFF00000000ull) != 0; // 16x2 halves
-                    for (int q = 0; q < 4; ++q) {
-                        sub_[4 + q] += (vb & (0x000F000F000F000Full << (4 * q))) != 0; // 4x4 blocks
-                        sub_[8 + q] += (vb & (0xFFFFull << (16 * q))) != 0;            // 16x1 rows
-                    }
-                    sub_[12] += vb != 0;
-                }
-#endif
                 // A lane that does not blend this entry carries alpha 0 through the recurrences: the product keeps its
                 // value, Bd + 0 * d leaves the colour behind alone, all terms come out 0.
                 // (No second wave-level skip: the staging floor already implies alpha >= 1/255 somewhere.)
@@ -460,9 +416,6 @@ __global__ void __launch_bounds__(256, LCGS_BWD_WAVES) k_render_backward(CamPara
             uint32_t rows = grad_base;
             // rows 0 .. 3 of the wave hold entries A, C, B, D of a group = list slots 0, 2, 1, 3 (bytes into the group's four u16)
             const uint32_t my_slot = 2u * ((((lane >> 4) & 1u) << 1) | (lane >> 5));
-#if LCGS_BWD_KO == 1 // (measuring builds only: no reduction -- the walk and the evaluation alone)
-            float sink = 0.0f;
-#endif
             for (uint32_t i = 0u; i < n_walk; i += 4u) {
                 const uint2    four = *reinterpret_cast<const uint2*>(&s_list[wave][i]);
                 const uint32_t p0   = (uint32_t)__builtin_amdgcn_readfirstlane((int)four.x);
@@ -476,26 +429,14 @@ __global__ void __launch_bounds__(256, LCGS_BWD_WAVES) k_render_backward(CamPara
                 asm("v_writelane_b32 %0, %1, 15" : "+v"(rows) : "s"(row));
                 evaluate(p0 >> 16, B, row);
                 asm("v_writelane_b32 %0, %1, 47" : "+v"(rows) : "s"(row));
-#if LCGS_BWD_KO == 1
-                for (int g = 0; g < 6; ++g) sink += A[g] + B[g];
-#else
                 swap32_add<6>(A, B, pair);
-#endif
                 evaluate(p1 & 0xFFFFu, A, row);
                 asm("v_writelane_b32 %0, %1, 31" : "+v"(rows) : "s"(row));
                 evaluate(p1 >> 16, B, row);
                 asm("v_writelane_b32 %0, %1, 63" : "+v"(rows) : "s"(row));
-#if LCGS_BWD_KO == 1
-                for (int g = 0; g < 6; ++g) sink += A[g] + B[g];
-                sink += __builtin_bit_cast(float, rows) + dx_row;
-#else
                 swap32_add<6>(A, B, quad);
                 reduce_quad_and_add(pair, quad, dx_row, rows, is_row_end);
-#endif
             }
-#if LCGS_BWD_KO == 1
-            if (sink == 12345.678f) s_grad[0][tid] = sink;
-#endif
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the raw LDS adds above have landed
         __syncthreads();
@@ -503,9 +444,6 @@ __global__ void __launch_bounds__(256, LCGS_BWD_WAVES) k_render_backward(CamPara
         // contiguous bytes (MI355X_MICROARCH "Global float atomics": 64 lanes in 64 different rows are ~17x
         // slower), so consecutive lanes own one entry's gradient row instead of one lane per entry: 16 lanes per
         // entry (9 of them active; shifts and masks instead of a division by 12 in a loop that runs every round).
-#if LCGS_BWD_KO == 3 // (measuring builds only: no flush)
-        if (lo == 0xFFFFFFFFu)
-#endif
         for (uint32_t cidx = tid; cidx < n_flush * 16u; cidx += 256u) {
             const uint32_t g   = cidx & 15u;
             const uint2    fe  = s_flush[cidx >> 4];
@@ -530,40 +468,8 @@ __global__ void __launch_bounds__(256, LCGS_BWD_WAVES) k_render_backward(CamPara
         }
         hi = lo;
     }
-#ifdef LCGS_BWD_STATS
-    if (lane == 0u) {
-        const unsigned long long n = st_[0] - st_[3]; // this tile's walked count for my strip (st_[3] = walked before this tile)
-        uint32_t b = 0;
-        while (b < 15u && (1ull << b) < n) ++b;
-        atomicAdd(&g_bwd_stats[8 + b], 1ull);
-        atomicAdd(&g_bwd_stats[3], n ? 1ull : 0ull);
-        if (wave == 0u) atomicAdd(&g_bwd_stats[5], 1ull);
-        // [24..27] sum over strips of the LONGEST sub-block stream (8x4 halves, 16x2 halves, 4x4 blocks, 16x1 rows);
-        // [28] entries that blend anywhere; [29..31] sums of the sub-block streams (8x4, 4x4, 16x1)
-        auto mx = [](uint32_t a, uint32_t b) { return a > b ? a : b; };
-        atomicAdd(&g_bwd_stats[24], (unsigned long long)mx(sub_[0], sub_[1]));
-        atomicAdd(&g_bwd_stats[25], (unsigned long long)mx(sub_[2], sub_[3]));
-        atomicAdd(&g_bwd_stats[26], (unsigned long long)mx(mx(sub_[4], sub_[5]), mx(sub_[6], sub_[7])));
-        atomicAdd(&g_bwd_stats[27], (unsigned long long)mx(mx(sub_[8], sub_[9]), mx(sub_[10], sub_[11])));
-        atomicAdd(&g_bwd_stats[28], (unsigned long long)sub_[12]);
-        atomicAdd(&g_bwd_stats[29], (unsigned long long)(sub_[0] + sub_[1]));
-        atomicAdd(&g_bwd_stats[30], (unsigned long long)(sub_[4] + sub_[5] + sub_[6] + sub_[7]));
-        atomicAdd(&g_bwd_stats[31], (unsigned long long)(sub_[8] + sub_[9] + sub_[10] + sub_[11]));
-    }
-    st_[3] = st_[0];
-#endif
     if (!PERSIST) break;
   }
-#ifdef LCGS_BWD_STATS
-    if (lane == 0u) {
-        atomicAdd(&g_bwd_stats[0], st_[0]);
-        atomicAdd(&g_bwd_stats[1], st_[1]);
-        atomicAdd(&g_bwd_stats[2], st_[2]);
-        if (wave == 0u) atomicAdd(&g_bwd_stats[4], st_[4]);
-        atomicAdd(&g_bwd_stats[6], st_[6]);
-        atomicAdd(&g_bwd_stats[7], st_[7]);
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1220,15 +1126,3 @@ void launch_preprocess_backward_adam(int64_t v_hint, const CamParams& cp, float 
 
 } // namespace lcgs
 
-#ifdef LCGS_BWD_STATS
-// (measuring builds only; not declared in include/lcgs_hip.h)
-extern "C" __attribute__((visibility("default"))) int lcgs_debug_bwd_stats(unsigned long long* out, int reset)
-{
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(lcgs::g_bwd_stats), sizeof(unsigned long long) * 32) != hipSuccess) return 1;
-    if (reset) {
-        unsigned long long z[32] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(lcgs::g_bwd_stats), z, sizeof z) != hipSuccess) return 1;
-    }
-    return 0;
-}
-#endif

@@ -20,10 +20,9 @@ FILES = ["tests/test_gpu_fused.py", "tests/test_gpu_backward.py",
 
 
 # persistent: bounded grids of tile workgroups pulling from a counter (what camera batches / lcgs_fit_views use while several
-# frames are in flight), forced for EVERY frame and for the render-backward; cu-partition: sort chain and renderer on
-# CU-masked streams (a measured-and-kept-as-hook experiment of round 4).  Same frames, bit for bit.
-@pytest.mark.parametrize("hook", [{"LCGS_GRAPH": "1"}, {"LCGS_RENDER_WGS_PER_CU": "3", "LCGS_BWD_WGS_PER_CU": "2"},
-                                  {"LCGS_CHAIN_CUS": "32"}], ids=["hipgraph", "persistent", "cu-partition"])
+# frames are in flight), forced for EVERY frame and for the render-backward.  Same frames, bit for bit.
+@pytest.mark.parametrize("hook", [{"LCGS_GRAPH": "1"}, {"LCGS_RENDER_WGS_PER_CU": "3", "LCGS_BWD_WGS_PER_CU": "2"}],
+                         ids=["hipgraph", "persistent"])
 def test_parity_suites_under_tuning_hook(hook):
     env = dict(os.environ, **hook)
     res = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"] + FILES,
@@ -54,12 +53,8 @@ def test_backward_suite_without_kept_masks():
 # Per-block pair lists (frames without backward state; by default only from ~3 M pairs up, which no small test scene reaches)
 # forced on: the fused-frame, ingest and random-sweep suites -- every frame against the oracle bit for bit, camera batches, LOD,
 # half-precision coefficients, overflow handling -- and forced off.
-# Round 6: frames that KEEP backward state can follow the same decision -- their renderer writes every tile's own list while it
-# stages its block's (render.hip COMPACT) and the backward walks those.  Built, correct, 1.1 % slower (REJECTED.md): not the
-# default, kept behind LCGS_COARSE_KEEP=1 as the A/B hook -- the backward, training and ownership suites run through it here.
-@pytest.mark.parametrize("mode", [{"LCGS_COARSE_LISTS": "1"}, {"LCGS_COARSE_LISTS": "0"},
-                                  {"LCGS_COARSE_LISTS": "1", "LCGS_COARSE_KEEP": "1"}],
-                         ids=["block-lists", "tile-lists", "block-lists-also-for-keep-state-frames"])
+@pytest.mark.parametrize("mode", [{"LCGS_COARSE_LISTS": "1"}, {"LCGS_COARSE_LISTS": "0"}],
+                         ids=["block-lists", "tile-lists"])
 def test_parity_suites_under_forced_list_granularity(mode):
     env = dict(os.environ, **mode)
     res = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",

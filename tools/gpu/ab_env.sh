@@ -1,5 +1,5 @@
 # A/B of tuning hooks (environment variables) with one library on one box:
-#   gpurun -- bash tools/gpu/ab_env.sh "LCGS_DEPTH_BUCKETS=0" "LCGS_DEPTH_BUCKETS=1024" ...
+#   bash tools/gpu/ab_env.sh "LCGS_COARSE_LISTS=0" "LCGS_COARSE_LISTS=1" ...
 # Each setting runs the short forward bench twice, interleaved (clock / placement drift shows up as spread).
 cd $GRAFT_REPO_ROOT
 B="python bench.py --steps 100 --warmup 10 --full --no-cpu-baseline --no-train-step --no-stage-path --no-spatial --no-backward --no-batch"

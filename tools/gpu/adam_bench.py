@@ -1,5 +1,4 @@
-"""Times the dense optimiser step alone (lcgs_adam_step on 6.13 M degree-3 splats): gpurun -- python tools/gpu/adam_bench.py
-LCGS_ADAM_VARIANT selects experimental kernels (train.hip)."""
+"""Times the dense optimiser step alone (lcgs_adam_step on 6.13 M degree-3 splats): python tools/gpu/adam_bench.py"""
 import os
 import sys
 import time
@@ -31,5 +30,5 @@ r.ctx.synchronize()
 torch.cuda.synchronize()
 ms = (time.perf_counter() - t0) * 1e3 / N
 gb = P * 59 * 4 * 7 / 1e9
-print(os.environ.get("LCGS_ADAM_VARIANT", "0"), f"{ms:.3f} ms per dense step, {gb / ms:.2f} TB/s of 7 x 236 B/splat",
+print(f"{ms:.3f} ms per dense step, {gb / ms:.2f} TB/s of 7 x 236 B/splat",
       "checksum", float(raw["sh"].double().sum()))

@@ -1,5 +1,5 @@
 # FETCH_SIZE of the forward renderer under two settings of an environment hook:
-#   gpurun -- bash tools/gpu/pmc_fetch_ab.sh LCGS_TILE_ORDER_XCD 0 1
+#   bash tools/gpu/pmc_fetch_ab.sh LCGS_COARSE_LISTS 0 1
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 V=$1; shift
