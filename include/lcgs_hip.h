@@ -243,7 +243,27 @@ LCGS_API lcgs_status lcgs_render_backward_adam(lcgs_context* ctx, const float* d
 /* *d_loss = mean((img - target)^2), d_dL_dimg = its gradient (what lcgs_render_backward takes).  Device pointers. */
 LCGS_API lcgs_status lcgs_l2_loss_backward(lcgs_context* ctx, int width, int height, const float* d_img_chw, const float* d_target_chw,
                                            float* d_dL_dimg, float* d_loss);
-/* The views of ONE optimiser step: forward(keep_state) -> L2 loss vs d_targets[j] -> backward per view, dense gradients
+/* The 3DGS training loss of two CHW float32 images [3][H][W] (the layout lcgs_render_forward writes):
+ *   window      w[k] = exp(-(k - 5)^2 / (2 1.5^2)) / sum, k = 0..10, as binary32 constants rounded from the binary64 values; the
+ *               2-D window G = w w^T, applied per channel with ZERO padding of 5 (conv2d(padding = 5, groups = 3))
+ *   statistics  mu1 = G*x, mu2 = G*y, s1 = G*x^2 - mu1^2, s2 = G*y^2 - mu2^2, s12 = G*xy - mu1 mu2; C1 = 0.01^2, C2 = 0.03^2
+ *   ssim        ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)) per element; SSIM = its mean over 3 H W
+ *   loss        (1 - lambda) L1 + lambda (1 - SSIM), L1 = mean|x - y|
+ *   gradient    dL/dx = (1 - lambda) sign(x - y) / n - (lambda / n) [ G*a + 2 x (G*b) + y (G*c) ], n = 3 H W, sign(0) = 0,
+ *               a = d ssim / d mu1 with s1 and s12 expanded (it includes the -2 mu1 and -mu2 terms), b = d ssim / d s1,
+ *               c = d ssim / d s12; G is symmetric, so the adjoint of the zero-padded convolution is that convolution
+ * *d_loss = (1 - lambda_dssim) * mean|img - target| + lambda_dssim * (1 - SSIM(img, target)), the 3DGS training loss;
+ * d_dL_dimg (nullable: evaluation only) = its gradient w.r.t. img, what lcgs_render_backward takes;
+ * d_terms (nullable) = { L1, SSIM }.  Device pointers; only enqueues; same inputs -> same bits. */
+LCGS_API lcgs_status lcgs_photometric_loss_backward(lcgs_context* ctx, int width, int height, const float* d_img_chw,
+                                                    const float* d_target_chw, float lambda_dssim, float* d_dL_dimg,
+                                                    float* d_loss, float* d_terms);
+#define LCGS_LOSS_L2 0
+#define LCGS_LOSS_PHOTOMETRIC 1
+/* The loss lcgs_fit_views applies (default LCGS_LOSS_L2: unchanged behaviour). */
+LCGS_API lcgs_status lcgs_set_fit_loss(lcgs_context* ctx, int kind, float lambda_dssim);
+/* The views of ONE optimiser step: forward(keep_state) -> the selected loss (lcgs_set_fit_loss; L2 unless told otherwise) vs
+ * d_targets[j] -> backward per view, dense gradients
  * summed into `grads`, d_losses[j] (device); views alternate between the context and its sibling.  The context's stream
  * waits for the batch; the context holds the last view's frame state. */
 LCGS_API lcgs_status lcgs_fit_views(lcgs_context* ctx, int num_views, const lcgs_camera* cameras, const float bg_color[3],

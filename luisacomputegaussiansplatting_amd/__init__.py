@@ -21,6 +21,8 @@ from .api import (  # noqa: F401
     GSTileSplatterAccelProxy,
     GSTileSplatterInputProxy,
     GPUPointsProxy,
+    LOSS_L2,
+    LOSS_PHOTOMETRIC,
     LcgsError,
     Renderer,
     SHProcessor,

@@ -170,7 +170,11 @@ EXPORTED_SYMBOLS = [
     "lcgs_adam_step_sparse", "lcgs_sparse_touched_rows", "lcgs_sparse_message_words", "lcgs_sparse_pack",
     "lcgs_sparse_accumulate", "lcgs_scene_declare_static", "lcgs_owner_project", "lcgs_owner_project_views", "lcgs_owner_counts", "lcgs_owner_render", "lcgs_owner_render_backward", "lcgs_owner_backward",
     "lcgs_densify_accumulate", "lcgs_densify", "lcgs_opacity_reset",
+    "lcgs_photometric_loss_backward", "lcgs_set_fit_loss",
 ]
+
+# lcgs_set_fit_loss kinds (LCGS_LOSS_* in include/lcgs_hip.h)
+LOSS_L2, LOSS_PHOTOMETRIC = 0, 1
 
 
 def load_library():
@@ -215,6 +219,9 @@ def load_library():
     lib.lcgs_densify.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DensifyConfig), ps, pp, pp, pp, pp, pp, pp, pp, ps,
                                  C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.lcgs_opacity_reset.argtypes = [C.c_void_p, C.c_int, C.c_float, pp, pp, pp, pp]
+    lib.lcgs_photometric_loss_backward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lcgs_set_fit_loss.argtypes = [C.c_void_p, C.c_int, C.c_float]
     _lib = lib
     return lib
 
@@ -620,9 +627,9 @@ class Renderer:
 
     def fit_views(self, cams, targets, dpos, dscale, drotq, dsh, dopacity, losses, bg=(0.0, 0.0, 0.0),
                   scale_modifier: float = 1.0):
-        """lcgs_fit_views: the views of one optimiser step -- forward, L2 loss against targets[j], backward -- with the
-        dense gradients summed into the five arrays and losses[j] (device tensor of len(cams) floats) = view j's loss;
-        consecutive views overlap (forward beside the previous backward)."""
+        """lcgs_fit_views: the views of one optimiser step -- forward, the loss selected by set_fit_loss (L2 unless told
+        otherwise) against targets[j], backward -- with the dense gradients summed into the five arrays and losses[j] (device
+        tensor of len(cams) floats) = view j's loss; consecutive views overlap (forward beside the previous backward)."""
         n = len(cams)
         if len(targets) != n:
             raise ValueError("one target image per camera")
@@ -693,6 +700,19 @@ class Renderer:
         _, H, W = img.shape
         _check(load_library().lcgs_l2_loss_backward(self.ctx._h, C.c_int(W), C.c_int(H), _ptr(img), _ptr(target),
                                                     _ptr(dL_dimg), _ptr(loss)))
+
+    def photometric_loss_backward(self, img, target, dL_dimg, loss, lambda_dssim: float = 0.2, terms=None):
+        """lcgs_photometric_loss_backward: loss[0] = (1 - lambda) mean|img - target| + lambda (1 - SSIM(img, target)), the 3DGS
+        training loss (11 x 11 Gaussian window, sigma 1.5, zero padding); dL_dimg (None: evaluation only) = its gradient
+        w.r.t. img; terms (optional, 2 floats) = (L1, SSIM).  Device tensors, img / target CHW float32; the same inputs give
+        the same bits."""
+        _, H, W = img.shape
+        _check(load_library().lcgs_photometric_loss_backward(self.ctx._h, C.c_int(W), C.c_int(H), _ptr(img), _ptr(target),
+                                                             C.c_float(lambda_dssim), _ptr(dL_dimg), _ptr(loss), _ptr(terms)))
+
+    def set_fit_loss(self, kind: int, lambda_dssim: float = 0.2):
+        """lcgs_set_fit_loss: the loss fit_views applies from now on -- LOSS_L2 (default) or LOSS_PHOTOMETRIC"""
+        _check(load_library().lcgs_set_fit_loss(self.ctx._h, C.c_int(kind), C.c_float(lambda_dssim)))
 
     def visible_rows(self):
         """lcgs_visible_rows of the last forward frame: (splat index of every compact row, row count) as a device

@@ -446,6 +446,8 @@ lcgs_status prepare_twin(lcgs_context* ctx)
             LCGS_TRY(lcgs_scene_bind(t, ctx->P, ctx->sh_deg, ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->opacity));
         t->use_half_sh    = false;
         t->lod_min_radius = ctx->lod_min_radius;
+        t->fit_loss       = ctx->fit_loss;
+        t->fit_lambda     = ctx->fit_lambda;
         t->coarse_mode    = ctx->coarse_mode;
         t->coarse_on      = ctx->coarse_on;
         t->coarse_yield   = ctx->coarse_yield;

@@ -8,6 +8,7 @@
 //   abi_backward.cpp  lcgs_render_backward and its variants (compact rows, accumulate, fused Adam)
 //   abi_train.cpp     lcgs_adam_step, lcgs_fit_views
 //   abi_densify.cpp   adaptive density control: lcgs_densify_accumulate, lcgs_densify, lcgs_opacity_reset
+//   abi_loss.cpp      lcgs_photometric_loss_backward, lcgs_set_fit_loss
 #pragma once
 
 #include "common.hpp"

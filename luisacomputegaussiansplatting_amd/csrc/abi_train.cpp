@@ -1,5 +1,6 @@
 // abi_train.cpp -- the C ABI, part 6: the optimiser step (csrc/kernels/train.hip) and multi-view steps on one GPU
-// (lcgs_fit_views: a view's forward beside the previous view's backward, on the context and its sibling).
+// (lcgs_fit_views: a view's forward beside the previous view's backward, on the context and its sibling; the loss is the one
+// lcgs_set_fit_loss selected, abi_loss.cpp).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -78,8 +79,12 @@ lcgs_status lcgs_fit_views(lcgs_context* ctx, int num_views, const lcgs_camera* 
         LCGS_TRY(c->fit_dL.ensure(img_bytes));
         if (!c->ev_fit_bwd) LCGS_HIP_CHECK(hipEventCreateWithFlags(&c->ev_fit_bwd, hipEventDisableTiming));
         LCGS_TRY(lcgs_render_forward(c, &cameras[j], bg_color, scale_modifier, c->fit_img.as<float>(), nullptr, 1, nullptr));
-        LCGS_TRY(lcgs_l2_loss_backward(c, cameras[j].width, cameras[j].height, c->fit_img.as<float>(), d_targets[j],
-                                       c->fit_dL.as<float>(), d_losses + j));
+        if (ctx->fit_loss == LCGS_LOSS_PHOTOMETRIC)
+            LCGS_TRY(lcgs_photometric_loss_backward(c, cameras[j].width, cameras[j].height, c->fit_img.as<float>(), d_targets[j],
+                                                    ctx->fit_lambda, c->fit_dL.as<float>(), d_losses + j, nullptr));
+        else
+            LCGS_TRY(lcgs_l2_loss_backward(c, cameras[j].width, cameras[j].height, c->fit_img.as<float>(), d_targets[j],
+                                           c->fit_dL.as<float>(), d_losses + j));
         // the gradient arrays are shared: this view's backward after the previous view's (on the other context)
         if (prev && prev != c) LCGS_HIP_CHECK(hipStreamWaitEvent(c->stream, prev->ev_fit_bwd, 0));
         LCGS_TRY(j == 0 ? lcgs_render_backward(c, c->fit_dL.as<float>(), grads)

@@ -2,6 +2,7 @@
 //   lcgs-app --ply <path> [--res WxH] [--out dir] [--world colmap|blender] [--exp_N N] [--backend hip]
 //            [--path fused|stage|deferred] [--synth kind:count:seed] [--ingest device|host] [--cameras file]
 //            [--order file|spatial] [--pose garden|lego] [--gpus N] [--backward [--owner] [--comm-selftest]] [--fit K]
+//            [--fused-adam] [--loss l2|photometric] [--lambda-dssim f]
 // Same flags (app/main.cpp:52-124; `--key=value` and `--key value`, app/command_parser.hpp:5-79), the same
 // hard-coded look-at camera (app/main.cpp:191-207), the same frame loop (:266-308), the same output:
 // <out>/<ply stem>_<backend>.png, CHW float -> vertically flipped RGB8 with a truncating *255 (:323-339).
@@ -68,10 +69,13 @@ void usage(const char* argv0)
            "                           scene; 30 s per phase).  A failure is printed and ends the run with a non-zero status\n");
     printf("  --fit <K>                Training without a Python binding (doc/roadmap.md:4), as a demonstration: the loaded scene's\n"
            "                           frame is the target, opacities and base colours are perturbed, K optimiser steps\n"
-           "                           (forward, L2 loss, backward, Adam) pull them back; prints the loss per step.  With\n"
+           "                           (forward, loss (--loss), backward, Adam) pull them back; prints the loss per step.  With\n"
            "                           --cameras every step covers all views of the file (lcgs_fit_views)\n");
     printf("  --fused-adam             With --fit on one view: the optimiser is applied inside the backward's per-splat kernel\n"
            "                           (lcgs_render_backward_adam: on-screen splats only, no gradient arrays)\n");
+    printf("  --loss <l2|photometric>  With --fit: mean squared error (default) or the 3DGS training loss\n"
+           "                           (1 - lambda) L1 + lambda (1 - SSIM) (lcgs_photometric_loss_backward)\n");
+    printf("  --lambda-dssim <f>       With --loss photometric: the weight of the 1 - SSIM term, in [0,1] (default: 0.2)\n");
     printf("  --display                Not supported (headless)\n");
 }
 
@@ -88,7 +92,8 @@ int main(int argc, char** argv)
 {
     unsigned    W = 1600, H = 1063; // app/main.cpp:38
     std::string ply_path = "gsplat.ply", backend = "hip", out_dir = "out", world = "colmap", path = "fused", synth;
-    std::string ingest = "device", cameras_file, order = "auto", pose = "garden";
+    std::string ingest = "device", cameras_file, order = "auto", pose = "garden", loss_kind = "l2";
+    float       lambda_dssim = 0.2f;
     int         exp_N = 1, gpus = 1, fit_steps = 0;
     bool        backward = false, fused_adam = false, owner = false, comm_selftest = false;
     // parse_command (app/command_parser.hpp:5-79): strip leading dashes, `key=value` or `key value`
@@ -152,6 +157,15 @@ int main(int argc, char** argv)
             if (fit_steps < 1 || fit_steps > 100000) die("--fit out of range");
         }
         else if (key == "fused-adam" || key == "fused_adam") fused_adam = true;
+        else if (key == "loss") {
+            if (value != "l2" && value != "photometric") die("Invalid loss: '" + value + "'. Expected l2 or photometric");
+            loss_kind = value;
+        } else if (key == "lambda-dssim" || key == "lambda_dssim") {
+            char* end = nullptr;
+            lambda_dssim = value.empty() ? -1.0f : std::strtof(value.c_str(), &end);
+            if (value.empty() || *end != '\0' || !(lambda_dssim >= 0.0f && lambda_dssim <= 1.0f))
+                die("--lambda-dssim must be a number in [0,1]");
+        }
         else if (key == "display") die("--display needs a GUI; this build is headless");
         else die("unknown option --" + key);
     }
@@ -349,7 +363,7 @@ int main(int argc, char** argv)
             std::vector<float> h_pos(n3), h_scale(n3), h_rotq(n4), h_sh(n48), h_op(P);
             lcgs::check(lcgs_scene_download(device.ctx(), h_pos.data(), h_scale.data(), h_rotq.data(), h_sh.data(), h_op.data()));
             // one target per view of --cameras (the scene's own frames): an optimiser step covers all of them
-            // (lcgs_fit_views: forward -> L2 loss -> backward per view, gradients summed, consecutive views overlapping)
+            // (lcgs_fit_views: forward -> the loss of --loss -> backward per view, gradients summed, consecutive views overlapping)
             lcgs::Camera cam = make_camera(views[0]);
             lcgs::Scene  scene(device);
             std::vector<lcgs::Camera>         cams;
@@ -362,6 +376,8 @@ int main(int argc, char** argv)
                 target_ptrs.push_back(targets.back().data());
             }
             const int           nv = (int)cams.size();
+            const bool          photometric = loss_kind == "photometric";
+            if (photometric) device.set_fit_loss(LCGS_LOSS_PHOTOMETRIC, lambda_dssim);
             lcgs::Buffer<float> d_loss((size_t)nv);
             std::vector<float>  h_loss((size_t)nv);
             // raw 3DGS parameters (log-scale, opacity logit, un-normalised quaternion) of the PERTURBED scene
@@ -398,10 +414,14 @@ int main(int argc, char** argv)
             lcgs::Buffer<float> d_dL(fused_adam ? (size_t)W * H * 3 : 1);
             for (int it = 0; it < fit_steps; ++it) {
                 cfg.step = it + 1;
-                if (fused_adam) { // forward (kept state) -> L2 loss and its gradient -> backward with Adam folded in
+                if (fused_adam) { // forward (kept state) -> the loss and its gradient -> backward with Adam folded in
                     scene.render(cams[0], d_img, bg, 1.0f, /*keep_state=*/true);
-                    lcgs::check(lcgs_l2_loss_backward(device.ctx(), (int)W, (int)H, d_img.data(), target_ptrs[0], d_dL.data(),
-                                                      d_loss.data()));
+                    if (photometric)
+                        device.photometric_loss_backward((int)W, (int)H, d_img.data(), target_ptrs[0], d_dL.data(), d_loss.data(),
+                                                         lambda_dssim);
+                    else
+                        lcgs::check(lcgs_l2_loss_backward(device.ctx(), (int)W, (int)H, d_img.data(), target_ptrs[0], d_dL.data(),
+                                                          d_loss.data()));
                     lcgs::check(lcgs_render_backward_adam(device.ctx(), d_dL.data(), P, 3, &cfg, &raw, &mm, &vv, &act));
                 } else {
                     scene.fit_views(cams, target_ptrs, grads, d_loss.data(), bg);

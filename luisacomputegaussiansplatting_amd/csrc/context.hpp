@@ -160,6 +160,11 @@ struct lcgs_context {
     // lcgs_fit_views: the view's image and loss gradient (per context: two views are in flight), the order of the
     // backward passes across the two contexts
     DeviceBuffer fit_img, fit_dL;
+    // lcgs_photometric_loss_backward: per-workgroup partial sums, then the planes a, b, c (loss.hip); the loss lcgs_fit_views
+    // applies (lcgs_set_fit_loss; handed to the sibling in prepare_twin)
+    DeviceBuffer loss_ws;
+    int          fit_loss   = LCGS_LOSS_L2;
+    float        fit_lambda = 0.2f;
     hipEvent_t   ev_fit_bwd = nullptr;
     // launch-size hints from the last synchronised frame (live counts stay on the device; larger counts are
     // still handled correctly by chunk striding)

@@ -229,6 +229,20 @@ void launch_densify_scatter(int64_t P, int sh_floats, const uint8_t* action, con
                             uint32_t* src_row, hipStream_t stream);
 // raw = min(raw, ceiling), m = v = 0, act = sigmoid(raw)
 void launch_opacity_reset(int64_t P, float ceiling, float* raw, float* m, float* v, float* act, hipStream_t stream);
+// ---- loss.hip : the 3DGS photometric loss, (1 - lambda) L1 + lambda (1 - SSIM), and its gradient ----
+// Both passes tile a channel into 32 x 16 outputs, one workgroup each; partial sums are indexed by workgroup.
+int64_t photometric_workgroups(int W, int H);
+// pass A: per-pixel ssim and |x - y| summed per workgroup into partials[wg] = { sum ssim, sum |x - y| }; abc (nullable:
+// evaluation only) = the three planes [3][3 H W] of d ssim / d mu1 (expanded), / d sigma1^2, / d sigma12
+void launch_photometric_stats(int W, int H, const float* img, const float* target, float* abc, double* partials,
+                              hipStream_t stream);
+// pass B: dL[i] = (1 - lambda) sign(x - y) / n - (lambda / n) (G*a + 2 x G*b + y G*c), every element written once
+// (lambda == 0: abc is not read)
+void launch_photometric_grad(int W, int H, const float* img, const float* target, const float* abc, float lambda, float* dL,
+                             hipStream_t stream);
+// the partials summed in index order -> loss[0]; terms (nullable) = { L1, SSIM }
+void launch_photometric_finish(int W, int H, const double* partials, float lambda, float* loss, float* terms,
+                               hipStream_t stream);
 // backward.hip: the per-splat half of the backward with the on-screen-only Adam update applied where the gradients are
 // formed (degree 3, frames that kept the colour Jacobian): no gradient rows are written at all
 void launch_preprocess_backward_adam(int64_t v_hint, const CamParams& cp, float scale_modifier, const float* pos,

@@ -1,0 +1,268 @@
+// loss.hip -- the 3DGS photometric loss (1 - lambda) mean|x - y| + lambda (1 - SSIM(x, y)) and its gradient with respect to x
+// (the definition is the contract in include/lcgs_hip.h).  No reference counterpart (doc/roadmap.md:4 only
+// names training).  Two passes over 32 x 16 output tiles of one channel, one 256-thread workgroup each, both a separable
+// 11-tap convolution staged through LDS (a row pass into LDS planes, a column pass into registers):
+//   pass A  x, y (tile + 5-pixel halo, zeros outside the image) -> the five statistics -> ssim and its three partial
+//           derivatives a, b, c per pixel (stored for pass B) + one { sum ssim, sum |x - y| } pair per workgroup
+//   pass B  a, b, c (tile + halo, zeros outside the image: the window is symmetric, so the adjoint of the zero-padded
+//           convolution is the same convolution) -> G*a + 2 x G*b + y G*c -> dL/dx with the L1 term, written once
+//   finish  one workgroup sums the pairs in index order -> loss, { L1, SSIM }
+// Nothing is accumulated with atomics: the same inputs give the same bits.
+// Precision: sigma^2 = G*x^2 - mu^2 cancels in the flat regions rendered frames are made of (both terms ~ x^2, the
+// difference is compared with C2 = 9e-4), so pass A carries its planes, statistics and the ssim algebra in binary64 (x^2 and
+// x y are then exact) and rounds a, b, c once; every sum over pixels is binary64 too.  Pass B has no such difference of
+// squares: binary32 planes, binary64 column accumulators and final expression, one rounding of the result.
+// LDS pitches (64 banks of 4 bytes; a wave is two tile rows of 32 columns):
+//   row-filtered planes: pitch 32 elements.  binary32 (pass B): the two rows of a wave are 32 words apart, so its 64 lanes
+//   read 64 consecutive words, one per bank.  binary64 (pass A): a 64-bit read is served 32 lanes at a time, and the 32
+//   lanes of one row read 64 consecutive words.  Either way the column pass, which walks the same column down consecutive
+//   rows, is conflict free.
+//   staged inputs: the planes of one row sit side by side at a 48-word spacing (42 used) and the row pitch is 32 mod 64 words
+//   (96 for x | y, 160 for a | b | c), so the row pass is conflict free for the same reason.
+#include "launch.hpp"
+#include "stream_access.hpp"
+
+namespace lcgs
+{
+namespace
+{
+constexpr int kR = 5, kTaps = 2 * kR + 1; // the 11 x 11 window
+constexpr int kTW = 32, kTH = 16;         // outputs of a workgroup
+constexpr int kInW = kTW + 2 * kR, kInH = kTH + 2 * kR; // ... and what they read: 42 x 26
+constexpr int kSlot = 48;                 // spacing of the planes inside a staged row
+constexpr int kPitchA = 96, kPitchB = 160;
+constexpr int kThreads = 256;
+static_assert(kInW <= kSlot && kSlot + kInW <= kPitchA && 2 * kSlot + kInW <= kPitchB, "staged planes overlap");
+static_assert(kPitchA % 64 == 32 && kPitchB % 64 == 32, "row pitch must be 32 mod 64 banks");
+
+// w[k] = exp(-(k - 5)^2 / (2 1.5^2)) / sum, the binary64 values rounded to binary32
+__device__ const float kGauss[kTaps] = { 0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c4p-3f, 0x1.10656p-2f,
+                                         0x1.b43c4p-3f,   0x1.bff0fep-4f, 0x1.26eb18p-5f, 0x1.f1fe02p-8f, 0x1.0d956cp-10f };
+constexpr double kC1 = 0.01 * 0.01, kC2 = 0.03 * 0.03;
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// ---- pass A
+template <bool STORE>
+__global__ void __launch_bounds__(kThreads) k_photometric_stats(int W, int H, const float* __restrict__ img,
+                                                                const float* __restrict__ target, float* __restrict__ abc,
+                                                                double* __restrict__ partials)
+{
+    __shared__ float  s_in[kInH][kPitchA];  // x at [0, 42), y at [48, 90)
+    __shared__ double s_row[5][kInH][kTW];  // row-filtered x, y, x^2, y^2, x y
+    __shared__ double s_red[2][kThreads / 64];
+    const int     tid = threadIdx.x;
+    const int     x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+    const int64_t plane = (int64_t)W * H, chan = (int64_t)blockIdx.z * plane;
+    for (int i = tid; i < kInH * kInW; i += kThreads) {
+        const int  r = i / kInW, c = i - r * kInW;
+        const int  gy = y0 - kR + r, gx = x0 - kR + c;
+        const bool in = gx >= 0 && gx < W && gy >= 0 && gy < H;
+        const int64_t o = chan + (int64_t)gy * W + gx;
+        s_in[r][c]         = in ? img[o] : 0.0f;
+        s_in[r][kSlot + c] = in ? target[o] : 0.0f;
+    }
+    __syncthreads();
+    for (int i = tid; i < kInH * kTW; i += kThreads) {
+        const int r = i >> 5, c = i & 31;
+        double    sx = 0.0, sy = 0.0, sxx = 0.0, syy = 0.0, sxy = 0.0;
+#pragma unroll
+        for (int k = 0; k < kTaps; ++k) {
+            const double w = (double)kGauss[k], xv = (double)s_in[r][c + k], yv = (double)s_in[r][kSlot + c + k];
+            sx  = fma(w, xv, sx);
+            sy  = fma(w, yv, sy);
+            sxx = fma(w, xv * xv, sxx);
+            syy = fma(w, yv * yv, syy);
+            sxy = fma(w, xv * yv, sxy);
+        }
+        s_row[0][r][c] = sx;
+        s_row[1][r][c] = sy;
+        s_row[2][r][c] = sxx;
+        s_row[3][r][c] = syy;
+        s_row[4][r][c] = sxy;
+    }
+    __syncthreads();
+    double sum_ssim = 0.0, sum_l1 = 0.0;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int r = (tid >> 5) + half * (kTH / 2), c = tid & 31;
+        double    m1 = 0.0, m2 = 0.0, e11 = 0.0, e22 = 0.0, e12 = 0.0;
+#pragma unroll
+        for (int k = 0; k < kTaps; ++k) {
+            const double w = (double)kGauss[k];
+            m1  = fma(w, s_row[0][r + k][c], m1);
+            m2  = fma(w, s_row[1][r + k][c], m2);
+            e11 = fma(w, s_row[2][r + k][c], e11);
+            e22 = fma(w, s_row[3][r + k][c], e22);
+            e12 = fma(w, s_row[4][r + k][c], e12);
+        }
+        const int gx = x0 + c, gy = y0 + r;
+        if (gx < W && gy < H) {
+            const double s11 = e11 - m1 * m1, s22 = e22 - m2 * m2, s12 = e12 - m1 * m2;
+            const double A1 = 2.0 * m1 * m2 + kC1, A2 = 2.0 * s12 + kC2;
+            const double B1 = m1 * m1 + m2 * m2 + kC1, B2 = s11 + s22 + kC2;
+            const double inv = 1.0 / (B1 * B2), ssim = A1 * A2 * inv;
+            sum_ssim += ssim;
+            sum_l1 += fabs((double)s_in[r + kR][c + kR] - (double)s_in[r + kR][kSlot + c + kR]);
+            if (STORE) {
+                // b = d ssim / d sigma1^2, c = d / d sigma12; a = d / d mu1 with sigma1^2 = G*x^2 - mu1^2 and
+                // sigma12 = G*xy - mu1 mu2 expanded: the partial at fixed sigmas, - 2 mu1 b - mu2 c
+                const double    db = -ssim / B2, dc = 2.0 * A1 * inv;
+                const double    da = 2.0 * (m2 * A2 * inv - m1 * ssim / B1) - 2.0 * m1 * db - m2 * dc;
+                const int64_t   o  = chan + (int64_t)gy * W + gx;
+                const int64_t   n  = 3 * plane;
+                abc[o]         = (float)da;
+                abc[n + o]     = (float)db;
+                abc[2 * n + o] = (float)dc;
+            }
+        }
+    }
+    sum_ssim = wave_sum(sum_ssim);
+    sum_l1   = wave_sum(sum_l1);
+    if ((tid & 63) == 0) {
+        s_red[0][tid >> 6] = sum_ssim;
+        s_red[1][tid >> 6] = sum_l1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int64_t wg = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        partials[2 * wg + 0] = (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]);
+        partials[2 * wg + 1] = (s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]);
+    }
+}
+
+// ---- pass B
+__global__ void __launch_bounds__(kThreads) k_photometric_grad(int W, int H, const float* __restrict__ img,
+                                                               const float* __restrict__ target, const float* __restrict__ abc,
+                                                               float lambda, float* __restrict__ dL)
+{
+    __shared__ float s_in[kInH][kPitchB];  // a at [0, 42), b at [48, 90), c at [96, 138)
+    __shared__ float s_row[3][kInH][kTW];
+    const int     tid = threadIdx.x;
+    const int     x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+    const int64_t plane = (int64_t)W * H, chan = (int64_t)blockIdx.z * plane, n = 3 * plane;
+    const double  l1_scale = (1.0 - (double)lambda) / (double)n, ssim_scale = (double)lambda / (double)n;
+    if (lambda == 0.0f) { // the L1 term alone: the workspace is not read (it may hold anything)
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const int gx = x0 + (tid & 31), gy = y0 + (tid >> 5) + half * (kTH / 2);
+            if (gx < W && gy < H) {
+                const int64_t o = chan + (int64_t)gy * W + gx;
+                const float   xv = ld_stream(img + o), yv = ld_stream(target + o);
+                dL[o] = (float)(l1_scale * (double)((xv > yv) - (xv < yv)));
+            }
+        }
+        return;
+    }
+    for (int i = tid; i < kInH * kInW; i += kThreads) {
+        const int  r = i / kInW, c = i - r * kInW;
+        const int  gy = y0 - kR + r, gx = x0 - kR + c;
+        const bool in = gx >= 0 && gx < W && gy >= 0 && gy < H;
+        const int64_t o = chan + (int64_t)gy * W + gx;
+        s_in[r][c]             = in ? abc[o] : 0.0f;
+        s_in[r][kSlot + c]     = in ? abc[n + o] : 0.0f;
+        s_in[r][2 * kSlot + c] = in ? abc[2 * n + o] : 0.0f;
+    }
+    __syncthreads();
+    for (int i = tid; i < kInH * kTW; i += kThreads) {
+        const int r = i >> 5, c = i & 31;
+        float     sa = 0.0f, sb = 0.0f, sc = 0.0f;
+#pragma unroll
+        for (int k = 0; k < kTaps; ++k) {
+            const float w = kGauss[k];
+            sa = fmaf(w, s_in[r][c + k], sa);
+            sb = fmaf(w, s_in[r][kSlot + c + k], sb);
+            sc = fmaf(w, s_in[r][2 * kSlot + c + k], sc);
+        }
+        s_row[0][r][c] = sa;
+        s_row[1][r][c] = sb;
+        s_row[2][r][c] = sc;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int r = (tid >> 5) + half * (kTH / 2), c = tid & 31;
+        const int gx = x0 + c, gy = y0 + r;
+        if (gx >= W || gy >= H) continue;
+        double ga = 0.0, gb = 0.0, gc = 0.0;
+#pragma unroll
+        for (int k = 0; k < kTaps; ++k) {
+            const double w = (double)kGauss[k];
+            ga = fma(w, (double)s_row[0][r + k][c], ga);
+            gb = fma(w, (double)s_row[1][r + k][c], gb);
+            gc = fma(w, (double)s_row[2][r + k][c], gc);
+        }
+        const int64_t o  = chan + (int64_t)gy * W + gx;
+        const float   xv = ld_stream(img + o), yv = ld_stream(target + o);
+        const double  sgn = (double)((xv > yv) - (xv < yv)); // sign(0) = 0
+        dL[o] = (float)(l1_scale * sgn - ssim_scale * (ga + 2.0 * (double)xv * gb + (double)yv * gc));
+    }
+}
+
+// ---- finish: the workgroups' pairs in index order (each thread a contiguous run, then the 256 run sums in order)
+__global__ void __launch_bounds__(kThreads) k_photometric_finish(int64_t num, double n, const double* __restrict__ partials,
+                                                                 float lambda, float* __restrict__ loss, float* __restrict__ terms)
+{
+    __shared__ double s_sum[2][kThreads];
+    const int64_t     run = (num + kThreads - 1) / kThreads;
+    const int64_t     lo = (int64_t)threadIdx.x * run, hi = lo + run < num ? lo + run : num;
+    double            a = 0.0, b = 0.0;
+    for (int64_t i = lo; i < hi; ++i) {
+        a += partials[2 * i + 0];
+        b += partials[2 * i + 1];
+    }
+    s_sum[0][threadIdx.x] = a;
+    s_sum[1][threadIdx.x] = b;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a = 0.0, b = 0.0;
+        for (int t = 0; t < kThreads; ++t) {
+            a += s_sum[0][t];
+            b += s_sum[1][t];
+        }
+        const double ssim = a / n, l1 = b / n, lam = (double)lambda;
+        loss[0] = (float)((1.0 - lam) * l1 + lam * (1.0 - ssim));
+        if (terms) {
+            terms[0] = (float)l1;
+            terms[1] = (float)ssim;
+        }
+    }
+}
+
+inline dim3 tile_grid(int W, int H) { return dim3((unsigned)((W + kTW - 1) / kTW), (unsigned)((H + kTH - 1) / kTH), 3u); }
+} // namespace
+
+int64_t photometric_workgroups(int W, int H)
+{
+    const dim3 g = tile_grid(W, H);
+    return (int64_t)g.x * g.y * g.z;
+}
+
+void launch_photometric_stats(int W, int H, const float* img, const float* target, float* abc, double* partials,
+                              hipStream_t stream)
+{
+    if (abc)
+        hipLaunchKernelGGL(k_photometric_stats<true>, tile_grid(W, H), dim3(kThreads), 0, stream, W, H, img, target, abc, partials);
+    else
+        hipLaunchKernelGGL(k_photometric_stats<false>, tile_grid(W, H), dim3(kThreads), 0, stream, W, H, img, target, abc, partials);
+}
+
+void launch_photometric_grad(int W, int H, const float* img, const float* target, const float* abc, float lambda, float* dL,
+                             hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_photometric_grad, tile_grid(W, H), dim3(kThreads), 0, stream, W, H, img, target, abc, lambda, dL);
+}
+
+void launch_photometric_finish(int W, int H, const double* partials, float lambda, float* loss, float* terms,
+                               hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_photometric_finish, dim3(1), dim3(kThreads), 0, stream, photometric_workgroups(W, H),
+                       3.0 * (double)W * (double)H, partials, lambda, loss, terms);
+}
+
+} // namespace lcgs

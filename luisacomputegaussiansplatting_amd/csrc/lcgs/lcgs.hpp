@@ -98,6 +98,15 @@ public:
     void          synchronize() { check(lcgs_synchronize(m_ctx)); }
     template <typename T>
     Buffer<T> create_buffer(size_t n) { return Buffer<T>(n); }
+    // the 3DGS training loss (1 - lambda) L1 + lambda (1 - SSIM) of two CHW images and its gradient w.r.t. img (device
+    // pointers; d_dL_dimg may be NULL: evaluation only; d_terms, nullable, = { L1, SSIM })
+    void photometric_loss_backward(int width, int height, const float* d_img, const float* d_target, float* d_dL_dimg,
+                                   float* d_loss, float lambda_dssim = 0.2f, float* d_terms = nullptr)
+    {
+        check(lcgs_photometric_loss_backward(m_ctx, width, height, d_img, d_target, lambda_dssim, d_dL_dimg, d_loss, d_terms));
+    }
+    // the loss Scene::fit_views applies: LCGS_LOSS_L2 (default) or LCGS_LOSS_PHOTOMETRIC
+    void set_fit_loss(int kind, float lambda_dssim = 0.2f) { check(lcgs_set_fit_loss(m_ctx, kind, lambda_dssim)); }
 
 private:
     lcgs_context* m_ctx = nullptr;
@@ -235,7 +244,8 @@ public:
     {
         check(lcgs_render_backward_accumulate(m_dev->ctx(), dL_dimg.ptr, &grads));
     }
-    // the views of one optimiser step: forward -> L2 loss against targets[j] -> backward, gradients summed into `grads`,
+    // the views of one optimiser step: forward -> the loss Device::set_fit_loss selected (L2 unless told otherwise) against
+    // targets[j] -> backward, gradients summed into `grads`,
     // d_losses[j] = view j's loss; a view's forward runs beside the previous view's backward (lcgs_fit_views)
     void fit_views(const std::vector<Camera>& cams, const std::vector<const float*>& targets, const lcgs_grads& grads,
                    float* d_losses, const float bg[3], float scale_modifier = 1.0f)
