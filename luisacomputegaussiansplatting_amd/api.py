@@ -9,6 +9,9 @@ Reference interfaces mirrored here (paths relative to the reference repository):
   * ``Renderer`` (the per-frame loop body) ........  app/main.cpp:266-308
 
 Device buffers are torch CUDA(=HIP) tensors; only their ``data_ptr()`` crosses the C ABI.
+
+The C ABI is declared ONCE here: ``STRUCTS`` (the ctypes mirror of every struct of include/lcgs_hip.h) and ``SIGNATURES``
+(restype and argtypes of every function), both held to the header by tests/test_abi.py.  Call sites pass plain Python values.
 """
 from __future__ import annotations
 
@@ -44,12 +47,14 @@ def build_library(force: bool = False) -> str:
     return library_path()
 
 
-class _SelftestReport(C.Structure):
-    """lcgs_comm_selftest_report"""
+# ---------------------------------------------------------------------------------------------- struct mirrors
+# constants of include/lcgs_hip.h the mirrors and the wrappers need
+LCGS_MAX_STAGES, LCGS_MAX_RANKS = 16, 64
+LCGS_ERR_STATE = 8
+# lcgs_set_fit_loss kinds (LCGS_LOSS_* in include/lcgs_hip.h)
+LOSS_L2, LOSS_PHOTOMETRIC = 0, 1
 
-    _fields_ = [("world_size", C.c_int), ("rank", C.c_int), ("allreduce_ok", C.c_int), ("allreduce_ms", C.c_double),
-                ("p2p_ok", C.c_int), ("p2p_ms", C.c_double), ("owner_step_ok", C.c_int), ("owner_step_ms", C.c_double),
-                ("owner_max_grad_err", C.c_double), ("timed_out", C.c_int), ("message", C.c_char * 256)]
+_KEYS = ("pos", "scale", "rotq", "sh", "opacity")
 
 
 class Camera(C.Structure):
@@ -110,7 +115,7 @@ class _TileOutput(C.Structure):
 
 
 class _StageTimes(C.Structure):
-    _fields_ = [("count", C.c_int), ("name", C.c_char_p * 16), ("ms", C.c_float * 16)]
+    _fields_ = [("count", C.c_int), ("name", C.c_char_p * LCGS_MAX_STAGES), ("ms", C.c_float * LCGS_MAX_STAGES)]
 
 
 class _FrameStats(C.Structure):
@@ -144,37 +149,158 @@ class _DensifyConfig(C.Structure):
                 ("min_opacity", C.c_float), ("max_screen_size", C.c_int), ("seed", C.c_uint64)]
 
 
+class _SparseRows(C.Structure):
+    _fields_ = [("d_rows", C.c_void_p), ("num_rows", C.c_int64), ("owner_first", C.c_int64 * (LCGS_MAX_RANKS + 2))]
+
+
+class _CommStats(C.Structure):
+    _fields_ = [("bytes_sent", C.c_int64), ("bytes_received", C.c_int64), ("touched_rows", C.c_int64),
+                ("collective_groups", C.c_int)]
+
+
+class _SelftestReport(C.Structure):
+    _fields_ = [("world_size", C.c_int), ("rank", C.c_int), ("allreduce_ok", C.c_int), ("allreduce_ms", C.c_double),
+                ("p2p_ok", C.c_int), ("p2p_ms", C.c_double), ("owner_step_ok", C.c_int), ("owner_step_ms", C.c_double),
+                ("owner_max_grad_err", C.c_double), ("timed_out", C.c_int), ("message", C.c_char * 256)]
+
+
 class _SceneHost(C.Structure):
     _fields_ = [("num_gaussians", C.c_int), ("sh_degree", C.c_int), ("pos", C.POINTER(C.c_float)),
                 ("feature", C.POINTER(C.c_float)), ("opacity", C.POINTER(C.c_float)),
                 ("scale", C.POINTER(C.c_float)), ("rotq", C.POINTER(C.c_float))]
 
 
-# every symbol include/lcgs_hip.h declares (checked by tests/test_abi.py)
-EXPORTED_SYMBOLS = [
-    "lcgs_version", "lcgs_last_error", "lcgs_create", "lcgs_destroy", "lcgs_set_stream", "lcgs_synchronize",
-    "lcgs_get_lookat_cam", "lcgs_local_to_world_matrix", "lcgs_world_to_local_matrix", "lcgs_projection_matrix",
-    "lcgs_sh_process", "lcgs_project_forward", "lcgs_tile_splat_forward", "lcgs_set_stage_mode", "lcgs_stage_flush",
-    "lcgs_inclusive_sum_u32",
-    "lcgs_sort_pairs_u64_u32", "lcgs_scene_bind", "lcgs_scene_upload", "lcgs_render_forward",
-    "lcgs_set_profiling", "lcgs_get_stage_times", "lcgs_get_frame_stats", "lcgs_debug_last_lists", "lcgs_debug_last_state", "lcgs_set_list_policy", "lcgs_debug_blend_exp",
-    "lcgs_render_backward", "lcgs_render_backward_adam", "lcgs_fit_views", "lcgs_render_backward_accumulate", "lcgs_render_backward_compact", "lcgs_visible_rows", "lcgs_ply_read", "lcgs_ply_write_raw", "lcgs_scene_host_free", "lcgs_synth_scene",
-    "lcgs_image_to_rgb8", "lcgs_image_to_rgb8_device", "lcgs_write_png", "lcgs_l2_loss_backward",
-    "lcgs_scene_load_ply", "lcgs_scene_pointers", "lcgs_scene_download", "lcgs_scene_reorder_spatial", "lcgs_adam_step",
-    "lcgs_render_forward_batch", "lcgs_scene_use_half_sh", "lcgs_scene_modified", "lcgs_debug_verify_derived",
-    "lcgs_comm_owner_rows", "lcgs_owner_step_forward", "lcgs_owner_step_backward", "lcgs_owner_step_set_async",
-    "lcgs_owner_step_finish", "lcgs_comm_selftest", "lcgs_loopback_group_create",
-    "lcgs_loopback_group_destroy", "lcgs_comm_create_loopback",
-    "lcgs_set_ingest_order", "lcgs_scene_permutation", "lcgs_set_lod", "lcgs_comm_unique_id", "lcgs_comm_create", "lcgs_comm_destroy", "lcgs_comm_info", "lcgs_comm_set_transport", "lcgs_comm_shard_rows",
-    "lcgs_grads_allreduce", "lcgs_adam_step_sharded", "lcgs_comm_track_touched_rows", "lcgs_comm_get_stats",
-    "lcgs_adam_step_sparse", "lcgs_sparse_touched_rows", "lcgs_sparse_message_words", "lcgs_sparse_pack",
-    "lcgs_sparse_accumulate", "lcgs_scene_declare_static", "lcgs_owner_project", "lcgs_owner_project_views", "lcgs_owner_counts", "lcgs_owner_render", "lcgs_owner_render_backward", "lcgs_owner_backward",
-    "lcgs_densify_accumulate", "lcgs_densify", "lcgs_opacity_reset",
-    "lcgs_photometric_loss_backward", "lcgs_set_fit_loss",
-]
+# the header's struct name -> its mirror: every struct include/lcgs_hip.h defines with a body, except lcgs_comm_id (128
+# opaque bytes the host carries between ranks: any 128-byte buffer, passed as a plain address)
+STRUCTS = {
+    "lcgs_camera": Camera, "lcgs_tile_accel": _TileAccel, "lcgs_tile_input": _TileInput, "lcgs_tile_output": _TileOutput,
+    "lcgs_stage_times": _StageTimes, "lcgs_frame_stats": _FrameStats, "lcgs_grads": _Grads, "lcgs_params": _Params,
+    "lcgs_adam_config": _AdamConfig, "lcgs_densify_stats": _DensifyStats, "lcgs_densify_config": _DensifyConfig,
+    "lcgs_sparse_rows": _SparseRows, "lcgs_comm_stats": _CommStats, "lcgs_comm_selftest_report": _SelftestReport,
+    "lcgs_scene_host": _SceneHost,
+}
 
-# lcgs_set_fit_loss kinds (LCGS_LOSS_* in include/lcgs_hip.h)
-LOSS_L2, LOSS_PHOTOMETRIC = 0, 1
+
+# ---------------------------------------------------------------------------------------------- signatures
+def _signatures() -> dict:
+    """name -> (restype, argtypes) of every function include/lcgs_hip.h declares, in the header's order.
+
+    lcgs_status -> c_int, void -> None; scalars are the exact ctypes scalar; const char* -> c_char_p; int* / int64_t*
+    out-parameters -> POINTER of the scalar; a pointer to a struct of STRUCTS -> POINTER(mirror); handle out-parameters and
+    arrays of pointers -> POINTER(c_void_p); everything else that is an address (opaque handles, device and host data,
+    `float x[3]` parameters, lcgs_comm_id*) -> c_void_p."""
+    st, i, i64, u64, f, d, s, p = C.c_int, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_char_p, C.c_void_p
+    pi, pi64, pp = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_void_p)
+    ptr = {name[len("lcgs_"):]: C.POINTER(mirror) for name, mirror in STRUCTS.items()}
+    cam, grads, params, adam = ptr["camera"], ptr["grads"], ptr["params"], ptr["adam_config"]
+    dstats, packs = ptr["densify_stats"], [ptr["params"]] * 4
+    return {
+        # library / context
+        "lcgs_version": (s, []),
+        "lcgs_last_error": (s, []),
+        "lcgs_create": (st, [i, p, pp]),
+        "lcgs_destroy": (st, [p]),
+        "lcgs_set_stream": (st, [p, p]),
+        "lcgs_synchronize": (st, [p]),
+        # host camera helpers
+        "lcgs_get_lookat_cam": (None, [p, p, p, cam]),
+        "lcgs_local_to_world_matrix": (None, [cam, p]),
+        "lcgs_world_to_local_matrix": (None, [cam, p]),
+        "lcgs_projection_matrix": (None, [f, f, f, f, p]),
+        # stage-level operators
+        "lcgs_sh_process": (st, [p, i, p, cam, p, p, i, i]),
+        "lcgs_project_forward": (st, [p, i, p, p, p, f, p, p, p, cam, i]),
+        "lcgs_tile_splat_forward": (st, [p, ptr["tile_accel"], ptr["tile_input"], ptr["tile_output"], i, pi]),
+        "lcgs_set_stage_mode": (st, [p, i]),
+        "lcgs_stage_flush": (st, [p]),
+        "lcgs_inclusive_sum_u32": (st, [p, p, p, i64]),
+        "lcgs_sort_pairs_u64_u32": (st, [p, p, p, p, p, i64, i, i]),
+        # the scene a context renders
+        "lcgs_scene_bind": (st, [p, i, i, p, p, p, p, p]),
+        "lcgs_scene_upload": (st, [p, i, i, p, p, p, p, p]),
+        "lcgs_scene_load_ply": (st, [p, s, pi]),
+        "lcgs_set_ingest_order": (st, [p, i]),
+        "lcgs_scene_reorder_spatial": (st, [p, p]),
+        "lcgs_scene_permutation": (st, [p, pp]),
+        "lcgs_scene_pointers": (st, [p, pi, pi, pp, pp, pp, pp, pp]),
+        "lcgs_scene_modified": (st, [p]),
+        "lcgs_debug_verify_derived": (st, [p, pi64]),
+        "lcgs_scene_declare_static": (st, [p, i, p, p, p]),
+        "lcgs_scene_use_half_sh": (st, [p, i]),
+        "lcgs_set_lod": (st, [p, i]),
+        "lcgs_scene_download": (st, [p, p, p, p, p, p]),
+        # the fused frame
+        "lcgs_render_forward": (st, [p, cam, p, f, p, p, i, pi]),
+        "lcgs_render_forward_batch": (st, [p, i, cam, p, f, pp]),
+        "lcgs_set_profiling": (st, [p, i]),
+        "lcgs_get_stage_times": (st, [p, ptr["stage_times"]]),
+        "lcgs_get_frame_stats": (st, [p, ptr["frame_stats"]]),
+        "lcgs_set_list_policy": (st, [p, i]),
+        "lcgs_debug_last_lists": (st, [p, p, p]),
+        "lcgs_debug_last_state": (st, [p, p, p]),
+        "lcgs_debug_blend_exp": (st, [p, p, p, i64]),
+        # backward
+        "lcgs_render_backward": (st, [p, p, grads]),
+        "lcgs_render_backward_accumulate": (st, [p, p, grads]),
+        "lcgs_render_backward_compact": (st, [p, p, grads]),
+        "lcgs_visible_rows": (st, [p, pp, pp]),
+        # optimiser step, losses
+        "lcgs_adam_step": (st, [p, i, i, adam, grads, *packs]),
+        "lcgs_render_backward_adam": (st, [p, p, i, i, adam, *packs]),
+        "lcgs_l2_loss_backward": (st, [p, i, i, p, p, p, p]),
+        "lcgs_photometric_loss_backward": (st, [p, i, i, p, p, f, p, p, p]),
+        "lcgs_set_fit_loss": (st, [p, i, f]),
+        "lcgs_fit_views": (st, [p, i, cam, p, f, pp, grads, p]),
+        # adaptive density control
+        "lcgs_densify_accumulate": (st, [p, i, dstats]),
+        "lcgs_densify": (st, [p, i, i, ptr["densify_config"], dstats, *packs, *packs[:3], dstats, i64, p, p, pi64]),
+        "lcgs_opacity_reset": (st, [p, i, f, *packs]),
+        # multi-GPU
+        "lcgs_comm_unique_id": (st, [p]),
+        "lcgs_comm_create": (st, [p, p, i, i, pp]),
+        "lcgs_comm_destroy": (st, [p]),
+        "lcgs_comm_info": (st, [p, pi, pi]),
+        "lcgs_comm_set_transport": (st, [p, i]),
+        "lcgs_comm_shard_rows": (None, [i64, i, i, pi64, pi64]),
+        "lcgs_grads_allreduce": (st, [p, p, i, i, grads]),
+        "lcgs_adam_step_sharded": (st, [p, p, i, i, adam, grads, *packs]),
+        "lcgs_comm_track_touched_rows": (st, [p, i]),
+        "lcgs_comm_get_stats": (st, [p, ptr["comm_stats"]]),
+        "lcgs_adam_step_sparse": (st, [p, p, i, i, adam, grads, *packs]),
+        "lcgs_sparse_touched_rows": (st, [p, p, i, i, ptr["sparse_rows"]]),
+        "lcgs_sparse_message_words": (i64, [i64, i]),
+        "lcgs_sparse_pack": (st, [p, i, grads, p, i64, p]),
+        "lcgs_sparse_accumulate": (st, [p, i, grads, p, i64, i64, i64]),
+        # splat ownership
+        "lcgs_owner_project": (st, [p, i, cam, f, i, i, i, p, p, pi]),
+        "lcgs_owner_project_views": (st, [p, i, i, cam, f, i, i, i, pp, pp]),
+        "lcgs_owner_counts": (st, [p, i, i, pi]),
+        "lcgs_owner_render": (st, [p, cam, p, i, p, p, p, i]),
+        "lcgs_owner_render_backward": (st, [p, p, p]),
+        "lcgs_owner_backward": (st, [p, i, p, grads, i]),
+        "lcgs_comm_owner_rows": (None, [i64, i, i, pi64, pi64]),
+        "lcgs_owner_step_forward": (st, [p, p, cam, p, f, p]),
+        "lcgs_owner_step_backward": (st, [p, p, p, grads]),
+        "lcgs_owner_step_set_async": (st, [p, i]),
+        "lcgs_owner_step_finish": (st, [p, p, pi]),
+        "lcgs_comm_selftest": (st, [p, p, d, ptr["comm_selftest_report"]]),
+        "lcgs_loopback_group_create": (st, [i, pp]),
+        "lcgs_loopback_group_destroy": (st, [p]),
+        "lcgs_comm_create_loopback": (st, [p, p, i, pp]),
+        # scene ingest / image egress
+        "lcgs_ply_read": (st, [s, ptr["scene_host"]]),
+        "lcgs_ply_write_raw": (st, [s, i, p, p, p, p, p, p]),
+        "lcgs_scene_host_free": (None, [ptr["scene_host"]]),
+        "lcgs_synth_scene": (st, [i, u64, i64, i64, p, p, p, p, p]),
+        "lcgs_image_to_rgb8": (None, [i, i, p, p]),
+        "lcgs_image_to_rgb8_device": (st, [p, i, i, p, p]),
+        "lcgs_write_png": (st, [s, i, i, p]),
+    }
+
+
+SIGNATURES = _signatures()
+# every symbol include/lcgs_hip.h declares (checked by tests/test_abi.py)
+EXPORTED_SYMBOLS = list(SIGNATURES)
 
 
 def load_library():
@@ -194,34 +320,9 @@ def load_library():
         raise LcgsError(-1, f"{path} is missing: run luisacomputegaussiansplatting_amd.build_library() "
                             f"(or __graft_entry__.build()); there is no CPU fallback")
     lib = C.CDLL(path)
-    lib.lcgs_version.restype = C.c_char_p
-    lib.lcgs_last_error.restype = C.c_char_p
-    for name in EXPORTED_SYMBOLS:
+    for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(lib, name)
-        if name not in ("lcgs_version", "lcgs_last_error", "lcgs_get_lookat_cam", "lcgs_local_to_world_matrix",
-                        "lcgs_world_to_local_matrix", "lcgs_projection_matrix", "lcgs_scene_host_free",
-                        "lcgs_image_to_rgb8", "lcgs_comm_shard_rows", "lcgs_sparse_message_words", "lcgs_comm_owner_rows"):
-            fn.restype = C.c_int
-    lib.lcgs_get_lookat_cam.restype = None
-    lib.lcgs_local_to_world_matrix.restype = None
-    lib.lcgs_world_to_local_matrix.restype = None
-    lib.lcgs_projection_matrix.restype = None
-    lib.lcgs_scene_host_free.restype = None
-    lib.lcgs_image_to_rgb8.restype = None
-    lib.lcgs_comm_shard_rows.restype = None
-    lib.lcgs_comm_owner_rows.restype = None
-    lib.lcgs_sparse_message_words.restype = C.c_int64
-    lib.lcgs_sparse_message_words.argtypes = [C.c_int64, C.c_int]
-    lib.lcgs_comm_shard_rows.argtypes = [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.lcgs_projection_matrix.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float)]
-    pp, ps = C.POINTER(_Params), C.POINTER(_DensifyStats)
-    lib.lcgs_densify_accumulate.argtypes = [C.c_void_p, C.c_int, ps]
-    lib.lcgs_densify.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DensifyConfig), ps, pp, pp, pp, pp, pp, pp, pp, ps,
-                                 C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
-    lib.lcgs_opacity_reset.argtypes = [C.c_void_p, C.c_int, C.c_float, pp, pp, pp, pp]
-    lib.lcgs_photometric_loss_backward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
-                                                   C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.lcgs_set_fit_loss.argtypes = [C.c_void_p, C.c_int, C.c_float]
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -248,6 +349,25 @@ def _ptr(t) -> C.c_void_p:
         assert t.flags["C_CONTIGUOUS"]
         return C.c_void_p(t.ctypes.data)
     raise TypeError(type(t))
+
+
+def _grads(g) -> _Grads:
+    """lcgs_grads of a dict with the keys pos / scale / rotq / sh / opacity, or of the five buffers in that order"""
+    return _Grads(*[_ptr(t) for t in ([g[k] for k in _KEYS] if isinstance(g, dict) else g)])
+
+
+def _params(*dicts, partial: bool = False) -> list:
+    """one lcgs_params per dict (keys as above; partial: a missing key is a NULL member)"""
+    return [_Params(*[_ptr(d.get(k) if partial else d[k]) for k in _KEYS]) for d in dicts]
+
+
+def _densify_stats(d: dict) -> _DensifyStats:
+    return _DensifyStats(_ptr(d["grad_accum"]), _ptr(d["denom"]), _ptr(d["max_radii"]))
+
+
+def _adam_config(lr: dict, betas, eps: float, step: int, visible_only: int) -> _AdamConfig:
+    return _AdamConfig(lr["pos"], lr["sh_dc"], lr["sh_rest"], lr["opacity"], lr["scale"], lr["rot"], betas[0], betas[1], eps,
+                       int(step), int(visible_only))
 
 
 # ---------------------------------------------------------------------------------------------- camera
@@ -279,8 +399,7 @@ def world_to_local_matrix(cam: Camera) -> np.ndarray:
 
 
 def projection_matrix(tanfovx: float, tanfovy: float, znear: float = 0.1, zfar: float = 100.0) -> np.ndarray:
-    return _mat(load_library().lcgs_projection_matrix, C.c_float(tanfovx), C.c_float(tanfovy), C.c_float(znear),
-                C.c_float(zfar))
+    return _mat(load_library().lcgs_projection_matrix, tanfovx, tanfovy, znear, zfar)
 
 
 # ---------------------------------------------------------------------------------------------- context
@@ -298,7 +417,7 @@ class Context:
             except ImportError:
                 stream = 0
         self._h = C.c_void_p(0)
-        _check(lib.lcgs_create(C.c_int(device_id), C.c_void_p(stream or 0), C.byref(self._h)))
+        _check(lib.lcgs_create(device_id, stream, C.byref(self._h)))
         self.device_id = device_id
 
     def close(self):
@@ -316,28 +435,27 @@ class Context:
         _check(load_library().lcgs_synchronize(self._h))
 
     def set_stream(self, stream: int):
-        _check(load_library().lcgs_set_stream(self._h, C.c_void_p(stream)))
+        _check(load_library().lcgs_set_stream(self._h, stream))
 
     def set_stage_mode(self, mode: str):
         """lcgs_set_stage_mode: "exact" (default: every operator runs at once and leaves the reference's buffers behind) or
         "deferred" (process / forward are recorded, a matching splatter call renders the fused frame instead)"""
-        _check(load_library().lcgs_set_stage_mode(self._h, C.c_int({"exact": 0, "deferred": 1}[mode])))
+        _check(load_library().lcgs_set_stage_mode(self._h, {"exact": 0, "deferred": 1}[mode]))
 
     def stage_flush(self):
         _check(load_library().lcgs_stage_flush(self._h))
 
     def blend_exp(self, d_x, d_out, n: int):
         """diagnostics: the compositing loop's exp (gs_math.hpp::blend_exp) over n device values"""
-        _check(load_library().lcgs_debug_blend_exp(self._h, _ptr(d_x), _ptr(d_out), C.c_int64(n)))
+        _check(load_library().lcgs_debug_blend_exp(self._h, _ptr(d_x), _ptr(d_out), n))
 
     # lcpp primitives
     def inclusive_sum(self, d_in, d_out, n: int):
-        _check(load_library().lcgs_inclusive_sum_u32(self._h, _ptr(d_in), _ptr(d_out), C.c_int64(n)))
+        _check(load_library().lcgs_inclusive_sum_u32(self._h, _ptr(d_in), _ptr(d_out), n))
 
     def sort_pairs(self, keys_in, keys_out, vals_in, vals_out, n: int, begin_bit: int = 0, end_bit: int = 64):
         _check(load_library().lcgs_sort_pairs_u64_u32(self._h, _ptr(keys_in), _ptr(keys_out), _ptr(vals_in),
-                                                      _ptr(vals_out), C.c_int64(n), C.c_int(begin_bit),
-                                                      C.c_int(end_bit)))
+                                                      _ptr(vals_out), n, begin_bit, end_bit))
 
 
 _default_ctx: Optional[Context] = None
@@ -419,8 +537,8 @@ class SHProcessor:
     def process(self, proxy: GPUPointsProxy, camera: Camera, sh, color, channel: int = 3, level: int = 3):
         if self.ctx is None:
             raise LcgsError(-1, "SHProcessor.create() was not called")
-        _check(load_library().lcgs_sh_process(self.ctx._h, C.c_int(proxy.N), _ptr(proxy.pos), C.byref(camera),
-                                              _ptr(sh), _ptr(color), C.c_int(level), C.c_int(channel)))
+        _check(load_library().lcgs_sh_process(self.ctx._h, proxy.N, _ptr(proxy.pos), C.byref(camera), _ptr(sh), _ptr(color),
+                                              level, channel))
 
 
 class GSProjector:
@@ -437,9 +555,8 @@ class GSProjector:
         if self.ctx is None:
             raise LcgsError(-1, "GSProjector.create() was not called")
         _check(load_library().lcgs_project_forward(
-            self.ctx._h, C.c_int(input.num_gaussians), _ptr(input.pos), _ptr(input.scale), _ptr(input.rotq),
-            C.c_float(input.scale_modifier), _ptr(output.means_2d), _ptr(output.covs_2d), _ptr(output.depth),
-            C.byref(cam), C.c_int(1 if use_focal else 0)))
+            self.ctx._h, input.num_gaussians, _ptr(input.pos), _ptr(input.scale), _ptr(input.rotq), input.scale_modifier,
+            _ptr(output.means_2d), _ptr(output.covs_2d), _ptr(output.depth), C.byref(cam), bool(use_focal)))
 
 
 class GSTileSplatter:
@@ -468,8 +585,8 @@ class GSTileSplatter:
         o = _TileOutput(int(output.height), int(output.width), _ptr(output.target_img), _ptr(output.radii),
                         _ptr(output.final_T), _ptr(output.n_contrib))
         n = C.c_int(0)
-        _check(load_library().lcgs_tile_splat_forward(self.ctx._h, C.byref(a), C.byref(i), C.byref(o),
-                                                      C.c_int(1 if use_focal else 0), C.byref(n)))
+        _check(load_library().lcgs_tile_splat_forward(self.ctx._h, C.byref(a), C.byref(i), C.byref(o), bool(use_focal),
+                                                      C.byref(n)))
         self.num_rendered = n.value
         return n.value
 
@@ -492,18 +609,17 @@ class Renderer:
         self._keep = [pos, scale, rotq, sh, opacity]
         self.P, self.sh_degree = P, sh_degree
         self._generation += 1
-        _check(load_library().lcgs_scene_bind(self.ctx._h, C.c_int(P), C.c_int(sh_degree), _ptr(pos), _ptr(scale),
-                                              _ptr(rotq), _ptr(sh), _ptr(opacity)))
+        _check(load_library().lcgs_scene_bind(self.ctx._h, P, sh_degree, _ptr(pos), _ptr(scale), _ptr(rotq), _ptr(sh),
+                                              _ptr(opacity)))
 
     def declare_static(self, pos=None, scale=None, rotq=None):
         """lcgs_scene_declare_static: caller-owned arrays that do not change between frames get the cull pass's 16-byte
         {position, extent bound} rows (what a context-owned scene has by itself).  No arguments: withdraw."""
         if pos is None:
-            _check(load_library().lcgs_scene_declare_static(self.ctx._h, C.c_int(0), None, None, None))
+            _check(load_library().lcgs_scene_declare_static(self.ctx._h, 0, None, None, None))
             return
         self._static = [pos, scale, rotq]
-        _check(load_library().lcgs_scene_declare_static(self.ctx._h, C.c_int(int(pos.shape[0])), _ptr(pos), _ptr(scale),
-                                                        _ptr(rotq)))
+        _check(load_library().lcgs_scene_declare_static(self.ctx._h, int(pos.shape[0]), _ptr(pos), _ptr(scale), _ptr(rotq)))
 
     def reorder_scene_spatial(self):
         """lcgs_scene_reorder_spatial: the context re-orders its scene along a Morton curve and renders from its own
@@ -516,22 +632,24 @@ class Renderer:
         self._keep = None  # the caller's arrays are no longer read
         return perm
 
+    def _set_ingest_order(self, order: Optional[str]):
+        if order is not None:
+            _check(load_library().lcgs_set_ingest_order(self.ctx._h, {"file": 0, "spatial": 1}[order]))
+
     def upload_scene(self, scene: dict, sh_degree: int = 3, order: Optional[str] = None):
         """lcgs_scene_upload: host arrays -> device copies owned by the context, kept in spatial order by default
         (order="file" keeps the given order); see permutation() / scene_tensors()."""
-        if order is not None:
-            _check(load_library().lcgs_set_ingest_order(self.ctx._h, C.c_int({"file": 0, "spatial": 1}[order])))
-        arrs = [np.ascontiguousarray(scene[k], dtype=np.float32) for k in ("pos", "scale", "rotq", "sh", "opacity")]
+        self._set_ingest_order(order)
+        arrs = [np.ascontiguousarray(scene[k], dtype=np.float32) for k in _KEYS]
         P = int(arrs[0].reshape(-1, 3).shape[0])
         self.P, self.sh_degree = P, sh_degree
         self._generation += 1
-        _check(load_library().lcgs_scene_upload(self.ctx._h, C.c_int(P), C.c_int(sh_degree), *[_ptr(a) for a in arrs]))
+        _check(load_library().lcgs_scene_upload(self.ctx._h, P, sh_degree, *[_ptr(a) for a in arrs]))
 
     def load_ply(self, path: str, order: Optional[str] = None) -> int:
         """read_gs_ply + upload with the de-interleave / activations on the device (lcgs_scene_load_ply).  order:
         "spatial" (the library's default: the context keeps its scene along a Morton curve) or "file"."""
-        if order is not None:
-            _check(load_library().lcgs_set_ingest_order(self.ctx._h, C.c_int({"file": 0, "spatial": 1}[order])))
+        self._set_ingest_order(order)
         n = C.c_int(0)
         _check(load_library().lcgs_scene_load_ply(self.ctx._h, path.encode(), C.byref(n)))
         self.P, self.sh_degree, self._keep = n.value, 3, []
@@ -552,12 +670,12 @@ class Renderer:
         The C ABI hands these out as const: the context keeps data derived from them (include/lcgs_hip.h).  torch has no
         read-only tensors, so the views are writable -- after writing them in place by anything but the library's own
         optimiser steps, call scene_modified(), or frames cull from stale rows (verify_derived() is the test-mode guard)."""
-        ptrs = [C.c_void_p() for _ in range(5)]
+        ptrs = [C.c_void_p() for _ in _KEYS]
         n, deg = C.c_int(0), C.c_int(0)
         _check(load_library().lcgs_scene_pointers(self.ctx._h, C.byref(n), C.byref(deg), *[C.byref(p) for p in ptrs]))
         P, feat = n.value, (deg.value + 1) ** 2 * 3
         shapes = {"pos": (P, 3), "scale": (P, 3), "rotq": (P, 4), "sh": (P, feat), "opacity": (P,)}
-        return {k: self._device_view(p.value, shapes[k], "<f4") for k, p in zip(("pos", "scale", "rotq", "sh", "opacity"), ptrs)}
+        return {k: self._device_view(p.value, shapes[k], "<f4") for k, p in zip(_KEYS, ptrs)}
 
     def scene_modified(self):
         """lcgs_scene_modified: the bound arrays were written behind the library's back; derived data is dropped / rebuilt."""
@@ -577,12 +695,12 @@ class Renderer:
 
     def use_half_sh(self, enable: bool = True):
         """lcgs_scene_use_half_sh: opt-in f16 copy of the SH coefficients for the fused forward (outside the 1e-4 bar)."""
-        _check(load_library().lcgs_scene_use_half_sh(self.ctx._h, C.c_int(1 if enable else 0)))
+        _check(load_library().lcgs_scene_use_half_sh(self.ctx._h, bool(enable)))
 
     def set_lod(self, min_radius_px: int):
         """lcgs_set_lod: opt-in footprint cull (0 = off): splats whose reference radius is below min_radius_px pixels are
         dropped from the fused frame.  Changes the image; never the default."""
-        _check(load_library().lcgs_set_lod(self.ctx._h, C.c_int(int(min_radius_px))))
+        _check(load_library().lcgs_set_lod(self.ctx._h, int(min_radius_px)))
 
     def download_scene(self) -> dict:
         """Host copies of the bound scene (same keys and shapes as read_gs_ply)."""
@@ -590,17 +708,15 @@ class Renderer:
         out = {"pos": np.zeros((P, 3), np.float32), "scale": np.zeros((P, 3), np.float32),
                "rotq": np.zeros((P, 4), np.float32), "sh": np.zeros((P, feat), np.float32),
                "opacity": np.zeros((P,), np.float32)}
-        _check(load_library().lcgs_scene_download(self.ctx._h, *[_ptr(out[k]) for k in
-                                                                  ("pos", "scale", "rotq", "sh", "opacity")]))
+        _check(load_library().lcgs_scene_download(self.ctx._h, *[_ptr(out[k]) for k in _KEYS]))
         return out
 
     def forward(self, cam: Camera, img, bg=(0.0, 0.0, 0.0), scale_modifier: float = 1.0, radii=None,
                 keep_state: bool = False, sync: bool = True) -> Optional[int]:
         n = C.c_int(0)
         self._generation += 1
-        _check(load_library().lcgs_render_forward(self.ctx._h, C.byref(cam), _f3(bg), C.c_float(scale_modifier),
-                                                  _ptr(img), _ptr(radii), C.c_int(1 if keep_state else 0),
-                                                  C.byref(n) if sync else None))
+        _check(load_library().lcgs_render_forward(self.ctx._h, C.byref(cam), _f3(bg), scale_modifier, _ptr(img), _ptr(radii),
+                                                  bool(keep_state), C.byref(n) if sync else None))
         return n.value if sync else None
 
     def forward_batch(self, cams, imgs, bg=(0.0, 0.0, 0.0), scale_modifier: float = 1.0):
@@ -610,8 +726,7 @@ class Renderer:
         cam_arr = (Camera * n)(*cams)
         ptrs = (C.c_void_p * n)(*[_ptr(t).value for t in imgs])
         self._generation += 1
-        _check(load_library().lcgs_render_forward_batch(self.ctx._h, C.c_int(n), cam_arr, _f3(bg),
-                                                        C.c_float(scale_modifier), ptrs))
+        _check(load_library().lcgs_render_forward_batch(self.ctx._h, n, cam_arr, _f3(bg), scale_modifier, ptrs))
 
     def backward(self, dL_dimg, dpos, dscale, drotq, dsh, dopacity, compact: bool = False, accumulate: bool = False):
         """lcgs_render_backward; compact=True: lcgs_render_backward_compact (row r = the frame's r-th on-screen
@@ -619,7 +734,7 @@ class Renderer:
         rows added to what the arrays hold: a further view of a multi-view batch)."""
         if compact and accumulate:
             raise ValueError("compact rows belong to one frame: they cannot be accumulated over views")
-        g = _Grads(_ptr(dpos), _ptr(dscale), _ptr(drotq), _ptr(dsh), _ptr(dopacity))
+        g = _grads((dpos, dscale, drotq, dsh, dopacity))
         lib = load_library()
         fn = lib.lcgs_render_backward_compact if compact else (lib.lcgs_render_backward_accumulate if accumulate
                                                                else lib.lcgs_render_backward)
@@ -635,9 +750,9 @@ class Renderer:
             raise ValueError("one target image per camera")
         cam_arr = (Camera * n)(*cams)
         ptrs = (C.c_void_p * n)(*[_ptr(t).value for t in targets])
-        g = _Grads(_ptr(dpos), _ptr(dscale), _ptr(drotq), _ptr(dsh), _ptr(dopacity))
-        _check(load_library().lcgs_fit_views(self.ctx._h, C.c_int(n), cam_arr, _f3(bg), C.c_float(scale_modifier), ptrs,
-                                             C.byref(g), _ptr(losses)))
+        g = _grads((dpos, dscale, drotq, dsh, dopacity))
+        _check(load_library().lcgs_fit_views(self.ctx._h, n, cam_arr, _f3(bg), scale_modifier, ptrs, C.byref(g),
+                                             _ptr(losses)))
         self._generation += 1
 
     # ---- splat ownership: the frame in two halves
@@ -653,9 +768,8 @@ class Renderer:
         out_rows = torch.empty(max(row_count, 1), dtype=torch.int32, device=dev)
         out_recs = torch.empty(max(row_count, 1), self.OWNER_RECORD_FLOATS, dtype=torch.float32, device=dev)
         n = C.c_int(0)
-        _check(load_library().lcgs_owner_project(self.ctx._h, C.c_int(slot), C.byref(cam), C.c_float(scale_modifier),
-                                                 C.c_int(row_first), C.c_int(row_count), C.c_int(1 if keep_state else 0),
-                                                 _ptr(out_rows), _ptr(out_recs), C.byref(n)))
+        _check(load_library().lcgs_owner_project(self.ctx._h, slot, C.byref(cam), scale_modifier, row_first, row_count,
+                                                 bool(keep_state), _ptr(out_rows), _ptr(out_recs), C.byref(n)))
         out_rows, out_recs = out_rows[:n.value], out_recs[:n.value]
         self._generation += 1
         return out_rows, out_recs
@@ -672,17 +786,17 @@ class Renderer:
         # lcgs_owner_project_views: the N pipelines side by side on the context's lanes, joined on its stream
         rows_p = (C.c_void_p * N)(*[o[0].data_ptr() for o in outs])
         recs_p = (C.c_void_p * N)(*[o[1].data_ptr() for o in outs])
-        _check(lib.lcgs_owner_project_views(self.ctx._h, C.c_int(0), C.c_int(N), (Camera * N)(*cams), C.c_float(scale_modifier),
-                                            C.c_int(row_first), C.c_int(row_count), C.c_int(1 if keep_state else 0), rows_p, recs_p))
-        counts = (C.c_int * len(outs))()
-        _check(lib.lcgs_owner_counts(self.ctx._h, C.c_int(0), C.c_int(len(outs)), counts))
+        _check(lib.lcgs_owner_project_views(self.ctx._h, 0, N, (Camera * N)(*cams), scale_modifier, row_first, row_count,
+                                            bool(keep_state), rows_p, recs_p))
+        counts = (C.c_int * N)()
+        _check(lib.lcgs_owner_counts(self.ctx._h, 0, N, counts))
         self._generation += 1
         return [(r[:counts[v]], q[:counts[v]]) for v, (r, q) in enumerate(outs)]
 
     def owner_render(self, cam: "Camera", rows, recs, img, bg=(0.0, 0.0, 0.0), keep_state: bool = True):
         """lcgs_owner_render: the rest of the frame from received records (ascending global rows)"""
-        _check(load_library().lcgs_owner_render(self.ctx._h, C.byref(cam), _f3(bg), C.c_int(int(rows.shape[0])), _ptr(rows),
-                                                _ptr(recs), _ptr(img), C.c_int(1 if keep_state else 0)))
+        _check(load_library().lcgs_owner_render(self.ctx._h, C.byref(cam), _f3(bg), int(rows.shape[0]), _ptr(rows), _ptr(recs),
+                                                _ptr(img), bool(keep_state)))
         self._generation += 1
 
     def owner_render_backward(self, dL_dimg, grads2d):
@@ -691,15 +805,13 @@ class Renderer:
 
     def owner_backward(self, slot: int, grads2d, dpos, dscale, drotq, dsh, dopacity, accumulate: bool):
         """lcgs_owner_backward: the slot's rows' 2-D gradients -> parameter gradients at their rows of the full-size arrays"""
-        g = _Grads(_ptr(dpos), _ptr(dscale), _ptr(drotq), _ptr(dsh), _ptr(dopacity))
-        _check(load_library().lcgs_owner_backward(self.ctx._h, C.c_int(slot), _ptr(grads2d), C.byref(g),
-                                                  C.c_int(1 if accumulate else 0)))
+        g = _grads((dpos, dscale, drotq, dsh, dopacity))
+        _check(load_library().lcgs_owner_backward(self.ctx._h, slot, _ptr(grads2d), C.byref(g), bool(accumulate)))
 
     def l2_loss_backward(self, img, target, dL_dimg, loss):
         """lcgs_l2_loss_backward: loss[0] = mean((img - target)^2), dL_dimg = 2 (img - target) / numel (device tensors)"""
         _, H, W = img.shape
-        _check(load_library().lcgs_l2_loss_backward(self.ctx._h, C.c_int(W), C.c_int(H), _ptr(img), _ptr(target),
-                                                    _ptr(dL_dimg), _ptr(loss)))
+        _check(load_library().lcgs_l2_loss_backward(self.ctx._h, W, H, _ptr(img), _ptr(target), _ptr(dL_dimg), _ptr(loss)))
 
     def photometric_loss_backward(self, img, target, dL_dimg, loss, lambda_dssim: float = 0.2, terms=None):
         """lcgs_photometric_loss_backward: loss[0] = (1 - lambda) mean|img - target| + lambda (1 - SSIM(img, target)), the 3DGS
@@ -707,12 +819,12 @@ class Renderer:
         w.r.t. img; terms (optional, 2 floats) = (L1, SSIM).  Device tensors, img / target CHW float32; the same inputs give
         the same bits."""
         _, H, W = img.shape
-        _check(load_library().lcgs_photometric_loss_backward(self.ctx._h, C.c_int(W), C.c_int(H), _ptr(img), _ptr(target),
-                                                             C.c_float(lambda_dssim), _ptr(dL_dimg), _ptr(loss), _ptr(terms)))
+        _check(load_library().lcgs_photometric_loss_backward(self.ctx._h, W, H, _ptr(img), _ptr(target), lambda_dssim,
+                                                             _ptr(dL_dimg), _ptr(loss), _ptr(terms)))
 
     def set_fit_loss(self, kind: int, lambda_dssim: float = 0.2):
         """lcgs_set_fit_loss: the loss fit_views applies from now on -- LOSS_L2 (default) or LOSS_PHOTOMETRIC"""
-        _check(load_library().lcgs_set_fit_loss(self.ctx._h, C.c_int(kind), C.c_float(lambda_dssim)))
+        _check(load_library().lcgs_set_fit_loss(self.ctx._h, kind, lambda_dssim))
 
     def visible_rows(self):
         """lcgs_visible_rows of the last forward frame: (splat index of every compact row, row count) as a device
@@ -723,17 +835,12 @@ class Renderer:
         _check(load_library().lcgs_visible_rows(self.ctx._h, C.byref(rows), C.byref(count)))
         self.ctx.synchronize()
         n = self.frame_stats()["num_visible"]
-        dev = f"cuda:{self.ctx.device_id}"
         if n == 0:
-            return torch.empty(0, dtype=torch.int32, device=dev)
-
-        class _View:  # the context-owned device array, seen through the CUDA array interface; cloned before returning
-            __cuda_array_interface__ = {"shape": (n,), "typestr": "<i4", "data": (int(rows.value), False), "version": 2}
-
-        return torch.as_tensor(_View(), device=dev).clone()
+            return torch.empty(0, dtype=torch.int32, device=f"cuda:{self.ctx.device_id}")
+        return self._device_view(rows.value, (n,), "<i4").clone()  # the array is the context's: cloned before returning
 
     def set_profiling(self, enabled: bool):
-        _check(load_library().lcgs_set_profiling(self.ctx._h, C.c_int(1 if enabled else 0)))
+        _check(load_library().lcgs_set_profiling(self.ctx._h, bool(enabled)))
 
     def stage_times(self) -> dict:
         t = _StageTimes()
@@ -753,7 +860,7 @@ class Renderer:
 
     def set_list_policy(self, policy: str):
         """lcgs_set_list_policy: "tile" (the reference's per-tile lists), "block" (per 2 x 2 tiles), "auto" (default)"""
-        _check(load_library().lcgs_set_list_policy(self.ctx._h, C.c_int({"tile": 0, "block": 1, "auto": 2}[policy])))
+        _check(load_library().lcgs_set_list_policy(self.ctx._h, {"tile": 0, "block": 1, "auto": 2}[policy]))
 
     def last_state(self, d_final_T, d_n_contrib):
         """lcgs_debug_last_state: per pixel, what the last keep_state frame kept for its backward (final transmittance; 1-based
@@ -768,36 +875,27 @@ class Renderer:
         sh_rest, opacity, scale, rot.  compact_grads (with visible_only): `grads` hold backward(compact=True) rows."""
         if compact_grads and not visible_only:
             raise ValueError("compact gradient rows only exist for the on-screen splats: visible_only must be set")
-        keys = ("pos", "scale", "rotq", "sh", "opacity")
         P = int(raw["pos"].shape[0])
-        cfg = _AdamConfig(lr["pos"], lr["sh_dc"], lr["sh_rest"], lr["opacity"], lr["scale"], lr["rot"], betas[0], betas[1],
-                          eps, int(step), (2 if compact_grads else 1) if visible_only else 0)
-        g = _Grads(*[_ptr(grads[k]) for k in keys])
-        packs = [_Params(*[_ptr(d[k]) for k in keys]) for d in (raw, m, v, activated)]
-        _check(load_library().lcgs_adam_step(self.ctx._h, C.c_int(P), C.c_int(sh_degree), C.byref(cfg), C.byref(g),
-                                             *[C.byref(p) for p in packs]))
-
+        cfg = _adam_config(lr, betas, eps, step, (2 if compact_grads else 1) if visible_only else 0)
+        g, packs = _grads(grads), _params(raw, m, v, activated)
+        _check(load_library().lcgs_adam_step(self.ctx._h, P, sh_degree, C.byref(cfg), C.byref(g), *map(C.byref, packs)))
 
     def backward_adam(self, dL_dimg, raw: dict, m: dict, v: dict, activated: dict, step: int, lr: dict,
                       betas=(0.9, 0.999), eps: float = 1e-15, sh_degree: int = 3):
         """lcgs_render_backward_adam: the backward of the last keep_state frame with the on-screen-only Adam update applied
         where the per-splat gradients are formed -- no gradient arrays (= backward(compact=True) + adam_step(visible_only,
         compact_grads), bit for bit)."""
-        keys = ("pos", "scale", "rotq", "sh", "opacity")
         P = int(raw["pos"].shape[0])
-        cfg = _AdamConfig(lr["pos"], lr["sh_dc"], lr["sh_rest"], lr["opacity"], lr["scale"], lr["rot"], betas[0], betas[1],
-                          eps, int(step), 2)
-        packs = [_Params(*[_ptr(d[k]) for k in keys]) for d in (raw, m, v, activated)]
-        _check(load_library().lcgs_render_backward_adam(self.ctx._h, _ptr(dL_dimg), C.c_int(P), C.c_int(sh_degree),
-                                                        C.byref(cfg), *[C.byref(p) for p in packs]))
-
+        cfg, packs = _adam_config(lr, betas, eps, step, 2), _params(raw, m, v, activated)
+        _check(load_library().lcgs_render_backward_adam(self.ctx._h, _ptr(dL_dimg), P, sh_degree, C.byref(cfg),
+                                                        *map(C.byref, packs)))
 
     # ---- adaptive density control (DESIGN.md 9)
     def densify_accumulate(self, stats: dict):
         """lcgs_densify_accumulate: the last keep_state frame and its backward -> stats["grad_accum"] (float32), ["denom"]
         (int32 bits of a uint32 count), ["max_radii"] (int32), device tensors of P entries, on-screen rows only."""
-        st = _DensifyStats(_ptr(stats["grad_accum"]), _ptr(stats["denom"]), _ptr(stats["max_radii"]))
-        _check(load_library().lcgs_densify_accumulate(self.ctx._h, C.c_int(int(stats["denom"].shape[0])), C.byref(st)))
+        st = _densify_stats(stats)
+        _check(load_library().lcgs_densify_accumulate(self.ctx._h, int(stats["denom"].shape[0]), C.byref(st)))
 
     def densify(self, stats: dict, raw: dict, m: dict, v: dict, out_raw: dict, out_m: dict, out_v: dict, out_activated: dict,
                 out_stats: dict, grad_threshold: float = 2e-4, percent_dense: float = 0.01, scene_extent: float = 1.0,
@@ -808,53 +906,43 @@ class Renderer:
         (default: out_raw["opacity"]'s length).  noise: [P, 2, 3] normals for the split children, None: the built-in sampler
         keyed by seed.  src_row: optional int32 [capacity], output row -> source row.  Raises LcgsError (status 5, .needed = rows)
         when the rewrite does not fit; nothing is written then.  Rebind out_activated and render a synchronising frame next."""
-        keys = ("pos", "scale", "rotq", "sh", "opacity")
         P = int(raw["opacity"].shape[0])
         cap = int(out_raw["opacity"].shape[0]) if capacity is None else int(capacity)
         cfg = _DensifyConfig(grad_threshold, percent_dense, scene_extent, min_opacity, int(max_screen_size), int(seed))
-        packs = [_Params(*[_ptr(d[k]) for k in keys]) for d in (raw, m, v, out_raw, out_m, out_v, out_activated)]
-        st = [_DensifyStats(_ptr(d["grad_accum"]), _ptr(d["denom"]), _ptr(d["max_radii"])) for d in (stats, out_stats)]
+        packs = _params(raw, m, v, out_raw, out_m, out_v, out_activated)
+        st, out_st = _densify_stats(stats), _densify_stats(out_stats)
         n = C.c_int64(0)
-        status = load_library().lcgs_densify(self.ctx._h, C.c_int(P), C.c_int(sh_degree), C.byref(cfg), C.byref(st[0]),
-                                             *[C.byref(p) for p in packs], C.byref(st[1]), C.c_int64(cap), _ptr(noise),
-                                             _ptr(src_row), C.byref(n))
-        if status != 0:
-            err = LcgsError(status, load_library().lcgs_last_error().decode(errors="replace"))
+        try:
+            _check(load_library().lcgs_densify(self.ctx._h, P, sh_degree, C.byref(cfg), C.byref(st), *map(C.byref, packs),
+                                               C.byref(out_st), cap, _ptr(noise), _ptr(src_row), C.byref(n)))
+        except LcgsError as err:
             err.needed = int(n.value)
-            raise err
+            raise
         return int(n.value)
 
     def opacity_reset(self, raw: dict, m: dict, v: dict, activated: dict, max_opacity: float = 0.01):
         """lcgs_opacity_reset: raw opacity = min(raw opacity, logit(max_opacity)), its moments zeroed, activated opacity
         rewritten.  Only the "opacity" entries of the dicts are needed."""
-        keys = ("pos", "scale", "rotq", "sh", "opacity")
         P = int(raw["opacity"].shape[0])
-        packs = [_Params(*[_ptr(d.get(k)) for k in keys]) for d in (raw, m, v, activated)]
-        _check(load_library().lcgs_opacity_reset(self.ctx._h, C.c_int(P), C.c_float(max_opacity), *[C.byref(p) for p in packs]))
+        packs = _params(raw, m, v, activated, partial=True)
+        _check(load_library().lcgs_opacity_reset(self.ctx._h, P, max_opacity, *map(C.byref, packs)))
 
 
-def _adam_config(lr: dict, betas, eps: float, step: int, visible_only: int) -> _AdamConfig:
-    return _AdamConfig(lr["pos"], lr["sh_dc"], lr["sh_rest"], lr["opacity"], lr["scale"], lr["rot"], betas[0], betas[1], eps,
-                       int(step), int(visible_only))
-
-
-_KEYS = ("pos", "scale", "rotq", "sh", "opacity")
+def _rows(fn, num_gaussians: int, world_size: int, rank: int):
+    first, count = C.c_int64(0), C.c_int64(0)
+    fn(num_gaussians, world_size, rank, C.byref(first), C.byref(count))
+    return first.value, count.value
 
 
 def shard_rows(num_gaussians: int, world_size: int, rank: int):
     """lcgs_comm_shard_rows: (first, count) of the rows rank `rank` owns in the sharded optimiser step; the last
     num_gaussians mod world_size rows (the tail) are kept by every rank.  Pure host arithmetic (no GPU needed)."""
-    first, count = C.c_int64(0), C.c_int64(0)
-    load_library().lcgs_comm_shard_rows(C.c_int64(num_gaussians), C.c_int(world_size), C.c_int(rank), C.byref(first),
-                                        C.byref(count))
-    return first.value, count.value
+    return _rows(load_library().lcgs_comm_shard_rows, num_gaussians, world_size, rank)
 
 
 def owner_rows(num_gaussians: int, world_size: int, rank: int):
     """lcgs_comm_owner_rows: (first, count) of the rows a rank OWNS in the ownership step (the tail with the last rank)"""
-    first, count = C.c_int64(0), C.c_int64(0)
-    load_library().lcgs_comm_owner_rows(C.c_int64(num_gaussians), C.c_int(world_size), C.c_int(rank), C.byref(first), C.byref(count))
-    return int(first.value), int(count.value)
+    return _rows(load_library().lcgs_comm_owner_rows, num_gaussians, world_size, rank)
 
 
 class LoopbackGroup:
@@ -864,7 +952,7 @@ class LoopbackGroup:
     def __init__(self, world_size: int):
         self.world_size = world_size
         self._h = C.c_void_p(0)
-        _check(load_library().lcgs_loopback_group_create(C.c_int(world_size), C.byref(self._h)))
+        _check(load_library().lcgs_loopback_group_create(world_size, C.byref(self._h)))
 
     def close(self):
         if self._h:
@@ -883,7 +971,7 @@ class Comm:
         if loopback is not None:  # an in-process communicator: N contexts on one device, one host thread each
             self.ctx, self.rank, self.world_size = ctx, rank, loopback.world_size
             self._h = C.c_void_p(0)
-            _check(lib.lcgs_comm_create_loopback(ctx._h, loopback._h, C.c_int(rank), C.byref(self._h)))
+            _check(lib.lcgs_comm_create_loopback(ctx._h, loopback._h, rank, C.byref(self._h)))
             return
         token = (C.c_char * 128)()
         if rank == 0:
@@ -896,7 +984,7 @@ class Comm:
             C.memmove(token, got, 128)
         self.ctx, self.rank, self.world_size = ctx, rank, world_size
         self._h = C.c_void_p(0)
-        _check(lib.lcgs_comm_create(ctx._h, token, C.c_int(rank), C.c_int(world_size), C.byref(self._h)))
+        _check(lib.lcgs_comm_create(ctx._h, token, rank, world_size, C.byref(self._h)))
 
     def close(self):
         if self._h:
@@ -924,11 +1012,11 @@ class Comm:
         """lcgs_owner_step_forward: the ownership step's first half with its transport -- this rank's rows projected for every
         view, records exchanged (RCCL send / recv, or the loopback), this rank's view rendered into img"""
         arr = (Camera * len(cams))(*cams)
-        _check(load_library().lcgs_owner_step_forward(self.ctx._h, self._h, arr, _f3(bg), C.c_float(scale_modifier), _ptr(img)))
+        _check(load_library().lcgs_owner_step_forward(self.ctx._h, self._h, arr, _f3(bg), scale_modifier, _ptr(img)))
 
     def owner_step_backward(self, dL_dimg, grads: dict):
         """lcgs_owner_step_backward: the view's 2-D gradients back to the owners, parameter gradients at this rank's own rows"""
-        g = _Grads(*[_ptr(grads[k]) for k in _KEYS])
+        g = _grads(grads)
         _check(load_library().lcgs_owner_step_backward(self.ctx._h, self._h, _ptr(dL_dimg), C.byref(g)))
 
     def selftest(self, timeout_s: float = 30.0, check: bool = True) -> dict:
@@ -936,7 +1024,7 @@ class Comm:
         in one group, an ownership step on a 10 000-splat scene with and without read-back -- each phase against timeout_s.
         Returns the report as a dict (`ok`, per-phase `*_ok` / `*_ms`, `timed_out`, `message`); check=True raises on failure."""
         rep = _SelftestReport()
-        status = load_library().lcgs_comm_selftest(self.ctx._h, self._h, C.c_double(timeout_s), C.byref(rep))
+        status = load_library().lcgs_comm_selftest(self.ctx._h, self._h, timeout_s, C.byref(rep))
         out = {"ok": status == 0, "world_size": int(rep.world_size), "rank": int(rep.rank),
                "allreduce_ok": int(rep.allreduce_ok), "allreduce_ms": round(float(rep.allreduce_ms), 3),
                "p2p_ok": int(rep.p2p_ok), "p2p_ms": round(float(rep.p2p_ms), 3),
@@ -950,7 +1038,7 @@ class Comm:
     def owner_step_set_async(self, enable: bool = True):
         """lcgs_owner_step_set_async: steps size their messages from the previous step's counts and read nothing back; every
         such step must be closed with owner_step_finish()"""
-        _check(load_library().lcgs_owner_step_set_async(self._h, C.c_int(1 if enable else 0)))
+        _check(load_library().lcgs_owner_step_set_async(self._h, bool(enable)))
 
     def owner_step_finish(self) -> bool:
         """lcgs_owner_step_finish: True = some rank's step was short (a clipped message, truncated pairs): EVERY rank calls
@@ -966,34 +1054,33 @@ class Comm:
             self.owner_step_backward(dL_dimg, grads)
             if not self.owner_step_finish():
                 return attempt
-        raise LcgsError("the ownership step did not settle after two repetitions")
+        raise LcgsError(LCGS_ERR_STATE, "the ownership step did not settle after two repetitions")
 
     def set_transport(self, transport: str):
         """lcgs_comm_set_transport: "f32" (default, exact) or "f16" (opt-in: half the bytes, ~sqrt(N) x 5e-4 relative)"""
-        _check(load_library().lcgs_comm_set_transport(self._h, C.c_int({"f32": 0, "f16": 1}[transport])))
+        _check(load_library().lcgs_comm_set_transport(self._h, {"f32": 0, "f16": 1}[transport]))
 
     def allreduce_grads(self, grads: dict, sh_degree: int = 3):
         """lcgs_grads_allreduce: in-place sum over the ranks of the five dense gradient arrays (chunked, overlapping the
         backward's tail); the context's stream waits for the result."""
         P = int(grads["pos"].shape[0])
-        g = _Grads(*[_ptr(grads[k]) for k in _KEYS])
-        _check(load_library().lcgs_grads_allreduce(self.ctx._h, self._h, C.c_int(P), C.c_int(sh_degree), C.byref(g)))
+        g = _grads(grads)
+        _check(load_library().lcgs_grads_allreduce(self.ctx._h, self._h, P, sh_degree, C.byref(g)))
+
+    def _adam_step(self, fn, grads, raw, m, v, activated, step, lr, betas, eps, sh_degree):
+        P = int(raw["pos"].shape[0])
+        cfg, g, packs = _adam_config(lr, betas, eps, step, 0), _grads(grads), _params(raw, m, v, activated)
+        _check(fn(self.ctx._h, self._h, P, sh_degree, C.byref(cfg), C.byref(g), *map(C.byref, packs)))
 
     def adam_step_sharded(self, grads: dict, raw: dict, m: dict, v: dict, activated: dict, step: int, lr: dict,
                           betas=(0.9, 0.999), eps: float = 1e-15, sh_degree: int = 3):
         """lcgs_adam_step_sharded: reduce-scatter -> Adam on the own rows (+ tail) -> all-gather of the activated arrays."""
-        P = int(raw["pos"].shape[0])
-        cfg = _adam_config(lr, betas, eps, step, 0)
-        g = _Grads(*[_ptr(grads[k]) for k in _KEYS])
-        packs = [_Params(*[_ptr(d[k]) for k in _KEYS]) for d in (raw, m, v, activated)]
-        _check(load_library().lcgs_adam_step_sharded(self.ctx._h, self._h, C.c_int(P), C.c_int(sh_degree), C.byref(cfg),
-                                                     C.byref(g), *[C.byref(p) for p in packs]))
-
+        self._adam_step(load_library().lcgs_adam_step_sharded, grads, raw, m, v, activated, step, lr, betas, eps, sh_degree)
 
     # ---- sparse gradient exchange (lcgs_hip.h "Sparse gradient exchange")
     def track_touched_rows(self, enable: bool = True):
         """lcgs_comm_track_touched_rows: dense backward passes on this context flag the rows their frame touched"""
-        _check(load_library().lcgs_comm_track_touched_rows(self._h, C.c_int(1 if enable else 0)))
+        _check(load_library().lcgs_comm_track_touched_rows(self._h, bool(enable)))
 
     def stats(self) -> dict:
         """lcgs_comm_get_stats: what the last collective call of this communicator moved (per GPU, from actual counts)"""
@@ -1005,50 +1092,35 @@ class Comm:
     def adam_step_sparse(self, grads: dict, raw: dict, m: dict, v: dict, activated: dict, step: int, lr: dict,
                          betas=(0.9, 0.999), eps: float = 1e-15, sh_degree: int = 3):
         """lcgs_adam_step_sparse: touched rows -> their owners (send / recv) -> Adam on the own rows -> all-gather"""
-        P = int(raw["pos"].shape[0])
-        cfg = _adam_config(lr, betas, eps, step, 0)
-        g = _Grads(*[_ptr(grads[k]) for k in _KEYS])
-        packs = [_Params(*[_ptr(d[k]) for k in _KEYS]) for d in (raw, m, v, activated)]
-        _check(load_library().lcgs_adam_step_sparse(self.ctx._h, self._h, C.c_int(P), C.c_int(sh_degree), C.byref(cfg),
-                                                    C.byref(g), *[C.byref(p) for p in packs]))
+        self._adam_step(load_library().lcgs_adam_step_sparse, grads, raw, m, v, activated, step, lr, betas, eps, sh_degree)
 
     def sparse_touched_rows(self, num_gaussians: int, world_size: Optional[int] = None):
         """lcgs_sparse_touched_rows -> (device address of the ascending row list, owner_first[0 .. N + 1]) for an exchange
         over `world_size` ranks (default: the communicator's own); consumes the step's touched set and synchronises"""
         n = self.world_size if world_size is None else world_size
         out = _SparseRows()
-        _check(load_library().lcgs_sparse_touched_rows(self.ctx._h, self._h, C.c_int(num_gaussians), C.c_int(n), C.byref(out)))
+        _check(load_library().lcgs_sparse_touched_rows(self.ctx._h, self._h, num_gaussians, n, C.byref(out)))
         return int(out.d_rows or 0), [int(out.owner_first[i]) for i in range(n + 2)]
 
     def sparse_pack(self, grads: dict, rows_addr: int, first: int, count: int, msg, sh_degree: int = 3):
         """lcgs_sparse_pack: rows [first, first + count) of the touched list -> one message (a float32 tensor of
         sparse_message_words(count) elements)"""
-        g = _Grads(*[_ptr(grads[k]) for k in _KEYS])
-        _check(load_library().lcgs_sparse_pack(self.ctx._h, C.c_int(sh_degree), C.byref(g), C.c_void_p(rows_addr + 4 * first),
-                                               C.c_int64(count), _ptr(msg)))
+        g = _grads(grads)
+        _check(load_library().lcgs_sparse_pack(self.ctx._h, sh_degree, C.byref(g), rows_addr + 4 * first, count, _ptr(msg)))
 
     def sparse_accumulate(self, grads: dict, msg, count: int, sh_degree: int = 3, row_first: int = 0, row_count: int = -1):
         """lcgs_sparse_accumulate: add a received message's rows to the dense gradient rows; only rows in
         [row_first, row_first + row_count) are accepted (default: every row of the arrays)"""
-        g = _Grads(*[_ptr(grads[k]) for k in _KEYS])
+        g = _grads(grads)
         if row_count < 0:
             row_first, row_count = 0, int(grads["pos"].shape[0])
-        _check(load_library().lcgs_sparse_accumulate(self.ctx._h, C.c_int(sh_degree), C.byref(g), _ptr(msg), C.c_int64(count),
-                                                     C.c_int64(row_first), C.c_int64(row_count)))
+        _check(load_library().lcgs_sparse_accumulate(self.ctx._h, sh_degree, C.byref(g), _ptr(msg), count, row_first,
+                                                     row_count))
 
 
 def sparse_message_words(count: int, sh_degree: int = 3) -> int:
     """4-byte words of a sparse-exchange message of `count` rows: indices + the five attribute blocks"""
     return count * (1 + 3 + 3 + 4 + (sh_degree + 1) ** 2 * 3 + 1)
-
-
-class _SparseRows(C.Structure):
-    _fields_ = [("d_rows", C.c_void_p), ("num_rows", C.c_int64), ("owner_first", C.c_int64 * 66)]
-
-
-class _CommStats(C.Structure):
-    _fields_ = [("bytes_sent", C.c_int64), ("bytes_received", C.c_int64), ("touched_rows", C.c_int64),
-                ("collective_groups", C.c_int)]
 
 
 def render_autograd(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh, opacity, bg=(0.0, 0.0, 0.0),
@@ -1121,7 +1193,7 @@ def read_gs_ply(path: str) -> dict:
 def write_ply_raw(path: str, pos, f_dc, f_rest, opacity_logit, log_scale, rot):
     a = [np.ascontiguousarray(x, dtype=np.float32) for x in (pos, f_dc, f_rest, opacity_logit, log_scale, rot)]
     P = int(a[0].reshape(-1, 3).shape[0])
-    _check(load_library().lcgs_ply_write_raw(path.encode(), C.c_int(P), *[_ptr(x) for x in a]))
+    _check(load_library().lcgs_ply_write_raw(path.encode(), P, *[_ptr(x) for x in a]))
 
 
 def synth_scene(kind: int, seed: int, count: int, first: int = 0) -> dict:
@@ -1131,8 +1203,7 @@ def synth_scene(kind: int, seed: int, count: int, first: int = 0) -> dict:
         "opacity": np.empty((count,), np.float32), "scale": np.empty((count, 3), np.float32),
         "rotq": np.empty((count, 4), np.float32),
     }
-    _check(load_library().lcgs_synth_scene(C.c_int(kind), C.c_uint64(seed), C.c_int64(first), C.c_int64(count),
-                                           _ptr(out["pos"]), _ptr(out["sh"]), _ptr(out["opacity"]),
+    _check(load_library().lcgs_synth_scene(kind, seed, first, count, _ptr(out["pos"]), _ptr(out["sh"]), _ptr(out["opacity"]),
                                            _ptr(out["scale"]), _ptr(out["rotq"])))
     return out
 
@@ -1142,11 +1213,11 @@ def image_to_rgb8(img_chw: np.ndarray) -> np.ndarray:
     img = np.ascontiguousarray(img_chw, dtype=np.float32)
     _, H, W = img.shape
     out = np.empty((H, W, 3), np.uint8)
-    load_library().lcgs_image_to_rgb8(C.c_int(W), C.c_int(H), _ptr(img), _ptr(out))
+    load_library().lcgs_image_to_rgb8(W, H, _ptr(img), _ptr(out))
     return out
 
 
 def write_png(path: str, rgb: np.ndarray):
     rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
     H, W, _ = rgb.shape
-    _check(load_library().lcgs_write_png(path.encode(), C.c_int(W), C.c_int(H), _ptr(rgb)))
+    _check(load_library().lcgs_write_png(path.encode(), W, H, _ptr(rgb)))
