@@ -309,6 +309,43 @@ LCGS_API lcgs_status lcgs_densify(lcgs_context* ctx, int num_gaussians, int sh_d
 LCGS_API lcgs_status lcgs_opacity_reset(lcgs_context* ctx, int num_gaussians, float max_opacity /* 3DGS: 0.01 */, const lcgs_params* raw,
                                         const lcgs_params* m, const lcgs_params* v, const lcgs_params* activated);
 
+/* ---- a scene from a point cloud (no reference counterpart: app/gaussians.cpp only loads trained PLYs) -------- */
+/* The mean squared distance to the three nearest neighbours, of n points p_i (binary32, AoS xyz xyz ...):
+ *   valid       a point is valid if all three coordinates are finite; an invalid point is nobody's neighbour
+ *   d2(i, j)    for valid i and valid j != i (another INDEX: coincident points are each other's neighbours at distance 0):
+ *               ((dx dx + dy dy) + dz dz), dx = p_i.x - p_j.x etc., every operation binary32 round-to-nearest, nothing contracted
+ *   a <= b <= c the m = min(3, valid others) smallest values of d2(i, .), as a multiset (ties are equal values: harmless)
+ *   dist2_i     ((a + b) + c) / 3.0f for m = 3;  (a + b) / 2.0f for m = 2;  a for m = 1;  0.0f for m = 0 or an invalid i
+ * The search is EXACT with respect to these computed binary32 values: dist2_i is a pure function of the multiset of points --
+ * independent of input order, launch shape, chunking and context; same inputs -> same bits, equal bit for bit to a brute-force
+ * binary32 restatement.  (What simple-knn's distCUDA2 computes, made exact and order-independent.) */
+#define LCGS_KNN_CHUNK 256 /* sorted points per query workgroup: sizes around its multiples are the kernels' edge cases */
+/* d_dist2[i] = dist2_i.  Device pointers; only enqueues.  num_points < 0 or > 2^31 - 1: LCGS_ERR_INVALID_ARG; 0: nothing is touched. */
+LCGS_API lcgs_status lcgs_knn_mean_dist2(lcgs_context* ctx, int64_t num_points, const float* d_pos, float* d_dist2);
+typedef struct lcgs_init_config {
+    float initial_opacity; /* 3DGS: 0.1; must lie in (0, 1) */
+    float min_dist2;       /* 3DGS: 1e-7; must be > 0 */
+} lcgs_init_config;
+/* 3DGS's create_from_pcd.  d_rgb: [n][3] in [0, 1].  Row i of out_raw / out_activated (layouts of lcgs_params; pos / sh of the two
+ * packs may alias):
+ *   pos          p_i (copied bit for bit)
+ *   raw scale    logf(sqrtf(fmaxf(dist2_i, min_dist2))) in all three components;  activated: the optimiser step's exp of it
+ *   raw rotq     (1, 0, 0, 0);  activated the same
+ *   sh           coefficient 0 = (rgb - 0.5f) / 0.28209479177387814f per channel, every other coefficient of the (deg+1)^2 exactly 0
+ *   raw opacity  log(p / (1 - p)), p = (double)initial_opacity, rounded once to binary32 on the host;  activated: the optimiser
+ *                step's sigmoid of it
+ * Moments are the caller's to zero.  The scene binding is not changed.  Only enqueues. */
+LCGS_API lcgs_status lcgs_scene_init_from_points(lcgs_context* ctx, int num_points, int sh_degree, const float* d_pos, const float* d_rgb,
+                                                 const lcgs_init_config* cfg, const lcgs_params* out_raw, const lcgs_params* out_activated);
+/* 3DGS's getNerfppNorm, host only: center = mean of the camera positions, *radius = 1.1 max |position - center| (binary64 inside,
+ * each output rounded once) -- the producer of lcgs_densify_config.scene_extent.  num_cameras >= 1. */
+LCGS_API lcgs_status lcgs_scene_extent(int num_cameras, const lcgs_camera* cameras, float center[3], float* radius);
+/* Host reader of a point-cloud PLY (binary little-endian or ascii): element vertex with x y z (float or double) and red green blue
+ * (uchar -> / 255.0f; or float, taken as is); other properties skipped by their declared size.  malloc'd outputs ([n][3] each),
+ * released with lcgs_points_free.  Status codes as lcgs_ply_read (missing file 6, format 7). */
+LCGS_API lcgs_status lcgs_points_read_ply(const char* path, int64_t* num_points, float** pos, float** rgb);
+LCGS_API void        lcgs_points_free(float* pos, float* rgb);
+
 /* ---- multi-GPU (no reference counterpart: one device, app/main.cpp:162-163) ------------------------ */
 /* One process per GPU, scene replicated, one view per GPU; RCCL is bound at run time (absent: LCGS_ERR_NO_DEVICE). */
 typedef struct lcgs_comm lcgs_comm;

@@ -29,12 +29,15 @@ from .api import (  # noqa: F401
     build_library,
     get_lookat_cam,
     image_to_rgb8,
+    knn_mean_dist2,
     library_path,
     load_library,
     local_to_world_matrix,
     projection_matrix,
     read_gs_ply,
+    read_points_ply,
     render_autograd,
+    scene_extent,
     shard_rows,
     synth_scene,
     world_to_local_matrix,

@@ -51,6 +51,7 @@ def build_library(force: bool = False) -> str:
 # constants of include/lcgs_hip.h the mirrors and the wrappers need
 LCGS_MAX_STAGES, LCGS_MAX_RANKS = 16, 64
 LCGS_ERR_STATE = 8
+LCGS_KNN_CHUNK = 256  # sorted points per query workgroup of the nearest-neighbour search (sizes around its multiples are edge cases)
 # lcgs_set_fit_loss kinds (LCGS_LOSS_* in include/lcgs_hip.h)
 LOSS_L2, LOSS_PHOTOMETRIC = 0, 1
 
@@ -149,6 +150,10 @@ class _DensifyConfig(C.Structure):
                 ("min_opacity", C.c_float), ("max_screen_size", C.c_int), ("seed", C.c_uint64)]
 
 
+class _InitConfig(C.Structure):
+    _fields_ = [("initial_opacity", C.c_float), ("min_dist2", C.c_float)]
+
+
 class _SparseRows(C.Structure):
     _fields_ = [("d_rows", C.c_void_p), ("num_rows", C.c_int64), ("owner_first", C.c_int64 * (LCGS_MAX_RANKS + 2))]
 
@@ -176,6 +181,7 @@ STRUCTS = {
     "lcgs_camera": Camera, "lcgs_tile_accel": _TileAccel, "lcgs_tile_input": _TileInput, "lcgs_tile_output": _TileOutput,
     "lcgs_stage_times": _StageTimes, "lcgs_frame_stats": _FrameStats, "lcgs_grads": _Grads, "lcgs_params": _Params,
     "lcgs_adam_config": _AdamConfig, "lcgs_densify_stats": _DensifyStats, "lcgs_densify_config": _DensifyConfig,
+    "lcgs_init_config": _InitConfig,
     "lcgs_sparse_rows": _SparseRows, "lcgs_comm_stats": _CommStats, "lcgs_comm_selftest_report": _SelftestReport,
     "lcgs_scene_host": _SceneHost,
 }
@@ -255,6 +261,12 @@ def _signatures() -> dict:
         "lcgs_densify_accumulate": (st, [p, i, dstats]),
         "lcgs_densify": (st, [p, i, i, ptr["densify_config"], dstats, *packs, *packs[:3], dstats, i64, p, p, pi64]),
         "lcgs_opacity_reset": (st, [p, i, f, *packs]),
+        # a scene from a point cloud
+        "lcgs_knn_mean_dist2": (st, [p, i64, p, p]),
+        "lcgs_scene_init_from_points": (st, [p, i, i, p, p, ptr["init_config"], *packs[:2]]),
+        "lcgs_scene_extent": (st, [i, cam, p, p]),
+        "lcgs_points_read_ply": (st, [s, pi64, pp, pp]),
+        "lcgs_points_free": (None, [p, p]),
         # multi-GPU
         "lcgs_comm_unique_id": (st, [p]),
         "lcgs_comm_create": (st, [p, p, i, i, pp]),
@@ -926,6 +938,64 @@ class Renderer:
         P = int(raw["opacity"].shape[0])
         packs = _params(raw, m, v, activated, partial=True)
         _check(load_library().lcgs_opacity_reset(self.ctx._h, P, max_opacity, *map(C.byref, packs)))
+
+
+    # ---- a scene from a point cloud
+    def init_from_points(self, pos, rgb, sh_degree: int = 3, initial_opacity: float = 0.1, min_dist2: float = 1e-7):
+        """lcgs_scene_init_from_points, 3DGS's create_from_pcd: device tensors pos [n, 3] and rgb [n, 3] in [0, 1] -> (raw,
+        activated), dicts of fresh device tensors keyed pos / scale / rotq / sh / opacity.  Scales come from the exact mean squared
+        distance to the three nearest neighbours; activated pos / sh ARE raw's.  Nothing is bound; moments are the caller's."""
+        import torch
+
+        n, feat = int(pos.shape[0]), (sh_degree + 1) ** 2 * 3
+        shapes = {"pos": (n, 3), "scale": (n, 3), "rotq": (n, 4), "sh": (n, feat), "opacity": (n,)}
+        raw = {k: torch.empty(shp, dtype=torch.float32, device=pos.device) for k, shp in shapes.items()}
+        act = {k: raw[k] if k in ("pos", "sh") else torch.empty_like(raw[k]) for k in _KEYS}
+        self.init_from_points_into(pos, rgb, raw, act, sh_degree, initial_opacity, min_dist2)
+        return raw, act
+
+    def init_from_points_into(self, pos, rgb, raw: dict, activated: dict, sh_degree: int = 3, initial_opacity: float = 0.1,
+                              min_dist2: float = 1e-7):
+        """the same into the caller's arrays (dicts as in adam_step; activated pos / sh may be raw's or separate buffers)"""
+        cfg = _InitConfig(initial_opacity, min_dist2)
+        packs = _params(raw, activated)
+        _check(load_library().lcgs_scene_init_from_points(self.ctx._h, int(pos.shape[0]), sh_degree, _ptr(pos), _ptr(rgb),
+                                                          C.byref(cfg), *map(C.byref, packs)))
+
+
+def knn_mean_dist2(ctx: Context, pos):
+    """lcgs_knn_mean_dist2: device tensor pos [n, 3] float32 -> device tensor [n], the mean squared distance of every point to
+    its three nearest neighbours (exact in binary32, independent of the order of the points; include/lcgs_hip.h has the definition)"""
+    import torch
+
+    out = torch.empty(int(pos.shape[0]), dtype=torch.float32, device=pos.device)
+    _check(load_library().lcgs_knn_mean_dist2(ctx._h, int(pos.shape[0]), _ptr(pos), _ptr(out)))
+    return out
+
+
+def scene_extent(cameras):
+    """lcgs_scene_extent, 3DGS's getNerfppNorm: (center float32 [3], radius) of a list of Camera -- radius is what
+    Renderer.densify takes as scene_extent"""
+    n = len(cameras)
+    center, radius = np.zeros(3, np.float32), np.zeros(1, np.float32)
+    _check(load_library().lcgs_scene_extent(n, (Camera * max(n, 1))(*cameras), _ptr(center), _ptr(radius)))
+    return center, float(radius[0])
+
+
+def read_points_ply(path: str) -> dict:
+    """lcgs_points_read_ply: a point-cloud PLY (x y z, red green blue) -> {"pos": float32 [n, 3], "rgb": float32 [n, 3] in [0, 1]}"""
+    lib = load_library()
+    n, pos, rgb = C.c_int64(0), C.c_void_p(), C.c_void_p()
+    _check(lib.lcgs_points_read_ply(path.encode(), C.byref(n), C.byref(pos), C.byref(rgb)))
+    try:
+        def grab(p):
+            if n.value == 0:
+                return np.zeros((0, 3), np.float32)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(n.value * 3,)).reshape(n.value, 3).copy()
+
+        return {"pos": grab(pos), "rgb": grab(rgb)}
+    finally:
+        lib.lcgs_points_free(pos, rgb)
 
 
 def _rows(fn, num_gaussians: int, world_size: int, rank: int):

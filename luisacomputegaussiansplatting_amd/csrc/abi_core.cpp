@@ -256,7 +256,9 @@ lcgs_status lcgs_destroy(lcgs_context* ctx)
                              &ctx->expand_ws, &ctx->final_T, &ctx->n_contrib, &ctx->list_idx, &ctx->grads2d, &ctx->tile_order[0], &ctx->tile_order[1], &ctx->st_keys_tmp,
                              &ctx->st_vals_tmp, &ctx->st_sort_temp, &ctx->st_scan_temp, &ctx->st_scalar, &ctx->sh_half, &ctx->strip_masks, &ctx->shjac, &ctx->tie_ws, &ctx->fused_grads, &ctx->bwd_counter, &ctx->st_flags, &ctx->st_keys_exp, &ctx->st_vals_exp,
                              &ctx->st_u32[0], &ctx->st_u32[1], &ctx->st_u32[2], &ctx->st_u32[3], &ctx->st_u32[4], &ctx->st_u32[5], &ctx->st_u32[6], &ctx->st_u32[7],
-                             &ctx->cull_bound_buf, &ctx->verify_ws, &ctx->st_win, &ctx->st_win2, &ctx->st_offs, &ctx->dn_emit, &ctx->dn_incl, &ctx->dn_action };
+                             &ctx->cull_bound_buf, &ctx->verify_ws, &ctx->st_win, &ctx->st_win2, &ctx->st_offs, &ctx->dn_emit, &ctx->dn_incl, &ctx->dn_action,
+                             &ctx->knn_keys[0], &ctx->knn_keys[1], &ctx->knn_vals[0], &ctx->knn_vals[1], &ctx->knn_sort_ws, &ctx->knn_sorted,
+                             &ctx->knn_boxes, &ctx->knn_grid, &ctx->knn_dist2 };
     for (DeviceBuffer* b : bufs) b->release();
     for (auto& s : ctx->owner)
         for (DeviceBuffer* b : { &s.vis, &s.shjac, &s.counts }) b->release();

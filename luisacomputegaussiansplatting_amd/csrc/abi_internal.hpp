@@ -9,6 +9,7 @@
 //   abi_train.cpp     lcgs_adam_step, lcgs_fit_views
 //   abi_densify.cpp   adaptive density control: lcgs_densify_accumulate, lcgs_densify, lcgs_opacity_reset
 //   abi_loss.cpp      lcgs_photometric_loss_backward, lcgs_set_fit_loss
+//   abi_init.cpp      a scene from a point cloud: lcgs_knn_mean_dist2, lcgs_scene_init_from_points, lcgs_scene_extent
 #pragma once
 
 #include "common.hpp"

@@ -152,6 +152,9 @@ struct lcgs_context {
     bool        g2d_backward_done = false;
     // lcgs_densify: emit counts, their inclusive sums, actions (one entry per source row)
     DeviceBuffer dn_emit, dn_incl, dn_action;
+    // lcgs_knn_mean_dist2 / lcgs_scene_init_from_points (abi_init.cpp): Morton keys and original indices (the sort's ping-pong),
+    // the sort's workspace, the sorted points, the per-chunk boxes, the box partials + grid, the init call's dist2
+    DeviceBuffer knn_keys[2], knn_vals[2], knn_sort_ws, knn_sorted, knn_boxes, knn_grid, knn_dist2;
     // lcgs_render_forward_batch: a sibling context (own workspace, own streams) that renders every other view, so
     // that one view's latency-bound sort chain overlaps the other's bandwidth- and VALU-bound kernels
     lcgs_context* twin         = nullptr;

@@ -80,9 +80,20 @@ lcgs_status fail(lcgs_status s, const std::string& msg)
     return s;
 }
 
-// Parses the header (fp is left at the first payload byte) and looks the 59 wanted columns up by name.
+// the 59 columns of a 3DGS scene in the order pos(3) dc(3) rest(45) opacity scale(3) rot(4)
+std::vector<std::string> gs_columns()
+{
+    std::vector<std::string> names = { "x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2" };
+    for (int i = 0; i < 45; ++i) names.push_back("f_rest_" + std::to_string(i));
+    names.push_back("opacity");
+    for (int i = 0; i < 3; ++i) names.push_back("scale_" + std::to_string(i));
+    for (int i = 0; i < 4; ++i) names.push_back("rot_" + std::to_string(i));
+    return names;
+}
+
+// Parses the header (fp is left at the first payload byte) and looks the wanted columns (`names`) up by name.
 lcgs_status parse_header(FILE* fp, std::vector<Prop>& props, int64_t& N, size_t& stride, bool& binary,
-                         std::vector<int>& want)
+                         std::vector<int>& want, const std::vector<std::string>& names)
 {
     props.clear();
     want.clear();
@@ -163,12 +174,6 @@ lcgs_status parse_header(FILE* fp, std::vector<Prop>& props, int64_t& N, size_t&
             if (props[i].name == name) return (int)i;
         return -1;
     };
-    // 59 columns in the order pos(3) dc(3) rest(45) opacity scale(3) rot(4)
-    std::vector<std::string> names = { "x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2" };
-    for (int i = 0; i < 45; ++i) names.push_back("f_rest_" + std::to_string(i));
-    names.push_back("opacity");
-    for (int i = 0; i < 3; ++i) names.push_back("scale_" + std::to_string(i));
-    for (int i = 0; i < 4; ++i) names.push_back("rot_" + std::to_string(i));
     for (auto& n : names) {
         int k = find(n);
         if (k < 0) {
@@ -208,7 +213,7 @@ lcgs_status lcgs_ply_read(const char* path, lcgs_scene_host* out)
     size_t            stride = 0;
     bool              binary = false;
     {
-        lcgs_status hs = parse_header(fp, props, N, stride, binary, want);
+        lcgs_status hs = parse_header(fp, props, N, stride, binary, want, gs_columns());
         if (hs != LCGS_OK) {
             fclose(fp);
             return hs;
@@ -279,6 +284,77 @@ lcgs_status lcgs_ply_read(const char* path, lcgs_scene_host* out)
     return LCGS_OK;
 }
 
+// A point cloud (what SfM leaves behind: COLMAP's points3D as PLY): x y z + red green blue of the vertex element, the same
+// header parser, every other property skipped by its declared size.
+lcgs_status lcgs_points_read_ply(const char* path, int64_t* num_points, float** pos, float** rgb)
+{
+    if (!path || !num_points || !pos || !rgb) return fail(LCGS_ERR_INVALID_ARG, "lcgs_points_read_ply: NULL argument");
+    *num_points = 0;
+    *pos = *rgb = nullptr;
+    FILE* fp = fopen(path, "rb");
+    if (!fp) return fail(LCGS_ERR_IO, std::string("cannot open ") + path);
+    std::vector<Prop> props;
+    std::vector<int>  want;
+    int64_t           N = -1;
+    size_t            stride = 0;
+    bool              binary = false;
+    lcgs_status       hs = parse_header(fp, props, N, stride, binary, want, { "x", "y", "z", "red", "green", "blue" });
+    if (hs == LCGS_OK) {
+        for (int w = 0; w < 3 && hs == LCGS_OK; ++w)
+            if (props[want[w]].type != 6 && props[want[w]].type != 7) hs = fail(LCGS_ERR_FORMAT, "x y z must be float or double");
+        for (int w = 3; w < 6 && hs == LCGS_OK; ++w)
+            if (props[want[w]].type != 1 && props[want[w]].type != 6) hs = fail(LCGS_ERR_FORMAT, "red green blue must be uchar or float");
+    }
+    if (hs != LCGS_OK) {
+        fclose(fp);
+        return hs;
+    }
+    const size_t n1 = (size_t)std::max<int64_t>(N, 1);
+    float*       p  = (float*)malloc(n1 * 3 * sizeof(float));
+    float*       c  = (float*)malloc(n1 * 3 * sizeof(float));
+    auto         drop = [&](lcgs_status st, const char* msg) {
+        fclose(fp);
+        free(p);
+        free(c);
+        return fail(st, msg);
+    };
+    if (!p || !c) return drop(LCGS_ERR_OUT_OF_MEMORY, "host allocation failed");
+    // a colour as the file types it: 8-bit values are v / 255, float values are taken as they are
+    auto colour = [&](int w, float v) { return props[want[w]].type == 1 ? v / 255.0f : v; };
+    if (binary) {
+        std::vector<unsigned char> rec(std::max<size_t>(stride, 1) * 4096);
+        for (int64_t j0 = 0; j0 < N; j0 += 4096) {
+            const size_t rows = (size_t)std::min<int64_t>(4096, N - j0);
+            if (fread(rec.data(), stride, rows, fp) != rows) return drop(LCGS_ERR_FORMAT, "PLY payload is truncated");
+            for (size_t r = 0; r < rows; ++r) {
+                const unsigned char* row = rec.data() + r * stride;
+                for (int w = 0; w < 3; ++w) p[3 * (j0 + r) + w] = load_as_float(row + props[want[w]].offset, props[want[w]].type);
+                for (int w = 3; w < 6; ++w)
+                    c[3 * (j0 + r) + w - 3] = colour(w, load_as_float(row + props[want[w]].offset, props[want[w]].type));
+            }
+        }
+    } else {
+        std::vector<double> row(props.size());
+        for (int64_t j = 0; j < N; ++j) {
+            for (double& v : row)
+                if (fscanf(fp, "%lf", &v) != 1) return drop(LCGS_ERR_FORMAT, "PLY ascii payload is truncated");
+            for (int w = 0; w < 3; ++w) p[3 * j + w] = (float)row[want[w]];
+            for (int w = 3; w < 6; ++w) c[3 * j + w - 3] = colour(w, (float)row[want[w]]);
+        }
+    }
+    fclose(fp);
+    *num_points = N;
+    *pos        = p;
+    *rgb        = c;
+    return LCGS_OK;
+}
+
+void lcgs_points_free(float* pos, float* rgb)
+{
+    free(pos);
+    free(rgb);
+}
+
 lcgs_status lcgs_ply_write_raw(const char* path, int num_gaussians, const float* pos, const float* f_dc,
                                const float* f_rest, const float* opacity_logit, const float* log_scale,
                                const float* rot)
@@ -329,7 +405,7 @@ lcgs_status ply_probe(const char* path, PlyProbe* out)
     std::vector<int>  want;
     bool              binary = false;
     size_t            stride = 0;
-    lcgs_status       hs     = parse_header(fp, props, out->num_vertices, stride, binary, want);
+    lcgs_status       hs     = parse_header(fp, props, out->num_vertices, stride, binary, want, gs_columns());
     if (hs != LCGS_OK) {
         fclose(fp);
         return hs;

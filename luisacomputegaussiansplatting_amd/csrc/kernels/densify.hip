@@ -10,6 +10,7 @@
 // HBM-bound once-through work like train.hip: one thread per source element (16 bytes where the layout allows), streaming
 // loads of the source, destination offsets monotone in the source index (coalesced stores), the zero moments of new rows
 // written here instead of by a memset over the whole array.  64-bit element indices throughout.
+#include "activations.hpp" // train.hip's exact expression sequences (the values equal what an Adam step writes)
 #include "launch.hpp"
 #include "stream_access.hpp"
 
@@ -17,15 +18,6 @@ namespace lcgs
 {
 namespace
 {
-
-// the activations, in train.hip's exact expression sequences (the values equal what an Adam step writes)
-__device__ __forceinline__ float act_exp(float x) { return expf(x); }
-__device__ __forceinline__ float act_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float4 act_unit(const float4& x)
-{
-    const float n2 = 1.0f / sqrtf(x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w);
-    return make_float4(x.x * n2, x.y * n2, x.z * n2, x.w * n2);
-}
 
 // ---- statistics of a step: one thread per on-screen row of the last frame (count on the device)
 __global__ void __launch_bounds__(256) k_densify_stats(const uint32_t* __restrict__ vis_index, const uint32_t* __restrict__ d_counts,

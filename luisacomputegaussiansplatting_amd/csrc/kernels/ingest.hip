@@ -90,19 +90,35 @@ __device__ __forceinline__ uint32_t spread3(uint32_t v) // 10 bits -> every thir
     return v;
 }
 
+__device__ __forceinline__ uint32_t morton_key(float x, float y, float z, float lox, float loy, float loz, float sx, float sy,
+                                               float sz)
+{
+    // (NaN compares false everywhere: it lands in cell 0)
+    auto cell = [](float p, float lo, float s) {
+        const float q = (p - lo) * s;
+        return q > 0.0f ? (q < 1023.0f ? (uint32_t)q : 1023u) : 0u;
+    };
+    return spread3(cell(x, lox, sx)) | (spread3(cell(y, loy, sy)) << 1) | (spread3(cell(z, loz, sz)) << 2);
+}
+
 __global__ void __launch_bounds__(256) k_morton_keys(int64_t P, const float* __restrict__ pos, float lox, float loy, float loz,
                                                      float sx, float sy, float sz, uint32_t* __restrict__ keys,
                                                      uint32_t* __restrict__ vals)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= P) return;
-    // (NaN compares false everywhere: it lands in cell 0)
-    auto cell = [](float p, float lo, float s) {
-        const float q = (p - lo) * s;
-        return q > 0.0f ? (q < 1023.0f ? (uint32_t)q : 1023u) : 0u;
-    };
-    keys[i] = spread3(cell(pos[3 * i], lox, sx)) | (spread3(cell(pos[3 * i + 1], loy, sy)) << 1) |
-              (spread3(cell(pos[3 * i + 2], loz, sz)) << 2);
+    keys[i] = morton_key(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], lox, loy, loz, sx, sy, sz);
+    vals[i] = (uint32_t)i;
+}
+// the same keys with the grid in DEVICE memory, grid[0..2] = lo, grid[3..5] = cells per unit (init.hip: the box is reduced on
+// the device and never read back)
+__global__ void __launch_bounds__(256) k_morton_keys_grid(int64_t P, const float* __restrict__ pos,
+                                                          const float* __restrict__ grid, uint32_t* __restrict__ keys,
+                                                          uint32_t* __restrict__ vals)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= P) return;
+    keys[i] = morton_key(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], grid[0], grid[1], grid[2], grid[3], grid[4], grid[5]);
     vals[i] = (uint32_t)i;
 }
 
@@ -140,6 +156,11 @@ void launch_morton_keys(int64_t P, const float* pos, const float lo[3], const fl
     if (P <= 0) return;
     hipLaunchKernelGGL(k_morton_keys, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream, P, pos, lo[0], lo[1], lo[2],
                        cells_per_unit[0], cells_per_unit[1], cells_per_unit[2], keys, vals);
+}
+void launch_morton_keys(int64_t P, const float* pos, const float* d_grid, uint32_t* keys, uint32_t* vals, hipStream_t stream)
+{
+    if (P <= 0) return;
+    hipLaunchKernelGGL(k_morton_keys_grid, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream, P, pos, d_grid, keys, vals);
 }
 void launch_gather_rows(int64_t rows, int row_floats, const uint32_t* perm, const float* src, float* dst, hipStream_t stream)
 {

@@ -263,7 +263,26 @@ int  pos_moment_blocks();
 void launch_pos_moments(int64_t P, const float* pos, double* partial, hipStream_t stream);
 void launch_morton_keys(int64_t P, const float* pos, const float lo[3], const float cells_per_unit[3], uint32_t* keys,
                         uint32_t* vals, hipStream_t stream);
+// (the same keys, the grid in device memory: d_grid[0..2] = lo, d_grid[3..5] = cells per unit)
+void launch_morton_keys(int64_t P, const float* pos, const float* d_grid, uint32_t* keys, uint32_t* vals, hipStream_t stream);
 void launch_gather_rows(int64_t rows, int row_floats, const uint32_t* perm, const float* src, float* dst, hipStream_t stream);
+// ---- init.hip : a scene from a point cloud -- exact 3-nearest-neighbour mean squared distances, 3DGS's initial rows ----
+constexpr int kKnnChunk = 256; // = LCGS_KNN_CHUNK: sorted points per chunk = lanes per query workgroup
+// what the box reduction leaves on the device: the Morton grid of the valid points (lo, cells per unit) and their count
+struct KnnGrid {
+    float    lo[3], cells[3];
+    uint32_t num_valid, pad;
+};
+size_t knn_box_partial_bytes();
+// exact min / max and count of the finite points -> *grid (two launches, no atomics)
+void launch_knn_grid(int64_t n, const float* pos, void* partial, KnnGrid* grid, hipStream_t stream);
+// sorted[r] = (pos[perm[r]], bits(perm[r])); boxes[2 c], boxes[2 c + 1] = lo, hi of chunk c's finite points (+inf, -inf: none)
+void launch_knn_gather_boxes(int64_t n, const float* pos, const uint32_t* perm, float4* sorted, float4* boxes, hipStream_t stream);
+// dist2[original index] of every point, as include/lcgs_hip.h defines it
+void launch_knn_query(int64_t n, const float4* sorted, const float4* boxes, const KnnGrid* grid, float* dist2, hipStream_t stream);
+// 3DGS's create_from_pcd rows in the caller's order (act.pos / act.sh may alias raw's)
+void launch_init_rows(int64_t n, int sh_floats, const float* pos, const float* rgb, const float* dist2, float min_dist2,
+                      float raw_opacity, const AdamArrays& raw, const AdamArrays& act, hipStream_t stream);
 void launch_tile_order(const uint32_t* ranges, uint32_t G, uint32_t* order, hipStream_t stream, uint32_t grid_x = 0,
                        uint32_t list_shift = 0);
 void launch_blend_exp(const float* x, float* out, int64_t n, hipStream_t stream);

@@ -13,6 +13,7 @@
 // HBM-bound elementwise work: every array is touched once, 16-byte accesses where the layout allows.  With a row
 // list (the dense ids -> splat index map of the last forward) only the splats that reached the screen are updated
 // ("sparse Adam": their moments are the only ones that change; 2.5x fewer bytes on the bicycle stand-in).
+#include "activations.hpp"
 #include "launch.hpp"
 #include "stream_access.hpp"
 
@@ -49,8 +50,8 @@ __global__ void __launch_bounds__(256) k_adam_rows(int64_t rows, const uint32_t*
         st_stream(v + i, vv);
         raw[i] = x;
         if (MODE == 0 && act != raw) act[i] = x; // (wave-uniform: the renderer's array is a separate buffer)
-        if (MODE == 1) act[i] = expf(x);
-        if (MODE == 2) act[i] = 1.0f / (1.0f + expf(-x));
+        if (MODE == 1) act[i] = act_exp(x);
+        if (MODE == 2) act[i] = act_sigmoid(x);
     }
 }
 

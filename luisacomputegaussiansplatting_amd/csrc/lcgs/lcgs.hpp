@@ -284,6 +284,18 @@ public:
     {
         check(lcgs_opacity_reset(m_dev->ctx(), num_gaussians, max_opacity, &raw, &m, &v, &activated));
     }
+    // a scene from a point cloud (3DGS's create_from_pcd; no reference counterpart): the exact mean squared distance to the three
+    // nearest neighbours, and the initial raw / activated rows built from it (nothing is bound; moments are the caller's to zero)
+    void knn_mean_dist2(int64_t num_points, const float* d_pos, float* d_dist2)
+    {
+        check(lcgs_knn_mean_dist2(m_dev->ctx(), num_points, d_pos, d_dist2));
+    }
+    void init_from_points(int num_points, const float* d_pos, const float* d_rgb, const lcgs_params& out_raw,
+                          const lcgs_params& out_activated, int sh_degree = 3, float initial_opacity = 0.1f, float min_dist2 = 1e-7f)
+    {
+        const lcgs_init_config cfg = { initial_opacity, min_dist2 };
+        check(lcgs_scene_init_from_points(m_dev->ctx(), num_points, sh_degree, d_pos, d_rgb, &cfg, &out_raw, &out_activated));
+    }
     // Morton order at ingest: the context renders from its own re-ordered copy; d_perm[r] = old index of new splat r
     void reorder_spatial(uint32_t* d_perm = nullptr) { check(lcgs_scene_reorder_spatial(m_dev->ctx(), d_perm)); }
 
