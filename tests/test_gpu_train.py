@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import adam_ref
 from conftest import make_scene
 from gpu_util import DEV, check_gradient_rows, gradient_row_bound
 
@@ -75,6 +76,17 @@ def test_adam_step_matches_torch(lcgs, P, aliased):
         assert np.allclose(a, b, rtol=2e-5, atol=2e-6), (k, np.abs(a - b).max())
         a, b = act[k].cpu().numpy().astype(np.float64), ref_act[k]
         assert np.allclose(a, b, rtol=2e-5, atol=2e-6), ("activated " + k, np.abs(a - b).max())
+    # the same three steps against the float64 restatement (tests/adam_ref.py, pinned to torch.optim.Adam on the CPU by
+    # tests/test_adam_ref.py): raw, activated AND the moments, per array within 3 E32 + 4 u S (the state is the kernels' own after step 1)
+    as_torch = lambda d: {k: torch.from_numpy(d[k]) for k in KEYS}
+    t64, t32 = [adam_ref.trajectory(as_torch(raw0), [as_torch(g) for g in grads_seq], dt, lr=LR, eps=eps)
+                for dt in (torch.float64, torch.float32)]
+    for name, pack in zip(adam_ref.ARRAYS, (raw, m, v, act)):
+        for k in KEYS:
+            diff = float((pack[k].cpu().double() - t64[name][k]).abs().max())
+            bound = adam_ref.trajectory_bound(t64[name][k], t32[name][k])
+            print(f"[adam] three steps P={P} {name}.{k}: diff / bound {diff / bound:.3f}")
+            assert diff <= bound, (name, k, diff, bound)
 
 
 def test_adam_visible_only_touches_survivors_only(lcgs):
