@@ -18,7 +18,7 @@
 //                          the 192-byte SH gradient rows leave through LDS as coalesced 16-byte stores.
 // Thresholds are constants for the derivative: near cull, alpha < 1/255 skip, T < 1e-4 stop and power > 0 gate the
 // sums; the 0.99 alpha cap, the colour clamp and a saturated cam_clamp axis pass no gradient.
-#include "launch.hpp"
+#include "adam_rows.hpp"
 #include "stream_access.hpp"
 #include "tile_common.hpp"
 
@@ -582,6 +582,29 @@ __device__ __forceinline__ void geom_backward_t(const CamParams& cp, FP scale_mo
     cov_trace = a + c;
 }
 
+// The global operands of survivor `vsafe` (dense id; lanes past V pass the last survivor's and discard the result), splat idx:
+// its 2-D gradient row and its pos / scale / rotq rows.  Everything is requested here, together: one memory round trip per
+// block instead of one per use.
+struct SplatOperands {
+    float  gmx, gmy, gA, gB, gC, gop, gcol[3]; // dL/d{pixel mean, conic, opacity, colour}
+    float  px, py, pz, sc0, sc1, sc2;
+    float4 q; // (r,x,y,z)
+};
+__device__ __forceinline__ SplatOperands load_splat_operands(uint32_t vsafe, int idx, const float* grads2d, const float* pos,
+                                                             const float* scale, const float* rotq)
+{
+    const float4* g2 = reinterpret_cast<const float4*>(grads2d + (size_t)vsafe * kG2D);
+    const float4  q0 = g2[0], q1 = g2[1];
+    const float   gcol2 = reinterpret_cast<const float*>(g2)[8];
+    SplatOperands in;
+    in.px = pos[3 * (size_t)idx + 0], in.py = pos[3 * (size_t)idx + 1], in.pz = pos[3 * (size_t)idx + 2];
+    in.sc0 = scale[3 * (size_t)idx + 0], in.sc1 = scale[3 * (size_t)idx + 1], in.sc2 = scale[3 * (size_t)idx + 2];
+    in.q = *reinterpret_cast<const float4*>(rotq + 4 * (size_t)idx);
+    in.gmx = q0.x, in.gmy = q0.y, in.gA = q0.z, in.gB = q0.w, in.gC = q1.x, in.gop = q1.y;
+    in.gcol[0] = q1.z, in.gcol[1] = q1.w, in.gcol[2] = gcol2;
+    return in;
+}
+
 // A footprint beyond this (trace of the 2-D covariance, px^2: radius ~ 3 sqrt(lambda_max) > 64 px) takes the algebra in f64.
 constexpr float kGiantCovTrace = 455.0f;
 // (Both precisions are inlined: the kernels' register count doubles and their occupancy halves -- preprocess-backward
@@ -593,16 +616,16 @@ constexpr float kGiantCovTrace = 455.0f;
 // terms, and ANY f32 evaluation loses them (the f32 CPU restatement is off by up to 1.7e-1 on such rows; the 2-D gradients
 // feeding this step are good to ~1e-4: profiles/r04_gradient_error_survey.txt).  0.4 % of the on-screen splats of the
 // bicycle stand-in qualify; the kernels calling this are HBM-bound, the divergent f64 pass hides under their stores.
-__device__ __forceinline__ void geom_backward(const CamParams& cp, float scale_modifier, float px, float py, float pz,
-                                              float sc0, float sc1, float sc2, float4 q, float gmx, float gmy, float gA,
-                                              float gB, float gC, float gp[3], float gs[3], float4& gq)
+__device__ __forceinline__ void geom_backward(const CamParams& cp, float scale_modifier, const SplatOperands& in, float gp[3],
+                                              float gs[3], float4& gq)
 {
     float dp[3], q4[4], tr;
-    geom_backward_t<float>(cp, scale_modifier, px, py, pz, sc0, sc1, sc2, q.x, q.y, q.z, q.w, gmx, gmy, gA, gB, gC, dp, gs, q4, tr);
+    geom_backward_t<float>(cp, scale_modifier, in.px, in.py, in.pz, in.sc0, in.sc1, in.sc2, in.q.x, in.q.y, in.q.z, in.q.w, in.gmx,
+                           in.gmy, in.gA, in.gB, in.gC, dp, gs, q4, tr);
     if (tr > kGiantCovTrace) {
         double dpd[3], gsd[3], q4d[4], trd;
-        geom_backward_t<double>(cp, scale_modifier, px, py, pz, sc0, sc1, sc2, q.x, q.y, q.z, q.w, gmx, gmy, gA, gB, gC, dpd, gsd,
-                                q4d, trd);
+        geom_backward_t<double>(cp, scale_modifier, in.px, in.py, in.pz, in.sc0, in.sc1, in.sc2, in.q.x, in.q.y, in.q.z, in.q.w,
+                                in.gmx, in.gmy, in.gA, in.gB, in.gC, dpd, gsd, q4d, trd);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             dp[i] = (float)dpd[i];
@@ -671,14 +694,7 @@ k_preprocess_backward(int sh_deg, CamParams cp, float scale_modifier, const floa
         const uint32_t wave_first = v0 + blk * 256u + wave * 64u;
         const uint32_t nvalid     = wave_first < V ? ((V - wave_first) < 64u ? (V - wave_first) : 64u) : 0u;
         float*         row = reinterpret_cast<float*>(&s_sh[wave][lane * 13]); // this lane's 48 floats (+4 pad)
-        // Every global operand of this splat is requested here, together with the SH rows below: one memory round
-        // trip per block instead of one per use (lanes past V read the last survivor's rows and discard them).
-        const float* g2 = grads2d + (size_t)(valid ? vid : V - 1) * kG2D;
-        const float4 q0 = reinterpret_cast<const float4*>(g2)[0], q1 = reinterpret_cast<const float4*>(g2)[1];
-        const float  gcol2 = g2[8];
-        const float  px = pos[3 * (size_t)idx + 0], py = pos[3 * (size_t)idx + 1], pz = pos[3 * (size_t)idx + 2];
-        const float  sc0 = scale[3 * (size_t)idx + 0], sc1 = scale[3 * (size_t)idx + 1], sc2 = scale[3 * (size_t)idx + 2];
-        const float4 q = *reinterpret_cast<const float4*>(rotq + 4 * (size_t)idx); // (r,x,y,z)
+        const SplatOperands in = load_splat_operands(valid ? vid : V - 1, idx, grads2d, pos, scale, rotq); // (with the SH rows below)
 
         // ---- stage the SH rows (coalesced), or fetch them lane-wise for other degrees
         __syncthreads();
@@ -697,13 +713,11 @@ k_preprocess_backward(int sh_deg, CamParams cp, float scale_modifier, const floa
         __syncthreads();
 
         if (valid) {
-            const float  gmx = q0.x, gmy = q0.y, gA = q0.z, gB = q0.w, gC = q1.x, gop = q1.y;
-            const float  gcol[3] = { q1.z, q1.w, gcol2 };
-            float        gp[3] = { 0.0f, 0.0f, 0.0f };
+            float gp[3] = { 0.0f, 0.0f, 0.0f };
 
             // ---- colour -> SH coefficients and position (through the view direction)
             {
-                const float dx = px - cp.campos[0], dy = py - cp.campos[1], dz = pz - cp.campos[2];
+                const float dx = in.px - cp.campos[0], dy = in.py - cp.campos[1], dz = in.pz - cp.campos[2];
                 const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
                 const float x = dx * inv, y = dy * inv, z = dz * inv;
                 const float xx = x * x, yy = y * y, zz = z * z;
@@ -719,7 +733,7 @@ k_preprocess_backward(int sh_deg, CamParams cp, float scale_modifier, const floa
 #undef LCGS_RAW
                 float g[3];
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) g[ch] = (raw[ch] > 0.0f && raw[ch] < 1.0f) ? gcol[ch] : 0.0f; // clamp mask
+                for (int ch = 0; ch < 3; ++ch) g[ch] = (raw[ch] > 0.0f && raw[ch] < 1.0f) ? in.gcol[ch] : 0.0f; // clamp mask
                 float ddx = 0.0f, ddy = 0.0f, ddz = 0.0f;
 #define LCGS_GRAD(k, B, DX, DY, DZ)                                                                                   \
     {                                                                                                                 \
@@ -743,10 +757,10 @@ k_preprocess_backward(int sh_deg, CamParams cp, float scale_modifier, const floa
 
             float  gs[3];
             float4 gq;
-            geom_backward(cp, scale_modifier, px, py, pz, sc0, sc1, sc2, q, gmx, gmy, gA, gB, gC, gp, gs, gq);
+            geom_backward(cp, scale_modifier, in, gp, gs, gq);
 
             const size_t orow = compact ? (size_t)vid : (size_t)idx; // compact: row = dense id (see launch.hpp)
-            store_geometry_rows(orow, accumulate, gp, gs, gq, gop, dL_dpos, dL_dscale, dL_drotq, dL_dopacity);
+            store_geometry_rows(orow, accumulate, gp, gs, gq, in.gop, dL_dpos, dL_dscale, dL_drotq, dL_dopacity);
         }
 
         // ---- SH gradient rows: 12 consecutive lanes write one splat's 192 contiguous bytes
@@ -783,6 +797,43 @@ k_preprocess_backward(int sh_deg, CamParams cp, float scale_modifier, const floa
 // a kernel that is bound by bytes in flight.
 constexpr int kJacPitch = 19; // floats per splat in the LDS slab (odd: conflict-free per-lane writes)
 
+// The colour step of that path for one splat: parks the 16 basis values of its view direction and its 3 clamp-masked
+// dL/dcolour in its slab slot `mine`, and returns the direction part of dL/dpos (from the kept Jacobian rows j0..j2) in gp.
+__device__ __forceinline__ void jac_colour_step(const CamParams& cp, const SplatOperands& in, float4 j0, float4 j1, float4 j2,
+                                                float* mine, float gp[3])
+{
+    const uint32_t mask = __float_as_uint(j2.y);
+    const float*   gcol = in.gcol;
+    const float dx = in.px - cp.campos[0], dy = in.py - cp.campos[1], dz = in.pz - cp.campos[2];
+    const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
+    const float x = dx * inv, y = dy * inv, z = dz * inv;
+    const float xx = x * x, yy = y * y, zz = z * z;
+#define LCGS_BASIS(k, B, DX, DY, DZ) mine[k] = (B);
+    LCGS_SH_TERMS(LCGS_BASIS)
+#undef LCGS_BASIS
+#pragma unroll
+    for (int c = 0; c < 3; ++c) mine[16 + c] = ((mask >> c) & 1u) ? gcol[c] : 0.0f; // clamp mask
+    // J rows of clamped channels are already zero: no mask needed here
+    const float ddx = gcol[0] * j0.x + gcol[1] * j0.w + gcol[2] * j1.z;
+    const float ddy = gcol[0] * j0.y + gcol[1] * j1.x + gcol[2] * j1.w;
+    const float ddz = gcol[0] * j0.z + gcol[1] * j1.y + gcol[2] * j2.x;
+    const float dd  = x * ddx + y * ddy + z * ddz;
+    gp[0] = (ddx - x * dd) * inv;
+    gp[1] = (ddy - y * dd) * inv;
+    gp[2] = (ddz - z * dd) * inv;
+}
+// float4 `part` (0..11) of a splat's 16 x 3 SH gradient row, formed from the 19 floats of its slab slot
+__device__ __forceinline__ float4 jac_outer_part(const float* slot, uint32_t part)
+{
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const uint32_t f = part * 4u + (uint32_t)e, k = f / 3u, ch = f - 3u * k; // row[k * 3 + ch]
+        v[e]             = slot[k] * slot[16u + ch];
+    }
+    return make_float4(v[0], v[1], v[2], v[3]);
+}
+
 __global__ void __launch_bounds__(256)
 k_preprocess_backward_jac(CamParams cp, float scale_modifier, const float* __restrict__ pos,
                           const float* __restrict__ scale, const float* __restrict__ rotq,
@@ -804,43 +855,15 @@ k_preprocess_backward_jac(CamParams cp, float scale_modifier, const float* __res
         const int      idx   = (int)vis_index[vsafe];
         const uint32_t wave_first = v0 + blk * 256u + wave * 64u;
         const uint32_t nvalid     = wave_first < V ? ((V - wave_first) < 64u ? (V - wave_first) : 64u) : 0u;
-        const float4* g2 = reinterpret_cast<const float4*>(grads2d + (size_t)vsafe * kG2D);
-        const float4  q0 = g2[0], q1 = g2[1];
-        const float   gcol2 = reinterpret_cast<const float*>(g2)[8];
-        const float4  j0 = shjac[(size_t)vsafe * 3 + 0], j1 = shjac[(size_t)vsafe * 3 + 1], j2 = shjac[(size_t)vsafe * 3 + 2];
-        const float   px = pos[3 * (size_t)idx + 0], py = pos[3 * (size_t)idx + 1], pz = pos[3 * (size_t)idx + 2];
-        const float   sc0 = scale[3 * (size_t)idx + 0], sc1 = scale[3 * (size_t)idx + 1], sc2 = scale[3 * (size_t)idx + 2];
-        const float4  q = *reinterpret_cast<const float4*>(rotq + 4 * (size_t)idx); // (r,x,y,z)
-        float*        mine = &s_outer[wave][lane * kJacPitch];
+        const SplatOperands in = load_splat_operands(vsafe, idx, grads2d, pos, scale, rotq);
+        const float4 j0 = shjac[(size_t)vsafe * 3 + 0], j1 = shjac[(size_t)vsafe * 3 + 1], j2 = shjac[(size_t)vsafe * 3 + 2];
         if (valid) {
-            const float    gmx = q0.x, gmy = q0.y, gA = q0.z, gB = q0.w, gC = q1.x, gop = q1.y;
-            const float    gcol[3] = { q1.z, q1.w, gcol2 };
-            const uint32_t mask    = __float_as_uint(j2.y);
-            float          gp[3];
-            {
-                const float dx = px - cp.campos[0], dy = py - cp.campos[1], dz = pz - cp.campos[2];
-                const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
-                const float x = dx * inv, y = dy * inv, z = dz * inv;
-                const float xx = x * x, yy = y * y, zz = z * z;
-#define LCGS_BASIS(k, B, DX, DY, DZ) mine[k] = (B);
-                LCGS_SH_TERMS(LCGS_BASIS)
-#undef LCGS_BASIS
-#pragma unroll
-                for (int c = 0; c < 3; ++c) mine[16 + c] = ((mask >> c) & 1u) ? gcol[c] : 0.0f; // clamp mask
-                // J rows of clamped channels are already zero: no mask needed here
-                const float ddx = gcol[0] * j0.x + gcol[1] * j0.w + gcol[2] * j1.z;
-                const float ddy = gcol[0] * j0.y + gcol[1] * j1.x + gcol[2] * j1.w;
-                const float ddz = gcol[0] * j0.z + gcol[1] * j1.y + gcol[2] * j2.x;
-                const float dd  = x * ddx + y * ddy + z * ddz;
-                gp[0] = (ddx - x * dd) * inv;
-                gp[1] = (ddy - y * dd) * inv;
-                gp[2] = (ddz - z * dd) * inv;
-            }
-            float  gs[3];
+            float  gp[3], gs[3];
             float4 gq;
-            geom_backward(cp, scale_modifier, px, py, pz, sc0, sc1, sc2, q, gmx, gmy, gA, gB, gC, gp, gs, gq);
+            jac_colour_step(cp, in, j0, j1, j2, &s_outer[wave][lane * kJacPitch], gp);
+            geom_backward(cp, scale_modifier, in, gp, gs, gq);
             const size_t orow = compact ? (size_t)vid : (size_t)idx; // compact: row = dense id (see launch.hpp)
-            store_geometry_rows(orow, accumulate, gp, gs, gq, gop, dL_dpos, dL_dscale, dL_drotq, dL_dopacity);
+            store_geometry_rows(orow, accumulate, gp, gs, gq, in.gop, dL_dpos, dL_dscale, dL_drotq, dL_dopacity);
         }
         __syncthreads();
         // ---- SH gradient rows: 12 consecutive lanes write one splat's 192 contiguous bytes
@@ -850,21 +873,15 @@ k_preprocess_backward_jac(CamParams cp, float scale_modifier, const float* __res
             const uint32_t slot = cidx / 12u, part = cidx - slot * 12u;
             const int      sidx = __shfl(idx, (int)slot, 64);
             if (slot < nvalid) {
-                const float* o = &s_outer[wave][slot * kJacPitch];
-                float        v[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const uint32_t f = part * 4u + (uint32_t)e, k = f / 3u, ch = f - 3u * k; // row[k * 3 + ch]
-                    v[e]             = o[k] * o[16u + ch];
-                }
+                float4       v    = jac_outer_part(&s_outer[wave][slot * kJacPitch], part);
                 const size_t orow = compact ? (size_t)(wave_first + slot) : (size_t)sidx;
                 float4*      dst  = reinterpret_cast<float4*>(dL_dsh + orow * 48) + part;
                 if (accumulate) {
                     const float4 o = *dst;
-                    v[0] += o.x; v[1] += o.y; v[2] += o.z; v[3] += o.w;
+                    v = make_float4(v.x + o.x, v.y + o.y, v.z + o.z, v.w + o.w);
                 }
                 // written once, read by the optimiser / the all-reduce a kernel later: a streaming store
-                st_stream(dst, make_float4(v[0], v[1], v[2], v[3]));
+                st_stream(dst, v);
             }
         }
         __syncthreads(); // the slab is reused by the next iteration
@@ -873,12 +890,13 @@ k_preprocess_backward_jac(CamParams cp, float scale_modifier, const float* __res
 
 // The same per-splat pass with the optimiser folded in (single-GPU training steps: lcgs_render_backward_adam).  The
 // gradients of a splat exist only in this lane's registers (geometry, opacity) and in the wave's LDS slab (the 16 + 3
-// factors of the SH outer product): the on-screen-only Adam update of train.hip -- the same adam_update, the same chain
-// rules, the same order of operations, so the result is train.hip's bit for bit -- is applied right here and NO gradient
-// row is ever written or read back (2 x 236 bytes per on-screen splat less; the separate step was 0.56 GB written by this
-// kernel + 0.56 GB read by the optimiser's on the bicycle stand-in).  Each lane owns its splat's rows in raw / m / v /
-// activated: read, updated, written by the same lane, so the in-place update of the arrays this very kernel reads
-// (the activated pos / scale / rotq are the renderer's scene arrays) needs no synchronisation.
+// factors of the SH outer product): the on-screen-only Adam update of train.hip is applied right here -- through the
+// functions of adam_rows.hpp that train.hip's kernels call, on gradients formed by the functions k_preprocess_backward_jac
+// calls, so the result is the two calls' bit for bit -- and NO gradient row is ever written or read back (2 x 236 bytes
+// per on-screen splat less; the separate step was 0.56 GB written by this kernel + 0.56 GB read by the optimiser's on the
+// bicycle stand-in).  Each lane owns its splat's rows in raw / m / v / activated: read, updated, written by the same lane,
+// so the in-place update of the arrays this very kernel reads (the activated pos / scale / rotq are the renderer's scene
+// arrays) needs no synchronisation.
 __global__ void __launch_bounds__(256)
 k_preprocess_backward_adam(CamParams cp, float scale_modifier, const float* pos, const float* scale, const float* rotq,
                            const uint32_t* __restrict__ vis_index, const uint32_t* __restrict__ d_counts,
@@ -895,89 +913,52 @@ k_preprocess_backward_adam(CamParams cp, float scale_modifier, const float* pos,
         const int      idx   = (int)vis_index[vsafe];
         const uint32_t wave_first = blk * 256u + wave * 64u;
         const uint32_t nvalid     = wave_first < V ? ((V - wave_first) < 64u ? (V - wave_first) : 64u) : 0u;
-        const float4* g2 = reinterpret_cast<const float4*>(grads2d + (size_t)vsafe * kG2D);
-        const float4  q0 = g2[0], q1 = g2[1];
-        const float   gcol2 = reinterpret_cast<const float*>(g2)[8];
-        const float4  j0 = shjac[(size_t)vsafe * 3 + 0], j1 = shjac[(size_t)vsafe * 3 + 1], j2 = shjac[(size_t)vsafe * 3 + 2];
-        const float   px = pos[3 * (size_t)idx + 0], py = pos[3 * (size_t)idx + 1], pz = pos[3 * (size_t)idx + 2];
-        const float   sc0 = scale[3 * (size_t)idx + 0], sc1 = scale[3 * (size_t)idx + 1], sc2 = scale[3 * (size_t)idx + 2];
-        const float4  q = *reinterpret_cast<const float4*>(rotq + 4 * (size_t)idx); // (r,x,y,z)
-        float*        mine = &s_outer[wave][lane * kJacPitch];
+        const SplatOperands in = load_splat_operands(vsafe, idx, grads2d, pos, scale, rotq);
+        const float4 j0 = shjac[(size_t)vsafe * 3 + 0], j1 = shjac[(size_t)vsafe * 3 + 1], j2 = shjac[(size_t)vsafe * 3 + 2];
         if (valid) {
-            const float    gmx = q0.x, gmy = q0.y, gA = q0.z, gB = q0.w, gC = q1.x, gop = q1.y;
-            const float    gcol[3] = { q1.z, q1.w, gcol2 };
-            const uint32_t mask    = __float_as_uint(j2.y);
-            float          gp[3];
-            {
-                const float dx = px - cp.campos[0], dy = py - cp.campos[1], dz = pz - cp.campos[2];
-                const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
-                const float x = dx * inv, y = dy * inv, z = dz * inv;
-                const float xx = x * x, yy = y * y, zz = z * z;
-#define LCGS_BASIS(k, B, DX, DY, DZ) mine[k] = (B);
-                LCGS_SH_TERMS(LCGS_BASIS)
-#undef LCGS_BASIS
-#pragma unroll
-                for (int c = 0; c < 3; ++c) mine[16 + c] = ((mask >> c) & 1u) ? gcol[c] : 0.0f; // clamp mask
-                const float ddx = gcol[0] * j0.x + gcol[1] * j0.w + gcol[2] * j1.z;
-                const float ddy = gcol[0] * j0.y + gcol[1] * j1.x + gcol[2] * j1.w;
-                const float ddz = gcol[0] * j0.z + gcol[1] * j1.y + gcol[2] * j2.x;
-                const float dd  = x * ddx + y * ddy + z * ddz;
-                gp[0] = (ddx - x * dd) * inv;
-                gp[1] = (ddy - y * dd) * inv;
-                gp[2] = (ddz - z * dd) * inv;
-            }
-            float  gs[3];
+            float  gp[3], gs[3];
             float4 gq;
-            geom_backward(cp, scale_modifier, px, py, pz, sc0, sc1, sc2, q, gmx, gmy, gA, gB, gC, gp, gs, gq);
+            jac_colour_step(cp, in, j0, j1, j2, &s_outer[wave][lane * kJacPitch], gp);
+            geom_backward(cp, scale_modifier, in, gp, gs, gq);
             // ---- Adam on this splat's geometry rows (train.hip: k_adam_rows<3,0>, <3,1>, k_adam_rot, <1,2>)
             const size_t i3 = 3 * (size_t)idx;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) { // pos: raw == activated value
-                float       mm = am.pos[i3 + c], vv = av.pos[i3 + c];
-                const float x  = raw.pos[i3 + c] - adam_update(gp[c], mm, vv, lr.pos, a);
+            for (int c = 0; c < 3; ++c) {
+                float x = raw.pos[i3 + c], mm = am.pos[i3 + c], vv = av.pos[i3 + c];
+                adam_plain(gp[c], x, mm, vv, lr.pos, a);
                 am.pos[i3 + c]  = mm;
                 av.pos[i3 + c]  = vv;
                 raw.pos[i3 + c] = x;
                 if (act.pos != raw.pos) act.pos[i3 + c] = x;
             }
 #pragma unroll
-            for (int c = 0; c < 3; ++c) { // scale = exp(raw): g_raw = g * s
-                const float g  = gs[c] * act.scale[i3 + c];
-                float       mm = am.scale[i3 + c], vv = av.scale[i3 + c];
-                const float x  = raw.scale[i3 + c] - adam_update(g, mm, vv, lr.scale, a);
+            for (int c = 0; c < 3; ++c) {
+                float x = raw.scale[i3 + c], mm = am.scale[i3 + c], vv = av.scale[i3 + c], sa = act.scale[i3 + c];
+                adam_scale(gs[c], x, mm, vv, sa, lr.scale, a);
                 am.scale[i3 + c]  = mm;
                 av.scale[i3 + c]  = vv;
                 raw.scale[i3 + c] = x;
-                act.scale[i3 + c] = expf(x);
+                act.scale[i3 + c] = sa;
             }
-            { // rotq = raw / |raw|: g_raw = (g - q (q . g)) / |raw|   (gq is (r,x,y,z), like the rows)
-                float4*      rr = reinterpret_cast<float4*>(raw.rotq) + idx;
-                float4*      rm = reinterpret_cast<float4*>(am.rotq) + idx;
-                float4*      rv = reinterpret_cast<float4*>(av.rotq) + idx;
-                float4*      ra = reinterpret_cast<float4*>(act.rotq) + idx;
-                const float4 g = gq, qa = *ra;
-                float4       x = *rr, mm = *rm, vv = *rv;
-                const float  inv_norm = 1.0f / sqrtf(x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w);
-                const float  qg       = qa.x * g.x + qa.y * g.y + qa.z * g.z + qa.w * g.w;
-                x.x -= adam_update((g.x - qa.x * qg) * inv_norm, mm.x, vv.x, lr.rot, a);
-                x.y -= adam_update((g.y - qa.y * qg) * inv_norm, mm.y, vv.y, lr.rot, a);
-                x.z -= adam_update((g.z - qa.z * qg) * inv_norm, mm.z, vv.z, lr.rot, a);
-                x.w -= adam_update((g.w - qa.w * qg) * inv_norm, mm.w, vv.w, lr.rot, a);
-                const float n2 = 1.0f / sqrtf(x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w);
+            { // (gq is (r,x,y,z), like the rows)
+                float4* rr = reinterpret_cast<float4*>(raw.rotq) + idx;
+                float4* rm = reinterpret_cast<float4*>(am.rotq) + idx;
+                float4* rv = reinterpret_cast<float4*>(av.rotq) + idx;
+                float4* ra = reinterpret_cast<float4*>(act.rotq) + idx;
+                float4  x = *rr, mm = *rm, vv = *rv, qa = *ra;
+                adam_quat(gq, x, mm, vv, qa, lr.rot, a);
                 *rr = x;
                 *rm = mm;
                 *rv = vv;
-                *ra = make_float4(x.x * n2, x.y * n2, x.z * n2, x.w * n2);
+                *ra = qa;
             }
-            { // opacity = sigmoid(raw): g_raw = g o (1 - o)
-                const float o  = act.opacity[idx];
-                const float g  = gop * o * (1.0f - o);
-                float       mm = am.opacity[idx], vv = av.opacity[idx];
-                const float x  = raw.opacity[idx] - adam_update(g, mm, vv, lr.opacity, a);
+            {
+                float x = raw.opacity[idx], mm = am.opacity[idx], vv = av.opacity[idx], o = act.opacity[idx];
+                adam_opacity(in.gop, x, mm, vv, o, lr.opacity, a);
                 am.opacity[idx]  = mm;
                 av.opacity[idx]  = vv;
                 raw.opacity[idx] = x;
-                act.opacity[idx] = 1.0f / (1.0f + expf(-x));
+                act.opacity[idx] = o;
             }
         }
         __syncthreads();
@@ -988,23 +969,13 @@ k_preprocess_backward_adam(CamParams cp, float scale_modifier, const float* pos,
             const uint32_t slot = cidx / 12u, part = cidx - slot * 12u;
             const int      sidx = __shfl(idx, (int)slot, 64);
             if (slot < nvalid) {
-                const float* o = &s_outer[wave][slot * kJacPitch];
-                float        g[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const uint32_t f = part * 4u + (uint32_t)e, k = f / 3u, ch = f - 3u * k; // row[k * 3 + ch]
-                    g[e]             = o[k] * o[16u + ch];
-                }
+                const float4 g  = jac_outer_part(&s_outer[wave][slot * kJacPitch], part);
                 const size_t r4 = (size_t)sidx * 12 + part;
                 float4*      xr = reinterpret_cast<float4*>(raw.sh) + r4;
                 float4*      xm = reinterpret_cast<float4*>(am.sh) + r4;
                 float4*      xv = reinterpret_cast<float4*>(av.sh) + r4;
                 float4       x = *xr, mm = *xm, vv = *xv;
-                const float  l = part == 0u ? lr.sh_dc : lr.sh_rest; // floats 0..2 of a row are the dc band
-                x.x -= adam_update(g[0], mm.x, vv.x, l, a);
-                x.y -= adam_update(g[1], mm.y, vv.y, l, a);
-                x.z -= adam_update(g[2], mm.z, vv.z, l, a);
-                x.w -= adam_update(g[3], mm.w, vv.w, lr.sh_rest, a);
+                adam_sh4(g, x, mm, vv, part, lr.sh_dc, lr.sh_rest, a);
                 *xr = x;
                 *xm = mm;
                 *xv = vv;
@@ -1097,16 +1068,14 @@ void launch_preprocess_backward(int64_t v_hint, int sh_deg, const CamParams& cp,
 {
     const int mode = (compact ? 1 : 0) | (accumulate ? 2 : 0);
     // (a slice's launch is sized for its share of the hint; larger live counts are strided)
-    int64_t blocks = (v_hint / (slice_bounds ? slices : 1) + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 65536) blocks = 65536;
+    const unsigned blocks = grid_256(v_hint / (slice_bounds ? slices : 1));
     if (shjac && sh_deg == 3 && (reinterpret_cast<uintptr_t>(dL_dsh) & 15) == 0) {
-        hipLaunchKernelGGL(k_preprocess_backward_jac, dim3((unsigned)blocks), dim3(256), 0, stream, cp, scale_modifier, pos,
+        hipLaunchKernelGGL(k_preprocess_backward_jac, dim3(blocks), dim3(256), 0, stream, cp, scale_modifier, pos,
                            scale, rotq, vis_index, d_counts, grads2d, shjac, dL_dpos, dL_dscale, dL_drotq, dL_dsh,
                            dL_dopacity, mode, slice_bounds, slice);
         return;
     }
-    hipLaunchKernelGGL(k_preprocess_backward, dim3((unsigned)blocks), dim3(256), 0, stream, sh_deg, cp, scale_modifier,
+    hipLaunchKernelGGL(k_preprocess_backward, dim3(blocks), dim3(256), 0, stream, sh_deg, cp, scale_modifier,
                        pos, scale, rotq, sh, vis_index, d_counts, grads2d, dL_dpos, dL_dscale, dL_drotq, dL_dsh,
                        dL_dopacity, mode, slice_bounds, slice);
 }
@@ -1117,10 +1086,7 @@ void launch_preprocess_backward_adam(int64_t v_hint, const CamParams& cp, float 
                                      const AdamArrays& v, const AdamArrays& act, const AdamRates& lr, const AdamStep& a,
                                      hipStream_t stream)
 {
-    int64_t blocks = (v_hint + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_preprocess_backward_adam, dim3((unsigned)blocks), dim3(256), 0, stream, cp, scale_modifier, pos, scale,
+    hipLaunchKernelGGL(k_preprocess_backward_adam, dim3(grid_256(v_hint)), dim3(256), 0, stream, cp, scale_modifier, pos, scale,
                        rotq, vis_index, d_counts, grads2d, shjac, raw, m, v, act, lr, a);
 }
 

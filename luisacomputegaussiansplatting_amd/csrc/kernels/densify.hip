@@ -222,19 +222,11 @@ __global__ void __launch_bounds__(256) k_opacity_reset(int64_t P, float ceiling,
     }
 }
 
-unsigned grid_for(int64_t elements)
-{
-    int64_t b = (elements + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 65536) b = 65536; // grid-stride beyond
-    return (unsigned)b;
-}
-
 template <int ROW, int MODE, typename T>
 void launch_rows(int64_t P, const uint8_t* action, const uint32_t* incl, const float* raw, const float* m, const float* v,
                  float* o_raw, float* o_m, float* o_v, float* o_act, float split_drop, uint32_t* src_row, hipStream_t stream)
 {
-    hipLaunchKernelGGL((k_densify_rows<ROW, MODE, T>), dim3(grid_for(P * ROW)), dim3(256), 0, stream, P, action, incl,
+    hipLaunchKernelGGL((k_densify_rows<ROW, MODE, T>), dim3(grid_256(P * ROW)), dim3(256), 0, stream, P, action, incl,
                        reinterpret_cast<const T*>(raw), reinterpret_cast<const T*>(m), reinterpret_cast<const T*>(v),
                        reinterpret_cast<T*>(o_raw), reinterpret_cast<T*>(o_m), reinterpret_cast<T*>(o_v),
                        reinterpret_cast<T*>(o_act), split_drop, src_row);
@@ -246,7 +238,7 @@ void launch_densify_stats(int64_t v_hint, int64_t P, const CamParams& cp, float 
                           const float* scale, const float* rotq, const uint32_t* vis_index, const uint32_t* d_counts,
                           const float* grads2d, float* grad_accum, uint32_t* denom, int32_t* max_radii, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_densify_stats, dim3(grid_for(std::max<int64_t>(v_hint, 1))), dim3(256), 0, stream, vis_index, d_counts,
+    hipLaunchKernelGGL(k_densify_stats, dim3(grid_256(std::max<int64_t>(v_hint, 1))), dim3(256), 0, stream, vis_index, d_counts,
                        P, cp, scale_modifier, pos, scale, rotq, grads2d, grad_accum, denom, max_radii);
 }
 
@@ -254,7 +246,7 @@ void launch_densify_classify(int64_t P, const DensifyRule& rule, const float* ra
                              const float* grad_accum, const uint32_t* denom, const int32_t* max_radii, uint32_t* emit,
                              uint8_t* action, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_densify_classify, dim3(grid_for(P)), dim3(256), 0, stream, P, rule, raw_scale, raw_opacity, grad_accum,
+    hipLaunchKernelGGL(k_densify_classify, dim3(grid_256(P)), dim3(256), 0, stream, P, rule, raw_scale, raw_opacity, grad_accum,
                        denom, max_radii, emit, action);
 }
 
@@ -263,7 +255,7 @@ void launch_densify_scatter(int64_t P, int sh_floats, const uint8_t* action, con
                             const AdamArrays& o_v, const AdamArrays& o_act, float split_drop, const float* noise, uint64_t seed,
                             uint32_t* src_row, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_densify_pos, dim3(grid_for(P)), dim3(256), 0, stream, P, action, incl, raw.pos, m.pos, v.pos, raw.scale,
+    hipLaunchKernelGGL(k_densify_pos, dim3(grid_256(P)), dim3(256), 0, stream, P, action, incl, raw.pos, m.pos, v.pos, raw.scale,
                        raw.rotq, noise, seed, o_raw.pos, o_m.pos, o_v.pos, o_act.pos);
     launch_rows<3, 1, float>(P, action, incl, raw.scale, m.scale, v.scale, o_raw.scale, o_m.scale, o_v.scale, o_act.scale,
                              split_drop, nullptr, stream);
@@ -287,7 +279,7 @@ void launch_densify_scatter(int64_t P, int sh_floats, const uint8_t* action, con
 
 void launch_opacity_reset(int64_t P, float ceiling, float* raw, float* m, float* v, float* act, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_opacity_reset, dim3(grid_for(P)), dim3(256), 0, stream, P, ceiling, raw, m, v, act);
+    hipLaunchKernelGGL(k_opacity_reset, dim3(grid_256(P)), dim3(256), 0, stream, P, ceiling, raw, m, v, act);
 }
 
 } // namespace lcgs

@@ -973,9 +973,7 @@ __global__ void __launch_bounds__(256) k_sh_to_half(int64_t n, const float* __re
 void launch_sh_to_half(int64_t n, const float* src, uint16_t* dst, hipStream_t stream)
 {
     if (n <= 0) return;
-    int64_t b = (n + 255) / 256;
-    if (b > 65536) b = 65536;
-    hipLaunchKernelGGL(k_sh_to_half, dim3((unsigned)b), dim3(256), 0, stream, n, src, reinterpret_cast<__half*>(dst));
+    hipLaunchKernelGGL(k_sh_to_half, dim3(grid_256(n)), dim3(256), 0, stream, n, src, reinterpret_cast<__half*>(dst));
 }
 
 

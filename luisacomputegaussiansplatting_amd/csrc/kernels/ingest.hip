@@ -167,13 +167,12 @@ void launch_gather_rows(int64_t rows, int row_floats, const uint32_t* perm, cons
     if (rows <= 0 || row_floats <= 0) return;
     const bool wide = (row_floats % 4 == 0) && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
     const int64_t total = wide ? rows * (row_floats / 4) : rows * row_floats;
-    int64_t       blocks = (total + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
+    const unsigned blocks = grid_256(total);
     if (wide)
-        hipLaunchKernelGGL(k_gather_rows16, dim3((unsigned)blocks), dim3(256), 0, stream, total, row_floats / 4, perm,
+        hipLaunchKernelGGL(k_gather_rows16, dim3(blocks), dim3(256), 0, stream, total, row_floats / 4, perm,
                            reinterpret_cast<const float4*>(src), reinterpret_cast<float4*>(dst));
     else
-        hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)blocks), dim3(256), 0, stream, total, row_floats, perm, src, dst);
+        hipLaunchKernelGGL(k_gather_rows, dim3(blocks), dim3(256), 0, stream, total, row_floats, perm, src, dst);
 }
 
 void launch_ply_activate(const unsigned char* raw, int64_t first, int64_t count, uint32_t stride, const PlyColumns& cols,

@@ -350,10 +350,8 @@ void launch_init_rows(int64_t n, int sh_floats, const float* pos, const float* r
     if (n <= 0) return;
     hipLaunchKernelGGL(k_init_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, pos, dist2, min_dist2, raw_opacity,
                        raw.pos, raw.scale, raw.rotq, raw.opacity, act.pos, act.scale, act.rotq, act.opacity);
-    const int64_t total  = n * sh_floats;
-    int64_t       blocks = (total + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_init_sh, dim3((unsigned)blocks), dim3(256), 0, stream, total, sh_floats, rgb, raw.sh, act.sh);
+    const int64_t total = n * sh_floats;
+    hipLaunchKernelGGL(k_init_sh, dim3(grid_256(total)), dim3(256), 0, stream, total, sh_floats, rgb, raw.sh, act.sh);
 }
 
 } // namespace lcgs

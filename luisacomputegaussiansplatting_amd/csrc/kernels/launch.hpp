@@ -10,6 +10,13 @@
 namespace lcgs
 {
 
+// workgroups of 256 lanes for `elements` items: one item per lane, at least one workgroup, at most 65536 (kernels stride beyond)
+inline unsigned grid_256(int64_t elements)
+{
+    const int64_t b = (elements + 255) / 256;
+    return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
+}
+
 // ---- stage_kernels.hip : one kernel per reference shader (buffers in the reference's layouts) ----
 void launch_sh_process(int P, int deg, const CamParams& cp, const float* pos, const float* sh, float* color,
                        hipStream_t stream);
@@ -182,7 +189,6 @@ void launch_get_ranges_u32(int64_t L_hint, uint32_t l_cap, uint32_t* d_counts, c
 void launch_map_to_index(int64_t L_cap, const uint32_t* d_counts, const uint32_t* list_vid, const uint32_t* vis_index,
                          uint32_t* list_idx, hipStream_t stream);
 
-// longest-list-first tile schedule for the renderers (order[G], a scheduling hint only)
 // optimiser step (train.hip): five attribute arrays each for gradients, raw parameters, Adam moments, activated values
 struct AdamArrays {
     float *pos, *scale, *rotq, *sh, *opacity;
@@ -190,18 +196,11 @@ struct AdamArrays {
 struct AdamRates {
     float pos, sh_dc, sh_rest, opacity, scale, rot;
 };
-// the step's scalars, and the update itself: ONE definition for train.hip's kernels and for the fused
-// preprocess-backward + Adam kernel of backward.hip (the two must agree bit for bit)
+// the step's scalars (the update itself and the per-attribute chain rules: adam_rows.hpp)
 struct AdamStep {
     float b1, b2, eps, inv_bc1, inv_sqrt_bc2;
 };
 AdamStep make_adam_step(float beta1, float beta2, float eps, int step);
-__device__ __forceinline__ float adam_update(float g, float& m, float& v, float lr, const AdamStep& a)
-{
-    m = a.b1 * m + (1.0f - a.b1) * g;
-    v = a.b2 * v + (1.0f - a.b2) * g * g;
-    return (lr * a.inv_bc1) * m / (sqrtf(v) * a.inv_sqrt_bc2 + a.eps);
-}
 // row_list != NULL: only rows row_list[0 .. *d_row_count) are updated (launch sized for row_hint rows)
 // grad_compact (row_list only): gradient row r belongs to splat row_list[r] (lcgs_render_backward_compact's layout)
 void launch_adam_step(int64_t P, int sh_floats, const uint32_t* row_list, const uint32_t* d_row_count, int64_t row_hint,
@@ -283,6 +282,7 @@ void launch_knn_query(int64_t n, const float4* sorted, const float4* boxes, cons
 // 3DGS's create_from_pcd rows in the caller's order (act.pos / act.sh may alias raw's)
 void launch_init_rows(int64_t n, int sh_floats, const float* pos, const float* rgb, const float* dist2, float min_dist2,
                       float raw_opacity, const AdamArrays& raw, const AdamArrays& act, hipStream_t stream);
+// longest-list-first tile schedule for the renderers (order[G], a scheduling hint only)
 void launch_tile_order(const uint32_t* ranges, uint32_t G, uint32_t* order, hipStream_t stream, uint32_t grid_x = 0,
                        uint32_t list_shift = 0);
 void launch_blend_exp(const float* x, float* out, int64_t n, hipStream_t stream);

@@ -13,8 +13,7 @@
 // HBM-bound elementwise work: every array is touched once, 16-byte accesses where the layout allows.  With a row
 // list (the dense ids -> splat index map of the last forward) only the splats that reached the screen are updated
 // ("sparse Adam": their moments are the only ones that change; 2.5x fewer bytes on the bicycle stand-in).
-#include "activations.hpp"
-#include "launch.hpp"
+#include "adam_rows.hpp"
 #include "stream_access.hpp"
 
 namespace lcgs
@@ -38,20 +37,19 @@ __global__ void __launch_bounds__(256) k_adam_rows(int64_t rows, const uint32_t*
         const int64_t r = e / ROW;
         const int     c = (int)(e - r * ROW);
         const int64_t i = (row_list ? (int64_t)row_list[r] : r) * ROW + c;
-        float         g = ld_stream(grad + (grad_compact ? e : i)); // compact gradients: row r of the list, not row of the splat
-        if (MODE == 1) g *= act[i];
-        if (MODE == 2) {
-            const float o = act[i];
-            g             = g * o * (1.0f - o);
-        }
-        float       mm = ld_stream(m + i), vv = ld_stream(v + i);
-        const float x  = raw[i] - adam_update(g, mm, vv, c < split ? lr0 : lr1, a);
+        const float   g = ld_stream(grad + (grad_compact ? e : i)); // compact gradients: row r of the list, not row of the splat
+        // the activated value (exp, sigmoid).  The plain mode has none: it neither reads nor writes s, and the 0 folds away
+        float         s = MODE == 0 ? 0.0f : act[i];
+        float         mm = ld_stream(m + i), vv = ld_stream(v + i), x = raw[i];
+        const float   l = c < split ? lr0 : lr1;
+        if (MODE == 0) adam_plain(g, x, mm, vv, l, a);
+        if (MODE == 1) adam_scale(g, x, mm, vv, s, l, a);
+        if (MODE == 2) adam_opacity(g, x, mm, vv, s, l, a);
         st_stream(m + i, mm);
         st_stream(v + i, vv);
         raw[i] = x;
         if (MODE == 0 && act != raw) act[i] = x; // (wave-uniform: the renderer's array is a separate buffer)
-        if (MODE == 1) act[i] = act_exp(x);
-        if (MODE == 2) act[i] = act_sigmoid(x);
+        if (MODE != 0) act[i] = s;
     }
 }
 
@@ -71,11 +69,7 @@ __global__ void __launch_bounds__(256) k_adam_sh48(int64_t rows, const uint32_t*
         const int64_t i = (row_list ? (int64_t)row_list[r] : r) * 12 + c;
         const float4  g = ld_stream(grad + (grad_compact ? e : i));
         float4        x = raw[i], mm = ld_stream(m + i), vv = ld_stream(v + i);
-        const float   l = c == 0 ? lr_dc : lr_rest; // floats 0..2 of a row are the dc band
-        x.x -= adam_update(g.x, mm.x, vv.x, l, a);
-        x.y -= adam_update(g.y, mm.y, vv.y, l, a);
-        x.z -= adam_update(g.z, mm.z, vv.z, l, a);
-        x.w -= adam_update(g.w, mm.w, vv.w, lr_rest, a);
+        adam_sh4(g, x, mm, vv, (uint32_t)c, lr_dc, lr_rest, a);
         raw[i] = x;
         st_stream(m + i, mm);
         st_stream(v + i, vv);
@@ -93,28 +87,14 @@ __global__ void __launch_bounds__(256) k_adam_rot(int64_t rows, const uint32_t* 
     const int64_t n_rows = d_row_count ? (int64_t)*d_row_count : rows;
     for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * 256) {
         const int64_t i  = row_list ? (int64_t)row_list[r] : r;
-        const float4  g  = ld_stream(grad + (grad_compact ? r : i)), q = act[i];
-        float4        x  = raw[i], mm = ld_stream(m + i), vv = ld_stream(v + i);
-        const float   inv_norm = 1.0f / sqrtf(x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w);
-        const float   qg       = q.x * g.x + q.y * g.y + q.z * g.z + q.w * g.w;
-        x.x -= adam_update((g.x - q.x * qg) * inv_norm, mm.x, vv.x, lr, a);
-        x.y -= adam_update((g.y - q.y * qg) * inv_norm, mm.y, vv.y, lr, a);
-        x.z -= adam_update((g.z - q.z * qg) * inv_norm, mm.z, vv.z, lr, a);
-        x.w -= adam_update((g.w - q.w * qg) * inv_norm, mm.w, vv.w, lr, a);
-        const float n2 = 1.0f / sqrtf(x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w);
+        const float4  g  = ld_stream(grad + (grad_compact ? r : i));
+        float4        x  = raw[i], mm = ld_stream(m + i), vv = ld_stream(v + i), q = act[i];
+        adam_quat(g, x, mm, vv, q, lr, a);
         raw[i] = x;
         st_stream(m + i, mm);
         st_stream(v + i, vv);
-        act[i] = make_float4(x.x * n2, x.y * n2, x.z * n2, x.w * n2);
+        act[i] = q;
     }
-}
-
-unsigned grid_for(int64_t elements)
-{
-    int64_t b = (elements + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 65536) b = 65536; // grid-stride beyond
-    return (unsigned)b;
 }
 
 } // namespace
@@ -140,11 +120,11 @@ void launch_adam_step(int64_t P, int sh_floats, const uint32_t* row_list, const 
     if (rows <= 0 && !d_row_count) return;
     const AdamStep a = make_adam_step(beta1, beta2, eps, step);
     const int64_t launch_rows = std::max<int64_t>(rows, 1);
-    hipLaunchKernelGGL((k_adam_rows<3, 0>), dim3(grid_for(launch_rows * 3)), dim3(256), 0, stream, rows, row_list, d_row_count,
+    hipLaunchKernelGGL((k_adam_rows<3, 0>), dim3(grid_256(launch_rows * 3)), dim3(256), 0, stream, rows, row_list, d_row_count,
                        grad.pos, raw.pos, m.pos, v.pos, act.pos, 3, lr.pos, lr.pos, a, gc);
-    hipLaunchKernelGGL((k_adam_rows<3, 1>), dim3(grid_for(launch_rows * 3)), dim3(256), 0, stream, rows, row_list, d_row_count,
+    hipLaunchKernelGGL((k_adam_rows<3, 1>), dim3(grid_256(launch_rows * 3)), dim3(256), 0, stream, rows, row_list, d_row_count,
                        grad.scale, raw.scale, m.scale, v.scale, act.scale, 3, lr.scale, lr.scale, a, gc);
-    hipLaunchKernelGGL(k_adam_rot, dim3(grid_for(launch_rows)), dim3(256), 0, stream, rows, row_list, d_row_count,
+    hipLaunchKernelGGL(k_adam_rot, dim3(grid_256(launch_rows)), dim3(256), 0, stream, rows, row_list, d_row_count,
                        reinterpret_cast<const float4*>(grad.rotq), reinterpret_cast<float4*>(raw.rotq),
                        reinterpret_cast<float4*>(m.rotq), reinterpret_cast<float4*>(v.rotq),
                        reinterpret_cast<float4*>(act.rotq), lr.rot, a, gc);
@@ -152,23 +132,23 @@ void launch_adam_step(int64_t P, int sh_floats, const uint32_t* row_list, const 
                               reinterpret_cast<uintptr_t>(m.sh) | reinterpret_cast<uintptr_t>(v.sh) |
                               reinterpret_cast<uintptr_t>(act.sh)) & 15) == 0;
     if (sh_floats == 48 && sh_aligned)
-        hipLaunchKernelGGL(k_adam_sh48, dim3(grid_for(launch_rows * 12)), dim3(256), 0, stream, rows, row_list, d_row_count,
+        hipLaunchKernelGGL(k_adam_sh48, dim3(grid_256(launch_rows * 12)), dim3(256), 0, stream, rows, row_list, d_row_count,
                            reinterpret_cast<const float4*>(grad.sh), reinterpret_cast<float4*>(raw.sh),
                            reinterpret_cast<float4*>(m.sh), reinterpret_cast<float4*>(v.sh),
                            reinterpret_cast<float4*>(act.sh), lr.sh_dc, lr.sh_rest, a, gc);
     else if (sh_floats == 48)
-        hipLaunchKernelGGL((k_adam_rows<48, 0>), dim3(grid_for(launch_rows * 48)), dim3(256), 0, stream, rows, row_list,
+        hipLaunchKernelGGL((k_adam_rows<48, 0>), dim3(grid_256(launch_rows * 48)), dim3(256), 0, stream, rows, row_list,
                            d_row_count, grad.sh, raw.sh, m.sh, v.sh, act.sh, 3, lr.sh_dc, lr.sh_rest, a, gc);
     else if (sh_floats == 27)
-        hipLaunchKernelGGL((k_adam_rows<27, 0>), dim3(grid_for(launch_rows * 27)), dim3(256), 0, stream, rows, row_list,
+        hipLaunchKernelGGL((k_adam_rows<27, 0>), dim3(grid_256(launch_rows * 27)), dim3(256), 0, stream, rows, row_list,
                            d_row_count, grad.sh, raw.sh, m.sh, v.sh, act.sh, 3, lr.sh_dc, lr.sh_rest, a, gc);
     else if (sh_floats == 12)
-        hipLaunchKernelGGL((k_adam_rows<12, 0>), dim3(grid_for(launch_rows * 12)), dim3(256), 0, stream, rows, row_list,
+        hipLaunchKernelGGL((k_adam_rows<12, 0>), dim3(grid_256(launch_rows * 12)), dim3(256), 0, stream, rows, row_list,
                            d_row_count, grad.sh, raw.sh, m.sh, v.sh, act.sh, 3, lr.sh_dc, lr.sh_rest, a, gc);
     else
-        hipLaunchKernelGGL((k_adam_rows<3, 0>), dim3(grid_for(launch_rows * 3)), dim3(256), 0, stream, rows, row_list,
+        hipLaunchKernelGGL((k_adam_rows<3, 0>), dim3(grid_256(launch_rows * 3)), dim3(256), 0, stream, rows, row_list,
                            d_row_count, grad.sh, raw.sh, m.sh, v.sh, act.sh, 3, lr.sh_dc, lr.sh_rest, a, gc);
-    hipLaunchKernelGGL((k_adam_rows<1, 2>), dim3(grid_for(launch_rows)), dim3(256), 0, stream, rows, row_list, d_row_count,
+    hipLaunchKernelGGL((k_adam_rows<1, 2>), dim3(grid_256(launch_rows)), dim3(256), 0, stream, rows, row_list, d_row_count,
                        grad.opacity, raw.opacity, m.opacity, v.opacity, act.opacity, 1, lr.opacity, lr.opacity, a, gc);
 }
 

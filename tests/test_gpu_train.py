@@ -400,3 +400,97 @@ def test_backward_adam_on_other_sh_degrees_runs_the_two_calls(lcgs):
     ctx.synchronize()
     assert not torch.equal(raw["opacity"], before) and torch.isfinite(raw["opacity"]).all()
     assert float((m["sh"] != 0).float().mean()) > 0.01
+
+
+def test_fused_step_equals_the_two_calls_bit_for_bit_on_a_lattice_frame(lcgs, oracle):
+    """lcgs_render_backward_adam against lcgs_render_backward_compact + lcgs_adam_step(visible_only = 2), torch.equal on all
+    five arrays of raw / m / v / activated, on a frame whose 2-D gradients are deterministic: 260 small splats (V = 260: two
+    workgroups of the per-splat kernels, the last wave with four valid lanes), each at the centre of its own 8 x 8-pixel
+    quadrant of a 320 x 200 frame with its pixel rectangle inside that quadrant.  A quadrant is one wave of the
+    render-backward, so every splat's 2-D gradient row is ONE wave's sums added once onto zero (one LDS add, one global add
+    per tile): no order of float atomics to differ in.  The reference's rect clamp leaves the last tile column and row
+    empty, so the lattice of every second quadrant in x and y has 19 x 12 = 228 usable sites; the other 32 splats sit on
+    the odd / odd quadrants of the first tiles (their own quadrant each, 11 px from the nearest lattice centre).  Those 32
+    share a 16 x 16 tile with lattice splats, and so do the lattice splats with them.  For these the argument rests on the
+    tile's other three waves contributing EXACT zeros: a foreign wave either skips the entry (its strip bit is clear) or
+    walks it with every lane below alpha = 1/255 (no pixel of a foreign quadrant lies inside the splat's reach, asserted
+    below), and such a lane carries alpha 0 and terms that are all 0.0; x + 0.0 == x in whatever order the LDS adds land.
+    40 more splats are culled: rows that did not reach the screen must be untouched."""
+    W, H, depth, n_off = 320, 200, 4.0, 40
+    pose = ([0.0, -4.0, 0.5], [0.0, 0.0, 0.5], [0.0, 0.0, 1.0])
+    ocam = oracle.lookat(*pose, width=W, height=H)
+    c, front, right, up = (np.array(v[:], dtype=np.float64) for v in (ocam.position, ocam.front, ocam.right, ocam.up))
+
+    def project(pos, scale, rotq):  # the oracle's pixel means, radii and tile counts
+        m2, z, cov = oracle.project(pos, scale, rotq, ocam)
+        means, _, tiles, radii = oracle.allocate_tiles(W, H, z, m2, cov)
+        return means.astype(np.float64), radii, tiles
+
+    # at a fixed depth the pixel mean is an affine function of the in-plane coordinates: fitted through three probes
+    probes = np.stack([c + depth * front, c + depth * front + right, c + depth * front + up]).astype(np.float32)
+    mp, _, _ = project(probes, np.full((3, 3), 1e-3, np.float32), np.tile(np.float32([1, 0, 0, 0]), (3, 1)))
+    A = np.stack([mp[1] - mp[0], mp[2] - mp[0]], axis=1)
+    even = [(qx, qy) for qy in range(0, 24, 2) for qx in range(0, 38, 2)]
+    quads = np.array(even + [(qx, qy) for qy in (1, 3) for qx in range(1, 33, 2)])  # 228 + 32
+    n_on = len(quads)
+    assert n_on == 260 and len({tuple(q) for q in quads}) == n_on
+    ab = np.linalg.solve(A, (8.0 * quads + 3.5 - mp[0]).T).T
+    rng = np.random.default_rng(11)
+    P = n_on + n_off
+    on = np.ones(P, dtype=bool)
+    on[100:100 + n_off] = False  # the culled block, in the middle of the index range
+    scene = make_scene(rng, P)
+    scene["pos"][on] = (c + depth * front + ab[:, :1] * right + ab[:, 1:] * up).astype(np.float32)
+    scene["pos"][~on] += 100.0
+    scene["scale"] = (rng.uniform(0.25, 0.4, (P, 3)) / np.sqrt(abs(np.linalg.det(A)))).astype(np.float32)  # 0.25 .. 0.4 px
+    scene["opacity"] = rng.uniform(0.2, 0.95, P).astype(np.float32)
+    # the precondition, on the CPU: every on-screen splat claims one tile and its rect [mean - r, mean + r] lies inside the
+    # pixels 8 q .. 8 q + 7 of its quadrant.  (r >= 3 sigma and alpha >= 1/255 ends within 3.33 sigma: it then reaches no
+    # pixel of another quadrant, whose nearest centre is 4.5 px from the mean.)
+    means, radii, tiles = project(scene["pos"], scene["scale"], scene["rotq"])
+    assert (tiles[on] == 1).all() and (radii[on] > 0).all() and (tiles[~on] == 0).all()
+    assert (np.floor(means[on] - radii[on, None]) >= 8 * quads).all() and (np.ceil(means[on] + radii[on, None]) <= 8 * quads + 7).all()
+
+    raw0 = {"pos": scene["pos"], "scale": np.log(scene["scale"]), "rotq": scene["rotq"] * 1.3, "sh": scene["sh"],
+            "opacity": np.log(scene["opacity"] / (1 - scene["opacity"]))}
+    raw0 = {k: torch.from_numpy(np.ascontiguousarray(val, dtype=np.float32)).to(DEV) for k, val in raw0.items()}
+    cam = lcgs.get_lookat_cam(*pose, width=W, height=H)
+    dL = torch.from_numpy(rng.normal(size=(3, H, W)).astype(np.float32)).to(DEV)
+    off = torch.from_numpy(~on).to(DEV)
+    for separate_act in (False, True):
+        out = {}
+        for fused in (False, True):
+            raw = {k: t.clone() for k, t in raw0.items()}
+            act = {k: t.clone() for k, t in _activate(raw).items()}
+            if not separate_act:
+                act["pos"], act["sh"] = raw["pos"], raw["sh"]  # identity activations: one array
+            m = {k: torch.zeros_like(raw[k]) for k in KEYS}
+            v = {k: torch.zeros_like(raw[k]) for k in KEYS}
+            r = lcgs.Renderer(lcgs.Context(0))
+            r.bind_scene(*[act[k] for k in KEYS])
+            r.forward(cam, torch.zeros(3, H, W, device=DEV), keep_state=True, sync=False)
+            if fused:
+                r.backward_adam(dL, raw, m, v, act, 1, LR, eps=1e-8)
+            else:
+                g, g2 = [{k: torch.zeros_like(raw[k]) for k in KEYS} for _ in range(2)]
+                r.backward(dL, *[g[k] for k in KEYS], compact=True)
+                r.backward(dL, *[g2[k] for k in KEYS], compact=True)
+                r.ctx.synchronize()
+                for k in KEYS:  # the premise: two backward passes of this frame give the same bits
+                    assert torch.equal(g[k], g2[k]), ("two compact backward passes differ", k)
+                    assert g[k].reshape(P, -1)[:n_on].abs().sum() > 0, k
+                r.adam_step(g, raw, m, v, act, 1, LR, eps=1e-8, visible_only=True, compact_grads=True)
+            r.ctx.synchronize()
+            assert r.frame_stats()["num_visible"] == n_on
+            assert torch.equal(r.visible_rows().long(), torch.nonzero(~off).ravel())
+            out[fused] = {"raw": raw, "m": m, "v": v, "act": act}
+        for name in ("raw", "m", "v", "act"):
+            for k in KEYS:
+                a, b = out[False][name][k], out[True][name][k]
+                assert torch.equal(a, b), (separate_act, name, k, int((a != b).sum()))
+        for k in KEYS:
+            got = out[True]
+            assert not torch.equal(got["raw"][k][~off], raw0[k][~off]), k  # it trained ...
+            assert torch.equal(got["raw"][k][off], raw0[k][off]), k  # ... and only the on-screen rows
+            assert (got["m"][k][off] == 0).all() and (got["v"][k][off] == 0).all(), k
+            assert torch.equal(got["act"][k][off], _activate(raw0)[k][off]), k
