@@ -273,3 +273,84 @@ def check_gradient_rows(g, scene, ocam, dL, bg=(0.0, 0.0, 0.0), scale_modifier=1
     for k, (w, i, bad) in res.items():
         assert w <= 1.0, f"{tag} {k}: {len(bad)} rows over their bound, worst row {i} at {w:.2f} x (rows {bad[:12].tolist()})"
     return worst
+
+
+# ------------------------------------------------------------------------------- views shared by the per-row route tests
+KEYS = ("pos", "scale", "rotq", "sh", "opacity")
+BG = (0.1, 0.2, 0.3)
+_CACHE = {}
+
+
+def cached(key, make):
+    if key not in _CACHE:
+        _CACHE[key] = make()
+    return _CACHE[key]
+
+
+class View:
+    """One (scene, pose, resolution, dL/dimg): the oracle's frame and the per-row bound, each computed once and then shared."""
+
+    def __init__(self, oracle, scene, pose, W, H, seed=0, bg=BG, sh_deg=3, dL=None, ref=None):
+        self.oracle, self.scene, self.pose, self.W, self.H, self.bg, self.sh_deg = oracle, scene, pose, W, H, bg, sh_deg
+        self.P = scene["pos"].shape[0]
+        self.ocam = oracle.lookat(*pose, width=W, height=H)
+        self.ref = ref if ref is not None else oracle.render(scene, self.ocam, bg=bg, sh_deg=sh_deg)
+        # `on`: the rows whose tile rectangle is not empty.  (radii > 0 alone also holds for a row in front of the camera whose
+        # rectangle misses the frame, which no list ever holds.)  The kernels' cull additionally drops a row whose rectangle,
+        # pruned by its opacity, is empty -- the oracle has no such rule, so the frame's survivors lie between `hit` (rows that
+        # reach a pixel: their gradient is not 0) and `on`; where a case needs an exact count it asserts that the two agree.
+        m2, depth, cov = oracle.project(scene["pos"], scene["scale"], scene["rotq"], self.ocam)
+        self.on = oracle.allocate_tiles(W, H, depth, m2, cov)[2] > 0
+        self.V = int(self.on.sum())
+        self.dL = dL if dL is not None else np.random.default_rng(seed).normal(size=(3, H, W)).astype(np.float32)
+        self._bound = self._ref32 = None
+
+    def other_dL(self, seed):
+        return View(self.oracle, self.scene, self.pose, self.W, self.H, seed, self.bg, self.sh_deg, ref=self.ref)
+
+    def cam(self):
+        import luisacomputegaussiansplatting_amd as L
+
+        return L.get_lookat_cam(*self.pose, width=self.W, height=self.H)
+
+    def ref32(self):
+        if self._ref32 is None:
+            self._ref32 = self.oracle.render_backward_full(self.scene, self.ocam, self.dL, bg=self.bg, sh_deg=self.sh_deg)
+        return self._ref32
+
+    @property
+    def hit(self):
+        """rows that reach at least one pixel of the f32 oracle's frame (the kernels' frame, bit for bit)"""
+        g = self.ref32()
+        return (g["opacity"] != 0) | (g["sh"].reshape(self.P, -1) != 0).any(axis=1)
+
+    def bound(self):
+        if self._bound is None:
+            self._bound = gradient_row_bound(self.scene, self.ocam, self.dL, bg=self.bg, sh_deg=self.sh_deg, ref32=self.ref32())
+        return self._bound
+
+    def survivors(self, r):
+        """the frame's on-screen rows (lcgs_visible_rows), between `hit` and `on`"""
+        rows = r.visible_rows().cpu().numpy()
+        assert r.frame_stats()["num_visible"] == rows.size
+        got = np.zeros(self.P, bool)
+        got[rows] = True
+        assert (rows[1:] > rows[:-1]).all() and not (got & ~self.on).any() and not (self.hit & ~got).any(), \
+            (rows.size, self.V, int(self.hit.sum()))
+        return rows
+
+
+def sum_bounds(views):
+    """the bound of a sum of views: the sum of the views' bounds, against the sum of their f64 references"""
+    bs = [v.bound() for v in views]
+    return ({k: sum(b[0][k] for b in bs) for k in KEYS}, {k: sum(b[1][k].astype(np.float64) for b in bs) for k in KEYS})
+
+
+def sevens(scene, sh_offset=0):
+    """gradient arrays the backward must overwrite; sh_offset: dL_dsh starts that many floats past a 16-byte boundary"""
+    g = {k: torch.full(scene[k].shape, 7.0, device=DEV) for k in KEYS}
+    if sh_offset:
+        flat = torch.full((scene["sh"].size + 4,), 7.0, device=DEV)
+        g["sh"] = flat[sh_offset:sh_offset + scene["sh"].size].view(scene["sh"].shape)
+        assert g["sh"].data_ptr() % 16 == 4 * sh_offset and g["sh"].is_contiguous()
+    return g

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import make_scene
-from gpu_util import DEV, assert_image_parity, upload_scene
+from gpu_util import DEV, assert_image_parity, cached, check_gradient_rows, gradient_row_bound, upload_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -90,6 +90,12 @@ def test_two_halves_equal_the_fused_frame_and_its_backward(lcgs, oracle, world, 
         zero_ref = (g_ref[k].reshape(P, -1) == 0).all(1)
         assert torch.equal((g[k].reshape(P, -1) == 0).all(1), zero_ref), k  # the same rows are exact zeros
         assert _rel(g[k], g_ref[k]) <= 1e-4, (k, _rel(g[k], g_ref[k]))  # (float-atomic order of the 2-D sums: two runs of ONE path differ by ~2e-5)
+    # ... and every row of every attribute within its bound against the f64 oracle (one bound per scene: the draws do not
+    # depend on `reordered`; row r of a re-ordered scene is file row permutation()[r])
+    bound = cached(("owner two halves", world), lambda: gradient_row_bound(scene, oracle.lookat(*POSE, width=W, height=H),
+                                                                           dL.cpu().numpy(), bg=bg))
+    perm = r.permutation().cpu().numpy().astype(np.int64) if reordered else None
+    check_gradient_rows(g, None, None, None, bound=bound, rows=perm, tag=f"two halves, {world} owners, reordered={reordered}")
 
 
 def test_views_accumulate_and_empty_ranges_are_harmless(lcgs):
