@@ -6,9 +6,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <new>
-#include <string>
-#include <vector>
 
 #include "abi_internal.hpp"
 
@@ -50,8 +47,7 @@ lcgs_status lcgs_render_backward_adam(lcgs_context* ctx, const float* d_dL_dimg,
 {
     LCGS_REQUIRE(ctx && d_dL_dimg && cfg && raw && m && v && activated, "NULL argument");
     LCGS_REQUIRE(num_gaussians == ctx->P && sh_degree == ctx->sh_deg, "num_gaussians / sh_degree must be the bound scene's");
-    LCGS_REQUIRE(cfg->step >= 1, "step counts from 1");
-    LCGS_REQUIRE(cfg->beta1 >= 0.0f && cfg->beta1 < 1.0f && cfg->beta2 >= 0.0f && cfg->beta2 < 1.0f, "betas must be in [0,1)");
+    LCGS_TRY(check_adam_config(cfg));
     const lcgs_params* packs[4] = { raw, m, v, activated };
     for (const lcgs_params* p : packs)
         LCGS_REQUIRE(p->pos && p->scale && p->rotq && p->sh && p->opacity, "NULL device pointer in a parameter pack");
@@ -64,7 +60,7 @@ lcgs_status lcgs_render_backward_adam(lcgs_context* ctx, const float* d_dL_dimg,
         // other SH degrees, frames without the kept colour Jacobian, unaligned rows: the same step as two calls on
         // context-owned compact gradient rows (identical result; the fused kernel exists for the degree-3 training case)
         LCGS_HIP_CHECK(hipSetDevice(ctx->device));
-        const size_t feat = (size_t)(ctx->sh_deg + 1) * (ctx->sh_deg + 1) * 3;
+        const size_t feat = sh_floats(ctx->sh_deg);
         const size_t rows = (size_t)ctx->P;
         auto         al   = [](size_t x) { return (x + 3) & ~(size_t)3; }; // every array starts on a 16-byte boundary
         const size_t o_scale = al(rows * 3), o_rotq = al(o_scale + rows * 3), o_sh = al(o_rotq + rows * 4),
@@ -78,10 +74,8 @@ lcgs_status lcgs_render_backward_adam(lcgs_context* ctx, const float* d_dL_dimg,
         return lcgs_adam_step(ctx, num_gaussians, sh_degree, &c2, &gr, raw, m, v, activated);
     }
     scene_arrays_written(ctx, activated->pos, activated->scale, activated->rotq); // (a context-owned scene trained in place)
-    auto      pack = [](const lcgs_params* p) { return AdamArrays{ p->pos, p->scale, p->rotq, p->sh, p->opacity }; };
-    FusedAdam fa   = { pack(raw), pack(m), pack(v), pack(activated),
-                       { cfg->lr_pos, cfg->lr_sh_dc, cfg->lr_sh_rest, cfg->lr_opacity, cfg->lr_scale, cfg->lr_rot },
-                       make_adam_step(cfg->beta1, cfg->beta2, cfg->eps, cfg->step) };
+    FusedAdam fa = { adam_arrays(raw), adam_arrays(m), adam_arrays(v), adam_arrays(activated), adam_rates(cfg),
+                     make_adam_step(cfg->beta1, cfg->beta2, cfg->eps, cfg->step) };
     lcgs_grads none{};
     return render_backward(ctx, d_dL_dimg, &none, /*compact=*/true, /*accumulate=*/false, &fa);
 }
@@ -120,7 +114,6 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
     LCGS_REQUIRE(ctx->last.cp.list_shift == 0u, "the kept frame lists its pairs per block: no backward walks those lists");
     hipStream_t  st   = ctx->stream;
     const size_t P    = (size_t)ctx->P;
-    const size_t feat = (size_t)(ctx->sh_deg + 1) * (ctx->sh_deg + 1) * 3;
     ctx->n_marks      = 0;
     LCGS_TRY(mark(ctx, "begin"));
     // dense per-splat gradients: splats that did not reach the screen get exact zeros.  The 236 B/splat zero-fill
@@ -133,16 +126,10 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
     // VALU-bound kernel is the memory system's either way).
     // (Per-stage profiling keeps the memsets, in order, as "zero_grads"; so do arrays too long for the kernel's 32-bit lengths.)
     const bool  dense_fill = !compact && !accumulate;
-    const bool  fill_in_kernel = dense_fill && !ctx->profiling && P * feat < ((size_t)1 << 32); // (u32 lengths)
+    DenseFill   fill;
+    const bool  fill_in_kernel = dense_fill && !ctx->profiling && dense_fill_rows(*grads, ctx->sh_deg, P, &fill); // (u32 lengths)
     const bool  overlap = !ctx->profiling && dense_fill && !fill_in_kernel;
     hipStream_t zs      = overlap ? ctx->aux_stream : st;
-    DenseFill   fill;
-    if (fill_in_kernel) {
-        fill.b0 = grads->d_dL_dpos; fill.b1 = grads->d_dL_dscale; fill.b2 = grads->d_dL_drotq; fill.b3 = grads->d_dL_dsh;
-        fill.b4 = grads->d_dL_dopacity;
-        const size_t n[5] = { P * 3, P * 3, P * 4, P * feat, P };
-        for (int a = 0; a < 5; ++a) fill.n[a] = (uint32_t)n[a];
-    }
     if (overlap) {
         LCGS_HIP_CHECK(hipEventRecord(ctx->ev_fork, st));
         LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
@@ -157,13 +144,7 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
         launch_slice_bounds(ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), (int64_t)P, ctx->grad_slices,
                             ctx->slice_bounds.as<uint32_t>(), zs); // (before the fill: ev_join / stream order covers it)
     }
-    if (dense_fill && !fill_in_kernel) {
-        LCGS_HIP_CHECK(hipMemsetAsync(grads->d_dL_dpos, 0, P * 3 * 4, zs));
-        LCGS_HIP_CHECK(hipMemsetAsync(grads->d_dL_dscale, 0, P * 3 * 4, zs));
-        LCGS_HIP_CHECK(hipMemsetAsync(grads->d_dL_drotq, 0, P * 4 * 4, zs));
-        LCGS_HIP_CHECK(hipMemsetAsync(grads->d_dL_dsh, 0, P * feat * 4, zs));
-        LCGS_HIP_CHECK(hipMemsetAsync(grads->d_dL_dopacity, 0, P * 4, zs));
-    }
+    if (dense_fill && !fill_in_kernel) LCGS_TRY(zero_grad_rows(*grads, ctx->sh_deg, P, zs));
     if (overlap) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->aux_stream));
     if (ctx->g2d_zeroed && !ctx->profiling) { // cleared by the forward's renderer (first backward of this frame only)
         ctx->g2d_zeroed = false;

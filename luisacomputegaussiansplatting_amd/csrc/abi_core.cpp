@@ -136,16 +136,13 @@ lcgs_status check_frame_flags(lcgs_context* ctx)
         // The pair workspace was too small for one or more frames since the last check (the device keeps the count and
         // the largest demand in sticky words, so a truncated asynchronous frame is not forgotten when later frames
         // fit): those images are truncated.  Grow for the next frame and clear the record.
-        uint64_t want = (uint64_t)ctx->h_counts[7] + ctx->h_counts[7] / 4;
-        if (want > 0x7FFFFFFFull) want = 0x7FFFFFFFull;
-        ctx->pair_capacity = std::max(ctx->pair_capacity, (uint32_t)want);
         char buf[320];
         snprintf(buf, sizeof(buf),
                  "%u asynchronous frame(s) needed more (tile, splat) pairs than the workspace held (up to %u); their "
                  "images are truncated.  The workspace has been grown: render those frames again",
                  ctx->h_counts[6], ctx->h_counts[7]);
-        ctx->h_counts[3] = ctx->h_counts[6] = ctx->h_counts[7] = 0;
-        LCGS_HIP_CHECK(hipMemsetAsync(ctx->counts.as<uint32_t>() + 6, 0, 8, ctx->stream));
+        const lcgs_status grown = grow_pair_capacity(ctx, ctx->h_counts[7]); // (beyond 2^31 - 1 pairs: nothing to grow to)
+        if (grown == LCGS_ERR_HIP) return grown;
         set_last_error(buf);
         return LCGS_ERR_CAPACITY;
     }

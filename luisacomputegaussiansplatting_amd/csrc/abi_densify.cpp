@@ -6,7 +6,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <string>
 
 #include "abi_internal.hpp"
 
@@ -93,11 +92,11 @@ lcgs_status lcgs_densify(lcgs_context* ctx, int num_gaussians, int sh_degree, co
     }
     if (total == 0) return LCGS_OK;
     scene_arrays_written(ctx, out_activated->pos, out_activated->scale, out_activated->rotq); // (destinations a context renders)
-    auto pack = [](const lcgs_params* p) { return AdamArrays{ p->pos, p->scale, p->rotq, p->sh, p->opacity }; };
     // ln 1.6 to binary32 (children are 1.6 x smaller: raw scale - ln 1.6), rounded once from the double value
     const float split_drop = (float)log((double)1.6f);
-    launch_densify_scatter(P, (sh_degree + 1) * (sh_degree + 1) * 3, ctx->dn_action.as<uint8_t>(), ctx->dn_incl.as<uint32_t>(),
-                           pack(raw), pack(m), pack(v), pack(out_raw), pack(out_m), pack(out_v), pack(out_activated),
+    launch_densify_scatter(P, (int)sh_floats(sh_degree), ctx->dn_action.as<uint8_t>(), ctx->dn_incl.as<uint32_t>(),
+                           adam_arrays(raw), adam_arrays(m), adam_arrays(v), adam_arrays(out_raw), adam_arrays(out_m), adam_arrays(out_v),
+                           adam_arrays(out_activated),
                            split_drop, d_noise, cfg->seed, d_src_row, st);
     LCGS_HIP_CHECK(hipMemsetAsync(out_stats->grad_accum, 0, (size_t)total * 4, st));
     LCGS_HIP_CHECK(hipMemsetAsync(out_stats->denom, 0, (size_t)total * 4, st));

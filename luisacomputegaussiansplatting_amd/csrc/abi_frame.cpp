@@ -1,17 +1,14 @@
 // abi_frame.cpp -- the C ABI, part 4: the fused frame -- workspace, the one-submission enqueue, 
 // lcgs_render_forward, camera batches and the sibling context they alternate with.
+#include <assert.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <new>
-#include <string>
-#include <vector>
 
 #include "abi_internal.hpp"
-#include "kernels/tie_order.hpp"
 
 using namespace lcgs;
 using namespace lcgs::abi;
@@ -88,112 +85,64 @@ lcgs_status ensure_fused_workspace(lcgs_context* ctx, const CamParams& cp, bool 
     return LCGS_OK;
 }
 
-} // namespace abi
-} // namespace lcgs
-
-namespace
+lcgs_status join_aux_stream(lcgs_context* ctx)
 {
-// enqueue one fused forward frame (no synchronisation)
-// d_fp: when non-NULL, camera / bg / scale_modifier are read from device memory by the kernels (graph replay)
-// in_capture: the frame is being recorded into a hipGraph (fixed pointers): no per-frame buffer alternation
-lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float bg[3], float scale_modifier,
-                            float* d_img, int32_t* d_radii, bool keep_state, const FrameParams* d_fp,
-                            bool in_capture = false)
+    if (!ctx->aux_pending) return LCGS_OK;
+    LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_aux_done, 0));
+    ctx->aux_pending = false;
+    return LCGS_OK;
+}
+
+lcgs_status use_zero_block(lcgs_context* ctx, int zb, bool cleared, hipStream_t st)
 {
-    const hipStream_t st = ctx->stream; // the stream whose order the caller sees
-    uint32_t*    d_counts = ctx->counts.as<uint32_t>();
-    const int    P        = ctx->P;
-    SplatRecord* recs     = ctx->recs.as<SplatRecord>();
-    const uint32_t G      = cp.grid_x * cp.grid_y;
-    ctx->n_marks          = 0;
-    LCGS_TRY(mark(ctx, "begin"));
+    if (!cleared) LCGS_HIP_CHECK(hipMemsetAsync(ctx->zero_ws[zb].ptr, 0, ctx->zero_bytes, st));
+    ctx->zero_ready[zb] = false;
+    ctx->ranges         = reinterpret_cast<uint32_t*>(ctx->zero_ws[zb].as<char>() + ctx->zero_scan_bytes);
+    ctx->work_counters  = reinterpret_cast<uint32_t*>(ctx->zero_ws[zb].as<char>() + ctx->zero_bytes - 256);
+    return LCGS_OK;
+}
 
-    // With per-stage profiling on, everything runs in order on the main stream so that stage times stay
-    // attributable; otherwise independent work moves to the auxiliary stream (see below).
-    const bool overlap  = !ctx->profiling;
-    const bool deferred = overlap && !in_capture;
-    // Zeroed per frame: the tile ranges (the reference zero-fills ranges too,
-    // gs_tile_splatter/impl.cpp:147).  Normally the auxiliary stream cleared this frame's copy during the last frame.
-    const int zb = deferred ? ctx->zero_cur : 0;
-    if (!deferred && ctx->aux_pending && !in_capture) {
-        // leaving the pipelined mode (profiling switched on): the auxiliary stream may still be filling a copy or
-        // writing a tile schedule this in-order frame is about to use
-        LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_aux_done, 0));
-        ctx->aux_pending = false;
-        for (bool& r : ctx->zero_ready) r = false;
-    }
-    if (!(deferred && ctx->zero_ready[zb])) LCGS_HIP_CHECK(hipMemsetAsync(ctx->zero_ws[zb].ptr, 0, ctx->zero_bytes, st));
-    ctx->zero_ready[zb]  = false;
-    ctx->ranges          = reinterpret_cast<uint32_t*>(ctx->zero_ws[zb].as<char>() + ctx->zero_scan_bytes);
-    ctx->work_counters   = reinterpret_cast<uint32_t*>(ctx->zero_ws[zb].as<char>() + ctx->zero_bytes - 256);
-    const DepthSortFirstPass dfirst = depth_sort_first_pass(P, ctx->sort_ws.ptr);
-    launch_cull_compact(P, cp, scale_modifier, d_fp, ctx->pos, ctx->scale, ctx->rotq, ctx->opacity, d_radii,
-                        ctx->cull_slab.as<uint4>(), ctx->chunk_info.as<uint2>(), dfirst, st, ctx->cull_rows());
-    LCGS_TRY(mark(ctx, "cull_compact"));
-    const int64_t hint_V = ctx->hint_V > 0 ? ctx->hint_V : P;
-    // (per-tile and per-block frames of one context keep a launch-size hint each: their pair counts differ by up to 3 x, and a
-    // context that alternates between them -- a viewer beside a trainer -- would size every forward-only frame for the other's)
-    const int64_t hint_own = cp.list_shift ? (ctx->hint_Lb > 0 ? ctx->hint_Lb : ctx->hint_L) : ctx->hint_L;
-    const int64_t hint_L   = hint_own > 0 ? hint_own : ctx->pair_capacity;
-    // survivors by depth bits (the low 32 bits of the reference key), sorted before duplication.  The first pass reads
-    // the cull pass's chunk slabs, hands out the dense ids and writes vis_index / rects; its completion is the fork
-    // point of the record builder.
-    // a scene the context re-ordered: equal depths must still blend in ascending FILE index, as in the reference
-    // (kernels/tie_order.hpp); the sorted values then carry a file-index tag above the dense id's id_bits
-    TieOrder tie;
-    uint32_t id_mask = 0xFFFFFFFFu;
-    if (ctx->perm_valid) {
-        tie.d_counts  = d_counts;
-        tie.vis_index = ctx->vis_index.as<uint32_t>();
-        tie.perm      = ctx->scene_perm.as<uint32_t>();
-        tie.id_bits   = (uint32_t)std::max(1, ceil_log2_u32((uint32_t)P));
-        tie.tag_shift = 2u * tie.id_bits > 32u ? 2u * tie.id_bits - 32u : 0u;
-        id_mask       = (1u << tie.id_bits) - 1u;
-        tie.scratch_k1 = ctx->tie_ws.as<uint32_t>(); // (sized by ensure_fused_workspace: no allocation in here)
-    }
-    launch_depth_sort_from_chunks(P, hint_V, ctx->cull_slab.as<uint4>(), ctx->chunk_info.as<uint2>(),
-                                  ctx->chunk_base.as<uint32_t>(), ctx->sortk[0].as<uint32_t>(), ctx->sortk[1].as<uint32_t>(),
-                                  ctx->sortv[0].as<uint32_t>(), ctx->sortv[1].as<uint32_t>(), ctx->vis_index.as<uint32_t>(),
-                                  ctx->rects.as<uint2>(), d_counts, ctx->sort_ws.ptr, st,
-                                  (overlap && !in_capture) ? ctx->ev_fork : nullptr, ctx->perm_valid ? &tie : nullptr);
-    const uint32_t* order = ctx->sortv[0].as<uint32_t>();
-    LCGS_TRY(mark(ctx, "depth_sort"));
-    // Record building (SH fetch + colour: bandwidth-bound) is independent of the rest of the sort chain (latency-bound
-    // short kernels): fork it onto the auxiliary stream so the two overlap; the renderer joins.
-    hipStream_t rec_stream = overlap ? ctx->aux_stream : st;
-    if (overlap) {
-        // (in a capture the fork is recorded here, after the whole depth sort; otherwise the first pass's scatter
-        //  dispatch carries it)
-        if (in_capture) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_fork, st));
-        LCGS_HIP_CHECK(hipStreamWaitEvent(rec_stream, ctx->ev_fork, 0));
-    }
-    launch_build_records((int)std::min<int64_t>(P, hint_V), ctx->sh_deg, cp, scale_modifier, d_fp, ctx->pos, ctx->scale,
-                         ctx->rotq, ctx->sh, ctx->opacity, ctx->vis_index.as<uint32_t>(), d_counts, recs, rec_stream,
-                         ctx->use_half_sh ? ctx->sh_half.as<uint16_t>() : nullptr,
-                         keep_state ? ctx->shjac.as<float4>() : nullptr);
-    ctx->last_has_jac = keep_state && build_records_writes_jacobian(ctx->sh_deg, ctx->sh, ctx->use_half_sh);
-    if (overlap) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->aux_stream));
-    // keep_state frames: the 2-D gradient rows the backward adds to are cleared by the RENDERER as a side job (render.hip):
-    // no launch on the auxiliary stream, no cross-stream wait in front of the render-backward
-    ctx->g2d_zeroed = false;
-    const bool g2d_in_render = deferred && keep_state;
-    LCGS_TRY(mark(ctx, "build_records"));
+FrameTie frame_tie_order(lcgs_context* ctx)
+{
+    FrameTie f;
+    f.on = ctx->perm_valid;
+    if (!f.on) return f;
+    f.tie.d_counts   = ctx->counts.as<uint32_t>();
+    f.tie.vis_index  = ctx->vis_index.as<uint32_t>();
+    f.tie.perm       = ctx->scene_perm.as<uint32_t>();
+    f.tie.id_bits    = (uint32_t)std::max(1, ceil_log2_u32((uint32_t)ctx->P));
+    f.tie.tag_shift  = 2u * f.tie.id_bits > 32u ? 2u * f.tie.id_bits - 32u : 0u;
+    f.id_mask        = (1u << f.tie.id_bits) - 1u;
+    f.tie.scratch_k1 = ctx->tie_ws.as<uint32_t>(); // (sized by ensure_fused_workspace: no allocation in a frame)
+    return f;
+}
 
+lcgs_status render_sorted_frame(lcgs_context* ctx, const CamParams& cp, const float bg[3], float* d_img, const SplatRecord* recs,
+                                const uint32_t* order, uint32_t id_mask, int64_t rows, int64_t hint_L, bool keep_state,
+                                const FrameParams* d_fp, const FrameTailOptions& opt)
+{
+    const hipStream_t st       = ctx->stream;
+    uint32_t*         d_counts = ctx->counts.as<uint32_t>();
+    const uint32_t    G        = cp.grid_x * cp.grid_y;
+    const bool        deferred = opt.pipelined;
+    const int         zb       = deferred ? ctx->zero_cur : 0; // (the zero block use_zero_block selected for this frame)
+    // per-tile lists: the list grid IS the tile grid (callers that never set list_shift pass cp.grid_x for it everywhere)
+    assert(cp.list_shift != 0u || (list_grid_x(cp) == cp.grid_x && list_grid_y(cp) == cp.grid_y));
     // stable partition by tile id: only ceil(log2 G) key bits are live.  The kernel that writes the pairs also leaves
     // the partition's first per-chunk digit counts in the sort workspace (the depth sort is done with it by then).
     const int tile_bits = std::max(1, ceil_log2_u32(list_grid_x(cp) * list_grid_y(cp)));
     const PairSortFirstPass first = pair_sort_first_pass(ctx->pair_capacity, hint_L, 0, tile_bits, ctx->sort_ws.ptr);
     const bool counted =
-        launch_expand(P, hint_V, hint_L, d_counts, list_grid_x(cp), order, ctx->rects.as<uint2>(), ctx->rects_sorted.as<uint2>(),
+        launch_expand(ctx->P, rows, hint_L, d_counts, list_grid_x(cp), order, ctx->rects.as<uint2>(), ctx->rects_sorted.as<uint2>(),
                       ctx->pairk[0].as<uint32_t>(), ctx->pairv[0].as<uint32_t>(), ctx->pair_capacity,
                       ctx->expand_ws.as<uint32_t>(), st, &first, id_mask);
-    LCGS_TRY(mark(ctx, "expand"));
+    if (opt.marks) LCGS_TRY(mark(ctx, "expand"));
 
     const int where2 = launch_pair_sort_u32(ctx->pairk[0].as<uint32_t>(), ctx->pairk[1].as<uint32_t>(),
                                             ctx->pairv[0].as<uint32_t>(), ctx->pairv[1].as<uint32_t>(), d_counts + 2,
                                             ctx->pair_capacity, hint_L, 0, tile_bits, ctx->sort_ws.ptr, st,
                                             /*first_hist_done=*/counted);
-    LCGS_TRY(mark(ctx, "tile_sort"));
+    if (opt.marks) LCGS_TRY(mark(ctx, "tile_sort"));
 
     launch_get_ranges_u32(hint_L, ctx->pair_capacity, d_counts, ctx->pairk[where2].as<uint32_t>(), ctx->ranges,
                           nullptr, st, deferred ? ctx->ev_ranges : nullptr);
@@ -210,7 +159,7 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
             ctx->order_G   = G;
         }
     }
-    LCGS_TRY(mark(ctx, "ranges"));
+    if (opt.marks) LCGS_TRY(mark(ctx, "ranges"));
     if (deferred) {
         // behind the records on the auxiliary stream, beside the renderer: this frame's list lengths -> next
         // frame's schedule, and the next frame's zeroed copy
@@ -225,19 +174,19 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
         ctx->order_cur         = ob; // written before the next frame's record builder runs: its renderer waits for that
     }
 
-    if (overlap) LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_join, 0)); // records are ready
-    // several frames in flight: a bounded, persistent grid (context.hpp) -- same image, free wave slots on every CU
-    const int      k_persist = ctx->persist_forced >= 0 ? ctx->persist_forced : (ctx->frames_in_flight ? ctx->persist_in_flight : 0);
-    const uint32_t persist_wgs = (deferred && k_persist > 0) ? (uint32_t)(k_persist * std::max(ctx->num_cus, 1)) : 0u;
+    if (opt.records_ready) LCGS_HIP_CHECK(hipStreamWaitEvent(st, opt.records_ready, 0));
     launch_render_forward_rec(cp, bg, ctx->ranges, ctx->pairv[where2].as<uint32_t>(), recs, d_img,
                               keep_state ? ctx->final_T.as<float>() : nullptr,
                               keep_state ? ctx->n_contrib.as<uint32_t>() : nullptr, d_counts, d_fp, order_now, st,
                               keep_state ? ctx->strip_masks.as<uint8_t>() : nullptr, deferred ? ctx->ev_render : nullptr,
-                              ctx->work_counters, persist_wgs, g2d_in_render ? ctx->grads2d.as<float>() : nullptr,
-                              g2d_in_render ? ctx->bwd_counter.as<uint32_t>() : nullptr);
-    ctx->g2d_zeroed = g2d_in_render; // (consumed by the first backward of this frame; same stream: no event)
+                              opt.work_counter ? ctx->work_counters : nullptr, opt.persist_wgs,
+                              opt.g2d_in_render ? ctx->grads2d.as<float>() : nullptr,
+                              opt.g2d_in_render ? ctx->bwd_counter.as<uint32_t>() : nullptr);
+    ctx->g2d_zeroed      = opt.g2d_in_render; // (consumed by the first backward of this frame; same stream: no event)
     ctx->last_tile_order = order_now;
-    LCGS_TRY(mark(ctx, "render"));
+    ctx->last.list_buf   = where2;
+    if (opt.marks) LCGS_TRY(mark(ctx, "render"));
+    if (opt.pair_verdict) launch_owner_pair_verdict(d_counts, opt.pair_verdict, st);
 
     if (deferred) {
         // the counter read-back leaves through the auxiliary stream: the next frame does not queue behind it
@@ -248,12 +197,123 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
     } else {
         LCGS_HIP_CHECK(hipMemcpyAsync(ctx->h_counts, d_counts, 40, hipMemcpyDeviceToHost, st));
     }
+    return LCGS_OK;
+}
+
+void keep_frame_state(lcgs_context* ctx, const CamParams& cp, const float bg[3], float scale_modifier, bool has_state)
+{
     ctx->last.valid          = true;
-    ctx->last.has_state      = keep_state;
+    ctx->last.has_state      = has_state;
     ctx->last.cp             = cp;
     ctx->last.scale_modifier = scale_modifier;
-    ctx->last.list_buf       = where2;
     memcpy(ctx->last.bg, bg, sizeof(float) * 3);
+}
+
+lcgs_status clear_pair_overflow(lcgs_context* ctx)
+{
+    ctx->h_counts[3] = ctx->h_counts[6] = ctx->h_counts[7] = 0;
+    LCGS_HIP_CHECK(hipMemsetAsync(ctx->counts.as<uint32_t>() + 6, 0, 8, ctx->stream));
+    return LCGS_OK;
+}
+
+lcgs_status grow_pair_capacity(lcgs_context* ctx, uint32_t pairs)
+{
+    LCGS_TRY(clear_pair_overflow(ctx));
+    const uint64_t want = (uint64_t)pairs + pairs / 4;
+    if (want > 0x7FFFFFFFull) {
+        set_last_error("num_rendered exceeds 2^31 pairs");
+        return LCGS_ERR_CAPACITY;
+    }
+    ctx->pair_capacity = std::max(ctx->pair_capacity, (uint32_t)want);
+    return LCGS_OK;
+}
+
+} // namespace abi
+} // namespace lcgs
+
+namespace
+{
+// enqueue one fused forward frame (no synchronisation): cull, depth sort and the record builder's fork here, the rest is
+// render_sorted_frame
+// d_fp: when non-NULL, camera / bg / scale_modifier are read from device memory by the kernels (graph replay)
+// in_capture: the frame is being recorded into a hipGraph (fixed pointers): no per-frame buffer alternation
+lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float bg[3], float scale_modifier,
+                            float* d_img, int32_t* d_radii, bool keep_state, const FrameParams* d_fp,
+                            bool in_capture = false)
+{
+    const hipStream_t st = ctx->stream; // the stream whose order the caller sees
+    uint32_t*    d_counts = ctx->counts.as<uint32_t>();
+    const int    P        = ctx->P;
+    SplatRecord* recs     = ctx->recs.as<SplatRecord>();
+    ctx->n_marks          = 0;
+    LCGS_TRY(mark(ctx, "begin"));
+
+    // With per-stage profiling on, everything runs in order on the main stream so that stage times stay
+    // attributable; otherwise independent work moves to the auxiliary stream (see below).
+    const bool overlap  = !ctx->profiling;
+    const bool deferred = overlap && !in_capture;
+    // Zeroed per frame: the tile ranges (the reference zero-fills ranges too,
+    // gs_tile_splatter/impl.cpp:147).  Normally the auxiliary stream cleared this frame's copy during the last frame.
+    const int zb = deferred ? ctx->zero_cur : 0;
+    if (!deferred && ctx->aux_pending && !in_capture) {
+        // leaving the pipelined mode (profiling switched on): the auxiliary stream may still be filling a copy or
+        // writing a tile schedule this in-order frame is about to use
+        LCGS_TRY(join_aux_stream(ctx));
+        for (bool& r : ctx->zero_ready) r = false;
+    }
+    LCGS_TRY(use_zero_block(ctx, zb, deferred && ctx->zero_ready[zb], st));
+    const DepthSortFirstPass dfirst = depth_sort_first_pass(P, ctx->sort_ws.ptr);
+    launch_cull_compact(P, cp, scale_modifier, d_fp, ctx->pos, ctx->scale, ctx->rotq, ctx->opacity, d_radii,
+                        ctx->cull_slab.as<uint4>(), ctx->chunk_info.as<uint2>(), dfirst, st, ctx->cull_rows());
+    LCGS_TRY(mark(ctx, "cull_compact"));
+    const int64_t hint_V = ctx->hint_V > 0 ? ctx->hint_V : P;
+    // (per-tile and per-block frames of one context keep a launch-size hint each: their pair counts differ by up to 3 x, and a
+    // context that alternates between them -- a viewer beside a trainer -- would size every forward-only frame for the other's)
+    const int64_t hint_own = cp.list_shift ? (ctx->hint_Lb > 0 ? ctx->hint_Lb : ctx->hint_L) : ctx->hint_L;
+    const int64_t hint_L   = hint_own > 0 ? hint_own : ctx->pair_capacity;
+    // survivors by depth bits (the low 32 bits of the reference key), sorted before duplication.  The first pass reads
+    // the cull pass's chunk slabs, hands out the dense ids and writes vis_index / rects; its completion is the fork
+    // point of the record builder.
+    // a scene the context re-ordered: equal depths must still blend in ascending FILE index, as in the reference
+    // (kernels/tie_order.hpp); the sorted values then carry a file-index tag above the dense id's id_bits
+    const FrameTie ft = frame_tie_order(ctx);
+    launch_depth_sort_from_chunks(P, hint_V, ctx->cull_slab.as<uint4>(), ctx->chunk_info.as<uint2>(),
+                                  ctx->chunk_base.as<uint32_t>(), ctx->sortk[0].as<uint32_t>(), ctx->sortk[1].as<uint32_t>(),
+                                  ctx->sortv[0].as<uint32_t>(), ctx->sortv[1].as<uint32_t>(), ctx->vis_index.as<uint32_t>(),
+                                  ctx->rects.as<uint2>(), d_counts, ctx->sort_ws.ptr, st,
+                                  (overlap && !in_capture) ? ctx->ev_fork : nullptr, ft.on ? &ft.tie : nullptr);
+    LCGS_TRY(mark(ctx, "depth_sort"));
+    // Record building (SH fetch + colour: bandwidth-bound) is independent of the rest of the sort chain (latency-bound
+    // short kernels): fork it onto the auxiliary stream so the two overlap; the renderer joins.
+    hipStream_t rec_stream = overlap ? ctx->aux_stream : st;
+    if (overlap) {
+        // (in a capture the fork is recorded here, after the whole depth sort; otherwise the first pass's scatter
+        //  dispatch carries it)
+        if (in_capture) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_fork, st));
+        LCGS_HIP_CHECK(hipStreamWaitEvent(rec_stream, ctx->ev_fork, 0));
+    }
+    launch_build_records((int)std::min<int64_t>(P, hint_V), ctx->sh_deg, cp, scale_modifier, d_fp, ctx->pos, ctx->scale,
+                         ctx->rotq, ctx->sh, ctx->opacity, ctx->vis_index.as<uint32_t>(), d_counts, recs, rec_stream,
+                         ctx->use_half_sh ? ctx->sh_half.as<uint16_t>() : nullptr,
+                         keep_state ? ctx->shjac.as<float4>() : nullptr);
+    ctx->last_has_jac = keep_state && build_records_writes_jacobian(ctx->sh_deg, ctx->sh, ctx->use_half_sh);
+    if (overlap) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->aux_stream));
+    LCGS_TRY(mark(ctx, "build_records"));
+
+    FrameTailOptions opt;
+    opt.pipelined    = deferred;
+    opt.marks        = true;
+    opt.work_counter = true;
+    // several frames in flight: a bounded, persistent grid (context.hpp) -- same image, free wave slots on every CU
+    const int k_persist = ctx->persist_forced >= 0 ? ctx->persist_forced : (ctx->frames_in_flight ? ctx->persist_in_flight : 0);
+    opt.persist_wgs     = (deferred && k_persist > 0) ? (uint32_t)(k_persist * std::max(ctx->num_cus, 1)) : 0u;
+    // keep_state frames: the 2-D gradient rows the backward adds to are cleared by the RENDERER as a side job (render.hip):
+    // no launch on the auxiliary stream, no cross-stream wait in front of the render-backward
+    opt.g2d_in_render = deferred && keep_state;
+    opt.records_ready = overlap ? ctx->ev_join : nullptr;
+    LCGS_TRY(render_sorted_frame(ctx, cp, bg, d_img, recs, ctx->sortv[0].as<uint32_t>(), ft.id_mask, hint_V, hint_L, keep_state, d_fp,
+                                 opt));
+    keep_frame_state(ctx, cp, bg, scale_modifier, keep_state);
     return LCGS_OK;
 }
 } // namespace
@@ -319,11 +379,8 @@ lcgs_status lcgs_render_forward(lcgs_context* ctx, const lcgs_camera* camera, co
                 ctx->graph_key = key;
             }
             LCGS_HIP_CHECK(hipGraphLaunch(ctx->graph_exec, ctx->stream));
-            ctx->last.valid          = true;
-            ctx->last.has_state      = keep_state != 0;
-            ctx->last.cp             = cp;
-            ctx->last.scale_modifier = scale_modifier;
-            memcpy(ctx->last.bg, bg_color, sizeof(float) * 3);
+            // (a replay records no more than this: not list_buf, last_tile_order or last_has_jac -- docs/DESIGN_LONG.md)
+            keep_frame_state(ctx, cp, bg_color, scale_modifier, keep_state != 0);
         } else {
             LCGS_TRY(enqueue_forward(ctx, cp, bg_color, scale_modifier, d_img, d_radii, keep_state != 0, nullptr));
         }
@@ -340,12 +397,8 @@ lcgs_status lcgs_render_forward(lcgs_context* ctx, const lcgs_camera* camera, co
         if (ctx->h_counts[5] != 0) return check_frame_flags(ctx);
         // launch-size hints for the following asynchronous frames
         // (kept unless the live counts leave the [hint/2, hint] band, so a captured graph stays valid)
-        if ((int64_t)ctx->h_counts[0] > ctx->hint_V || (int64_t)ctx->h_counts[0] * 2 < ctx->hint_V)
-            ctx->hint_V = (int64_t)ctx->h_counts[0] + ctx->h_counts[0] / 4 + 4096;
-        {
-            int64_t& hl = cp.list_shift ? ctx->hint_Lb : ctx->hint_L;
-            if ((int64_t)ctx->h_counts[4] > hl || (int64_t)ctx->h_counts[4] * 2 < hl) hl = (int64_t)ctx->h_counts[4] + ctx->h_counts[4] / 4 + 4096;
-        }
+        update_hint(ctx->hint_V, ctx->h_counts[0]);
+        update_hint(cp.list_shift ? ctx->hint_Lb : ctx->hint_L, ctx->h_counts[4]);
         {   // per-block lists for the following frames without backward state?  (context.hpp coarse_mode)  The decision is
             // made in PER-TILE pairs whichever granularity this frame used: a per-tile frame has the count itself and notes
             // its share of the reference's num_rendered (the pruning's yield: a property of the scene, 0.58 on the bicycle
@@ -366,17 +419,8 @@ lcgs_status lcgs_render_forward(lcgs_context* ctx, const lcgs_camera* camera, co
         ctx->stats.list_shift = cp.list_shift;
         // overflow bookkeeping: [3] this frame, [6] / [7] every frame since the last read-back (sticky on the device)
         const bool     own    = ctx->h_counts[3] != 0;
-        const uint32_t sticky = ctx->h_counts[6], sticky_want = ctx->h_counts[7];
-        if (sticky) {
-            ctx->h_counts[6] = ctx->h_counts[7] = 0;
-            LCGS_HIP_CHECK(hipMemsetAsync(ctx->counts.as<uint32_t>() + 6, 0, 8, ctx->stream));
-            uint64_t want = (uint64_t)sticky_want + sticky_want / 4;
-            if (want > 0x7FFFFFFFull) {
-                set_last_error("num_rendered exceeds 2^31 pairs");
-                return LCGS_ERR_CAPACITY;
-            }
-            ctx->pair_capacity = std::max(ctx->pair_capacity, (uint32_t)want);
-        }
+        const uint32_t sticky = ctx->h_counts[6];
+        if (sticky) LCGS_TRY(grow_pair_capacity(ctx, ctx->h_counts[7]));
         if (sticky > (own ? 1u : 0u)) earlier_truncated += sticky - (own ? 1u : 0u);
         if (own) continue; // pair buffers were too small for this view: grown above, redo the frame
         if (earlier_truncated) {

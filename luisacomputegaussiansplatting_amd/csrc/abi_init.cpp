@@ -85,9 +85,8 @@ lcgs_status lcgs_scene_init_from_points(lcgs_context* ctx, int num_points, int s
     // logit(initial_opacity) to binary32, rounded once from the double value
     const double p           = (double)cfg->initial_opacity;
     const float  raw_opacity = (float)log(p / (1.0 - p));
-    auto         pack        = [](const lcgs_params* q) { return AdamArrays{ q->pos, q->scale, q->rotq, q->sh, q->opacity }; };
-    launch_init_rows(n, (sh_degree + 1) * (sh_degree + 1) * 3, d_pos, d_rgb, ctx->knn_dist2.as<float>(), cfg->min_dist2, raw_opacity,
-                     pack(out_raw), pack(out_activated), ctx->stream);
+    launch_init_rows(n, (int)sh_floats(sh_degree), d_pos, d_rgb, ctx->knn_dist2.as<float>(), cfg->min_dist2, raw_opacity,
+                     adam_arrays(out_raw), adam_arrays(out_activated), ctx->stream);
     LCGS_TRY(mark(ctx, "init_rows"));
     LCGS_HIP_CHECK(hipGetLastError());
     if (ctx->profiling) LCGS_TRY(collect_marks(ctx));

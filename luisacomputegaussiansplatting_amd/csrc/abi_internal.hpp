@@ -10,11 +10,15 @@
 //   abi_densify.cpp   adaptive density control: lcgs_densify_accumulate, lcgs_densify, lcgs_opacity_reset
 //   abi_loss.cpp      lcgs_photometric_loss_backward, lcgs_set_fit_loss
 //   abi_init.cpp      a scene from a point cloud: lcgs_knn_mean_dist2, lcgs_scene_init_from_points, lcgs_scene_extent
+//   abi_owner.cpp     the frame in two halves (splat ownership): lcgs_owner_project / _render / _render_backward / _backward
 #pragma once
+
+#include <algorithm>
 
 #include "common.hpp"
 #include "context.hpp"
 #include "kernels/launch.hpp"
+#include "kernels/tie_order.hpp"
 
 #define LCGS_TRY(expr)                    \
     do {                                  \
@@ -32,6 +36,49 @@ inline int ceil_log2_u32(uint32_t v)
     while ((1ull << b) < v) ++b;
     return b;
 }
+
+// ---- rows [first, first + count) of the five attribute arrays (pos 3, scale 3, rotq 4, sh (deg + 1)^2 x 3, opacity 1 floats)
+inline size_t sh_floats(int deg) { return (size_t)(deg + 1) * (deg + 1) * 3; }
+struct RowFloats {
+    size_t n[5];
+    size_t operator[](int a) const { return n[a]; }
+};
+inline RowFloats row_floats(int deg) { return { { 3, 3, 4, sh_floats(deg), 1 } }; }
+struct SceneRows {
+    const float *pos, *scale, *rotq, *sh, *opacity;
+};
+inline SceneRows scene_rows(const lcgs_context* ctx) { return { ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->opacity }; }
+template <class Rows> // lcgs_grads, lcgs_params, SceneRows: five pointers in that order
+Rows rows_from(const Rows& r, int deg, size_t first)
+{
+    auto [pos, scale, rotq, sh, opacity] = r;
+    return { pos + 3 * first, scale + 3 * first, rotq + 4 * first, sh + sh_floats(deg) * first, opacity + first };
+}
+// the render-backward's zero-fill side job for `count` rows of (already offset) gradient arrays; false: an array is too long
+// for the kernel's 32-bit lengths
+inline bool dense_fill_rows(const lcgs_grads& g, int deg, size_t count, DenseFill* fill)
+{
+    if (count * sh_floats(deg) >= ((size_t)1 << 32)) return false;
+    const RowFloats w = row_floats(deg);
+    fill->b0 = g.d_dL_dpos, fill->b1 = g.d_dL_dscale, fill->b2 = g.d_dL_drotq, fill->b3 = g.d_dL_dsh, fill->b4 = g.d_dL_dopacity;
+    for (int a = 0; a < 5; ++a) fill->n[a] = (uint32_t)(count * w[a]);
+    return true;
+}
+// ... and the same rows cleared by five memsets on a stream
+inline lcgs_status zero_grad_rows(const lcgs_grads& g, int deg, size_t count, hipStream_t stream)
+{
+    float* const    arr[5] = { g.d_dL_dpos, g.d_dL_dscale, g.d_dL_drotq, g.d_dL_dsh, g.d_dL_dopacity };
+    const RowFloats w      = row_floats(deg);
+    for (int a = 0; a < 5; ++a) LCGS_HIP_CHECK(hipMemsetAsync(arr[a], 0, count * w[a] * 4, stream));
+    return LCGS_OK;
+}
+// ---- the optimiser's arguments from the C ABI's
+inline AdamArrays adam_arrays(const lcgs_params* p) { return { p->pos, p->scale, p->rotq, p->sh, p->opacity }; }
+inline AdamRates  adam_rates(const lcgs_adam_config* c)
+{
+    return { c->lr_pos, c->lr_sh_dc, c->lr_sh_rest, c->lr_opacity, c->lr_scale, c->lr_rot };
+}
+lcgs_status check_adam_config(const lcgs_adam_config* cfg); // abi_train.cpp
 
 // abi_core.cpp
 lcgs_status mark(lcgs_context* ctx, const char* name);          // per-stage timing mark (+ LCGS_DEBUG_SYNC)
@@ -70,6 +117,44 @@ void registry_remove(lcgs_context* ctx);
 void registry_publish(lcgs_context* ctx);
 // abi_frame.cpp
 lcgs_status ensure_fused_workspace(lcgs_context* ctx, const CamParams& cp, bool keep_state);
+// a pipelined frame of the context may still be using the workspace through the auxiliary stream: ctx->stream waits for it
+lcgs_status join_aux_stream(lcgs_context* ctx);
+// a frame's zeroed block (tile ranges + the persistent renderers' counters) is copy `zb`; cleared on `st` unless it already is
+lcgs_status use_zero_block(lcgs_context* ctx, int zb, bool cleared, hipStream_t st);
+// what the depth sort of a re-ordered scene needs to blend equal depths in FILE order (kernels/tie_order.hpp), and the bits
+// of a sorted value that are the dense id (on == false: the context holds the scene in file order)
+struct FrameTie {
+    TieOrder tie;
+    uint32_t id_mask = 0xFFFFFFFFu;
+    bool     on      = false;
+};
+FrameTie frame_tie_order(lcgs_context* ctx);
+// The second half of a frame, from a depth-sorted order of dense ids to the image: expand -> tile partition -> ranges ->
+// tile schedule -> renderer -> the 40-byte counter copy.  What differs between the fused frame and the one drawn from
+// received records (abi_owner.cpp, all defaults):
+struct FrameTailOptions {
+    bool       pipelined = false; // buffers rotate; next schedule, next zero block, counter copy on the auxiliary stream
+    bool       marks = false, work_counter = false; // per-stage timing marks; the renderer gets the frame's tile counter
+    uint32_t   persist_wgs   = 0;       // > 0: the renderer is a bounded persistent grid of this many workgroups
+    bool       g2d_in_render = false;   // the renderer clears the 2-D gradient rows as a side job
+    hipEvent_t records_ready = nullptr; // waited for in front of the renderer
+    uint32_t*  pair_verdict  = nullptr; // device word, |= 2 in front of the counter copy if the pair buffers were too small
+};
+// rows: the expansion's launch size (hint_V, or a known row count).  Leaves last.list_buf / last_tile_order for the backward.
+lcgs_status render_sorted_frame(lcgs_context* ctx, const CamParams& cp, const float bg[3], float* d_img, const SplatRecord* recs,
+                                const uint32_t* order, uint32_t id_mask, int64_t rows, int64_t hint_L, bool keep_state,
+                                const FrameParams* d_fp, const FrameTailOptions& opt);
+// the kept state of the last frame that every kind of frame records
+void keep_frame_state(lcgs_context* ctx, const CamParams& cp, const float bg[3], float scale_modifier, bool has_state);
+// launch-size hints follow the live counts once those leave the [hint / 2, hint] band (inside it a captured graph stays valid)
+inline void update_hint(int64_t& hint, uint32_t count)
+{
+    if ((int64_t)count > hint || (int64_t)count * 2 < hint) hint = (int64_t)count + count / 4 + 4096;
+}
+// clears the counters' overflow record ([3] the last frame's flag; [6] / [7] sticky: frames, largest demand) / ... and grows
+// pair_capacity for a demand of `pairs` with a quarter to spare, LCGS_ERR_CAPACITY beyond 2^31 - 1
+lcgs_status clear_pair_overflow(lcgs_context* ctx);
+lcgs_status grow_pair_capacity(lcgs_context* ctx, uint32_t pairs);
 lcgs_status prepare_twin(lcgs_context* ctx); // the sibling context of camera / view batches: created on first use, same scene
 
 // marks a context and its siblings as rendering several frames at once for the duration of a batch call

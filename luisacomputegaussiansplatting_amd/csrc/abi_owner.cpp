@@ -2,8 +2,9 @@
 // OWNS a range of rows runs the per-splat half of a view's frame on them (cull, compaction, SH colour: the packed 48-byte
 // records of the rows that reach that view's screen) and, later, the per-splat half of its backward; the GPU that RENDERS
 // the view runs everything from the depth sort on -- on records it received from the owners -- and the render-backward, and
-// hands the 2-D gradients back.  The kernels are the fused frame's own (abi_frame.cpp / abi_backward.cpp): only the seam
-// between the two halves is new.
+// hands the 2-D gradients back.  The kernels are the fused frame's own, and so is the host code from the sorted order to the
+// image (abi_frame.cpp render_sorted_frame) and the per-row helpers (abi_internal.hpp): only the seam between the two halves
+// -- the records unpacked into the depth sort's input, the 2-D gradient rows handed back -- is written here.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,22 +13,17 @@
 #include <algorithm>
 
 #include "abi_internal.hpp"
-#include "kernels/tie_order.hpp"
 
 using namespace lcgs;
 using namespace lcgs::abi;
 
 namespace
 {
-struct RowRange {
-    const float *pos, *scale, *rotq, *sh, *opacity;
+// the scratch of the cull / first-sort-pass stages: the context's own workspace and stream, or a lane's
+struct ProjectScratch {
+    hipStream_t         stream;
+    const DeviceBuffer &slab, &chunk_info, &chunk_base, *sortk, *sortv, &rects, &sort_ws;
 };
-RowRange shard_of(lcgs_context* ctx, int row_first)
-{
-    const size_t feat = (size_t)(ctx->sh_deg + 1) * (ctx->sh_deg + 1) * 3;
-    return { ctx->pos + 3 * (size_t)row_first, ctx->scale + 3 * (size_t)row_first, ctx->rotq + 4 * (size_t)row_first,
-             ctx->sh + feat * (size_t)row_first, ctx->opacity + (size_t)row_first };
-}
 
 // The per-splat half of one view's frame on the slot's row range: the fused frame's first stages -- cull, compaction (the depth
 // sort's first pass only: the renderer of the view sorts what it receives), colour + packed records -- on the context's own
@@ -41,23 +37,21 @@ lcgs_status project_rows(lcgs_context* ctx, int slot, const CamParams& cp, float
     LCGS_TRY(s.vis.ensure(n * 4 + 16));
     LCGS_TRY(s.counts.ensure(64));
     if (keep_state) LCGS_TRY(s.shjac.ensure(n * 48));
-    hipStream_t    st = lane ? lane->stream : ctx->stream;
-    const RowRange r  = shard_of(ctx, row_first);
-    uint32_t*      dc = s.counts.as<uint32_t>();
-    uint4*         slab       = lane ? lane->slab.as<uint4>() : ctx->cull_slab.as<uint4>();
-    uint2*         chunk_info = lane ? lane->chunk_info.as<uint2>() : ctx->chunk_info.as<uint2>();
-    uint32_t*      chunk_base = lane ? lane->chunk_base.as<uint32_t>() : ctx->chunk_base.as<uint32_t>();
-    uint32_t*      k0 = lane ? lane->sortk[0].as<uint32_t>() : ctx->sortk[0].as<uint32_t>();
-    uint32_t*      k1 = lane ? lane->sortk[1].as<uint32_t>() : ctx->sortk[1].as<uint32_t>();
-    uint32_t*      v0 = lane ? lane->sortv[0].as<uint32_t>() : ctx->sortv[0].as<uint32_t>();
-    uint32_t*      v1 = lane ? lane->sortv[1].as<uint32_t>() : ctx->sortv[1].as<uint32_t>();
-    uint2*         rects   = lane ? lane->rects.as<uint2>() : ctx->rects.as<uint2>();
-    void*          sort_ws = lane ? lane->sort_ws.ptr : ctx->sort_ws.ptr;
-    const DepthSortFirstPass dfirst = depth_sort_first_pass(row_count, sort_ws);
+    const ProjectScratch w =
+        lane ? ProjectScratch{ lane->stream, lane->slab, lane->chunk_info, lane->chunk_base, lane->sortk, lane->sortv, lane->rects, lane->sort_ws }
+             : ProjectScratch{ ctx->stream, ctx->cull_slab, ctx->chunk_info, ctx->chunk_base, ctx->sortk, ctx->sortv, ctx->rects, ctx->sort_ws };
+    const hipStream_t    st = w.stream;
+    const SceneRows      r  = rows_from(scene_rows(ctx), ctx->sh_deg, (size_t)row_first);
+    uint32_t*            dc = s.counts.as<uint32_t>();
+    uint4*               slab = w.slab.as<uint4>();
+    uint2*               chunk_info = w.chunk_info.as<uint2>();
+    const DepthSortFirstPass dfirst = depth_sort_first_pass(row_count, w.sort_ws.ptr);
     launch_cull_compact(row_count, cp, scale_modifier, nullptr, r.pos, r.scale, r.rotq, r.opacity, nullptr, slab, chunk_info, dfirst,
                         st, ctx->cull_rows() ? ctx->cull_rows() + row_first : nullptr); // (the scene's bound rows, if it has them)
-    launch_depth_sort_from_chunks(row_count, row_count, slab, chunk_info, chunk_base, k0, k1, v0, v1, s.vis.as<uint32_t>(), rects, dc,
-                                  sort_ws, st, nullptr, nullptr, /*first_pass_only=*/true);
+    launch_depth_sort_from_chunks(row_count, row_count, slab, chunk_info, w.chunk_base.as<uint32_t>(), w.sortk[0].as<uint32_t>(),
+                                  w.sortk[1].as<uint32_t>(), w.sortv[0].as<uint32_t>(), w.sortv[1].as<uint32_t>(),
+                                  s.vis.as<uint32_t>(), w.rects.as<uint2>(), dc, w.sort_ws.ptr, st, nullptr, nullptr,
+                                  /*first_pass_only=*/true);
     launch_build_records(row_count, ctx->sh_deg, cp, scale_modifier, nullptr, r.pos, r.scale, r.rotq, r.sh, r.opacity,
                          s.vis.as<uint32_t>(), dc, reinterpret_cast<SplatRecord*>(d_records), st, nullptr,
                          keep_state ? s.shjac.as<float4>() : nullptr);
@@ -95,10 +89,7 @@ lcgs_status lcgs_owner_project(lcgs_context* ctx, int slot, const lcgs_camera* c
     if (row_count == 0) return LCGS_OK;
     const CamParams cp = make_cam_params(*camera);
     LCGS_TRY(ensure_fused_workspace(ctx, cp, keep_state != 0));
-    if (ctx->aux_pending) { // a pipelined frame of this context may still be using the workspace through the auxiliary stream
-        LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_aux_done, 0));
-        ctx->aux_pending = false;
-    }
+    LCGS_TRY(join_aux_stream(ctx));
     LCGS_TRY(project_rows(ctx, slot, cp, scale_modifier, keep_state != 0, d_rows, d_records, nullptr));
     if (!num_rows) return LCGS_OK; // asynchronous: lcgs_owner_counts reads the count (with the other views' counts)
     return lcgs_owner_counts(ctx, slot, 1, num_rows);
@@ -137,10 +128,7 @@ lcgs_status lcgs_owner_project_views(lcgs_context* ctx, int first_slot, int num_
     }
     if (row_count == 0) return LCGS_OK;
     LCGS_TRY(ensure_fused_workspace(ctx, make_cam_params(cameras[0]), keep_state != 0));
-    if (ctx->aux_pending) {
-        LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_aux_done, 0));
-        ctx->aux_pending = false;
-    }
+    LCGS_TRY(join_aux_stream(ctx));
     if (lanes <= 1) { // one view (or the hook): the context's own workspace and stream
         for (int k = 0; k < num_views; ++k)
             LCGS_TRY(project_rows(ctx, first_slot + k, make_cam_params(cameras[k]), scale_modifier, keep_state != 0, d_rows[k],
@@ -234,111 +222,52 @@ lcgs_status lcgs::abi::owner_render_frame(lcgs_context* ctx, const lcgs_camera* 
     const CamParams    cp   = make_cam_params(*camera);
     hipStream_t        st   = ctx->stream;
     const SplatRecord* recs = reinterpret_cast<const SplatRecord*>(d_records);
-    const uint32_t     G    = cp.grid_x * cp.grid_y;
     for (int attempt = 0; attempt < 4; ++attempt) {
         LCGS_TRY(ensure_fused_workspace(ctx, cp, keep_state != 0));
         uint32_t* dc = ctx->counts.as<uint32_t>();
-        if (ctx->aux_pending) { // a pipelined frame of this context may still be using the auxiliary stream's buffers
-            LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_aux_done, 0));
-            ctx->aux_pending = false;
-        }
+        LCGS_TRY(join_aux_stream(ctx));
         for (bool& z : ctx->zero_ready) z = false;
-        LCGS_HIP_CHECK(hipMemsetAsync(ctx->zero_ws[0].ptr, 0, ctx->zero_bytes, st));
-        ctx->ranges        = reinterpret_cast<uint32_t*>(ctx->zero_ws[0].as<char>() + ctx->zero_scan_bytes);
-        ctx->work_counters = reinterpret_cast<uint32_t*>(ctx->zero_ws[0].as<char>() + ctx->zero_bytes - 256);
+        LCGS_TRY(use_zero_block(ctx, 0, /*cleared=*/false, st));
         // equal depths blend in ascending FILE index (tie_order.hpp): the received rows are ascending rows of the scene as
         // the contexts hold it -- its file order, unless the scene was re-ordered, in which case the tags restore it
-        TieOrder   tie;
-        uint32_t   id_mask = 0xFFFFFFFFu;
-        const bool tied    = ctx->perm_valid;
-        if (tied) {
-            tie.d_counts   = dc;
-            tie.vis_index  = ctx->vis_index.as<uint32_t>();
-            tie.perm       = ctx->scene_perm.as<uint32_t>();
-            tie.id_bits    = (uint32_t)std::max(1, ceil_log2_u32((uint32_t)ctx->P));
-            tie.tag_shift  = 2u * tie.id_bits > 32u ? 2u * tie.id_bits - 32u : 0u;
-            id_mask        = (1u << tie.id_bits) - 1u;
-            tie.scratch_k1 = ctx->tie_ws.as<uint32_t>();
-        }
+        const FrameTie  ft = frame_tie_order(ctx);
+        const TieOrder& tie = ft.tie;
         if (af)
-            launch_unpack_records_seg(af->segs, af->table, af->view, recs, d_rows, tied ? tie.perm : nullptr, tie.id_bits,
-                                      tie.tag_shift, ctx->sortk[0].as<uint32_t>(), ctx->sortv[0].as<uint32_t>(),
-                                      ctx->rects.as<uint2>(), ctx->vis_index.as<uint32_t>(), dc, af->overflow, (uint32_t)ctx->P,
-                                      cp.grid_x, cp.grid_y, st);
+            launch_unpack_records_seg(af->segs, af->table, af->view, recs, d_rows, tie.perm, tie.id_bits, tie.tag_shift,
+                                      ctx->sortk[0].as<uint32_t>(), ctx->sortv[0].as<uint32_t>(), ctx->rects.as<uint2>(),
+                                      ctx->vis_index.as<uint32_t>(), dc, af->overflow, (uint32_t)ctx->P, cp.grid_x, cp.grid_y, st);
         else
-            launch_unpack_records(num_rows, recs, d_rows, tied ? tie.perm : nullptr, tie.id_bits, tie.tag_shift,
-                                  ctx->sortk[0].as<uint32_t>(), ctx->sortv[0].as<uint32_t>(), ctx->rects.as<uint2>(),
-                                  ctx->vis_index.as<uint32_t>(), dc, (uint32_t)ctx->P, cp.grid_x, cp.grid_y, st);
+            launch_unpack_records(num_rows, recs, d_rows, tie.perm, tie.id_bits, tie.tag_shift, ctx->sortk[0].as<uint32_t>(),
+                                  ctx->sortv[0].as<uint32_t>(), ctx->rects.as<uint2>(), ctx->vis_index.as<uint32_t>(), dc,
+                                  (uint32_t)ctx->P, cp.grid_x, cp.grid_y, st);
         const int w = launch_pair_sort_u32(ctx->sortk[0].as<uint32_t>(), ctx->sortk[1].as<uint32_t>(),
                                            ctx->sortv[0].as<uint32_t>(), ctx->sortv[1].as<uint32_t>(), dc, ctx->P, num_rows, 0, 32,
                                            ctx->sort_ws.ptr, st);
-        if (tied)
+        if (ft.on)
             launch_fix_equal_depth_order(ctx->sortk[w].as<uint32_t>(), ctx->sortv[w].as<uint32_t>(),
                                          ctx->sortk[w ^ 1].as<uint32_t>(), ctx->sortv[w ^ 1].as<uint32_t>(), ctx->P, num_rows, tie,
                                          st);
-        const uint32_t*         order     = ctx->sortv[w].as<uint32_t>();
-        const int               tile_bits = std::max(1, ceil_log2_u32(G));
-        const int64_t           hint_L    = ctx->hint_L > 0 ? ctx->hint_L : ctx->pair_capacity;
-        const PairSortFirstPass first     = pair_sort_first_pass(ctx->pair_capacity, hint_L, 0, tile_bits, ctx->sort_ws.ptr);
-        const bool counted = launch_expand(ctx->P, num_rows, hint_L, dc, cp.grid_x, order, ctx->rects.as<uint2>(),
-                                           ctx->rects_sorted.as<uint2>(), ctx->pairk[0].as<uint32_t>(),
-                                           ctx->pairv[0].as<uint32_t>(), ctx->pair_capacity, ctx->expand_ws.as<uint32_t>(), st,
-                                           &first, id_mask);
-        const int where2 = launch_pair_sort_u32(ctx->pairk[0].as<uint32_t>(), ctx->pairk[1].as<uint32_t>(),
-                                                ctx->pairv[0].as<uint32_t>(), ctx->pairv[1].as<uint32_t>(), dc + 2,
-                                                ctx->pair_capacity, hint_L, 0, tile_bits, ctx->sort_ws.ptr, st, counted);
-        launch_get_ranges_u32(hint_L, ctx->pair_capacity, dc, ctx->pairk[where2].as<uint32_t>(), ctx->ranges, nullptr, st, nullptr);
-        uint32_t* order_now = ctx->tile_order[0].as<uint32_t>();
-        launch_tile_order(ctx->ranges, G, order_now, st, cp.grid_x, 0u);
+        // in order, on tile_order[0], no marks, no tile counter, no side job, no events (FrameTailOptions' defaults); without
+        // read-back the pair-buffer verdict travels with the step's flag, the counters to the pinned block
+        FrameTailOptions opt;
+        opt.pair_verdict = af ? af->overflow : nullptr;
+        LCGS_TRY(render_sorted_frame(ctx, cp, bg_color, d_img, recs, ctx->sortv[w].as<uint32_t>(), ft.id_mask, num_rows,
+                                     ctx->hint_L > 0 ? ctx->hint_L : ctx->pair_capacity, keep_state != 0, nullptr, opt));
         ctx->order_G = 0; // (the pipelined frames' schedule buffers were used out of turn)
-        launch_render_forward_rec(cp, bg_color, ctx->ranges, ctx->pairv[where2].as<uint32_t>(), recs, d_img,
-                                  keep_state ? ctx->final_T.as<float>() : nullptr,
-                                  keep_state ? ctx->n_contrib.as<uint32_t>() : nullptr, dc, nullptr, order_now, st,
-                                  keep_state ? ctx->strip_masks.as<uint8_t>() : nullptr, nullptr);
         LCGS_HIP_CHECK(hipGetLastError());
-        if (af) { // no read-back: the verdict travels with the step's flag, the counters to the pinned block
-            launch_owner_pair_verdict(dc, af->overflow, st);
-            LCGS_HIP_CHECK(hipMemcpyAsync(ctx->h_counts, dc, 40, hipMemcpyDeviceToHost, st));
-            ctx->counts_pending      = false;
-            ctx->last.valid          = true;
-            ctx->last.has_state      = keep_state != 0;
-            ctx->last.cp             = cp;
-            ctx->last.scale_modifier = 1.0f;
-            ctx->last.list_buf       = where2;
-            memcpy(ctx->last.bg, bg_color, sizeof(float) * 3);
-            ctx->last_tile_order = order_now;
-            ctx->owner_recs      = recs;
-            ctx->owner_rows      = num_rows;
-            ctx->g2d_zeroed      = false;
-            return LCGS_OK;
-        }
-        LCGS_HIP_CHECK(hipMemcpyAsync(ctx->h_counts, dc, 40, hipMemcpyDeviceToHost, st));
-        LCGS_HIP_CHECK(hipStreamSynchronize(st));
         ctx->counts_pending = false;
-        if ((int64_t)ctx->h_counts[4] > ctx->hint_L || (int64_t)ctx->h_counts[4] * 2 < ctx->hint_L)
-            ctx->hint_L = (int64_t)ctx->h_counts[4] + ctx->h_counts[4] / 4 + 4096;
-        if (ctx->h_counts[3] != 0) { // the pair workspace was too small for this view: grow, redo
-            const uint64_t want = (uint64_t)ctx->h_counts[7] + ctx->h_counts[7] / 4;
-            LCGS_REQUIRE(want <= 0x7FFFFFFFull, "num_rendered exceeds 2^31 pairs");
-            ctx->pair_capacity = std::max(ctx->pair_capacity, (uint32_t)want);
-            ctx->h_counts[3] = ctx->h_counts[6] = ctx->h_counts[7] = 0;
-            LCGS_HIP_CHECK(hipMemsetAsync(dc + 6, 0, 8, st));
-            continue;
+        if (!af) {
+            LCGS_HIP_CHECK(hipStreamSynchronize(st));
+            update_hint(ctx->hint_L, ctx->h_counts[4]);
+            if (ctx->h_counts[3] != 0) { // the pair workspace was too small for this view: grow, redo
+                LCGS_TRY(grow_pair_capacity(ctx, ctx->h_counts[7]));
+                continue;
+            }
+            if (ctx->h_counts[6] != 0) LCGS_TRY(clear_pair_overflow(ctx)); // (a sticky record this frame did not add to: dropped)
         }
-        if (ctx->h_counts[6] != 0) { // (sticky record of this very frame's demand: nothing left to report)
-            ctx->h_counts[6] = ctx->h_counts[7] = 0;
-            LCGS_HIP_CHECK(hipMemsetAsync(dc + 6, 0, 8, st));
-        }
-        ctx->last.valid          = true;
-        ctx->last.has_state      = keep_state != 0;
-        ctx->last.cp             = cp;
-        ctx->last.scale_modifier = 1.0f;
-        ctx->last.list_buf       = where2;
-        memcpy(ctx->last.bg, bg_color, sizeof(float) * 3);
-        ctx->last_tile_order = order_now;
-        ctx->owner_recs      = recs;
-        ctx->owner_rows      = num_rows;
-        ctx->g2d_zeroed      = false;
+        keep_frame_state(ctx, cp, bg_color, /*scale_modifier=*/1.0f, keep_state != 0);
+        ctx->owner_recs = recs;
+        ctx->owner_rows = num_rows;
         return LCGS_OK;
     }
     set_last_error("pair buffer growth did not converge");
@@ -350,14 +279,13 @@ lcgs_status lcgs::abi::owner_render_frame(lcgs_context* ctx, const lcgs_camera* 
 void lcgs::abi::owner_frame_settle(lcgs_context* ctx)
 {
     if (!ctx->h_counts) return;
-    if ((int64_t)ctx->h_counts[4] > ctx->hint_L || (int64_t)ctx->h_counts[4] * 2 < ctx->hint_L)
-        ctx->hint_L = (int64_t)ctx->h_counts[4] + ctx->h_counts[4] / 4 + 4096;
-    if (ctx->h_counts[3] != 0 || ctx->h_counts[6] != 0) {
-        const uint64_t want = (uint64_t)ctx->h_counts[7] + ctx->h_counts[7] / 4;
-        if (want <= 0x7FFFFFFFull) ctx->pair_capacity = std::max(ctx->pair_capacity, (uint32_t)want);
-        ctx->h_counts[3] = ctx->h_counts[6] = ctx->h_counts[7] = 0;
-        (void)hipMemsetAsync(ctx->counts.as<uint32_t>() + 6, 0, 8, ctx->stream); // (the sticky record: reported here)
-    }
+    update_hint(ctx->hint_L, ctx->h_counts[4]);
+    // Word [6] as well as [3], unlike lcgs_owner_render's synchronous loop.  A frame that overflows raises both (fused_forward.hip),
+    // so for the step's own frame [6] adds nothing; what it adds is the record of EARLIER frames nobody read back (asynchronous
+    // fused frames of this context, a step that was never finished): they are grown for here, as lcgs_render_forward does.
+    // The synchronous loop reads behind every attempt, meets such a record only with [3] == 0 and drops it without growing;
+    // no reason for that difference was found -- both conditions are the ones the code had before the rules were shared.
+    if (ctx->h_counts[3] != 0 || ctx->h_counts[6] != 0) (void)grow_pair_capacity(ctx, ctx->h_counts[7]); // (the sticky record: reported here)
 }
 
 extern "C" {
@@ -419,32 +347,21 @@ lcgs_status lcgs::abi::owner_backward_rows(lcgs_context* ctx, int slot, const fl
         set_last_error("lcgs_owner_backward needs a preceding lcgs_owner_project into this slot");
         return LCGS_ERR_STATE;
     }
-    hipStream_t  st   = ctx->stream;
-    const size_t feat = (size_t)(ctx->sh_deg + 1) * (ctx->sh_deg + 1) * 3, f = (size_t)s.row_first, c = (size_t)s.row_count;
-    float *gp = grads->d_dL_dpos + 3 * f, *gs = grads->d_dL_dscale + 3 * f, *gq = grads->d_dL_drotq + 4 * f,
-          *gsh = grads->d_dL_dsh + feat * f, *go = grads->d_dL_dopacity + f;
-    if (mode == 0) { // the first view of the step: every row of the range that is not on its screen is an exact zero
-        LCGS_HIP_CHECK(hipMemsetAsync(gp, 0, c * 3 * 4, st));
-        LCGS_HIP_CHECK(hipMemsetAsync(gs, 0, c * 3 * 4, st));
-        LCGS_HIP_CHECK(hipMemsetAsync(gq, 0, c * 4 * 4, st));
-        LCGS_HIP_CHECK(hipMemsetAsync(gsh, 0, c * feat * 4, st));
-        LCGS_HIP_CHECK(hipMemsetAsync(go, 0, c * 4, st));
-    }
+    hipStream_t      st = ctx->stream;
+    const lcgs_grads g  = rows_from(*grads, ctx->sh_deg, (size_t)s.row_first);
+    // the first view of the step: every row of the range that is not on its screen is an exact zero
+    if (mode == 0) LCGS_TRY(zero_grad_rows(g, ctx->sh_deg, (size_t)s.row_count, st));
     if (s.num < 0) {
         set_last_error("the slot's row count is still on the device: call lcgs_owner_counts after an asynchronous lcgs_owner_project");
         return LCGS_ERR_STATE;
     }
     if (s.num == 0) return LCGS_OK;
     LCGS_REQUIRE(d_grads2d != nullptr, "NULL 2-D gradients");
-    const RowRange r = shard_of(ctx, s.row_first);
+    const SceneRows r = rows_from(scene_rows(ctx), ctx->sh_deg, (size_t)s.row_first);
     launch_preprocess_backward(s.num, ctx->sh_deg, s.cp, s.scale_modifier, r.pos, r.scale, r.rotq, r.sh, s.vis.as<uint32_t>(),
-                               s.counts.as<uint32_t>(), d_grads2d, gp, gs, gq, gsh, go, st,
-                               s.has_jac ? s.shjac.as<float4>() : nullptr, /*compact=*/false, nullptr, 0, 1, /*accumulate=*/mode == 1);
+                               s.counts.as<uint32_t>(), d_grads2d, g.d_dL_dpos, g.d_dL_dscale, g.d_dL_drotq, g.d_dL_dsh,
+                               g.d_dL_dopacity, st, s.has_jac ? s.shjac.as<float4>() : nullptr, /*compact=*/false, nullptr, 0, 1,
+                               /*accumulate=*/mode == 1);
     LCGS_HIP_CHECK(hipGetLastError());
     return LCGS_OK;
 }
-
-
-extern "C" {
-
-} // extern "C"

@@ -120,9 +120,8 @@ void registry_publish(lcgs_context* ctx)
     e->key_scale = ctx->cull_bound ? ctx->cull_key.scale : nullptr;
     e->key_rotq  = ctx->cull_bound ? ctx->cull_key.rotq : nullptr;
     e->key_P     = ctx->cull_bound ? ctx->cull_key.P : 0;
-    const size_t feat = (size_t)(ctx->sh_deg + 1) * (ctx->sh_deg + 1) * 3;
-    const float* arr[5]    = { ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->opacity };
-    const size_t floats[5] = { 3, 3, 4, feat, 1 };
+    const float*    arr[5] = { ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->opacity };
+    const RowFloats floats = row_floats(ctx->sh_deg);
     for (int i = 0; i < 5; ++i) {
         e->arr[i]        = arr[i];
         e->arr_floats[i] = floats[i] * (size_t)std::max(ctx->P, 0);
@@ -160,9 +159,8 @@ void scene_arrays_written(lcgs_context* ctx, const float* pos, const float* scal
 // siblings are handled by the caller.
 void scene_modified_elsewhere(lcgs_context* ctx)
 {
-    const size_t feat       = (size_t)(ctx->sh_deg + 1) * (ctx->sh_deg + 1) * 3;
-    const float* arr[5]     = { ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->opacity };
-    const size_t floats[5]  = { 3, 3, 4, feat, 1 };
+    const float*    arr[5] = { ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->opacity };
+    const RowFloats floats = row_floats(ctx->sh_deg);
     std::lock_guard<std::mutex> lock(g_registry_mutex);
     for (Published& e : g_registry) {
         if (same_thread_family(ctx, e.ctx)) continue;
@@ -293,14 +291,13 @@ lcgs_status lcgs_scene_upload(lcgs_context* ctx, int num_gaussians, int sh_degre
     LCGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "sh_degree must be in [0,3]");
     if (num_gaussians > 0) LCGS_REQUIRE(h_pos && h_scale && h_rotq && h_sh && h_opacity, "NULL host pointer");
     const size_t P        = (size_t)num_gaussians;
-    const size_t feat     = (size_t)(sh_degree + 1) * (sh_degree + 1) * 3;
-    const size_t sizes[5] = { P * 3 * 4, P * 3 * 4, P * 4 * 4, P * feat * 4, P * 4 };
-    const float* src[5]   = { h_pos, h_scale, h_rotq, h_sh, h_opacity };
+    const RowFloats rowf  = row_floats(sh_degree);
+    const float*    src[5] = { h_pos, h_scale, h_rotq, h_sh, h_opacity };
     ctx->perm_for_owned = false; // owned[] is rewritten in the given order
     for (int i = 0; i < 5; ++i) {
-        LCGS_TRY(ctx->owned[i].ensure(std::max<size_t>(sizes[i], 16)));
-        if (sizes[i])
-            LCGS_HIP_CHECK(hipMemcpyAsync(ctx->owned[i].ptr, src[i], sizes[i], hipMemcpyHostToDevice, ctx->stream));
+        const size_t bytes = P * rowf[i] * 4;
+        LCGS_TRY(ctx->owned[i].ensure(std::max<size_t>(bytes, 16)));
+        if (bytes) LCGS_HIP_CHECK(hipMemcpyAsync(ctx->owned[i].ptr, src[i], bytes, hipMemcpyHostToDevice, ctx->stream));
     }
     LCGS_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // app/main.cpp:223
     LCGS_TRY(lcgs_scene_bind(ctx, num_gaussians, sh_degree, ctx->owned[0].as<float>(), ctx->owned[1].as<float>(),
@@ -356,8 +353,7 @@ lcgs_status lcgs_scene_reorder_spatial(lcgs_context* ctx, uint32_t* d_perm)
         if (s == LCGS_OK) s = vals[i].ensure((size_t)P * 4);
     }
     if (s == LCGS_OK) s = ws.ensure(pair_sort_ws_bytes(P));
-    const size_t feat    = (size_t)(ctx->sh_deg + 1) * (ctx->sh_deg + 1) * 3;
-    const int    rowf[5] = { 3, 3, 4, (int)feat, 1 };
+    const RowFloats rowf = row_floats(ctx->sh_deg);
     for (int i = 0; i < 5 && s == LCGS_OK; ++i) s = fresh[i].ensure(std::max<size_t>((size_t)P * rowf[i] * 4, 16));
     if (s != LCGS_OK) {
         drop();
@@ -369,7 +365,7 @@ lcgs_status lcgs_scene_reorder_spatial(lcgs_context* ctx, uint32_t* d_perm)
                                            vals[1].as<uint32_t>(), nullptr, P, P, 0, 30, ws.ptr, st);
     const uint32_t* perm   = vals[where].as<uint32_t>();
     const float*    src[5] = { ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->opacity };
-    for (int i = 0; i < 5; ++i) launch_gather_rows(P, rowf[i], perm, src[i], fresh[i].as<float>(), st);
+    for (int i = 0; i < 5; ++i) launch_gather_rows(P, (int)rowf[i], perm, src[i], fresh[i].as<float>(), st);
     e = hipGetLastError();
     DeviceBuffer kept_perm;
     if (e == hipSuccess && kept_perm.ensure((size_t)P * 4) != LCGS_OK) e = hipErrorOutOfMemory;
@@ -457,12 +453,11 @@ lcgs_status lcgs_scene_download(lcgs_context* ctx, float* h_pos, float* h_scale,
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
     const size_t P    = (size_t)ctx->P;
-    const size_t feat = (size_t)(ctx->sh_deg + 1) * (ctx->sh_deg + 1) * 3;
-    const size_t sizes[5] = { P * 3 * 4, P * 3 * 4, P * 4 * 4, P * feat * 4, P * 4 };
-    const float* src[5]   = { ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->opacity };
-    float*       dst[5]   = { h_pos, h_scale, h_rotq, h_sh, h_opacity };
+    const RowFloats rowf  = row_floats(ctx->sh_deg);
+    const float*    src[5] = { ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->opacity };
+    float*          dst[5] = { h_pos, h_scale, h_rotq, h_sh, h_opacity };
     for (int i = 0; i < 5; ++i)
-        if (dst[i] && sizes[i]) LCGS_HIP_CHECK(hipMemcpyAsync(dst[i], src[i], sizes[i], hipMemcpyDeviceToHost, ctx->stream));
+        if (dst[i] && P) LCGS_HIP_CHECK(hipMemcpyAsync(dst[i], src[i], P * rowf[i] * 4, hipMemcpyDeviceToHost, ctx->stream));
     LCGS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return LCGS_OK;
 }

@@ -7,14 +7,18 @@
 #include <string.h>
 
 #include <algorithm>
-#include <new>
-#include <string>
-#include <vector>
 
 #include "abi_internal.hpp"
 
 using namespace lcgs;
 using namespace lcgs::abi;
+
+lcgs_status lcgs::abi::check_adam_config(const lcgs_adam_config* cfg)
+{
+    LCGS_REQUIRE(cfg->step >= 1, "step counts from 1");
+    LCGS_REQUIRE(cfg->beta1 >= 0.0f && cfg->beta1 < 1.0f && cfg->beta2 >= 0.0f && cfg->beta2 < 1.0f, "betas must be in [0,1)");
+    return LCGS_OK;
+}
 
 extern "C" {
 
@@ -25,8 +29,7 @@ lcgs_status lcgs_adam_step(lcgs_context* ctx, int num_gaussians, int sh_degree, 
     LCGS_REQUIRE(ctx && cfg && grads && raw && m && v && activated, "NULL argument");
     LCGS_REQUIRE(num_gaussians >= 0, "num_gaussians is negative");
     LCGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "sh_degree must be in [0,3]");
-    LCGS_REQUIRE(cfg->step >= 1, "step counts from 1");
-    LCGS_REQUIRE(cfg->beta1 >= 0.0f && cfg->beta1 < 1.0f && cfg->beta2 >= 0.0f && cfg->beta2 < 1.0f, "betas must be in [0,1)");
+    LCGS_TRY(check_adam_config(cfg));
     // (before the empty-range return: a rank whose shard is empty still belongs to a step that rewrites the arrays)
     scene_arrays_written(ctx, activated->pos, activated->scale, activated->rotq); // (a context-owned scene trained in place)
     if (num_gaussians == 0) return LCGS_OK;
@@ -46,12 +49,10 @@ lcgs_status lcgs_adam_step(lcgs_context* ctx, int num_gaussians, int sh_degree, 
         d_rows   = ctx->counts.as<uint32_t>(); // [0] = survivors of the last frame
         hint     = ctx->hint_V > 0 ? std::min<int64_t>(ctx->hint_V, num_gaussians) : num_gaussians;
     }
-    auto pack = [](const lcgs_params* p) { return AdamArrays{ p->pos, p->scale, p->rotq, p->sh, p->opacity }; };
     const AdamArrays g = { grads->d_dL_dpos, grads->d_dL_dscale, grads->d_dL_drotq, grads->d_dL_dsh, grads->d_dL_dopacity };
-    const AdamRates  lr = { cfg->lr_pos, cfg->lr_sh_dc, cfg->lr_sh_rest, cfg->lr_opacity, cfg->lr_scale, cfg->lr_rot };
-    launch_adam_step(num_gaussians, (sh_degree + 1) * (sh_degree + 1) * 3, row_list, d_rows, hint, g, pack(raw), pack(m),
-                     pack(v), pack(activated), lr, cfg->beta1, cfg->beta2, cfg->eps, cfg->step, ctx->stream,
-                     /*grad_compact=*/cfg->visible_only == 2);
+    launch_adam_step(num_gaussians, (int)sh_floats(sh_degree), row_list, d_rows, hint, g, adam_arrays(raw), adam_arrays(m),
+                     adam_arrays(v), adam_arrays(activated), adam_rates(cfg), cfg->beta1, cfg->beta2, cfg->eps, cfg->step,
+                     ctx->stream, /*grad_compact=*/cfg->visible_only == 2);
     LCGS_HIP_CHECK(hipGetLastError());
     return LCGS_OK;
 }

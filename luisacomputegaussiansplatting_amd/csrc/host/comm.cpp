@@ -124,20 +124,17 @@ lcgs_status need_rccl()
 }
 
 struct AttrRows {
-    float* ptr[5];
-    size_t width[5]; // floats per splat: pos 3, scale 3, rotq 4, sh (deg+1)^2*3, opacity 1
+    float*         ptr[5];
+    abi::RowFloats width; // floats per splat: pos 3, scale 3, rotq 4, sh (deg+1)^2*3, opacity 1
 };
 
 AttrRows attr_rows(const lcgs_grads* g, int sh_degree)
 {
-    const size_t feat = (size_t)(sh_degree + 1) * (sh_degree + 1) * 3;
-    return { { g->d_dL_dpos, g->d_dL_dscale, g->d_dL_drotq, g->d_dL_dsh, g->d_dL_dopacity }, { 3, 3, 4, feat, 1 } };
+    return { { g->d_dL_dpos, g->d_dL_dscale, g->d_dL_drotq, g->d_dL_dsh, g->d_dL_dopacity }, abi::row_floats(sh_degree) };
 }
-
 AttrRows attr_rows(const lcgs_params* p, int sh_degree)
 {
-    const size_t feat = (size_t)(sh_degree + 1) * (sh_degree + 1) * 3;
-    return { { p->pos, p->scale, p->rotq, p->sh, p->opacity }, { 3, 3, 4, feat, 1 } };
+    return { { p->pos, p->scale, p->rotq, p->sh, p->opacity }, abi::row_floats(sh_degree) };
 }
 
 } // namespace
@@ -508,7 +505,7 @@ struct LoopGuard {
     }
 };
 
-size_t row_bytes(int sh_degree) { return (size_t)(3 + 3 + 4 + (sh_degree + 1) * (sh_degree + 1) * 3 + 1) * 4; }
+size_t row_bytes(int sh_degree) { return (3 + 3 + 4 + abi::sh_floats(sh_degree) + 1) * 4; }
 
 // lcgs_adam_step on the rank's own rows [first, first + count) and on the tail rows every rank keeps (fewer than N)
 lcgs_status adam_own_rows(lcgs_context* ctx, lcgs_comm* c, int64_t P, int sh_degree, const lcgs_adam_config* cfg,
@@ -518,19 +515,10 @@ lcgs_status adam_own_rows(lcgs_context* ctx, lcgs_comm* c, int64_t P, int sh_deg
     int64_t first = 0, count = 0;
     lcgs_comm_shard_rows(P, c->world, c->rank, &first, &count);
     const int64_t tail0 = count * c->world, tail = P - tail0;
-    auto sub = [&](const lcgs_params* p, int64_t row) {
-        const AttrRows a = attr_rows(p, sh_degree);
-        lcgs_params    o;
-        o.pos = a.ptr[0] + (size_t)row * a.width[0]; o.scale = a.ptr[1] + (size_t)row * a.width[1];
-        o.rotq = a.ptr[2] + (size_t)row * a.width[2]; o.sh = a.ptr[3] + (size_t)row * a.width[3];
-        o.opacity = a.ptr[4] + (size_t)row * a.width[4];
-        return o;
-    };
+    auto sub = [&](const lcgs_params* p, int64_t row) { return abi::rows_from(*p, sh_degree, (size_t)row); };
     auto step_rows = [&](int64_t row, int64_t rows) -> lcgs_status {
         if (rows <= 0) return LCGS_OK;
-        lcgs_grads gg = { g.ptr[0] + (size_t)row * g.width[0], g.ptr[1] + (size_t)row * g.width[1],
-                          g.ptr[2] + (size_t)row * g.width[2], g.ptr[3] + (size_t)row * g.width[3],
-                          g.ptr[4] + (size_t)row * g.width[4] };
+        const lcgs_grads  gg = abi::rows_from(lcgs_grads{ g.ptr[0], g.ptr[1], g.ptr[2], g.ptr[3], g.ptr[4] }, sh_degree, (size_t)row);
         const lcgs_params r_ = sub(raw, row), m_ = sub(m, row), v_ = sub(v, row), a_ = sub(activated, row);
         return lcgs_adam_step(ctx, (int)rows, sh_degree, cfg, &gg, &r_, &m_, &v_, &a_);
     };
@@ -1367,17 +1355,10 @@ lcgs_status lcgs_owner_step_backward(lcgs_context* ctx, lcgs_comm* c, const floa
     // rows get room for my whole range)
     LCGS_TRY(c->g2d_all.ensure((size_t)std::max(n_all, alias ? count : (int64_t)0) * kG2dBytes + 16));
     // (the own rows of the dense gradient arrays are cleared as a side job of the render-backward: view 0 then ADDS like the rest)
-    const size_t feat = (size_t)(ctx->sh_deg + 1) * (ctx->sh_deg + 1) * 3;
-    const bool   filled = n_all > 0 && count > 0 && (size_t)count * feat < ((size_t)1 << 32) && grads->d_dL_dpos && grads->d_dL_dscale &&
-                        grads->d_dL_drotq && grads->d_dL_dsh && grads->d_dL_dopacity;
-    DenseFill fill;
-    if (filled) {
-        fill.b0 = grads->d_dL_dpos + 3 * (size_t)first, fill.b1 = grads->d_dL_dscale + 3 * (size_t)first;
-        fill.b2 = grads->d_dL_drotq + 4 * (size_t)first, fill.b3 = grads->d_dL_dsh + feat * (size_t)first;
-        fill.b4 = grads->d_dL_dopacity + (size_t)first;
-        const size_t n[5] = { (size_t)count * 3, (size_t)count * 3, (size_t)count * 4, (size_t)count * feat, (size_t)count };
-        for (int a = 0; a < 5; ++a) fill.n[a] = (uint32_t)n[a];
-    }
+    DenseFill  fill;
+    const bool filled = n_all > 0 && count > 0 && grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh &&
+                        grads->d_dL_dopacity &&
+                        abi::dense_fill_rows(abi::rows_from(*grads, ctx->sh_deg, (size_t)first), ctx->sh_deg, (size_t)count, &fill);
     if (n_all > 0) LCGS_TRY(abi::owner_render_backward_into(ctx, d_dL_dimg, c->g2d_all.as<float>(), filled ? &fill : nullptr));
     // ---- 2. every owner gets its rows' share back; I get my rows' share of every view
     int64_t gin_off[LCGS_MAX_RANKS + 1], total_in = 0;

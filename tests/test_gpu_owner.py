@@ -98,6 +98,51 @@ def test_two_halves_equal_the_fused_frame_and_its_backward(lcgs, oracle, world, 
     check_gradient_rows(g, None, None, None, bound=bound, rows=perm, tag=f"two halves, {world} owners, reordered={reordered}")
 
 
+def test_synchronous_owner_render_redoes_a_frame_that_overflows_the_pair_buffers(lcgs, oracle):
+    """lcgs_owner_render on a FRESH context whose frame needs more (tile, splat) pairs than the default workspace holds: the
+    synchronous call reads the counters back, grows the pair buffers and redoes the frame (abi_owner.cpp; the growth rule is the
+    fused frame's, abi_frame.cpp grow_pair_capacity).  The scene of test_fused_pair_buffer_growth: 6 000 large splats at
+    1920 x 1080, about 9.1 M pruned pairs against a default capacity of max(4 P, 2^22) = 4 194 304 (docs/TESTS.md).  The
+    image is the fused frame's bit for bit, the gradients lie inside the per-row bound, and a second lcgs_owner_render of the
+    view -- which now fits at the first attempt; the C ABI does not report attempts -- gives the same bits."""
+    rng = np.random.default_rng(13)
+    P, Wb, Hb = 6000, 1920, 1080
+    scene = make_scene(rng, P, log_scale=(-1.0, 0.2))
+    cam = lcgs.get_lookat_cam(*POSE, width=Wb, height=Hb)
+    bg = (0.1, 0.2, 0.3)
+    act = upload_scene(scene)
+    # the premise: the fused frame of a fresh context (per-tile lists: it keeps state) wants more pairs than the default holds
+    ref = lcgs.Renderer(lcgs.Context(0))
+    ref.bind_scene(*[act[k] for k in KEYS])
+    img_ref = torch.full((3, Hb, Wb), -1.0, device=DEV)
+    assert ref.forward(cam, img_ref, bg=bg, keep_state=True, sync=True) > 0
+    st_ref = ref.frame_stats()
+    print(f"[owner redo] fused frame: {st_ref['num_pairs']} pairs, default capacity {max(4 * P, 1 << 22)}")
+    assert st_ref["list_shift"] == 0 and st_ref["num_pairs"] > max(4 * P, 1 << 22)
+    # the two halves on another fresh context, one owner of all rows
+    r = lcgs.Renderer(lcgs.Context(0))
+    r.bind_scene(*[act[k] for k in KEYS])
+    rows, recs = r.owner_project(0, cam, 0, P)
+    assert rows.shape[0] == st_ref["num_visible"]
+    img = torch.full((3, Hb, Wb), -1.0, device=DEV)
+    r.owner_render(cam, rows, recs, img, bg=bg, keep_state=True)
+    assert torch.equal(img, img_ref), f"{int((img != img_ref).any(0).sum())} pixels differ from the fused frame"
+    assert r.frame_stats()["num_pairs"] == st_ref["num_pairs"]  # (a truncated frame reports the capacity)
+    dL = torch.from_numpy(rng.normal(size=(3, Hb, Wb)).astype(np.float32)).to(DEV)
+    g = {k: torch.full_like(act[k], 5.0) for k in KEYS}
+    g2d = torch.zeros(rows.shape[0], r.OWNER_GRAD_FLOATS, device=DEV)
+    r.owner_render_backward(dL, g2d)
+    r.owner_backward(0, g2d, *[g[k] for k in KEYS], accumulate=False)
+    r.ctx.synchronize()
+    bound = cached("owner redo", lambda: gradient_row_bound(scene, oracle.lookat(*POSE, width=Wb, height=Hb), dL.cpu().numpy(), bg=bg))
+    check_gradient_rows(g, None, None, None, bound=bound, tag="owner frame redone after a pair overflow")
+    # the same view again: the buffers hold it now
+    img2 = torch.full((3, Hb, Wb), -1.0, device=DEV)
+    r.owner_render(cam, rows, recs, img2, bg=bg, keep_state=True)
+    r.ctx.synchronize()
+    assert torch.equal(img2, img_ref) and r.frame_stats()["num_pairs"] == st_ref["num_pairs"]
+
+
 def test_views_accumulate_and_empty_ranges_are_harmless(lcgs):
     rng = np.random.default_rng(9)
     P = 12000
