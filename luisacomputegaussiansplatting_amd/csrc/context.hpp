@@ -1,5 +1,5 @@
 // context.hpp -- the (opaque to callers) lcgs_context, shared by the translation units behind the C ABI
-// (abi_*.cpp: frames, scene, optimiser -- see abi_internal.hpp; host/comm.cpp: the RCCL gradient collectives).
+// (abi_*.cpp: frames, scene, optimiser -- see abi_internal.hpp; host/comm_*.cpp: the RCCL gradient collectives).
 #pragma once
 
 #include <atomic>
@@ -13,9 +13,9 @@ namespace lcgs
 {
 constexpr int kMaxEvents    = LCGS_MAX_STAGES + 1;
 constexpr int kMaxGradSlices = 16; // splat-range slices of the dense gradient rows (chunked all-reduce)
-// (host/comm.cpp) a context that goes away before its communicator: the communicator forgets it
+// (host/comm_wire.cpp) a context that goes away before its communicator: the communicator forgets it
 void comm_forget_context(lcgs_comm* comm);
-// (host/comm.cpp) sparse exchange: a dense backward flags the rows of the frame it has just differentiated
+// (host/comm_grads.cpp) sparse exchange: a dense backward flags the rows of the frame it has just differentiated
 lcgs_status comm_mark_touched(lcgs_comm* comm, const uint32_t* vis_index, const uint32_t* d_counts, int64_t P, int64_t hint_V,
                               bool accumulate, hipStream_t stream);
 namespace abi
@@ -192,7 +192,7 @@ struct lcgs_context {
     } last;
     lcgs_frame_stats stats{};
 
-    // Chunked gradient all-reduce (host/comm.cpp).  With a communicator attached, the dense backward splits its
+    // Chunked gradient all-reduce (host/comm_grads.cpp).  With a communicator attached, the dense backward splits its
     // preprocess pass into `grad_slices` splat-range slices and records an event behind each; lcgs_grads_allreduce
     // starts reducing a slice's rows when its event fires, while the later slices are still being computed.
     lcgs_comm*   comm = nullptr;        // attached by lcgs_comm_create (not owned)

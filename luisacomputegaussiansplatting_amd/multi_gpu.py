@@ -152,7 +152,7 @@ class TorchCollective:
         pass
 
     def sparse_adam(self, engine, grads: dict, step: int):
-        """The protocol of lcgs_adam_step_sparse (csrc/host/comm.cpp) over a process group.  The engine supplies the
+        """The protocol of lcgs_adam_step_sparse (csrc/host/comm_grads.cpp) over a process group.  The engine supplies the
         three device stages -- touched rows, pack, accumulate -- (HipEngine: the C ABI's lcgs_sparse_*; the CPU tests:
         a numpy restatement); this method is the exchange: counts by all_gather, one message per peer by send / recv."""
         import torch

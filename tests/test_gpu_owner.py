@@ -308,7 +308,7 @@ def test_every_view_of_a_step_with_one_read_back(lcgs):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The ownership step WITH its transport through the C ABI (lcgs_owner_step_forward / _backward, host/comm.cpp)
+# The ownership step WITH its transport through the C ABI (lcgs_owner_step_forward / _backward, host/comm_owner.cpp)
 # ---------------------------------------------------------------------------------------------------------------------
 def _reference_views(lcgs, scene, cams, dLs, bg):
     """the ordinary path: every view's fused frame + the gradients of all views summed (file-order arrays)"""
@@ -328,7 +328,7 @@ def _reference_views(lcgs, scene, cams, dLs, bg):
 
 
 def _padded(n):
-    return n + n // 4 + 1024  # comm.cpp padded_rows (before the clip to the owner's range)
+    return n + n // 4 + 1024  # comm_owner.cpp padded_rows (before the clip to the owner's range)
 
 
 @pytest.mark.parametrize("self_p2p,async_steps", [(False, False), (True, False), (False, True), (True, True)])
@@ -367,6 +367,8 @@ def test_owner_step_through_rccl_at_world_size_one(lcgs, monkeypatch, self_p2p, 
                 assert _rel(g[k], g_ref[k]) <= 1e-4, k
         st = comm.stats()
         assert st["touched_rows"] == vis[0]
+        # forward + backward: the counts, the records, (a step without read-back: the flag,) the gradients
+        assert st["collective_groups"] == (4 if async_steps else 3)
         rows = min(P, _padded(vis[0])) if async_steps else vis[0]
         want = rows * (4 + 48 + 48) if self_p2p else 0
         assert st["bytes_sent"] == want and st["bytes_received"] == want, (st, want)
@@ -441,6 +443,7 @@ def test_owner_step_with_n_ranks_in_process(lcgs, world, reordered, async_steps)
         img, g, st, perm = out[me]
         assert torch.equal(img, imgs_ref[me]), f"rank {me}: {int((img != imgs_ref[me]).any(0).sum())} pixels differ"
         assert st["touched_rows"] == vis[me]
+        assert st["collective_groups"] == (4 if async_steps else 3)  # the counts, the records, (the flag,) the gradients
         first, count = lcgs.api.owner_rows(P, world, me)
         for k in KEYS:
             mine = g[k][first:first + count]

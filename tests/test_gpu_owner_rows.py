@@ -276,7 +276,7 @@ def test_a_reordered_scene(lcgs, oracle):
 
 # ---------------------------------------------------------------------------------------- B: the step with its transport
 def _padded(n, count):
-    return min(count, n + n // 4 + 1024)  # comm.cpp padded_rows
+    return min(count, n + n // 4 + 1024)  # comm_owner.cpp padded_rows
 
 
 def _ranges(P, world):
