@@ -222,6 +222,29 @@ LCGS_API lcgs_status lcgs_render_backward_compact(lcgs_context* ctx, const float
 /* (*d_rows)[r] = splat of compact row r, *d_count = device address of the row count.  Valid until the next forward. */
 LCGS_API lcgs_status lcgs_visible_rows(lcgs_context* ctx, const uint32_t** d_rows, const uint32_t** d_count);
 
+/* ---- depth and alpha maps of the last lcgs_render_forward(keep_state = 1), and their backward ---- */
+/* For pixel p let i run over the entries p blended: the list positions 1..n_contrib[p] that pass the frame's own per-pixel
+ * tests (binary32 expressions, exp, thresholds and order of the renderer).  With T_1 = 1, w_i = T_i alpha_i,
+ * T_{i+1} = T_i (1 - alpha_i):
+ *     alpha[p] = sum_i w_i          depth[p] = sum_i fl(w_i v_i)
+ * both summed in list order in binary32, starting from 0.  v_i is the splat's view-space z (LCGS_DEPTH_Z) or 1.0f / z, one
+ * IEEE division per splat (LCGS_DEPTH_INV_Z).  Neither map is normalised and no background is blended in: depth is the
+ * ACCUMULATED depth, divide by alpha for the expected depth.  A pixel outside every list, and every pixel of a frame that drew
+ * nothing, is 0 in both maps (such a frame leaves the colour image untouched; the maps are written).
+ * The backward treats thresholds as lcgs_render_backward does: constants; the 0.99 alpha cap passes nothing; a saturated pixel
+ * stops. */
+#define LCGS_DEPTH_Z 0
+#define LCGS_DEPTH_INV_Z 1
+/* d_depth, d_alpha: H*W floats each, either (not both) may be NULL.  Enqueues on the context's stream, reads nothing back. */
+LCGS_API lcgs_status lcgs_render_maps(lcgs_context* ctx, int mode, float* d_depth, float* d_alpha);
+/* The gradient of <dL_dimg, img> + <dL_ddepth, depth> + <dL_dalpha, alpha>: dense rows like lcgs_render_backward's, overwritten
+ * (accumulate = 0) or added to (accumulate != 0, like lcgs_render_backward_accumulate).  Any of the three incoming gradients
+ * may be NULL, not all three.  The per-splat pass is not sliced for the chunked all-reduce.  lcgs_densify_accumulate behind this
+ * call sees the COMBINED 2-D mean gradient (colour + depth + alpha), as 3DGS's viewspace gradient does under a depth loss.
+ * Both calls: LCGS_ERR_STATE without a keep_state frame, or after a frame drawn from received records (lcgs_owner_render). */
+LCGS_API lcgs_status lcgs_render_backward_maps(lcgs_context* ctx, const float* d_dL_dimg, int mode, const float* d_dL_ddepth,
+                                               const float* d_dL_dalpha, int accumulate, const lcgs_grads* grads);
+
 /* ---- optimiser step (doc/roadmap.md:4 names training; 3DGS parameterisation: scale = exp, opacity = sigmoid, rotq normalised) ---- */
 typedef struct lcgs_params {
     float *pos, *scale, *rotq, *sh, *opacity; /* device arrays laid out like the scene */

@@ -13,6 +13,8 @@ from .api import (  # noqa: F401
     Camera,
     Comm,
     Context,
+    DEPTH_INV_Z,
+    DEPTH_Z,
     GSProjector,
     GSProjectorInputProxy,
     GSProjectorOutputProxy,
@@ -37,6 +39,7 @@ from .api import (  # noqa: F401
     read_gs_ply,
     read_points_ply,
     render_autograd,
+    render_autograd_maps,
     scene_extent,
     shard_rows,
     synth_scene,

@@ -51,6 +51,8 @@ def build_library(force: bool = False) -> str:
 # constants of include/lcgs_hip.h the mirrors and the wrappers need
 LCGS_MAX_STAGES, LCGS_MAX_RANKS = 16, 64
 LCGS_ERR_STATE = 8
+DEPTH_Z, DEPTH_INV_Z = 0, 1  # LCGS_DEPTH_Z, LCGS_DEPTH_INV_Z
+_DEPTH_MODES = {"z": DEPTH_Z, "inv_z": DEPTH_INV_Z}
 LCGS_KNN_CHUNK = 256  # sorted points per query workgroup of the nearest-neighbour search (sizes around its multiples are edge cases)
 # lcgs_set_fit_loss kinds (LCGS_LOSS_* in include/lcgs_hip.h)
 LOSS_L2, LOSS_PHOTOMETRIC = 0, 1
@@ -250,6 +252,9 @@ def _signatures() -> dict:
         "lcgs_render_backward_accumulate": (st, [p, p, grads]),
         "lcgs_render_backward_compact": (st, [p, p, grads]),
         "lcgs_visible_rows": (st, [p, pp, pp]),
+        # depth and alpha maps
+        "lcgs_render_maps": (st, [p, i, p, p]),
+        "lcgs_render_backward_maps": (st, [p, p, i, p, p, i, grads]),
         # optimiser step, losses
         "lcgs_adam_step": (st, [p, i, i, adam, grads, *packs]),
         "lcgs_render_backward_adam": (st, [p, p, i, i, adam, *packs]),
@@ -752,6 +757,19 @@ class Renderer:
                                                                else lib.lcgs_render_backward)
         _check(fn(self.ctx._h, _ptr(dL_dimg), C.byref(g)))
 
+    def render_maps(self, depth, alpha, mode: str = "z"):
+        """lcgs_render_maps: the accumulated depth (mode "z": view-space z, "inv_z": 1 / z) and the accumulated opacity of the
+        last keep_state frame, H x W floats each; either may be None.  Enqueues only."""
+        _check(load_library().lcgs_render_maps(self.ctx._h, _DEPTH_MODES[mode], _ptr(depth), _ptr(alpha)))
+
+    def backward_maps(self, dL_dimg, dL_ddepth, dL_dalpha, dpos, dscale, drotq, dsh, dopacity, mode: str = "z",
+                      accumulate: bool = False):
+        """lcgs_render_backward_maps: dense rows of the gradient of <dL_dimg, img> + <dL_ddepth, depth> + <dL_dalpha, alpha>
+        for the last keep_state frame; any of the three incoming gradients may be None (not all)."""
+        g = _grads((dpos, dscale, drotq, dsh, dopacity))
+        _check(load_library().lcgs_render_backward_maps(self.ctx._h, _ptr(dL_dimg), _DEPTH_MODES[mode], _ptr(dL_ddepth),
+                                                        _ptr(dL_dalpha), bool(accumulate), C.byref(g)))
+
     def fit_views(self, cams, targets, dpos, dscale, drotq, dsh, dopacity, losses, bg=(0.0, 0.0, 0.0),
                   scale_modifier: float = 1.0):
         """lcgs_fit_views: the views of one optimiser step -- forward, the loss selected by set_fit_loss (L2 unless told
@@ -1232,6 +1250,52 @@ def render_autograd(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh, opa
                     renderer.forward(cam, scratch, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
                     ctx.generation = renderer._generation
                 renderer.backward(dL_dimg.contiguous(), *grads)
+            return tuple(g.view(s) for g, s in zip(grads, ctx.shapes))
+
+    return _Fn.apply(pos, scale, rotq, sh, opacity)
+
+
+def render_autograd_maps(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh, opacity, bg=(0.0, 0.0, 0.0),
+                         scale_modifier: float = 1.0, depth_mode: str = "z"):
+    """render_autograd with the frame's depth and alpha maps: returns (img [3, H, W], depth [H, W], alpha [H, W]) as
+    include/lcgs_hip.h defines them (accumulated depth of view z or, depth_mode="inv_z", of 1 / z; nothing normalised, no
+    background in the maps).  The backward runs lcgs_render_backward_maps with the three incoming gradients; an output the loss
+    does not use arrives as None (or zero-shaped) and is passed as NULL.  Like render_autograd it re-renders its own view
+    when the renderer's generation has moved."""
+    import torch
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, pos, scale, rotq, sh, opacity):
+            args = [t.detach().contiguous() for t in (pos, scale, rotq, sh, opacity)]
+            renderer.bind_scene(*args)
+            dev = args[0].device
+            img = torch.empty(3, cam.height, cam.width, device=dev, dtype=torch.float32)
+            depth = torch.empty(cam.height, cam.width, device=dev, dtype=torch.float32)
+            alpha = torch.empty(cam.height, cam.width, device=dev, dtype=torch.float32)
+            n = renderer.forward(cam, img, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
+            if n == 0:
+                img[:] = torch.tensor(bg, device=dev).view(3, 1, 1)  # nothing drawn: the image is the background
+            renderer.render_maps(depth, alpha, mode=depth_mode)
+            ctx.shapes = [t.shape for t in (pos, scale, rotq, sh, opacity)]
+            ctx.empty = n == 0
+            ctx.generation = renderer._generation
+            ctx.save_for_backward(*args)
+            ctx.set_materialize_grads(False)
+            return img, depth, alpha
+
+        @staticmethod
+        def backward(ctx, dL_dimg, dL_ddepth, dL_dalpha):
+            args = ctx.saved_tensors
+            grads = [torch.zeros_like(t) for t in args]
+            incoming = [None if g is None or g.numel() == 0 else g.contiguous() for g in (dL_dimg, dL_ddepth, dL_dalpha)]
+            if not ctx.empty and any(g is not None for g in incoming):
+                if renderer._generation != ctx.generation:  # the renderer's frame state is no longer this frame's
+                    renderer.bind_scene(*args)
+                    scratch = torch.empty(3, cam.height, cam.width, device=args[0].device, dtype=torch.float32)
+                    renderer.forward(cam, scratch, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
+                    ctx.generation = renderer._generation
+                renderer.backward_maps(*incoming, *grads, mode=depth_mode)
             return tuple(g.view(s) for g, s in zip(grads, ctx.shapes))
 
     return _Fn.apply(pos, scale, rotq, sh, opacity)

@@ -1,5 +1,6 @@
 // abi_backward.cpp -- the C ABI, part 5: the backward of the fused frame -- dense per-splat rows, compact
-// rows, accumulation over views, and the variant with the optimiser folded into the per-splat pass.
+// rows, accumulation over views, and the variant with the optimiser folded into the per-splat pass -- and the frame's depth
+// and alpha maps with their backward (kernels/maps.hip).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -20,8 +21,31 @@ struct FusedAdam {
     AdamRates  lr;
     AdamStep   step;
 };
+// the incoming gradients of the depth and alpha maps (lcgs_render_backward_maps): either pointer may be NULL
+struct MapGrads {
+    int          mode;
+    const float *d_dL_ddepth, *d_dL_dalpha;
+};
 lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcgs_grads* grads, bool compact,
-                            bool accumulate = false, const FusedAdam* fused = nullptr);
+                            bool accumulate = false, const FusedAdam* fused = nullptr, const MapGrads* maps = nullptr);
+// the state both map entry points need: a keep-state frame of this context's own records, lists per tile
+lcgs_status check_maps_state(lcgs_context* ctx, const char* who)
+{
+    if (!ctx->frame_state_valid() || !ctx->last.has_state) {
+        set_last_error((std::string(who) + " needs a preceding lcgs_render_forward(..., keep_state = 1)").c_str());
+        return LCGS_ERR_STATE;
+    }
+    if (ctx->owner_recs) { // the last frame was lcgs_owner_render's: its records are not this context's own
+        set_last_error((std::string(who) + ": the last frame was drawn from received records (lcgs_owner_render)").c_str());
+        return LCGS_ERR_STATE;
+    }
+    LCGS_REQUIRE(ctx->last.cp.list_shift == 0u, "the kept frame lists its pairs per block: no backward walks those lists");
+    return LCGS_OK;
+}
+const uint8_t* kept_strip_masks(lcgs_context* ctx)
+{
+    return render_forward_writes_strip_masks() && ctx->bwd_use_masks ? ctx->strip_masks.as<uint8_t>() : nullptr;
+}
 }
 
 extern "C" {
@@ -80,6 +104,33 @@ lcgs_status lcgs_render_backward_adam(lcgs_context* ctx, const float* d_dL_dimg,
     return render_backward(ctx, d_dL_dimg, &none, /*compact=*/true, /*accumulate=*/false, &fa);
 }
 
+lcgs_status lcgs_render_maps(lcgs_context* ctx, int mode, float* d_depth, float* d_alpha)
+{
+    LCGS_REQUIRE(ctx, "NULL argument");
+    LCGS_REQUIRE(mode == LCGS_DEPTH_Z || mode == LCGS_DEPTH_INV_Z, "mode must be LCGS_DEPTH_Z or LCGS_DEPTH_INV_Z");
+    LCGS_REQUIRE(d_depth || d_alpha, "both outputs are NULL");
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    LCGS_TRY(check_maps_state(ctx, "lcgs_render_maps"));
+    launch_render_maps(ctx->last.cp, ctx->ranges, ctx->pairv[ctx->last.list_buf].as<uint32_t>(), ctx->recs.as<SplatRecord>(),
+                       ctx->n_contrib.as<uint32_t>(), kept_strip_masks(ctx), ctx->counts.as<uint32_t>(), ctx->last_tile_order,
+                       mode, d_depth, d_alpha, ctx->stream);
+    LCGS_HIP_CHECK(hipGetLastError());
+    return LCGS_OK;
+}
+
+lcgs_status lcgs_render_backward_maps(lcgs_context* ctx, const float* d_dL_dimg, int mode, const float* d_dL_ddepth,
+                                      const float* d_dL_dalpha, int accumulate, const lcgs_grads* grads)
+{
+    LCGS_REQUIRE(ctx && grads, "NULL argument");
+    LCGS_REQUIRE(mode == LCGS_DEPTH_Z || mode == LCGS_DEPTH_INV_Z, "mode must be LCGS_DEPTH_Z or LCGS_DEPTH_INV_Z");
+    LCGS_REQUIRE(d_dL_dimg || d_dL_ddepth || d_dL_dalpha, "all three incoming gradients are NULL");
+    LCGS_REQUIRE(grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh && grads->d_dL_dopacity,
+                 "NULL gradient buffer");
+    const MapGrads maps = { mode, d_dL_ddepth, d_dL_dalpha };
+    return render_backward(ctx, d_dL_dimg, grads, /*compact=*/false, accumulate != 0, nullptr,
+                           (d_dL_ddepth || d_dL_dalpha) ? &maps : nullptr);
+}
+
 lcgs_status lcgs_visible_rows(lcgs_context* ctx, const uint32_t** d_rows, const uint32_t** d_count)
 {
     LCGS_REQUIRE(ctx && d_rows && d_count, "NULL argument");
@@ -94,9 +145,9 @@ lcgs_status lcgs_visible_rows(lcgs_context* ctx, const uint32_t** d_rows, const 
 namespace
 {
 lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcgs_grads* grads, bool compact,
-                            bool accumulate, const FusedAdam* fused)
+                            bool accumulate, const FusedAdam* fused, const MapGrads* maps)
 {
-    LCGS_REQUIRE(ctx && d_dL_dimg && grads, "NULL argument");
+    LCGS_REQUIRE(ctx && (d_dL_dimg || maps) && grads, "NULL argument");
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
     LCGS_REQUIRE(fused || (grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh &&
                            grads->d_dL_dopacity),
@@ -127,7 +178,8 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
     // (Per-stage profiling keeps the memsets, in order, as "zero_grads"; so do arrays too long for the kernel's 32-bit lengths.)
     const bool  dense_fill = !compact && !accumulate;
     DenseFill   fill;
-    const bool  fill_in_kernel = dense_fill && !ctx->profiling && dense_fill_rows(*grads, ctx->sh_deg, P, &fill); // (u32 lengths)
+    // (a maps backward without an image gradient launches no render-backward: the memsets clear the rows)
+    const bool  fill_in_kernel = dense_fill && d_dL_dimg && !ctx->profiling && dense_fill_rows(*grads, ctx->sh_deg, P, &fill); // (u32 lengths)
     const bool  overlap = !ctx->profiling && dense_fill && !fill_in_kernel;
     hipStream_t zs      = overlap ? ctx->aux_stream : st;
     if (overlap) {
@@ -136,7 +188,8 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
     }
     // dense rows with a communicator attached: the preprocess pass runs as splat-range slices so that the gradient
     // all-reduce (lcgs_grads_allreduce) can start on the first rows while the later ones are still being computed
-    const bool sliced = !compact && ctx->grad_slices > 1 && P >= 4096;
+    // (the maps backward adds to dL_dpos behind the preprocess pass: unsliced, so that no all-reduce starts on rows it has yet to finish)
+    const bool sliced = !compact && !maps && ctx->grad_slices > 1 && P >= 4096;
     if (sliced) {
         LCGS_TRY(ctx->slice_bounds.ensure((lcgs::kMaxGradSlices + 1) * sizeof(uint32_t)));
         for (int k = 0; k < ctx->grad_slices; ++k)
@@ -158,12 +211,20 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
     const int      k_bwd = ctx->persist_bwd_forced >= 0 ? ctx->persist_bwd_forced
                                                         : (ctx->frames_in_flight ? ctx->persist_bwd_in_flight : 0);
     const uint32_t bwd_wgs = (!ctx->profiling && k_bwd > 0) ? (uint32_t)(k_bwd * std::max(ctx->num_cus, 1)) : 0u;
-    launch_render_backward(ctx->last.cp, ctx->last.bg, ctx->ranges, ctx->pairv[ctx->last.list_buf].as<uint32_t>(),
-                           ctx->recs.as<SplatRecord>(), ctx->final_T.as<float>(), ctx->n_contrib.as<uint32_t>(),
-                           d_dL_dimg, ctx->grads2d.as<float>(), ctx->last_tile_order, st,
-                           render_forward_writes_strip_masks() && ctx->bwd_use_masks ? ctx->strip_masks.as<uint8_t>() : nullptr,
-                           ctx->counts.as<uint32_t>(), ctx->bwd_counter.as<uint32_t>(), bwd_wgs, fill_in_kernel ? &fill : nullptr);
-    LCGS_TRY(mark(ctx, "render_backward"));
+    if (d_dL_dimg) {
+        launch_render_backward(ctx->last.cp, ctx->last.bg, ctx->ranges, ctx->pairv[ctx->last.list_buf].as<uint32_t>(),
+                               ctx->recs.as<SplatRecord>(), ctx->final_T.as<float>(), ctx->n_contrib.as<uint32_t>(),
+                               d_dL_dimg, ctx->grads2d.as<float>(), ctx->last_tile_order, st, kept_strip_masks(ctx),
+                               ctx->counts.as<uint32_t>(), ctx->bwd_counter.as<uint32_t>(), bwd_wgs, fill_in_kernel ? &fill : nullptr);
+        LCGS_TRY(mark(ctx, "render_backward"));
+    }
+    if (maps) { // the two map channels add to the rows the colour walk (or the zeroing alone) left
+        launch_render_maps_backward(ctx->last.cp, ctx->ranges, ctx->pairv[ctx->last.list_buf].as<uint32_t>(),
+                                    ctx->recs.as<SplatRecord>(), ctx->final_T.as<float>(), ctx->n_contrib.as<uint32_t>(),
+                                    kept_strip_masks(ctx), ctx->counts.as<uint32_t>(), ctx->last_tile_order, maps->mode,
+                                    maps->d_dL_ddepth, maps->d_dL_dalpha, ctx->grads2d.as<float>(), st);
+        LCGS_TRY(mark(ctx, "render_maps_backward"));
+    }
     if (overlap) LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_join, 0));
     const int slices = fused ? 0 : (sliced ? ctx->grad_slices : 1);
     if (fused) // (compact, unsliced: the update is applied where the gradients are formed; nothing is written out)
@@ -180,6 +241,10 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
                                    sliced ? ctx->slice_bounds.as<uint32_t>() : nullptr, k, slices, accumulate);
         if (sliced) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_slice[k], st));
     }
+    if (maps && maps->d_dL_ddepth) // view z = front . pos + tz: the depth channel's dL/dvalue reaches the position rows directly
+        launch_maps_depth_to_pos(ctx->hint_V > 0 ? ctx->hint_V : (int64_t)P, ctx->last.cp, ctx->vis_index.as<uint32_t>(),
+                                 ctx->counts.as<uint32_t>(), ctx->recs.as<SplatRecord>(), ctx->grads2d.as<float>(), maps->mode,
+                                 grads->d_dL_dpos, st);
     ctx->slices_recorded = sliced ? slices : 0;
     ctx->slices_of       = sliced ? grads->d_dL_dpos : nullptr;
     // sparse exchange (opt-in, lcgs_comm_track_touched_rows): the rows this frame wrote join the step's touched set

@@ -126,7 +126,6 @@ constexpr uint32_t kNullEntry  = 256u;                // LDS row of the entry th
 constexpr uint32_t kRows       = 257u;                // rows per slab / accumulator columns: a round's 256 entries + the null entry
 constexpr uint32_t kSlab       = kRows * 16u;         // bytes per slab of s_rows
 constexpr uint32_t kListStride = 264u;                // 256 entries + 3 of padding, a multiple of four (8-byte rows)
-constexpr int kG2D = 12; // floats per splat in the 2-D gradient buffer: mean(2) conic(3) opacity(1) rgb(3) pad(3)
 
 // (six waves per SIMD: 80 VGPRs with 8 spilled registers per lane instead of 92 and five waves -- render-backward 0.71 ->
 //  0.67 ms, +1.6 % on the whole forward+backward step in same-box A/B runs; seven waves spill 19 and lose it again)

@@ -326,6 +326,9 @@ void     launch_sparse_accumulate(float* const grads[5], int sh_degree, const fl
                                   int64_t row_count, hipStream_t stream);
 
 // ---- backward.hip ----
+// floats per on-screen splat in the 2-D gradient buffer: mean(2) conic(3) opacity(1) rgb(3) value(1) pad(2).  Slot 9 is the
+// depth maps' dL/dvalue (maps.hip); the colour backward leaves it at the zero it was cleared to
+constexpr int kG2D = 12, kG2DValueSlot = 9;
 size_t grads2d_bytes(int64_t V_cap);
 // (bwd_counter, when given, is zeroed too: the persistent render-backward's tile counter)
 void   launch_zero_grads2d(const uint32_t* d_counts, float* grads2d, hipStream_t stream, uint32_t* bwd_counter = nullptr);
@@ -359,5 +362,20 @@ void   launch_preprocess_backward(int64_t v_hint, int sh_deg, const CamParams& c
 // bounds[0 .. slices]: dense-id boundaries of the splat-index ranges [k P / slices, (k + 1) P / slices), k < slices <= 63
 void   launch_slice_bounds(const uint32_t* vis_index, const uint32_t* d_counts, int64_t P, int slices, uint32_t* bounds,
                            hipStream_t stream);
+
+// ---- maps.hip : depth and alpha maps of the last keep-state frame and their backward ----
+constexpr int kDepthZ = 0, kDepthInvZ = 1; // = LCGS_DEPTH_Z, LCGS_DEPTH_INV_Z: a splat's value is its view z, or 1 / z
+// depth / alpha: H W floats each, either may be NULL; strip_masks NULL: every entry of the walk is fetched
+void launch_render_maps(const CamParams& cp, const uint32_t* ranges, const uint32_t* point_list, const SplatRecord* recs,
+                        const uint32_t* n_contrib, const uint8_t* strip_masks, const uint32_t* d_counts,
+                        const uint32_t* tile_order, int mode, float* depth, float* alpha, hipStream_t stream);
+// ADDS the sums of the two map channels to grads2d slots 0-5 and kG2DValueSlot (dL_ddepth / dL_dalpha: either may be NULL)
+void launch_render_maps_backward(const CamParams& cp, const uint32_t* ranges, const uint32_t* point_list,
+                                 const SplatRecord* recs, const float* final_T, const uint32_t* n_contrib,
+                                 const uint8_t* strip_masks, const uint32_t* d_counts, const uint32_t* tile_order, int mode,
+                                 const float* dL_ddepth, const float* dL_dalpha, float* grads2d, hipStream_t stream);
+// one lane per on-screen row: dL_dpos[row] += grads2d slot kG2DValueSlot x dvalue/dz x front (behind the preprocess-backward)
+void launch_maps_depth_to_pos(int64_t v_hint, const CamParams& cp, const uint32_t* vis_index, const uint32_t* d_counts,
+                              const SplatRecord* recs, const float* grads2d, int mode, float* dL_dpos, hipStream_t stream);
 
 } // namespace lcgs
