@@ -245,6 +245,44 @@ LCGS_API lcgs_status lcgs_render_maps(lcgs_context* ctx, int mode, float* d_dept
 LCGS_API lcgs_status lcgs_render_backward_maps(lcgs_context* ctx, const float* d_dL_dimg, int mode, const float* d_dL_ddepth,
                                                const float* d_dL_dalpha, int accumulate, const lcgs_grads* grads);
 
+/* ---- camera gradient: the frame differentiated with respect to its camera pose ---- */
+/* Twelve floats in the order of lcgs_camera's members: position[3], front[3], up[3], right[3].  They are the gradient of the
+ * scalar the LAST backward differentiated, <dL_dimg, img> + <dL_ddepth, depth> + <dL_dalpha, alpha>, the frame taken as a
+ * function of those twelve reals as INDEPENDENT variables with fov, aspect_ratio, width and height fixed.  The kernels' camera
+ * constants derive from them as the host derives them: campos = position, view rows right / up / front,
+ * t = -(right.position, up.position, front.position).  No orthonormality constraint is imposed: whoever parameterises the
+ * pose chains onto the twelve numbers (lcgs_camera_grad_to_twist does it for a twist in the camera's own frame).
+ * Thresholds, cull decisions, tile rectangles and list membership are constants, as in lcgs_render_backward.
+ * Per on-screen splat i, with d = pos_i - position, dv / dT0 / dT1 the gradients w.r.t. its view-space position (the depth
+ * channel's dL/dz included) and its two projected covariance axes, j00, j11, j02, j12 the projection Jacobian's entries and
+ * gdir the view-direction part of dL/dpos_i from the colour step:
+ *     g_position = - sum_i (right dv0 + up dv1 + front dv2 + gdir)        ( = - sum_i dL/dpos_i )
+ *     g_right    =   sum_i (dv0 d + j00 dT0)
+ *     g_up       =   sum_i (dv1 d + j11 dT1)
+ *     g_front    =   sum_i (dv2 d + j02 dT0 + j12 dT1)
+ * Per-splat terms are formed in the precision of the parameter pass (binary32; binary64 for screen-filling footprints), the
+ * twelve sums are accumulated in binary64 in a tree that depends on the number of on-screen rows only (no atomics: the same
+ * 2-D rows give the same bits) and rounded once.  A frame that drew nothing gives twelve zeros.
+ * Like lcgs_densify_accumulate the pass re-evaluates geometry from the BOUND arrays: call it before anything rewrites them
+ * (behind lcgs_render_backward_adam it sees the updated scene).
+ * Not offered: gradients w.r.t. fov / aspect_ratio, frames of the ownership step, pose gradients inside lcgs_fit_views. */
+/* The camera gradient of the last backward of the kept frame (any of lcgs_render_backward, _accumulate, _compact,
+ * lcgs_render_backward_maps, lcgs_render_backward_adam, lcgs_render_backward_camera), from the 2-D rows the context still
+ * holds.  d_dL_dcam: 12 floats, device, overwritten.  Enqueues on the context's stream, reads nothing back.
+ * LCGS_ERR_STATE: no keep_state frame, a frame of lcgs_owner_render, or no backward of the frame yet. */
+LCGS_API lcgs_status lcgs_camera_backward(lcgs_context* ctx, float* d_dL_dcam);
+/* Walks + camera pass, NO parameter gradients: the 2-D rows zeroed, the colour walk (d_dL_dimg), the maps walk (d_dL_ddepth /
+ * d_dL_dalpha, mode as in lcgs_render_backward_maps), lcgs_camera_backward.  Any of the three may be NULL, not all.  Counts as
+ * a backward of the frame: lcgs_densify_accumulate and lcgs_camera_backward work behind it. */
+LCGS_API lcgs_status lcgs_render_backward_camera(lcgs_context* ctx, const float* d_dL_dimg, int mode, const float* d_dL_ddepth,
+                                                 const float* d_dL_dalpha, float* d_dL_dcam);
+/* Host only: the 12 numbers -> the gradient w.r.t. a twist xi = (omega, tau) applied in the camera's own frame,
+ * [right up front]' = [right up front] exp([omega]x), position' = position + [right up front] tau, at xi = 0:
+ *     dL/dtau   = (right.g_position, up.g_position, front.g_position)
+ *     dL/domega = sum_k e_k x (Rc^T g_k),  e_0..2 = unit vectors, g_0..2 = g_right, g_up, g_front, Rc = [right up front]
+ * evaluated in binary64, each output rounded once.  dL_dxi: omega[3], tau[3]. */
+LCGS_API lcgs_status lcgs_camera_grad_to_twist(const lcgs_camera* cam, const float dL_dcam[12], float dL_dxi[6]);
+
 /* ---- optimiser step (doc/roadmap.md:4 names training; 3DGS parameterisation: scale = exp, opacity = sigmoid, rotq normalised) ---- */
 typedef struct lcgs_params {
     float *pos, *scale, *rotq, *sh, *opacity; /* device arrays laid out like the scene */

@@ -29,6 +29,8 @@ from .api import (  # noqa: F401
     Renderer,
     SHProcessor,
     build_library,
+    camera_grad_to_twist,
+    camera_with_vectors,
     get_lookat_cam,
     image_to_rgb8,
     knn_mean_dist2,
@@ -39,6 +41,7 @@ from .api import (  # noqa: F401
     read_gs_ply,
     read_points_ply,
     render_autograd,
+    render_autograd_camera,
     render_autograd_maps,
     scene_extent,
     shard_rows,

@@ -255,6 +255,10 @@ def _signatures() -> dict:
         # depth and alpha maps
         "lcgs_render_maps": (st, [p, i, p, p]),
         "lcgs_render_backward_maps": (st, [p, p, i, p, p, i, grads]),
+        # camera gradient
+        "lcgs_camera_backward": (st, [p, p]),
+        "lcgs_render_backward_camera": (st, [p, p, i, p, p, p]),
+        "lcgs_camera_grad_to_twist": (st, [cam, p, p]),
         # optimiser step, losses
         "lcgs_adam_step": (st, [p, i, i, adam, grads, *packs]),
         "lcgs_render_backward_adam": (st, [p, p, i, i, adam, *packs]),
@@ -769,6 +773,17 @@ class Renderer:
         g = _grads((dpos, dscale, drotq, dsh, dopacity))
         _check(load_library().lcgs_render_backward_maps(self.ctx._h, _ptr(dL_dimg), _DEPTH_MODES[mode], _ptr(dL_ddepth),
                                                         _ptr(dL_dalpha), bool(accumulate), C.byref(g)))
+
+    def camera_backward(self, out12):
+        """lcgs_camera_backward: the camera gradient of the last backward of the kept frame -- 12 floats on the device in the
+        order of Camera's members (position, front, up, right), overwritten.  Enqueues only."""
+        _check(load_library().lcgs_camera_backward(self.ctx._h, _ptr(out12)))
+
+    def backward_camera(self, dL_dimg, dL_ddepth, dL_dalpha, out12, mode: str = "z"):
+        """lcgs_render_backward_camera: the walks and the camera pass, no parameter gradients; any of the three incoming
+        gradients may be None (not all)."""
+        _check(load_library().lcgs_render_backward_camera(self.ctx._h, _ptr(dL_dimg), _DEPTH_MODES[mode], _ptr(dL_ddepth),
+                                                          _ptr(dL_dalpha), _ptr(out12)))
 
     def fit_views(self, cams, targets, dpos, dscale, drotq, dsh, dopacity, losses, bg=(0.0, 0.0, 0.0),
                   scale_modifier: float = 1.0):
@@ -1299,6 +1314,86 @@ def render_autograd_maps(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh
             return tuple(g.view(s) for g, s in zip(grads, ctx.shapes))
 
     return _Fn.apply(pos, scale, rotq, sh, opacity)
+
+
+CAM12_FIELDS = ("position", "front", "up", "right")  # the camera gradient's order: Camera's first four members
+
+
+def camera_grad_to_twist(cam: Camera, g12) -> np.ndarray:
+    """lcgs_camera_grad_to_twist (host only): the 12 numbers of a camera gradient -> the gradient w.r.t. a twist
+    (omega[3], tau[3]) applied in the camera's own frame, at zero."""
+    g = np.ascontiguousarray(np.asarray(g12, dtype=np.float32).reshape(12))
+    out = np.zeros(6, dtype=np.float32)
+    _check(load_library().lcgs_camera_grad_to_twist(C.byref(cam), g.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def camera_with_vectors(cam: Camera, v12) -> Camera:
+    """a copy of `cam` whose position / front / up / right are the twelve numbers of v12 (struct order)"""
+    v = np.asarray(v12, dtype=np.float32).reshape(4, 3)
+    out = Camera.from_dict(cam.to_dict())
+    for k, name in enumerate(CAM12_FIELDS):
+        for c in range(3):
+            getattr(out, name)[c] = float(v[k, c])
+    return out
+
+
+def render_autograd_camera(renderer: "Renderer", cam: Camera, cam12, pos, scale, rotq, sh, opacity, bg=(0.0, 0.0, 0.0),
+                           scale_modifier: float = 1.0, mode: str = "z"):
+    """render_autograd_maps with a differentiable pose: returns (img, depth, alpha); `cam12` is a float32 tensor of twelve in
+    the order of Camera's members (position, front, up, right) that REPLACES those four vectors of `cam` (fov, aspect ratio
+    and size are cam's).  The backward returns the camera gradient for cam12 (the twelve numbers as independent variables:
+    chain a pose parameterisation onto them, e.g. camera_grad_to_twist) plus the scene gradients.  When no scene tensor
+    requires grad it runs lcgs_render_backward_camera and allocates no parameter rows."""
+    import torch
+
+    view = camera_with_vectors(cam, cam12.detach().cpu().numpy())
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, cam12, pos, scale, rotq, sh, opacity):
+            args = [t.detach().contiguous() for t in (pos, scale, rotq, sh, opacity)]
+            renderer.bind_scene(*args)
+            dev = args[0].device
+            img = torch.empty(3, view.height, view.width, device=dev, dtype=torch.float32)
+            depth = torch.empty(view.height, view.width, device=dev, dtype=torch.float32)
+            alpha = torch.empty(view.height, view.width, device=dev, dtype=torch.float32)
+            n = renderer.forward(view, img, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
+            if n == 0:
+                img[:] = torch.tensor(bg, device=dev).view(3, 1, 1)  # nothing drawn: the image is the background
+            renderer.render_maps(depth, alpha, mode=mode)
+            ctx.shapes = [t.shape for t in (pos, scale, rotq, sh, opacity)]
+            ctx.cam_like = (cam12.shape, cam12.device)
+            ctx.empty = n == 0
+            ctx.generation = renderer._generation
+            ctx.save_for_backward(*args)
+            ctx.set_materialize_grads(False)
+            return img, depth, alpha
+
+        @staticmethod
+        def backward(ctx, dL_dimg, dL_ddepth, dL_dalpha):
+            args = ctx.saved_tensors
+            want_cam, want_scene = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:])
+            g12 = torch.zeros(12, device=args[0].device, dtype=torch.float32)
+            grads = [torch.zeros_like(t) for t in args] if want_scene else None
+            incoming = [None if g is None or g.numel() == 0 else g.contiguous() for g in (dL_dimg, dL_ddepth, dL_dalpha)]
+            if not ctx.empty and any(g is not None for g in incoming):
+                if renderer._generation != ctx.generation:  # the renderer's frame state is no longer this frame's
+                    renderer.bind_scene(*args)
+                    scratch = torch.empty(3, view.height, view.width, device=args[0].device, dtype=torch.float32)
+                    renderer.forward(view, scratch, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
+                    ctx.generation = renderer._generation
+                if want_scene:
+                    renderer.backward_maps(*incoming, *grads, mode=mode)
+                    if want_cam:
+                        renderer.camera_backward(g12)
+                else:
+                    renderer.backward_camera(*incoming, g12, mode=mode)
+            shape, dev = ctx.cam_like
+            scene = tuple(g.view(s) for g, s in zip(grads, ctx.shapes)) if want_scene else (None,) * 5
+            return (g12.to(dev).view(shape) if want_cam else None,) + scene
+
+    return _Fn.apply(cam12, pos, scale, rotq, sh, opacity)
 
 
 # ---------------------------------------------------------------------------------------------- host io

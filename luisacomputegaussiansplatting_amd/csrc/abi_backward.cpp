@@ -1,6 +1,6 @@
 // abi_backward.cpp -- the C ABI, part 5: the backward of the fused frame -- dense per-splat rows, compact
 // rows, accumulation over views, and the variant with the optimiser folded into the per-splat pass -- and the frame's depth
-// and alpha maps with their backward (kernels/maps.hip).
+// and alpha maps with their backward (kernels/maps.hip), and the camera gradient (kernels/camera_grad.hip).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,7 +27,18 @@ struct MapGrads {
     const float *d_dL_ddepth, *d_dL_dalpha;
 };
 lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcgs_grads* grads, bool compact,
-                            bool accumulate = false, const FusedAdam* fused = nullptr, const MapGrads* maps = nullptr);
+                            bool accumulate = false, const FusedAdam* fused = nullptr, const MapGrads* maps = nullptr,
+                            float* d_camera_only = nullptr);
+// the camera pass over the 2-D rows the context holds (kernels/camera_grad.hip)
+lcgs_status camera_pass(lcgs_context* ctx, float* d_dL_dcam)
+{
+    LCGS_TRY(ctx->cam_slab.ensure(camera_grad_slab_bytes((int64_t)ctx->P)));
+    launch_camera_grad(ctx->hint_V > 0 ? ctx->hint_V : (int64_t)ctx->P, ctx->sh_deg, ctx->last.cp, ctx->last.scale_modifier,
+                       ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(),
+                       ctx->grads2d.as<float>(), ctx->last_has_jac ? ctx->shjac.as<float4>() : nullptr,
+                       ctx->recs.as<SplatRecord>(), ctx->g2d_value_mode, ctx->cam_slab.as<double>(), d_dL_dcam, ctx->stream);
+    return LCGS_OK;
+}
 // the state both map entry points need: a keep-state frame of this context's own records, lists per tile
 lcgs_status check_maps_state(lcgs_context* ctx, const char* who)
 {
@@ -131,6 +142,50 @@ lcgs_status lcgs_render_backward_maps(lcgs_context* ctx, const float* d_dL_dimg,
                            (d_dL_ddepth || d_dL_dalpha) ? &maps : nullptr);
 }
 
+lcgs_status lcgs_camera_backward(lcgs_context* ctx, float* d_dL_dcam)
+{
+    LCGS_REQUIRE(ctx && d_dL_dcam, "NULL argument");
+    LCGS_TRY(check_maps_state(ctx, "lcgs_camera_backward"));
+    if (!ctx->g2d_backward_done) {
+        set_last_error("lcgs_camera_backward needs a backward of the last frame (its 2-D gradient rows are only zeros until then)");
+        return LCGS_ERR_STATE;
+    }
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    LCGS_TRY(camera_pass(ctx, d_dL_dcam));
+    LCGS_HIP_CHECK(hipGetLastError());
+    return LCGS_OK;
+}
+
+lcgs_status lcgs_render_backward_camera(lcgs_context* ctx, const float* d_dL_dimg, int mode, const float* d_dL_ddepth,
+                                        const float* d_dL_dalpha, float* d_dL_dcam)
+{
+    LCGS_REQUIRE(ctx && d_dL_dcam, "NULL argument");
+    LCGS_REQUIRE(mode == LCGS_DEPTH_Z || mode == LCGS_DEPTH_INV_Z, "mode must be LCGS_DEPTH_Z or LCGS_DEPTH_INV_Z");
+    LCGS_REQUIRE(d_dL_dimg || d_dL_ddepth || d_dL_dalpha, "all three incoming gradients are NULL");
+    const MapGrads maps = { mode, d_dL_ddepth, d_dL_dalpha };
+    lcgs_grads     none{};
+    return render_backward(ctx, d_dL_dimg, &none, /*compact=*/true, /*accumulate=*/false, nullptr,
+                           (d_dL_ddepth || d_dL_dalpha) ? &maps : nullptr, d_dL_dcam);
+}
+
+lcgs_status lcgs_camera_grad_to_twist(const lcgs_camera* cam, const float dL_dcam[12], float dL_dxi[6])
+{
+    LCGS_REQUIRE(cam && dL_dcam && dL_dxi, "NULL argument");
+    const float* axes[3] = { cam->right, cam->up, cam->front }; // columns of Rc
+    const float* g[3]    = { dL_dcam + 9, dL_dcam + 6, dL_dcam + 3 }; // g_right, g_up, g_front
+    double       m[3][3]; // m[k] = Rc^T g_k
+    for (int k = 0; k < 3; ++k)
+        for (int r = 0; r < 3; ++r)
+            m[k][r] = (double)axes[r][0] * g[k][0] + (double)axes[r][1] * g[k][1] + (double)axes[r][2] * g[k][2];
+    // sum_k e_k x m[k]:  e_0 x a = (0, -a2, a1), e_1 x a = (a2, 0, -a0), e_2 x a = (-a1, a0, 0)
+    dL_dxi[0] = (float)(m[1][2] - m[2][1]);
+    dL_dxi[1] = (float)(m[2][0] - m[0][2]);
+    dL_dxi[2] = (float)(m[0][1] - m[1][0]);
+    for (int r = 0; r < 3; ++r)
+        dL_dxi[3 + r] = (float)((double)axes[r][0] * dL_dcam[0] + (double)axes[r][1] * dL_dcam[1] + (double)axes[r][2] * dL_dcam[2]);
+    return LCGS_OK;
+}
+
 lcgs_status lcgs_visible_rows(lcgs_context* ctx, const uint32_t** d_rows, const uint32_t** d_count)
 {
     LCGS_REQUIRE(ctx && d_rows && d_count, "NULL argument");
@@ -145,11 +200,12 @@ lcgs_status lcgs_visible_rows(lcgs_context* ctx, const uint32_t** d_rows, const 
 namespace
 {
 lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcgs_grads* grads, bool compact,
-                            bool accumulate, const FusedAdam* fused, const MapGrads* maps)
+                            bool accumulate, const FusedAdam* fused, const MapGrads* maps, float* d_camera_only)
 {
+    const bool params = !d_camera_only; // (lcgs_render_backward_camera: the walks and the camera pass, no per-splat rows)
     LCGS_REQUIRE(ctx && (d_dL_dimg || maps) && grads, "NULL argument");
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
-    LCGS_REQUIRE(fused || (grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh &&
+    LCGS_REQUIRE(fused || !params || (grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh &&
                            grads->d_dL_dopacity),
                  "NULL gradient buffer");
     if (!ctx->frame_state_valid() || !ctx->last.has_state) {
@@ -161,6 +217,7 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
         return LCGS_ERR_STATE;
     }
     LCGS_REQUIRE((reinterpret_cast<uintptr_t>(grads->d_dL_drotq) & 15) == 0, "dL_drotq must be 16-byte aligned");
+    if (!params) LCGS_TRY(ctx->cam_slab.ensure(camera_grad_slab_bytes((int64_t)ctx->P))); // (before any device work)
     // (the render-backward walks per-tile lists, and lcgs_render_forward never puts a frame that keeps state on per-block ones)
     LCGS_REQUIRE(ctx->last.cp.list_shift == 0u, "the kept frame lists its pairs per block: no backward walks those lists");
     hipStream_t  st   = ctx->stream;
@@ -226,7 +283,7 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
         LCGS_TRY(mark(ctx, "render_maps_backward"));
     }
     if (overlap) LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_join, 0));
-    const int slices = fused ? 0 : (sliced ? ctx->grad_slices : 1);
+    const int slices = (fused || !params) ? 0 : (sliced ? ctx->grad_slices : 1);
     if (fused) // (compact, unsliced: the update is applied where the gradients are formed; nothing is written out)
         launch_preprocess_backward_adam(ctx->hint_V > 0 ? ctx->hint_V : (int64_t)P, ctx->last.cp, ctx->last.scale_modifier,
                                         ctx->pos, ctx->scale, ctx->rotq, ctx->vis_index.as<uint32_t>(),
@@ -241,17 +298,19 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
                                    sliced ? ctx->slice_bounds.as<uint32_t>() : nullptr, k, slices, accumulate);
         if (sliced) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_slice[k], st));
     }
-    if (maps && maps->d_dL_ddepth) // view z = front . pos + tz: the depth channel's dL/dvalue reaches the position rows directly
+    if (params && maps && maps->d_dL_ddepth) // view z = front . pos + tz: the depth channel's dL/dvalue reaches the position rows directly
         launch_maps_depth_to_pos(ctx->hint_V > 0 ? ctx->hint_V : (int64_t)P, ctx->last.cp, ctx->vis_index.as<uint32_t>(),
                                  ctx->counts.as<uint32_t>(), ctx->recs.as<SplatRecord>(), ctx->grads2d.as<float>(), maps->mode,
                                  grads->d_dL_dpos, st);
     ctx->slices_recorded = sliced ? slices : 0;
     ctx->slices_of       = sliced ? grads->d_dL_dpos : nullptr;
     // sparse exchange (opt-in, lcgs_comm_track_touched_rows): the rows this frame wrote join the step's touched set
-    if (!compact && !fused && ctx->comm)
+    if (params && !compact && !fused && ctx->comm)
         LCGS_TRY(lcgs::comm_mark_touched(ctx->comm, ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), (int64_t)P,
                                          ctx->hint_V, accumulate, st));
     ctx->g2d_backward_done = true; // the frame's 2-D gradient rows now hold a backward's sums (lcgs_densify_accumulate)
+    ctx->g2d_value_mode    = (maps && maps->d_dL_ddepth) ? maps->mode : -1; // (every backward starts from zeroed rows)
+    if (!params) LCGS_TRY(camera_pass(ctx, d_camera_only));
     LCGS_TRY(mark(ctx, "preprocess_backward"));
     LCGS_HIP_CHECK(hipGetLastError());
     if (ctx->profiling) {

@@ -150,6 +150,9 @@ struct lcgs_context {
     bool        g2d_zeroed  = false;
     // a backward has run on the last keep-state frame: until then its 2-D gradient rows are only zeros (lcgs_densify_accumulate)
     bool        g2d_backward_done = false;
+    // ... and the depth mode of the backward that wrote their value slot (kG2DValueSlot), -1: none did (lcgs_camera_backward)
+    int         g2d_value_mode = -1;
+    DeviceBuffer cam_slab; // lcgs_camera_backward: per-block partial sums (camera_grad_slab_bytes)
     // lcgs_densify: emit counts, their inclusive sums, actions (one entry per source row)
     DeviceBuffer dn_emit, dn_incl, dn_action;
     // lcgs_knn_mean_dist2 / lcgs_scene_init_from_points (abi_init.cpp): Morton keys and original indices (the sort's ping-pong),

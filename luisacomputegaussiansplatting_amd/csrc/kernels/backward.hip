@@ -19,6 +19,7 @@
 // Thresholds are constants for the derivative: near cull, alpha < 1/255 skip, T < 1e-4 stop and power > 0 gate the
 // sums; the 0.99 alpha cap, the colour clamp and a saturated cam_clamp axis pass no gradient.
 #include "adam_rows.hpp"
+#include "splat_backward.hpp"
 #include "stream_access.hpp"
 #include "tile_common.hpp"
 
@@ -471,173 +472,7 @@ __global__ void __launch_bounds__(256, LCGS_BWD_WAVES) k_render_backward(CamPara
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// 2-D gradients -> parameter gradients, one lane per surviving splat.
-// ---------------------------------------------------------------------------------------------------------------
-// dL/d{pixel mean (gmx, gmy), conic (gA, gB, gC)} -> dL/d{pos (gp), scale (gs), rotq (gq: r,x,y,z)} through the EWA
-// projection, in precision R.  The forward quantities are recomputed (the order of gs_math.hpp is irrelevant for the
-// derivative).  cov_trace = a + c of the filtered 2-D covariance (>= its larger eigenvalue: the splat's footprint).
-template <typename FP>
-__device__ __forceinline__ void geom_backward_t(const CamParams& cp, FP scale_modifier, FP px, FP py, FP pz, FP sc0, FP sc1, FP sc2,
-                                                FP qw_, FP qx_, FP qy_, FP qz_, FP gmx, FP gmy, FP gA, FP gB, FP gC, FP gp[3], FP gs[3],
-                                                FP gq[4], FP& cov_trace)
-{
-    // ---- geometry: recompute the forward quantities (gs_math.hpp order is irrelevant for the derivative)
-    FP v[3];
-    v[0] = FP((cp.right[0])) * px + FP((cp.right[1])) * py + FP((cp.right[2])) * pz + FP(cp.tx);
-    v[1] = FP((cp.up[0])) * px + FP((cp.up[1])) * py + FP((cp.up[2])) * pz + FP(cp.ty);
-    v[2] = FP((cp.front[0])) * px + FP((cp.front[1])) * py + FP((cp.front[2])) * pz + FP(cp.tz);
-    const FP limx = FP(1.3) * FP(cp.tanfovx), limy = FP(1.3) * FP(cp.tanfovy);
-    const FP rx = v[0] / v[2], ry = v[1] / v[2];
-    const int   clx = (rx < -limx) ? -1 : (rx > limx ? 1 : 0);
-    const int   cly = (ry < -limy) ? -1 : (ry > limy ? 1 : 0);
-    const FP tx = (clx ? FP(clx) * limx : rx) * v[2];
-    const FP ty = (cly ? FP(cly) * limy : ry) * v[2];
-    const FP tz = v[2];
-    const FP sc[3] = { scale_modifier * sc0, scale_modifier * sc1, scale_modifier * sc2 };
-    const FP x = qx_, y = qy_, z = qz_, w = qw_;
-    FP Rm[3][3];
-    Rm[0][0] = FP(1.0) - FP(2.0) * y * y - FP(2.0) * z * z; Rm[0][1] = FP(2.0) * x * y - FP(2.0) * z * w; Rm[0][2] = FP(2.0) * x * z + FP(2.0) * y * w;
-    Rm[1][0] = FP(2.0) * x * y + FP(2.0) * z * w; Rm[1][1] = FP(1.0) - FP(2.0) * x * x - FP(2.0) * z * z; Rm[1][2] = FP(2.0) * y * z - FP(2.0) * x * w;
-    Rm[2][0] = FP(2.0) * x * z - FP(2.0) * y * w; Rm[2][1] = FP(2.0) * y * z + FP(2.0) * x * w; Rm[2][2] = FP(1.0) - FP(2.0) * x * x - FP(2.0) * y * y;
-    FP M[3][3], Sig[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) M[r][k] = Rm[r][k] * sc[k];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) Sig[r][k] = M[r][0] * M[k][0] + M[r][1] * M[k][1] + M[r][2] * M[k][2];
-    const FP j00 = FP(cp.focalx) / tz, j11 = FP(cp.focaly) / tz, j02 = -FP(cp.focalx) * tx / (tz * tz),
-                j12 = -FP(cp.focaly) * ty / (tz * tz);
-    FP T0[3], T1[3], ST0[3], ST1[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        T0[r] = FP(cp.right[r]) * j00 + FP(cp.front[r]) * j02;
-        T1[r] = FP(cp.up[r]) * j11 + FP(cp.front[r]) * j12;
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        ST0[r] = Sig[r][0] * T0[0] + Sig[r][1] * T0[1] + Sig[r][2] * T0[2];
-        ST1[r] = Sig[r][0] * T1[0] + Sig[r][1] * T1[1] + Sig[r][2] * T1[2];
-    }
-    const FP a = T0[0] * ST0[0] + T0[1] * ST0[1] + T0[2] * ST0[2] + FP(0.3);
-    const FP b = T1[0] * ST0[0] + T1[1] * ST0[1] + T1[2] * ST0[2];
-    const FP c = T1[0] * ST1[0] + T1[1] * ST1[1] + T1[2] * ST1[2] + FP(0.3);
-    const FP D = a * c - b * b + FP(1e-6);
-    const FP iD2 = FP(1.0) / (D * D);
-    const FP g00 = (-c * c * gA + b * c * gB + (D - a * c) * gC) * iD2;
-    const FP g11 = ((D - a * c) * gA + a * b * gB - a * a * gC) * iD2;
-    const FP g01 = (FP(2.0) * b * c * gA - (D + FP(2.0) * b * b) * gB + FP(2.0) * a * b * gC) * iD2;
-    FP Gm[3][3], dT0[3], dT1[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) Gm[r][k] = g00 * T0[r] * T0[k] + g01 * T1[r] * T0[k] + g11 * T1[r] * T1[k];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        dT0[r] = FP(2.0) * g00 * ST0[r] + g01 * ST1[r];
-        dT1[r] = FP(2.0) * g11 * ST1[r] + g01 * ST0[r];
-    }
-    const FP dj00 = FP(cp.right[0]) * dT0[0] + FP(cp.right[1]) * dT0[1] + FP(cp.right[2]) * dT0[2];
-    const FP dj02 = FP(cp.front[0]) * dT0[0] + FP(cp.front[1]) * dT0[1] + FP(cp.front[2]) * dT0[2];
-    const FP dj11 = FP(cp.up[0]) * dT1[0] + FP(cp.up[1]) * dT1[1] + FP(cp.up[2]) * dT1[2];
-    const FP dj12 = FP(cp.front[0]) * dT1[0] + FP(cp.front[1]) * dT1[1] + FP(cp.front[2]) * dT1[2];
-    const FP itz2 = FP(1.0) / (tz * tz), itz3 = itz2 / tz;
-    const FP dtx = dj02 * (-FP(cp.focalx) * itz2);
-    const FP dty = dj12 * (-FP(cp.focaly) * itz2);
-    const FP dtz = dj00 * (-FP(cp.focalx) * itz2) + dj11 * (-FP(cp.focaly) * itz2) + dj02 * (FP(2.0) * FP(cp.focalx) * tx * itz3) +
-                      dj12 * (FP(2.0) * FP(cp.focaly) * ty * itz3);
-    FP dv[3];
-    dv[0] = clx ? FP(0.0) : dtx;
-    dv[1] = cly ? FP(0.0) : dty;
-    dv[2] = dtz + (clx ? dtx * FP(clx) * limx : FP(0.0)) + (cly ? dty * FP(cly) * limy : FP(0.0));
-    const FP pw = FP(1.0) / (v[2] + FP(1e-6));
-    dv[0] += gmx * FP(cp.focalx) * pw;
-    dv[1] += gmy * FP(cp.focaly) * pw;
-    dv[2] += -(gmx * FP(cp.focalx) * v[0] + gmy * FP(cp.focaly) * v[1]) * pw * pw;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) gp[i] = FP(cp.right[i]) * dv[0] + FP(cp.up[i]) * dv[1] + FP(cp.front[i]) * dv[2];
-
-    FP dM[3][3], dRm[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            dM[r][k] = (Gm[r][0] + Gm[0][r]) * M[0][k] + (Gm[r][1] + Gm[1][r]) * M[1][k] + (Gm[r][2] + Gm[2][r]) * M[2][k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        gs[k] = scale_modifier * (dM[0][k] * Rm[0][k] + dM[1][k] * Rm[1][k] + dM[2][k] * Rm[2][k]);
-#pragma unroll
-        for (int r = 0; r < 3; ++r) dRm[r][k] = dM[r][k] * sc[k];
-    }
-    const FP gx_ = FP(2.0) * (y * (dRm[0][1] + dRm[1][0]) + z * (dRm[0][2] + dRm[2][0]) + w * (dRm[2][1] - dRm[1][2])) - FP(4.0) * x * (dRm[1][1] + dRm[2][2]);
-    const FP gy_ = FP(2.0) * (x * (dRm[0][1] + dRm[1][0]) + z * (dRm[1][2] + dRm[2][1]) + w * (dRm[0][2] - dRm[2][0])) - FP(4.0) * y * (dRm[0][0] + dRm[2][2]);
-    const FP gz_ = FP(2.0) * (x * (dRm[0][2] + dRm[2][0]) + y * (dRm[1][2] + dRm[2][1]) + w * (dRm[1][0] - dRm[0][1])) - FP(4.0) * z * (dRm[0][0] + dRm[1][1]);
-    const FP gw_ = FP(2.0) * (z * (dRm[1][0] - dRm[0][1]) + y * (dRm[0][2] - dRm[2][0]) + x * (dRm[2][1] - dRm[1][2]));
-
-    gq[0] = gw_; gq[1] = gx_; gq[2] = gy_; gq[3] = gz_; // (r, x, y, z)
-    cov_trace = a + c;
-}
-
-// The global operands of survivor `vsafe` (dense id; lanes past V pass the last survivor's and discard the result), splat idx:
-// its 2-D gradient row and its pos / scale / rotq rows.  Everything is requested here, together: one memory round trip per
-// block instead of one per use.
-struct SplatOperands {
-    float  gmx, gmy, gA, gB, gC, gop, gcol[3]; // dL/d{pixel mean, conic, opacity, colour}
-    float  px, py, pz, sc0, sc1, sc2;
-    float4 q; // (r,x,y,z)
-};
-__device__ __forceinline__ SplatOperands load_splat_operands(uint32_t vsafe, int idx, const float* grads2d, const float* pos,
-                                                             const float* scale, const float* rotq)
-{
-    const float4* g2 = reinterpret_cast<const float4*>(grads2d + (size_t)vsafe * kG2D);
-    const float4  q0 = g2[0], q1 = g2[1];
-    const float   gcol2 = reinterpret_cast<const float*>(g2)[8];
-    SplatOperands in;
-    in.px = pos[3 * (size_t)idx + 0], in.py = pos[3 * (size_t)idx + 1], in.pz = pos[3 * (size_t)idx + 2];
-    in.sc0 = scale[3 * (size_t)idx + 0], in.sc1 = scale[3 * (size_t)idx + 1], in.sc2 = scale[3 * (size_t)idx + 2];
-    in.q = *reinterpret_cast<const float4*>(rotq + 4 * (size_t)idx);
-    in.gmx = q0.x, in.gmy = q0.y, in.gA = q0.z, in.gB = q0.w, in.gC = q1.x, in.gop = q1.y;
-    in.gcol[0] = q1.z, in.gcol[1] = q1.w, in.gcol[2] = gcol2;
-    return in;
-}
-
-// A footprint beyond this (trace of the 2-D covariance, px^2: radius ~ 3 sqrt(lambda_max) > 64 px) takes the algebra in f64.
-constexpr float kGiantCovTrace = 455.0f;
-// (Both precisions are inlined: the kernels' register count doubles and their occupancy halves -- preprocess-backward
-//  0.181 -> 0.185 ms on the bicycle stand-in.  Holding them to the f32 occupancy with __launch_bounds__ spills the f64 branch
-//  to scratch and costs 0.05 ms: measured, gpurun_out/r4_ab_f64.log.)
-
-// The f32 algebra, and -- for screen-filling splats only -- the same algebra again in f64.  Their 2-D covariance is ~1e5 and
-// their conic ~1e-6: conic -> covariance -> Sigma -> scale / quaternion multiplies sums that cancel to a 1e-3..1e-5 of their
-// terms, and ANY f32 evaluation loses them (the f32 CPU restatement is off by up to 1.7e-1 on such rows; the 2-D gradients
-// feeding this step are good to ~1e-4: profiles/r04_gradient_error_survey.txt).  0.4 % of the on-screen splats of the
-// bicycle stand-in qualify; the kernels calling this are HBM-bound, the divergent f64 pass hides under their stores.
-__device__ __forceinline__ void geom_backward(const CamParams& cp, float scale_modifier, const SplatOperands& in, float gp[3],
-                                              float gs[3], float4& gq)
-{
-    float dp[3], q4[4], tr;
-    geom_backward_t<float>(cp, scale_modifier, in.px, in.py, in.pz, in.sc0, in.sc1, in.sc2, in.q.x, in.q.y, in.q.z, in.q.w, in.gmx,
-                           in.gmy, in.gA, in.gB, in.gC, dp, gs, q4, tr);
-    if (tr > kGiantCovTrace) {
-        double dpd[3], gsd[3], q4d[4], trd;
-        geom_backward_t<double>(cp, scale_modifier, in.px, in.py, in.pz, in.sc0, in.sc1, in.sc2, in.q.x, in.q.y, in.q.z, in.q.w,
-                                in.gmx, in.gmy, in.gA, in.gB, in.gC, dpd, gsd, q4d, trd);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            dp[i] = (float)dpd[i];
-            gs[i] = (float)gsd[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) q4[i] = (float)q4d[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) gp[i] += dp[i];
-    gq = make_float4(q4[0], q4[1], q4[2], q4[3]);
-}
-
+// (the per-splat expressions -- geom_backward, the operands' loads, the two colour steps -- are splat_backward.hpp's)
 // One lane per surviving splat (dense ids).  The splat's 48 SH coefficients arrive through the wave's LDS slab
 // (cooperative 16-byte loads, 12 lanes per 192-byte row), the SH gradient row is written back IN PLACE into the
 // slab as it is produced (so it never lives in registers next to the geometry Jacobians) and leaves as coalesced
@@ -715,44 +550,7 @@ k_preprocess_backward(int sh_deg, CamParams cp, float scale_modifier, const floa
             float gp[3] = { 0.0f, 0.0f, 0.0f };
 
             // ---- colour -> SH coefficients and position (through the view direction)
-            {
-                const float dx = in.px - cp.campos[0], dy = in.py - cp.campos[1], dz = in.pz - cp.campos[2];
-                const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
-                const float x = dx * inv, y = dy * inv, z = dz * inv;
-                const float xx = x * x, yy = y * y, zz = z * z;
-                float raw[3] = { 0.5f, 0.5f, 0.5f };
-#define LCGS_RAW(k, B, DX, DY, DZ)                                                                                    \
-    if (k < feat) {                                                                                                   \
-        const float bk = (B);                                                                                         \
-        raw[0] += bk * row[k * 3 + 0];                                                                                \
-        raw[1] += bk * row[k * 3 + 1];                                                                                \
-        raw[2] += bk * row[k * 3 + 2];                                                                                \
-    }
-                LCGS_SH_TERMS(LCGS_RAW)
-#undef LCGS_RAW
-                float g[3];
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) g[ch] = (raw[ch] > 0.0f && raw[ch] < 1.0f) ? in.gcol[ch] : 0.0f; // clamp mask
-                float ddx = 0.0f, ddy = 0.0f, ddz = 0.0f;
-#define LCGS_GRAD(k, B, DX, DY, DZ)                                                                                   \
-    {                                                                                                                 \
-        const float c0 = row[k * 3 + 0], c1 = row[k * 3 + 1], c2 = row[k * 3 + 2];                                    \
-        const float bk = (k < feat) ? (B) : 0.0f;                                                                     \
-        const float wk = (k < feat) ? g[0] * c0 + g[1] * c1 + g[2] * c2 : 0.0f;                                       \
-        ddx += wk * (DX);                                                                                             \
-        ddy += wk * (DY);                                                                                             \
-        ddz += wk * (DZ);                                                                                             \
-        row[k * 3 + 0] = bk * g[0];                                                                                   \
-        row[k * 3 + 1] = bk * g[1];                                                                                   \
-        row[k * 3 + 2] = bk * g[2];                                                                                   \
-    }
-                LCGS_SH_TERMS(LCGS_GRAD)
-#undef LCGS_GRAD
-                const float dd = x * ddx + y * ddy + z * ddz;
-                gp[0] += (ddx - x * dd) * inv;
-                gp[1] += (ddy - y * dd) * inv;
-                gp[2] += (ddz - z * dd) * inv;
-            }
+            sh_colour_step<true>(cp, in, feat, row, gp);
 
             float  gs[3];
             float4 gq;
@@ -796,31 +594,6 @@ k_preprocess_backward(int sh_deg, CamParams cp, float scale_modifier, const floa
 // a kernel that is bound by bytes in flight.
 constexpr int kJacPitch = 19; // floats per splat in the LDS slab (odd: conflict-free per-lane writes)
 
-// The colour step of that path for one splat: parks the 16 basis values of its view direction and its 3 clamp-masked
-// dL/dcolour in its slab slot `mine`, and returns the direction part of dL/dpos (from the kept Jacobian rows j0..j2) in gp.
-__device__ __forceinline__ void jac_colour_step(const CamParams& cp, const SplatOperands& in, float4 j0, float4 j1, float4 j2,
-                                                float* mine, float gp[3])
-{
-    const uint32_t mask = __float_as_uint(j2.y);
-    const float*   gcol = in.gcol;
-    const float dx = in.px - cp.campos[0], dy = in.py - cp.campos[1], dz = in.pz - cp.campos[2];
-    const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
-    const float x = dx * inv, y = dy * inv, z = dz * inv;
-    const float xx = x * x, yy = y * y, zz = z * z;
-#define LCGS_BASIS(k, B, DX, DY, DZ) mine[k] = (B);
-    LCGS_SH_TERMS(LCGS_BASIS)
-#undef LCGS_BASIS
-#pragma unroll
-    for (int c = 0; c < 3; ++c) mine[16 + c] = ((mask >> c) & 1u) ? gcol[c] : 0.0f; // clamp mask
-    // J rows of clamped channels are already zero: no mask needed here
-    const float ddx = gcol[0] * j0.x + gcol[1] * j0.w + gcol[2] * j1.z;
-    const float ddy = gcol[0] * j0.y + gcol[1] * j1.x + gcol[2] * j1.w;
-    const float ddz = gcol[0] * j0.z + gcol[1] * j1.y + gcol[2] * j2.x;
-    const float dd  = x * ddx + y * ddy + z * ddz;
-    gp[0] = (ddx - x * dd) * inv;
-    gp[1] = (ddy - y * dd) * inv;
-    gp[2] = (ddz - z * dd) * inv;
-}
 // float4 `part` (0..11) of a splat's 16 x 3 SH gradient row, formed from the 19 floats of its slab slot
 __device__ __forceinline__ float4 jac_outer_part(const float* slot, uint32_t part)
 {

@@ -1,0 +1,146 @@
+// camera_grad.hip -- the gradient of the last backward's scalar with respect to the camera pose: twelve floats in the order of
+// lcgs_camera's members (position, front, up, right; the contract is in include/lcgs_hip.h, the algebra in DESIGN.md 9).  The
+// reference has no backward at all; this is the second consumer of the 2-D gradient rows a backward leaves in the context.
+//
+//   k_camera_grad         one lane per on-screen row (dense ids), 256-lane workgroups, grid-stride over FIXED blocks of 256
+//                         rows.  The per-splat expressions are the preprocess-backward's own (splat_backward.hpp): the colour
+//                         step's direction part of dL/dpos -- from the kept Jacobian (JAC) or from the coefficient rows staged
+//                         through LDS as k_preprocess_backward stages them -- and geom_backward_t, which hands out dv, dT0, dT1
+//                         and the four projection-Jacobian entries instead of dropping them.  Twelve doubles per lane, summed
+//                         over the wave with a fixed butterfly of cross-lane moves, over the four waves through LDS in wave
+//                         order; block b's twelve sums go to slab entry b with plain stores.
+//   k_camera_grad_finish  one workgroup adds the slab entries in index order (21 interleaved runs per component, then the runs
+//                         in order) and writes the twelve floats, each rounded once.  The entry count comes from d_counts[0].
+// No atomics: the summation tree depends on the number of on-screen rows only -- not on the grid, the launch hint or timing --
+// so the same 2-D rows give the same bits.
+#include "splat_backward.hpp"
+
+namespace lcgs
+{
+namespace
+{
+constexpr int kCamTerms = 12;
+constexpr int kFinishRuns = 21; // 21 x 12 = 252 of the finish kernel's 256 lanes
+
+__device__ __forceinline__ double wave_sum(double x)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
+template <bool JAC>
+__global__ void __launch_bounds__(256)
+k_camera_grad(int sh_deg, CamParams cp, float scale_modifier, const float* __restrict__ pos, const float* __restrict__ scale,
+              const float* __restrict__ rotq, const float* __restrict__ sh, const uint32_t* __restrict__ vis_index,
+              const uint32_t* __restrict__ d_counts, const float* __restrict__ grads2d, const float4* __restrict__ shjac,
+              const SplatRecord* __restrict__ recs, int depth_mode, double* __restrict__ slab)
+{
+    __shared__ float4 s_sh[JAC ? 1 : 4][JAC ? 1 : 64 * 13]; // (the coefficient rows' slab: the SH-row path only)
+    __shared__ double s_part[4][kCamTerms];
+    const uint32_t V = d_counts[0];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int feat = (sh_deg + 1) * (sh_deg + 1);
+    const bool staged = sh_deg == 3 && ((reinterpret_cast<uintptr_t>(sh) & 15) == 0);
+    for (uint32_t blk = blockIdx.x; (uint64_t)blk * 256u < V; blk += gridDim.x) { // (no row at all: no pass, no V - 1)
+        const uint32_t vid   = blk * 256u + threadIdx.x;
+        const bool     valid = vid < V;
+        const uint32_t vsafe = valid ? vid : V - 1;
+        const int      idx   = (int)vis_index[vsafe];
+        const SplatOperands in = load_splat_operands(vsafe, idx, grads2d, pos, scale, rotq);
+        float gdir[3] = { 0.0f, 0.0f, 0.0f };
+        if constexpr (JAC) {
+            const float4 j0 = shjac[(size_t)vsafe * 3 + 0], j1 = shjac[(size_t)vsafe * 3 + 1], j2 = shjac[(size_t)vsafe * 3 + 2];
+            jac_colour_step<false>(cp, in, j0, j1, j2, nullptr, gdir);
+        } else {
+            // ---- stage the SH rows (coalesced), or fetch them lane-wise for other degrees: k_preprocess_backward's staging
+            const uint32_t wave_first = blk * 256u + wave * 64u;
+            const uint32_t nvalid     = wave_first < V ? ((V - wave_first) < 64u ? (V - wave_first) : 64u) : 0u;
+            float*         row = reinterpret_cast<float*>(&s_sh[wave][lane * 13]);
+            __syncthreads(); // the previous block's readers are done with the slab
+            if (staged) {
+#pragma unroll
+                for (int i = 0; i < 12; ++i) {
+                    const uint32_t c    = (uint32_t)i * 64u + lane;
+                    const uint32_t slot = c / 12u, part = c - slot * 12u;
+                    const int      sidx = __shfl(idx, (int)slot, 64);
+                    if (slot < nvalid)
+                        s_sh[wave][slot * 13u + part] = reinterpret_cast<const float4*>(sh + (size_t)sidx * 48)[part];
+                }
+            } else if (valid) {
+                const float* s = sh + (size_t)idx * feat * 3;
+                for (int k = 0; k < 48; ++k) row[k] = k < feat * 3 ? s[k] : 0.0f;
+            }
+            __syncthreads();
+            if (valid) sh_colour_step<false>(cp, in, feat, row, gdir);
+        }
+        double t[kCamTerms];
+#pragma unroll
+        for (int k = 0; k < kCamTerms; ++k) t[k] = 0.0;
+        if (valid) {
+            // the depth channel's dL/dvalue reaches view z directly (maps.hip k_maps_depth_to_pos: the same expression)
+            float gz = 0.0f;
+            if (depth_mode >= 0) {
+                const float gv = grads2d[(size_t)vid * kG2D + kG2DValueSlot];
+                if (gv != 0.0f) {
+                    const float z = recs[vid].depth;
+                    gz            = depth_mode == kDepthInvZ ? -gv / (z * z) : gv;
+                }
+            }
+            camera_terms(cp, scale_modifier, in, gdir, gz, t);
+        }
+        // ---- the block's twelve sums: butterfly over the wave, then the four waves in order
+#pragma unroll
+        for (int k = 0; k < kCamTerms; ++k) t[k] = wave_sum(t[k]);
+        __syncthreads(); // the previous block's s_part is read
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < kCamTerms; ++k) s_part[wave][k] = t[k];
+        }
+        __syncthreads();
+        if (threadIdx.x < (unsigned)kCamTerms) {
+            const int k = (int)threadIdx.x;
+            slab[(size_t)blk * kCamTerms + k] = ((s_part[0][k] + s_part[1][k]) + s_part[2][k]) + s_part[3][k];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_camera_grad_finish(const uint32_t* __restrict__ d_counts, const double* __restrict__ slab,
+                                                            float* __restrict__ out)
+{
+    __shared__ double s_run[kFinishRuns][kCamTerms];
+    const uint32_t V = d_counts[0];
+    const uint32_t entries = V / 256u + ((V & 255u) ? 1u : 0u);
+    const uint32_t t = threadIdx.x, run = t / (uint32_t)kCamTerms, k = t - run * (uint32_t)kCamTerms;
+    if (run < (uint32_t)kFinishRuns) {
+        double a = 0.0;
+        for (uint32_t e = run; e < entries; e += (uint32_t)kFinishRuns) a += slab[(size_t)e * kCamTerms + k]; // (21 entries = 2016 contiguous bytes per step)
+        s_run[run][k] = a;
+    }
+    __syncthreads();
+    if (t < (uint32_t)kCamTerms) {
+        double a = 0.0;
+        for (int r = 0; r < kFinishRuns; ++r) a += s_run[r][t];
+        out[t] = (float)a; // (a frame without on-screen rows: twelve zeros)
+    }
+}
+} // namespace
+
+size_t camera_grad_slab_bytes(int64_t P) { return (size_t)((P + 255) / 256) * kCamTerms * sizeof(double); }
+
+void launch_camera_grad(int64_t v_hint, int sh_deg, const CamParams& cp, float scale_modifier, const float* pos, const float* scale,
+                        const float* rotq, const float* sh, const uint32_t* vis_index, const uint32_t* d_counts,
+                        const float* grads2d, const float4* shjac, const SplatRecord* recs, int depth_mode, double* slab,
+                        float* dL_dcam, hipStream_t stream)
+{
+    const unsigned blocks = grid_256(v_hint);
+    if (shjac && sh_deg == 3)
+        hipLaunchKernelGGL(k_camera_grad<true>, dim3(blocks), dim3(256), 0, stream, sh_deg, cp, scale_modifier, pos, scale, rotq, sh,
+                           vis_index, d_counts, grads2d, shjac, recs, depth_mode, slab);
+    else
+        hipLaunchKernelGGL(k_camera_grad<false>, dim3(blocks), dim3(256), 0, stream, sh_deg, cp, scale_modifier, pos, scale, rotq, sh,
+                           vis_index, d_counts, grads2d, shjac, recs, depth_mode, slab);
+    hipLaunchKernelGGL(k_camera_grad_finish, dim3(1), dim3(256), 0, stream, d_counts, slab, dL_dcam);
+}
+
+} // namespace lcgs

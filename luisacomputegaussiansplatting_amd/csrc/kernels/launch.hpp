@@ -378,4 +378,15 @@ void launch_render_maps_backward(const CamParams& cp, const uint32_t* ranges, co
 void launch_maps_depth_to_pos(int64_t v_hint, const CamParams& cp, const uint32_t* vis_index, const uint32_t* d_counts,
                               const SplatRecord* recs, const float* grads2d, int mode, float* dL_dpos, hipStream_t stream);
 
+// ---- camera_grad.hip : the camera gradient of the last backward, from the 2-D rows it left ----
+// the context-owned slab: twelve doubles per block of 256 on-screen rows
+size_t camera_grad_slab_bytes(int64_t P);
+// dL_dcam: 12 floats (position, front, up, right), overwritten.  shjac: the kept colour Jacobian or NULL (then the direction
+// part comes from the sh rows); depth_mode: the depth mode of the backward that wrote grads2d slot kG2DValueSlot, -1: none.
+// Two launches (per-block sums, then one workgroup that adds them in a fixed order); no atomics
+void launch_camera_grad(int64_t v_hint, int sh_deg, const CamParams& cp, float scale_modifier, const float* pos, const float* scale,
+                        const float* rotq, const float* sh, const uint32_t* vis_index, const uint32_t* d_counts,
+                        const float* grads2d, const float4* shjac, const SplatRecord* recs, int depth_mode, double* slab,
+                        float* dL_dcam, hipStream_t stream);
+
 } // namespace lcgs

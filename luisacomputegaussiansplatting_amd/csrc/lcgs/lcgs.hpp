@@ -107,10 +107,23 @@ public:
     }
     // the loss Scene::fit_views applies: LCGS_LOSS_L2 (default) or LCGS_LOSS_PHOTOMETRIC
     void set_fit_loss(int kind, float lambda_dssim = 0.2f) { check(lcgs_set_fit_loss(m_ctx, kind, lambda_dssim)); }
+    // the camera gradient (12 device floats: position, front, up, right) of the last backward of the kept frame
+    void camera_backward(float* d_dL_dcam) { check(lcgs_camera_backward(m_ctx, d_dL_dcam)); }
+    // walks + camera pass without parameter gradients; any of the three incoming gradients may be NULL, not all
+    void render_backward_camera(const float* d_dL_dimg, const float* d_dL_ddepth, const float* d_dL_dalpha, float* d_dL_dcam,
+                                int mode = LCGS_DEPTH_Z)
+    {
+        check(lcgs_render_backward_camera(m_ctx, d_dL_dimg, mode, d_dL_ddepth, d_dL_dalpha, d_dL_dcam));
+    }
 
 private:
     lcgs_context* m_ctx = nullptr;
 };
+// host only: a camera gradient -> the gradient w.r.t. a twist (omega[3], tau[3]) applied in the camera's own frame
+inline void camera_grad_to_twist(const lcgs_camera& cam, const float dL_dcam[12], float dL_dxi[6])
+{
+    check(lcgs_camera_grad_to_twist(&cam, dL_dcam, dL_dxi));
+}
 
 // ---- proxies: lcgs/include/lcgs/sh_preprocessor.h:16-20, gs_projector.h:16-28, proxy.h:43-71 ----
 struct GPUPointsProxy {
