@@ -207,6 +207,9 @@ LCGS_API lcgs_status lcgs_set_list_policy(lcgs_context* ctx, int policy);
 LCGS_API lcgs_status lcgs_debug_last_lists(lcgs_context* ctx, uint32_t* d_list, uint32_t* d_ranges);
 LCGS_API lcgs_status lcgs_debug_last_state(lcgs_context* ctx, float* d_final_T, uint32_t* d_n_contrib);
 LCGS_API lcgs_status lcgs_debug_blend_exp(lcgs_context* ctx, const float* d_x, float* d_out, int64_t n);
+/* Debug/test hook: forward frames of this context whose cull and sort chain ran on the head stream (enqueue-only frames of a
+ * context-owned scene), those of them that chained behind the frame before, and those that rendered with the bounded grid. */
+LCGS_API lcgs_status lcgs_debug_pipeline_counts(lcgs_context* ctx, uint64_t* piped, uint64_t* chained, uint64_t* bounded);
 
 /* ---- backward of the last lcgs_render_forward(keep_state = 1) (no reference counterpart, README.md:70) ---- */
 /* Outputs w.r.t. the ACTIVATED inputs: dL/dpos[3P], dL/dscale[3P], dL/drotq[4P] (as stored; 16-byte aligned),

@@ -247,6 +247,7 @@ def _signatures() -> dict:
         "lcgs_debug_last_lists": (st, [p, p, p]),
         "lcgs_debug_last_state": (st, [p, p, p]),
         "lcgs_debug_blend_exp": (st, [p, p, p, i64]),
+        "lcgs_debug_pipeline_counts": (st, [p, p, p, p]),
         # backward
         "lcgs_render_backward": (st, [p, p, grads]),
         "lcgs_render_backward_accumulate": (st, [p, p, grads]),
@@ -902,6 +903,13 @@ class Renderer:
         with keep_state=True; a frame without it lists its pairs per block of 2 x 2 tiles (the first ceil(gx / 2) * ceil(gy / 2)
         ranges, row-major; the rest zero).  Either argument may be None."""
         _check(load_library().lcgs_debug_last_lists(self.ctx._h, _ptr(d_list), _ptr(d_ranges)))
+
+    def pipeline_counts(self) -> dict:
+        """lcgs_debug_pipeline_counts: forward frames that ran their head on the head stream, that chained, that used the
+        bounded renderer grid"""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(load_library().lcgs_debug_pipeline_counts(self.ctx._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"piped": a.value, "chained": b.value, "bounded": c.value}
 
     def set_list_policy(self, policy: str):
         """lcgs_set_list_policy: "tile" (the reference's per-tile lists), "block" (per 2 x 2 tiles), "auto" (default)"""

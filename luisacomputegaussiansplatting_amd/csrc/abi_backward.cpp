@@ -63,16 +63,19 @@ extern "C" {
 
 lcgs_status lcgs_render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcgs_grads* grads)
 {
+    LCGS_ENTRY(ctx);
     return render_backward(ctx, d_dL_dimg, grads, /*compact=*/false);
 }
 
 lcgs_status lcgs_render_backward_compact(lcgs_context* ctx, const float* d_dL_dimg, const lcgs_grads* grads)
 {
+    LCGS_ENTRY(ctx);
     return render_backward(ctx, d_dL_dimg, grads, /*compact=*/true);
 }
 
 lcgs_status lcgs_render_backward_accumulate(lcgs_context* ctx, const float* d_dL_dimg, const lcgs_grads* grads)
 {
+    LCGS_ENTRY(ctx);
     return render_backward(ctx, d_dL_dimg, grads, /*compact=*/false, /*accumulate=*/true);
 }
 
@@ -81,6 +84,7 @@ lcgs_status lcgs_render_backward_adam(lcgs_context* ctx, const float* d_dL_dimg,
                                       const lcgs_params* v, const lcgs_params* activated)
 {
     LCGS_REQUIRE(ctx && d_dL_dimg && cfg && raw && m && v && activated, "NULL argument");
+    LCGS_ENTRY(ctx);
     LCGS_REQUIRE(num_gaussians == ctx->P && sh_degree == ctx->sh_deg, "num_gaussians / sh_degree must be the bound scene's");
     LCGS_TRY(check_adam_config(cfg));
     const lcgs_params* packs[4] = { raw, m, v, activated };
@@ -120,6 +124,7 @@ lcgs_status lcgs_render_maps(lcgs_context* ctx, int mode, float* d_depth, float*
     LCGS_REQUIRE(ctx, "NULL argument");
     LCGS_REQUIRE(mode == LCGS_DEPTH_Z || mode == LCGS_DEPTH_INV_Z, "mode must be LCGS_DEPTH_Z or LCGS_DEPTH_INV_Z");
     LCGS_REQUIRE(d_depth || d_alpha, "both outputs are NULL");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     LCGS_TRY(check_maps_state(ctx, "lcgs_render_maps"));
     launch_render_maps(ctx->last.cp, ctx->ranges, ctx->pairv[ctx->last.list_buf].as<uint32_t>(), ctx->recs.as<SplatRecord>(),
@@ -138,6 +143,7 @@ lcgs_status lcgs_render_backward_maps(lcgs_context* ctx, const float* d_dL_dimg,
     LCGS_REQUIRE(grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh && grads->d_dL_dopacity,
                  "NULL gradient buffer");
     const MapGrads maps = { mode, d_dL_ddepth, d_dL_dalpha };
+    LCGS_ENTRY(ctx);
     return render_backward(ctx, d_dL_dimg, grads, /*compact=*/false, accumulate != 0, nullptr,
                            (d_dL_ddepth || d_dL_dalpha) ? &maps : nullptr);
 }
@@ -145,6 +151,7 @@ lcgs_status lcgs_render_backward_maps(lcgs_context* ctx, const float* d_dL_dimg,
 lcgs_status lcgs_camera_backward(lcgs_context* ctx, float* d_dL_dcam)
 {
     LCGS_REQUIRE(ctx && d_dL_dcam, "NULL argument");
+    LCGS_ENTRY(ctx);
     LCGS_TRY(check_maps_state(ctx, "lcgs_camera_backward"));
     if (!ctx->g2d_backward_done) {
         set_last_error("lcgs_camera_backward needs a backward of the last frame (its 2-D gradient rows are only zeros until then)");
@@ -164,6 +171,7 @@ lcgs_status lcgs_render_backward_camera(lcgs_context* ctx, const float* d_dL_dim
     LCGS_REQUIRE(d_dL_dimg || d_dL_ddepth || d_dL_dalpha, "all three incoming gradients are NULL");
     const MapGrads maps = { mode, d_dL_ddepth, d_dL_dalpha };
     lcgs_grads     none{};
+    LCGS_ENTRY(ctx);
     return render_backward(ctx, d_dL_dimg, &none, /*compact=*/true, /*accumulate=*/false, nullptr,
                            (d_dL_ddepth || d_dL_dalpha) ? &maps : nullptr, d_dL_dcam);
 }
@@ -189,6 +197,7 @@ lcgs_status lcgs_camera_grad_to_twist(const lcgs_camera* cam, const float dL_dca
 lcgs_status lcgs_visible_rows(lcgs_context* ctx, const uint32_t** d_rows, const uint32_t** d_count)
 {
     LCGS_REQUIRE(ctx && d_rows && d_count, "NULL argument");
+    LCGS_ENTRY(ctx);
     LCGS_REQUIRE(ctx->frame_state_valid(), "no frame rendered yet");
     *d_rows  = ctx->vis_index.as<uint32_t>();
     *d_count = ctx->counts.as<uint32_t>(); // [0] = on-screen splats of the last frame

@@ -69,6 +69,7 @@ namespace lcgs
 {
 hipStream_t context_stream(lcgs_context* ctx) { return ctx->stream; }
 int         context_device(lcgs_context* ctx) { return ctx->device; }
+void        context_count_call(lcgs_context* ctx) { ++ctx->op_seq; }
 } // namespace lcgs
 
 namespace lcgs
@@ -200,6 +201,7 @@ lcgs_status lcgs_create(int device_id, void* stream, lcgs_context** out_ctx)
     if (const char* e = getenv("LCGS_STAGE_MAILBOX")) ctx->stage_mailbox = e[0] != '0';      // A/B hook
     if (const char* e = getenv("LCGS_COARSE_LISTS")) ctx->coarse_mode = e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2); // A/B / test hook
     if (const char* e = getenv("LCGS_BWD_USE_MASKS")) ctx->bwd_use_masks = e[0] != '0';      // test hook: the launcher's mask-less form
+    if (const char* e = getenv("LCGS_PIPELINE")) ctx->pipeline = e[0] != '0'; // A/B and test hook: 0 = every frame in single-stream order
     if (const char* e = getenv("LCGS_STAGE_SORT")) ctx->stage_sort = e[0] == 'l' ? 1 : (e[0] == 's' ? 2 : 0); // test hook
     // The auxiliary stream has the LOWEST dispatch priority: its bandwidth-bound workgroups fill the gaps the main
     // stream's short, latency-bound kernels leave instead of competing with them.
@@ -211,7 +213,8 @@ lcgs_status lcgs_create(int device_id, void* stream, lcgs_context** out_ctx)
         if (se != hipSuccess) se = hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking);
     }
     for (hipEvent_t* ev : { &ctx->ev_fork, &ctx->ev_join, &ctx->ev_ranges, &ctx->ev_aux_done, &ctx->ev_render, &ctx->ev_counts,
-                            &ctx->ev_g2d_zero })
+                            &ctx->ev_g2d_zero, &ctx->ev_pipe_entry, &ctx->ev_pipe_render[0], &ctx->ev_pipe_render[1],
+                            &ctx->ev_pipe_aux[0], &ctx->ev_pipe_aux[1] })
         if (se == hipSuccess) se = hipEventCreateWithFlags(ev, hipEventDisableTiming);
     if (se != hipSuccess) {
         lcgs_status s = hip_fail(se, "aux stream / events", __FILE__, __LINE__);
@@ -226,6 +229,7 @@ lcgs_status lcgs_create(int device_id, void* stream, lcgs_context** out_ctx)
 lcgs_status lcgs_destroy(lcgs_context* ctx)
 {
     if (!ctx) return LCGS_OK;
+    LCGS_ENTRY(ctx);
     abi::registry_remove(ctx);
     (void)hipSetDevice(ctx->device);
     (void)lcgs_stage_flush(ctx); // deferred stage calls still recorded: their outputs are the caller's buffers
@@ -239,15 +243,12 @@ lcgs_status lcgs_destroy(lcgs_context* ctx)
         (void)lcgs_destroy(ctx->twin);
         ctx->twin = nullptr;
     }
-    if (ctx->twin_stream) {
-        (void)hipStreamSynchronize(ctx->twin_stream);
-        (void)hipStreamDestroy(ctx->twin_stream);
-    }
     for (hipEvent_t ev : { ctx->ev_batch_fork, ctx->ev_batch_join })
         if (ev) (void)hipEventDestroy(ev);
     (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->head_stream) (void)hipStreamSynchronize(ctx->head_stream);
     if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
-    DeviceBuffer* bufs[] = { &ctx->recs, &ctx->sortk[0], &ctx->sortk[1], &ctx->sortv[0], &ctx->sortv[1], &ctx->vis_index,
+    DeviceBuffer* bufs[] = { &ctx->recs, &ctx->recs_b, &ctx->pairv[2], &ctx->sortk[0], &ctx->sortk[1], &ctx->sortv[0], &ctx->sortv[1], &ctx->vis_index,
                              &ctx->rects, &ctx->rects_sorted, &ctx->cull_slab, &ctx->chunk_info, &ctx->chunk_base, &ctx->pairk[0], &ctx->pairk[1], &ctx->pairv[0],
                              &ctx->pairv[1], &ctx->zero_ws[0], &ctx->zero_ws[1], &ctx->zero_ws[2], &ctx->counts, &ctx->sort_ws,
                              &ctx->expand_ws, &ctx->final_T, &ctx->n_contrib, &ctx->list_idx, &ctx->grads2d, &ctx->tile_order[0], &ctx->tile_order[1], &ctx->st_keys_tmp,
@@ -276,8 +277,10 @@ lcgs_status lcgs_destroy(lcgs_context* ctx)
         (void)hipStreamSynchronize(ctx->aux_stream);
         (void)hipStreamDestroy(ctx->aux_stream);
     }
+    if (ctx->head_stream) (void)hipStreamDestroy(ctx->head_stream); // (synchronised above, with the other two)
     for (hipEvent_t ev : { ctx->ev_fork, ctx->ev_join, ctx->ev_ranges, ctx->ev_aux_done, ctx->ev_render, ctx->ev_counts,
-                           ctx->ev_g2d_zero })
+                           ctx->ev_g2d_zero, ctx->ev_pipe_entry, ctx->ev_pipe_render[0], ctx->ev_pipe_render[1],
+                           ctx->ev_pipe_aux[0], ctx->ev_pipe_aux[1] })
         if (ev) (void)hipEventDestroy(ev);
     ctx->fit_img.release();
     ctx->fit_dL.release();
@@ -301,6 +304,7 @@ lcgs_status lcgs_destroy(lcgs_context* ctx)
 lcgs_status lcgs_set_stream(lcgs_context* ctx, void* stream)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     if (ctx->stream != reinterpret_cast<hipStream_t>(stream)) {
         // deferred stage calls were recorded against the OLD stream's order: they run there, before the switch
         LCGS_TRY(lcgs_stage_flush(ctx));
@@ -316,6 +320,7 @@ lcgs_status lcgs_set_stream(lcgs_context* ctx, void* stream)
 lcgs_status lcgs_synchronize(lcgs_context* ctx)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     LCGS_TRY(lcgs_stage_flush(ctx)); // deferred stage mode: whatever was recorded is produced before the caller looks
     LCGS_TRY(sync_frame(ctx));
     lcgs_status twin_status = LCGS_OK;
@@ -331,6 +336,7 @@ lcgs_status lcgs_synchronize(lcgs_context* ctx)
 lcgs_status lcgs_set_profiling(lcgs_context* ctx, int enabled)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     ctx->profiling = enabled != 0;
     return LCGS_OK;
 }
@@ -338,6 +344,7 @@ lcgs_status lcgs_set_profiling(lcgs_context* ctx, int enabled)
 lcgs_status lcgs_get_stage_times(lcgs_context* ctx, lcgs_stage_times* out)
 {
     LCGS_REQUIRE(ctx && out, "NULL argument");
+    LCGS_ENTRY(ctx);
     *out = ctx->times;
     return LCGS_OK;
 }
@@ -345,6 +352,7 @@ lcgs_status lcgs_get_stage_times(lcgs_context* ctx, lcgs_stage_times* out)
 lcgs_status lcgs_get_frame_stats(lcgs_context* ctx, lcgs_frame_stats* out)
 {
     LCGS_REQUIRE(ctx && out, "NULL argument");
+    LCGS_ENTRY(ctx);
     LCGS_REQUIRE(ctx->frame_state_valid(), "no frame rendered yet");
     LCGS_TRY(sync_frame(ctx));
     ctx->stats.num_gaussians = ctx->P;
@@ -362,6 +370,7 @@ lcgs_status lcgs_get_frame_stats(lcgs_context* ctx, lcgs_frame_stats* out)
 // reference's point_list holds) and the tile ranges.  d_list must hold num_pairs entries, d_ranges 2*G.
 lcgs_status lcgs_debug_last_lists(lcgs_context* ctx, uint32_t* d_list, uint32_t* d_ranges)
 {
+    LCGS_ENTRY(ctx);
     LCGS_REQUIRE(ctx && ctx->frame_state_valid(), "no frame rendered yet");
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
     LCGS_TRY(sync_frame(ctx));
@@ -381,6 +390,7 @@ lcgs_status lcgs_debug_last_lists(lcgs_context* ctx, uint32_t* d_list, uint32_t*
 // or the library's decision from the last synchronised frame's counts (the default).
 lcgs_status lcgs_set_list_policy(lcgs_context* ctx, int policy)
 {
+    LCGS_ENTRY(ctx);
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
     LCGS_REQUIRE(policy == LCGS_LISTS_PER_TILE || policy == LCGS_LISTS_PER_BLOCK || policy == LCGS_LISTS_AUTO, "unknown list policy");
     for (lcgs_context* c = ctx; c; c = c->twin) c->coarse_mode = policy;
@@ -392,6 +402,7 @@ lcgs_status lcgs_set_list_policy(lcgs_context* ctx, int policy)
 // last contributor.
 lcgs_status lcgs_debug_last_state(lcgs_context* ctx, float* d_final_T, uint32_t* d_n_contrib)
 {
+    LCGS_ENTRY(ctx);
     LCGS_REQUIRE(ctx && ctx->frame_state_valid() && ctx->last.has_state, "no keep_state frame rendered yet");
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t n = (size_t)ctx->last.cp.width * ctx->last.cp.height;
@@ -401,10 +412,23 @@ lcgs_status lcgs_debug_last_state(lcgs_context* ctx, float* d_final_T, uint32_t*
     return LCGS_OK;
 }
 
+// Debug/test hook: how many forward frames of this context ran their head on the head stream, how many of those chained
+// behind the frame before them, and how many of those rendered with the bounded grid
+lcgs_status lcgs_debug_pipeline_counts(lcgs_context* ctx, uint64_t* piped, uint64_t* chained, uint64_t* bounded)
+{
+    LCGS_REQUIRE(ctx && piped && chained && bounded, "NULL argument");
+    LCGS_ENTRY(ctx);
+    *piped   = ctx->pipe_frames;
+    *chained = ctx->pipe_chained;
+    *bounded = ctx->pipe_bounded;
+    return LCGS_OK;
+}
+
 // Debug/parity hook: the compositing loop's exp on its own (gs_math.hpp::blend_exp).
 lcgs_status lcgs_debug_blend_exp(lcgs_context* ctx, const float* d_x, float* d_out, int64_t n)
 {
     LCGS_REQUIRE(ctx && (n == 0 || (d_x && d_out)) && n >= 0, "null pointer / negative count");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     launch_blend_exp(d_x, d_out, n, ctx->stream);
     LCGS_HIP_CHECK(hipGetLastError());

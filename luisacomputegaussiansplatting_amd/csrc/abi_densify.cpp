@@ -18,6 +18,7 @@ lcgs_status lcgs_densify_accumulate(lcgs_context* ctx, int num_gaussians, const 
 {
     LCGS_REQUIRE(ctx && stats, "NULL argument");
     LCGS_REQUIRE(stats->grad_accum && stats->denom && stats->max_radii, "NULL device pointer in the statistics");
+    LCGS_ENTRY(ctx);
     if (!ctx->frame_state_valid() || !ctx->last.has_state) {
         set_last_error("lcgs_densify_accumulate needs a preceding lcgs_render_forward(..., keep_state = 1) of this scene");
         return LCGS_ERR_STATE;
@@ -64,6 +65,7 @@ lcgs_status lcgs_densify(lcgs_context* ctx, int num_gaussians, int sh_degree, co
                  "NULL device pointer in the statistics");
     LCGS_REQUIRE(out_raw->pos != raw->pos && out_m->pos != m->pos && out_v->pos != v->pos && out_stats->denom != stats->denom,
                  "the rewrite is out of place: destinations must not alias sources");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t   st = ctx->stream;
     const int64_t P  = num_gaussians;
@@ -111,6 +113,7 @@ lcgs_status lcgs_opacity_reset(lcgs_context* ctx, int num_gaussians, float max_o
     LCGS_REQUIRE(ctx && raw && m && v && activated, "NULL argument");
     LCGS_REQUIRE(num_gaussians >= 0, "num_gaussians is negative");
     LCGS_REQUIRE(max_opacity > 0.0f && max_opacity < 1.0f, "max_opacity must be in (0,1)");
+    LCGS_ENTRY(ctx);
     scene_arrays_written(ctx, activated->pos, activated->scale, activated->rotq);
     if (num_gaussians == 0) return LCGS_OK;
     LCGS_REQUIRE(raw->opacity && m->opacity && v->opacity && activated->opacity, "NULL opacity pointer in a parameter pack");

@@ -85,10 +85,20 @@ lcgs_status ensure_fused_workspace(lcgs_context* ctx, const CamParams& cp, bool 
     return LCGS_OK;
 }
 
+// The head stream exists from the first frame that needs it -- a pipelined frame, or a batch: the SIBLING context of camera
+// and view batches runs on it, since the two uses never coincide (frames of a batch are not pipelined) and a process has few
+// hardware queues: with a stream each, the sibling's auxiliary stream came to share a queue with the caller's stream and the
+// camera batch lost 12 % (profiles/pipelined_frames_ab.txt).  Default priority (the highest was measured: inside the noise).
+lcgs_status ensure_head_stream(lcgs_context* ctx)
+{
+    if (!ctx->head_stream) LCGS_HIP_CHECK(hipStreamCreateWithFlags(&ctx->head_stream, hipStreamNonBlocking));
+    return LCGS_OK;
+}
+
 lcgs_status join_aux_stream(lcgs_context* ctx)
 {
     if (!ctx->aux_pending) return LCGS_OK;
-    LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_aux_done, 0));
+    LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->aux_done_last, 0));
     ctx->aux_pending = false;
     return LCGS_OK;
 }
@@ -122,6 +132,8 @@ lcgs_status render_sorted_frame(lcgs_context* ctx, const CamParams& cp, const fl
                                 const FrameParams* d_fp, const FrameTailOptions& opt)
 {
     const hipStream_t st       = ctx->stream;
+    const bool        piped    = opt.head != nullptr; // (context.hpp head_stream) only the renderer runs on st
+    const hipStream_t hs       = piped ? opt.head : st;
     uint32_t*         d_counts = ctx->counts.as<uint32_t>();
     const uint32_t    G        = cp.grid_x * cp.grid_y;
     const bool        deferred = opt.pipelined;
@@ -132,20 +144,31 @@ lcgs_status render_sorted_frame(lcgs_context* ctx, const CamParams& cp, const fl
     // the partition's first per-chunk digit counts in the sort workspace (the depth sort is done with it by then).
     const int tile_bits = std::max(1, ceil_log2_u32(list_grid_x(cp) * list_grid_y(cp)));
     const PairSortFirstPass first = pair_sort_first_pass(ctx->pair_capacity, hint_L, 0, tile_bits, ctx->sort_ws.ptr);
+    // the value buffers the pairs ping-pong between.  A pipelined frame takes the two of three that are NOT the last frame's
+    // final list: that frame's renderer may still be reading it, and wherever this frame's partition ends it ends elsewhere
+    int vb[2] = { 0, 1 };
+    if (piped) {
+        const int keep = ctx->last.list_buf;
+        vb[0] = keep == 0 ? 1 : 0;
+        vb[1] = keep == 2 ? 1 : 2;
+    }
     const bool counted =
         launch_expand(ctx->P, rows, hint_L, d_counts, list_grid_x(cp), order, ctx->rects.as<uint2>(), ctx->rects_sorted.as<uint2>(),
-                      ctx->pairk[0].as<uint32_t>(), ctx->pairv[0].as<uint32_t>(), ctx->pair_capacity,
-                      ctx->expand_ws.as<uint32_t>(), st, &first, id_mask);
+                      ctx->pairk[0].as<uint32_t>(), ctx->pairv[vb[0]].as<uint32_t>(), ctx->pair_capacity,
+                      ctx->expand_ws.as<uint32_t>(), hs, &first, id_mask);
     if (opt.marks) LCGS_TRY(mark(ctx, "expand"));
 
     const int where2 = launch_pair_sort_u32(ctx->pairk[0].as<uint32_t>(), ctx->pairk[1].as<uint32_t>(),
-                                            ctx->pairv[0].as<uint32_t>(), ctx->pairv[1].as<uint32_t>(), d_counts + 2,
-                                            ctx->pair_capacity, hint_L, 0, tile_bits, ctx->sort_ws.ptr, st,
+                                            ctx->pairv[vb[0]].as<uint32_t>(), ctx->pairv[vb[1]].as<uint32_t>(), d_counts + 2,
+                                            ctx->pair_capacity, hint_L, 0, tile_bits, ctx->sort_ws.ptr, hs,
                                             /*first_hist_done=*/counted);
+    const int list_buf = vb[where2];
     if (opt.marks) LCGS_TRY(mark(ctx, "tile_sort"));
 
+    // (a pipelined frame's renderer reads its two counter words from the frame's zeroed block, behind the tile counters)
+    uint32_t* const frame_words = piped ? ctx->work_counters + 2 : nullptr;
     launch_get_ranges_u32(hint_L, ctx->pair_capacity, d_counts, ctx->pairk[where2].as<uint32_t>(), ctx->ranges,
-                          nullptr, st, deferred ? ctx->ev_ranges : nullptr);
+                          nullptr, hs, deferred ? ctx->ev_ranges : nullptr, frame_words);
     // tile schedule: the newest complete order if it matches this grid, else computed here
     uint32_t* order_now = nullptr;
     if (deferred && ctx->order_G == G) {
@@ -153,11 +176,13 @@ lcgs_status render_sorted_frame(lcgs_context* ctx, const CamParams& cp, const fl
     } else {
         const int ob = deferred ? (ctx->order_cur ^ 1) : 0;
         order_now    = ctx->tile_order[ob].as<uint32_t>();
-        launch_tile_order(ctx->ranges, G, order_now, st, cp.grid_x, cp.list_shift);
+        launch_tile_order(ctx->ranges, G, order_now, hs, cp.grid_x, cp.list_shift);
         if (deferred) {
             ctx->order_cur = ob;
             ctx->order_G   = G;
         }
+        // (the head now ends here, not with the ranges dispatch that carried the event)
+        if (piped) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_ranges, hs));
     }
     if (opt.marks) LCGS_TRY(mark(ctx, "ranges"));
     if (deferred) {
@@ -165,30 +190,43 @@ lcgs_status render_sorted_frame(lcgs_context* ctx, const CamParams& cp, const fl
         // frame's schedule, and the next frame's zeroed copy
         const int ob = ctx->order_cur ^ 1, znext = (zb + 2) % 3; // the copy of the frame after the next
         LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_ranges, 0)); // (carried by the ranges dispatch)
+        // pipelined: the schedule and the zeroed block recycled here are the PREVIOUS frame's, whose renderer may still run
+        if (piped) LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_pipe_render[opt.parity ^ 1], 0));
         launch_tile_order(ctx->ranges, G, ctx->tile_order[ob].as<uint32_t>(), ctx->aux_stream, cp.grid_x, cp.list_shift);
         LCGS_HIP_CHECK(hipMemsetAsync(ctx->zero_ws[znext].ptr, 0, ctx->zero_bytes, ctx->aux_stream));
-        LCGS_HIP_CHECK(hipEventRecord(ctx->ev_aux_done, ctx->aux_stream));
+        ctx->aux_done_last = piped ? ctx->ev_pipe_aux[opt.parity] : ctx->ev_aux_done;
+        LCGS_HIP_CHECK(hipEventRecord(ctx->aux_done_last, ctx->aux_stream));
         ctx->aux_pending       = true;
         ctx->zero_ready[znext] = true;
         ctx->zero_cur          = (zb + 1) % 3;
         ctx->order_cur         = ob; // written before the next frame's record builder runs: its renderer waits for that
     }
 
+    if (piped) LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_ranges, 0)); // the head; behind it st is ordered after the whole frame
     if (opt.records_ready) LCGS_HIP_CHECK(hipStreamWaitEvent(st, opt.records_ready, 0));
-    launch_render_forward_rec(cp, bg, ctx->ranges, ctx->pairv[where2].as<uint32_t>(), recs, d_img,
+    launch_render_forward_rec(cp, bg, ctx->ranges, ctx->pairv[list_buf].as<uint32_t>(), recs, d_img,
                               keep_state ? ctx->final_T.as<float>() : nullptr,
-                              keep_state ? ctx->n_contrib.as<uint32_t>() : nullptr, d_counts, d_fp, order_now, st,
-                              keep_state ? ctx->strip_masks.as<uint8_t>() : nullptr, deferred ? ctx->ev_render : nullptr,
+                              keep_state ? ctx->n_contrib.as<uint32_t>() : nullptr, piped ? frame_words : d_counts, d_fp, order_now, st,
+                              keep_state ? ctx->strip_masks.as<uint8_t>() : nullptr,
+                              piped ? ctx->ev_pipe_render[opt.parity] : (deferred ? ctx->ev_render : nullptr),
                               opt.work_counter ? ctx->work_counters : nullptr, opt.persist_wgs,
                               opt.g2d_in_render ? ctx->grads2d.as<float>() : nullptr,
                               opt.g2d_in_render ? ctx->bwd_counter.as<uint32_t>() : nullptr);
     ctx->g2d_zeroed      = opt.g2d_in_render; // (consumed by the first backward of this frame; same stream: no event)
     ctx->last_tile_order = order_now;
-    ctx->last.list_buf   = where2;
+    ctx->last.list_buf   = list_buf;
     if (opt.marks) LCGS_TRY(mark(ctx, "render"));
     if (opt.pair_verdict) launch_owner_pair_verdict(d_counts, opt.pair_verdict, st);
 
-    if (deferred) {
+    if (piped) {
+        // the frame's OWN counts: copied behind its head, in front of the next head, which rewrites the block
+        LCGS_HIP_CHECK(hipMemcpyAsync(ctx->h_counts, d_counts, 40, hipMemcpyDeviceToHost, hs));
+        LCGS_HIP_CHECK(hipEventRecord(ctx->ev_counts, hs));
+        // ... and the caller's stream behind the copy, BEHIND the renderer just launched (which does not wait for it): whatever
+        // follows on that stream -- a single-stream frame, an owner frame, a stage operator -- rewrites the block and h_counts
+        LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_counts, 0));
+        ctx->counts_pending = true;
+    } else if (deferred) {
         // the counter read-back leaves through the auxiliary stream: the next frame does not queue behind it
         LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_render, 0)); // (carried by the render dispatch)
         LCGS_HIP_CHECK(hipMemcpyAsync(ctx->h_counts, d_counts, 40, hipMemcpyDeviceToHost, ctx->aux_stream));
@@ -237,14 +275,21 @@ namespace
 // render_sorted_frame
 // d_fp: when non-NULL, camera / bg / scale_modifier are read from device memory by the kernels (graph replay)
 // in_capture: the frame is being recorded into a hipGraph (fixed pointers): no per-frame buffer alternation
+// pipe: a pipelined in-order frame (context.hpp head_stream) -- everything in front of the renderer runs on the head stream;
+// Chained: behind another such frame with nothing in between, so the head starts beside that frame's renderer; Unchained: the
+// head first waits for the caller's stream, which is the single-stream order
+enum class Pipe { Off, Unchained, Chained };
 lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float bg[3], float scale_modifier,
                             float* d_img, int32_t* d_radii, bool keep_state, const FrameParams* d_fp,
-                            bool in_capture = false)
+                            bool in_capture = false, Pipe pipe = Pipe::Off)
 {
     const hipStream_t st = ctx->stream; // the stream whose order the caller sees
+    const bool        piped = pipe != Pipe::Off;
+    const hipStream_t hs = piped ? ctx->head_stream : st; // the stream of the cull pass and the sort chain
+    const int         par = (int)(ctx->pipe_frames & 1u);
     uint32_t*    d_counts = ctx->counts.as<uint32_t>();
     const int    P        = ctx->P;
-    SplatRecord* recs     = ctx->recs.as<SplatRecord>();
+    SplatRecord* recs     = (piped && par) ? ctx->recs_b.as<SplatRecord>() : ctx->recs.as<SplatRecord>();
     ctx->n_marks          = 0;
     LCGS_TRY(mark(ctx, "begin"));
 
@@ -261,10 +306,26 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
         LCGS_TRY(join_aux_stream(ctx));
         for (bool& r : ctx->zero_ready) r = false;
     }
-    LCGS_TRY(use_zero_block(ctx, zb, deferred && ctx->zero_ready[zb], st));
+    if (piped) {
+        if (pipe == Pipe::Unchained) {
+            LCGS_HIP_CHECK(hipEventRecord(ctx->ev_pipe_entry, st));
+            LCGS_HIP_CHECK(hipStreamWaitEvent(hs, ctx->ev_pipe_entry, 0));
+            // (... and for the auxiliary job of whatever frame came last: the frames that chain behind this one inherit both)
+            if (ctx->aux_pending) LCGS_HIP_CHECK(hipStreamWaitEvent(hs, ctx->aux_done_last, 0));
+        }
+        // this parity's buffers: the renderer of the frame before the last has finished with them (records, pair list,
+        // zeroed block), and the auxiliary job of that frame has cleared the block this head is about to fill
+        LCGS_HIP_CHECK(hipStreamWaitEvent(hs, ctx->ev_pipe_render[par], 0));
+        LCGS_HIP_CHECK(hipStreamWaitEvent(hs, ctx->ev_pipe_aux[par], 0));
+        // ... and the PREVIOUS frame's record builder has finished (ev_join names its latest record, that builder's): on the
+        // auxiliary stream it reads vis_index and d_counts[0], both single, which this head's depth sort rewrites.  In single-
+        // stream order the renderer that waited for the builder stood in between; a chained head has no renderer in front of it
+        LCGS_HIP_CHECK(hipStreamWaitEvent(hs, ctx->ev_join, 0));
+    }
+    LCGS_TRY(use_zero_block(ctx, zb, deferred && ctx->zero_ready[zb], hs));
     const DepthSortFirstPass dfirst = depth_sort_first_pass(P, ctx->sort_ws.ptr);
     launch_cull_compact(P, cp, scale_modifier, d_fp, ctx->pos, ctx->scale, ctx->rotq, ctx->opacity, d_radii,
-                        ctx->cull_slab.as<uint4>(), ctx->chunk_info.as<uint2>(), dfirst, st, ctx->cull_rows());
+                        ctx->cull_slab.as<uint4>(), ctx->chunk_info.as<uint2>(), dfirst, hs, ctx->cull_rows());
     LCGS_TRY(mark(ctx, "cull_compact"));
     const int64_t hint_V = ctx->hint_V > 0 ? ctx->hint_V : P;
     // (per-tile and per-block frames of one context keep a launch-size hint each: their pair counts differ by up to 3 x, and a
@@ -280,7 +341,7 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
     launch_depth_sort_from_chunks(P, hint_V, ctx->cull_slab.as<uint4>(), ctx->chunk_info.as<uint2>(),
                                   ctx->chunk_base.as<uint32_t>(), ctx->sortk[0].as<uint32_t>(), ctx->sortk[1].as<uint32_t>(),
                                   ctx->sortv[0].as<uint32_t>(), ctx->sortv[1].as<uint32_t>(), ctx->vis_index.as<uint32_t>(),
-                                  ctx->rects.as<uint2>(), d_counts, ctx->sort_ws.ptr, st,
+                                  ctx->rects.as<uint2>(), d_counts, ctx->sort_ws.ptr, hs,
                                   (overlap && !in_capture) ? ctx->ev_fork : nullptr, ft.on ? &ft.tie : nullptr);
     LCGS_TRY(mark(ctx, "depth_sort"));
     // Record building (SH fetch + colour: bandwidth-bound) is independent of the rest of the sort chain (latency-bound
@@ -307,14 +368,57 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
     // several frames in flight: a bounded, persistent grid (context.hpp) -- same image, free wave slots on every CU
     const int k_persist = ctx->persist_forced >= 0 ? ctx->persist_forced : (ctx->frames_in_flight ? ctx->persist_in_flight : 0);
     opt.persist_wgs     = (deferred && k_persist > 0) ? (uint32_t)(k_persist * std::max(ctx->num_cus, 1)) : 0u;
+    // a frame that chains expects the next head beside its renderer: the bounded grid leaves that head's short kernels wave
+    // slots on every CU (context.hpp pipe_render_wgs; one workgroup per tile starves the cull pass until the renderer drains)
+    // Only while the GPU is BEHIND the host: the previous frame's renderer has not finished when this frame is enqueued, so
+    // the next head will find this renderer running.  A viewer paced below the GPU's speed chains on the host but nothing
+    // overlaps on the GPU; alone, the bounded grid is the slower renderer (REJECTED.md), and such a frame keeps the full one.
+    if (pipe == Pipe::Chained) {
+        ctx->pipe_chained++;
+        const bool behind = hipEventQuery(ctx->ev_pipe_render[par ^ 1]) == hipErrorNotReady;
+        (void)hipGetLastError();
+        if (behind && ctx->persist_forced < 0) {
+            opt.persist_wgs = (uint32_t)(ctx->pipe_render_wgs * std::max(ctx->num_cus, 1));
+            ctx->pipe_bounded++;
+        }
+    }
     // keep_state frames: the 2-D gradient rows the backward adds to are cleared by the RENDERER as a side job (render.hip):
     // no launch on the auxiliary stream, no cross-stream wait in front of the render-backward
     opt.g2d_in_render = deferred && keep_state;
     opt.records_ready = overlap ? ctx->ev_join : nullptr;
+    opt.head          = piped ? hs : nullptr;
+    opt.parity        = par;
     LCGS_TRY(render_sorted_frame(ctx, cp, bg, d_img, recs, ctx->sortv[0].as<uint32_t>(), ft.id_mask, hint_V, hint_L, keep_state, d_fp,
                                  opt));
     keep_frame_state(ctx, cp, bg, scale_modifier, keep_state);
+    if (piped) ctx->pipe_frames++;
     return LCGS_OK;
+}
+
+// May this frame run its head on the head stream?  Forward-only and enqueue-only, no stage timing, no graph
+// replay, no capture on the caller's stream, no batch in flight (batches keep their sibling scheme).  It chains -- the head does
+// not wait for the caller's stream -- when the call before it on this context was such a frame of the same resolution and the
+// scene is the context's own with its derived rows intact: then nothing but the library writes it, and every writer of the
+// library is an entry point that breaks the chain (a caller who writes it through lcgs_scene_pointers owes
+// lcgs_scene_modified, an entry point too).
+Pipe pipeline_mode(lcgs_context* ctx, const CamParams& cp, const int32_t* d_radii, bool keep_state, const int* num_rendered)
+{
+    if (!ctx->pipeline || keep_state || d_radii || num_rendered || ctx->profiling || ctx->use_graph ||
+        ctx->frames_in_flight)
+        return Pipe::Off;
+    if (ctx->stream != nullptr) { // (the legacy stream cannot be captured)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+            (void)hipGetLastError();
+            return Pipe::Off;
+        }
+    }
+    const bool owned = ctx->P > 0 && ctx->pos == ctx->owned[0].ptr && ctx->scale == ctx->owned[1].ptr && ctx->rotq == ctx->owned[2].ptr &&
+                       ctx->sh == ctx->owned[3].ptr && ctx->opacity == ctx->owned[4].ptr && ctx->cull_rows() != nullptr;
+    const bool same = ctx->last.valid && ctx->last.cp.width == cp.width && ctx->last.cp.height == cp.height &&
+                      ctx->last.cp.list_shift == cp.list_shift;
+    if (!owned) return Pipe::Off; // (such a frame could never chain)
+    return (same && ctx->op_seq == ctx->pipe_left_seq + 1) ? Pipe::Chained : Pipe::Unchained;
 }
 } // namespace
 
@@ -325,6 +429,7 @@ lcgs_status lcgs_render_forward(lcgs_context* ctx, const lcgs_camera* camera, co
                                 int* num_rendered)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
     ctx->note_foreign_writes();
     LCGS_TRY(check_camera(camera));
@@ -383,7 +488,15 @@ lcgs_status lcgs_render_forward(lcgs_context* ctx, const lcgs_camera* camera, co
             // (a replay records no more than this: not list_buf, last_tile_order or last_has_jac -- docs/DESIGN_LONG.md)
             keep_frame_state(ctx, cp, bg_color, scale_modifier, keep_state != 0);
         } else {
-            LCGS_TRY(enqueue_forward(ctx, cp, bg_color, scale_modifier, d_img, d_radii, keep_state != 0, nullptr));
+            const Pipe pipe = pipeline_mode(ctx, cp, d_radii, keep_state != 0, num_rendered);
+            if (pipe != Pipe::Off) { // the head stream, the second record buffer and the third pair-value buffer (context.hpp)
+                LCGS_TRY(ensure_head_stream(ctx));
+                LCGS_TRY(ctx->recs_b.ensure((size_t)ctx->P * sizeof(SplatRecord)));
+                LCGS_TRY(ctx->pairv[2].ensure((size_t)ctx->pair_capacity * 4));
+            }
+            LCGS_TRY(enqueue_forward(ctx, cp, bg_color, scale_modifier, d_img, d_radii, keep_state != 0, nullptr,
+                                     /*in_capture=*/false, pipe));
+            if (pipe != Pipe::Off) ctx->pipe_left_seq = ctx->op_seq;
         }
         if (!num_rendered && !ctx->profiling) return LCGS_OK; // fully asynchronous frame
         LCGS_TRY(sync_frame(ctx));
@@ -451,6 +564,7 @@ lcgs_status lcgs_render_forward_batch(lcgs_context* ctx, int num_views, const lc
     LCGS_REQUIRE(num_views >= 0, "num_views is negative");
     if (num_views == 0) return LCGS_OK;
     LCGS_REQUIRE(cameras != nullptr && d_imgs != nullptr && bg_color != nullptr, "NULL argument");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     ctx->note_foreign_writes();
     const bool two = num_views > 1 && !ctx->profiling && !ctx->use_graph && ctx->P > 0;
@@ -463,7 +577,7 @@ lcgs_status lcgs_render_forward_batch(lcgs_context* ctx, int num_views, const lc
                                      nullptr));
     }
     if (two) { // the caller's stream waits for the sibling's frames
-        LCGS_HIP_CHECK(hipEventRecord(ctx->ev_batch_join, ctx->twin_stream));
+        LCGS_HIP_CHECK(hipEventRecord(ctx->ev_batch_join, ctx->head_stream));
         LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_batch_join, 0));
     }
     return LCGS_OK;
@@ -480,10 +594,10 @@ namespace abi
 lcgs_status prepare_twin(lcgs_context* ctx)
 {
     if (!ctx->twin) {
-        LCGS_HIP_CHECK(hipStreamCreateWithFlags(&ctx->twin_stream, hipStreamNonBlocking));
+        LCGS_TRY(ensure_head_stream(ctx));
         LCGS_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_batch_fork, hipEventDisableTiming));
         LCGS_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_batch_join, hipEventDisableTiming));
-        LCGS_TRY(lcgs_create(ctx->device, ctx->twin_stream, &ctx->twin));
+        LCGS_TRY(lcgs_create(ctx->device, ctx->head_stream, &ctx->twin));
     }
     {
         lcgs_context* t = ctx->twin;
@@ -519,7 +633,7 @@ lcgs_status prepare_twin(lcgs_context* ctx)
         t->hint_Lb       = std::max(t->hint_Lb, ctx->hint_Lb);
         t->pair_capacity = std::max(t->pair_capacity, ctx->pair_capacity);
         LCGS_HIP_CHECK(hipEventRecord(ctx->ev_batch_fork, ctx->stream));
-        LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->twin_stream, ctx->ev_batch_fork, 0));
+        LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->head_stream, ctx->ev_batch_fork, 0));
     }
     return LCGS_OK;
 }

@@ -57,6 +57,7 @@ lcgs_status lcgs_knn_mean_dist2(lcgs_context* ctx, int64_t num_points, const flo
     LCGS_REQUIRE(num_points <= (int64_t)INT32_MAX, "num_points exceeds 2^31 - 1 (the original index travels in 32 bits)");
     if (num_points == 0) return LCGS_OK;
     LCGS_REQUIRE(d_pos && d_dist2, "NULL device pointer");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     LCGS_TRY(enqueue_knn(ctx, num_points, d_pos, d_dist2));
     if (ctx->profiling) LCGS_TRY(collect_marks(ctx));
@@ -77,6 +78,7 @@ lcgs_status lcgs_scene_init_from_points(lcgs_context* ctx, int num_points, int s
         LCGS_REQUIRE(p->pos && p->scale && p->rotq && p->sh && p->opacity, "NULL device pointer in a parameter pack");
         LCGS_REQUIRE((reinterpret_cast<uintptr_t>(p->rotq) & 15) == 0, "rotq arrays must be 16-byte aligned");
     }
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     const int64_t n = num_points;
     LCGS_TRY(ctx->knn_dist2.ensure((size_t)n * 4));

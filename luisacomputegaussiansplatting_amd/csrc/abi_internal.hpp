@@ -119,6 +119,7 @@ void registry_publish(lcgs_context* ctx);
 lcgs_status ensure_fused_workspace(lcgs_context* ctx, const CamParams& cp, bool keep_state);
 // a pipelined frame of the context may still be using the workspace through the auxiliary stream: ctx->stream waits for it
 lcgs_status join_aux_stream(lcgs_context* ctx);
+lcgs_status ensure_head_stream(lcgs_context* ctx); // created on first use; also the stream of the batch sibling
 // a frame's zeroed block (tile ranges + the persistent renderers' counters) is copy `zb`; cleared on `st` unless it already is
 lcgs_status use_zero_block(lcgs_context* ctx, int zb, bool cleared, hipStream_t st);
 // what the depth sort of a re-ordered scene needs to blend equal depths in FILE order (kernels/tie_order.hpp), and the bits
@@ -139,6 +140,10 @@ struct FrameTailOptions {
     bool       g2d_in_render = false;   // the renderer clears the 2-D gradient rows as a side job
     hipEvent_t records_ready = nullptr; // waited for in front of the renderer
     uint32_t*  pair_verdict  = nullptr; // device word, |= 2 in front of the counter copy if the pair buffers were too small
+    // a pipelined in-order frame (context.hpp head_stream): expand -> ranges and the counter copy run on this stream, only the
+    // renderer on the context's; the frame's parity selects the events later calls wait for
+    hipStream_t head   = nullptr;
+    int         parity = 0;
 };
 // rows: the expansion's launch size (hint_V, or a known row count).  Leaves last.list_buf / last_tile_order for the backward.
 lcgs_status render_sorted_frame(lcgs_context* ctx, const CamParams& cp, const float bg[3], float* d_img, const SplatRecord* recs,

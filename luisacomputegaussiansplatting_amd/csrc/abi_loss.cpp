@@ -29,6 +29,7 @@ lcgs_status lcgs_photometric_loss_backward(lcgs_context* ctx, int width, int hei
     const size_t n = (size_t)width * height * 3;
     LCGS_REQUIRE(!d_dL_dimg || (!overlaps(d_dL_dimg, d_img_chw, n) && !overlaps(d_dL_dimg, d_target_chw, n)),
                  "d_dL_dimg must not alias the image or the target");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     // workspace: one pair of doubles per workgroup, then (gradient calls with an SSIM term) the planes a, b, c
     const size_t pair_bytes = (size_t)photometric_workgroups(width, height) * 2 * sizeof(double);
@@ -48,6 +49,7 @@ lcgs_status lcgs_set_fit_loss(lcgs_context* ctx, int kind, float lambda_dssim)
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
     LCGS_REQUIRE(kind == LCGS_LOSS_L2 || kind == LCGS_LOSS_PHOTOMETRIC, "unknown loss kind");
     LCGS_REQUIRE(isfinite(lambda_dssim) && lambda_dssim >= 0.0f && lambda_dssim <= 1.0f, "lambda_dssim must be in [0,1]");
+    LCGS_ENTRY(ctx);
     ctx->fit_loss   = kind;
     ctx->fit_lambda = lambda_dssim;
     return LCGS_OK;

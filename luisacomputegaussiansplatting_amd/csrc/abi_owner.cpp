@@ -76,6 +76,7 @@ lcgs_status lcgs_owner_project(lcgs_context* ctx, int slot, const lcgs_camera* c
     LCGS_REQUIRE(row_count == 0 || (d_rows && d_records), "NULL output buffer");
     LCGS_REQUIRE((reinterpret_cast<uintptr_t>(d_records) & 15) == 0, "records must be 16-byte aligned");
     LCGS_REQUIRE(slot >= 0 && slot < LCGS_MAX_OWNER_VIEWS, "slot out of range");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     LCGS_TRY(check_camera(camera));
     if (num_rows) *num_rows = 0;
@@ -104,6 +105,7 @@ lcgs_status lcgs_owner_project_views(lcgs_context* ctx, int first_slot, int num_
 {
     LCGS_REQUIRE(ctx && cameras && d_rows && d_records, "NULL argument");
     LCGS_REQUIRE(first_slot >= 0 && num_views >= 1 && first_slot + num_views <= LCGS_MAX_OWNER_VIEWS, "slots out of range");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     LCGS_REQUIRE(ctx->pos != nullptr && ctx->P > 0, "no scene bound");
     LCGS_REQUIRE(row_first >= 0 && row_count >= 0 && (int64_t)row_first + row_count <= ctx->P, "row range outside the scene");
@@ -173,6 +175,7 @@ lcgs_status lcgs_owner_counts(lcgs_context* ctx, int first_slot, int num_slots, 
 {
     LCGS_REQUIRE(ctx && num_rows, "NULL argument");
     LCGS_REQUIRE(first_slot >= 0 && num_slots >= 0 && first_slot + num_slots <= LCGS_MAX_OWNER_VIEWS, "slots out of range");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     if (!ctx->h_owner_counts)
         LCGS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_owner_counts), LCGS_MAX_OWNER_VIEWS * 4, hipHostMallocDefault));
@@ -197,6 +200,7 @@ lcgs_status lcgs_owner_counts(lcgs_context* ctx, int first_slot, int num_slots, 
 lcgs_status lcgs_owner_render(lcgs_context* ctx, const lcgs_camera* camera, const float bg_color[3], int num_rows,
                               const uint32_t* d_rows, const float* d_records, float* d_img, int keep_state)
 {
+    LCGS_ENTRY(ctx);
     return lcgs::abi::owner_render_frame(ctx, camera, bg_color, num_rows, d_rows, d_records, d_img, keep_state, nullptr);
 }
 
@@ -292,6 +296,7 @@ extern "C" {
 
 lcgs_status lcgs_owner_render_backward(lcgs_context* ctx, const float* d_dL_dimg, float* d_grads2d)
 {
+    LCGS_ENTRY(ctx);
     return lcgs::abi::owner_render_backward_into(ctx, d_dL_dimg, d_grads2d, nullptr);
 }
 
@@ -324,6 +329,7 @@ extern "C" {
 
 lcgs_status lcgs_owner_backward(lcgs_context* ctx, int slot, const float* d_grads2d, const lcgs_grads* grads, int accumulate)
 {
+    LCGS_ENTRY(ctx);
     return lcgs::abi::owner_backward_rows(ctx, slot, d_grads2d, grads, accumulate ? 1 : 0);
 }
 

@@ -190,6 +190,7 @@ lcgs_status lcgs_scene_bind(lcgs_context* ctx, int num_gaussians, int sh_degree,
     LCGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "sh_degree must be in [0,3]");
     if (num_gaussians > 0) LCGS_REQUIRE(d_pos && d_scale && d_rotq && d_sh && d_opacity, "NULL device pointer");
     LCGS_REQUIRE((reinterpret_cast<uintptr_t>(d_rotq) & 15) == 0, "rotq must be 16-byte aligned");
+    LCGS_ENTRY(ctx);
     ctx->P       = num_gaussians;
     ctx->sh_deg  = sh_degree;
     ctx->pos     = d_pos;
@@ -212,6 +213,7 @@ lcgs_status lcgs_scene_declare_static(lcgs_context* ctx, int num_gaussians, cons
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
     LCGS_REQUIRE(num_gaussians >= 0 && num_gaussians < (1 << 30), "num_gaussians out of range");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     if (num_gaussians == 0 || !d_pos) { // withdraw the declaration
         ctx->cull_bound = nullptr;
@@ -227,6 +229,7 @@ lcgs_status lcgs_scene_declare_static(lcgs_context* ctx, int num_gaussians, cons
 lcgs_status lcgs_scene_modified(lcgs_context* ctx)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     // whoever keeps rows derived from the bound arrays (this context, its siblings, another context on the same arrays)
     // drops them; this context builds its own again (context-owned arrays only, ordered on its stream behind the
@@ -243,6 +246,7 @@ lcgs_status lcgs_scene_modified(lcgs_context* ctx)
 lcgs_status lcgs_debug_verify_derived(lcgs_context* ctx, int64_t* stale_rows)
 {
     LCGS_REQUIRE(ctx && stale_rows, "NULL argument");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     *stale_rows = 0;
     const float4* rows = ctx->cull_rows();
@@ -262,6 +266,7 @@ lcgs_status lcgs_set_lod(lcgs_context* ctx, int min_radius_px)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
     LCGS_REQUIRE(min_radius_px >= 0 && min_radius_px <= 4096, "min_radius_px out of range");
+    LCGS_ENTRY(ctx);
     ctx->lod_min_radius = min_radius_px;
     if (ctx->twin) ctx->twin->lod_min_radius = min_radius_px;
     return LCGS_OK;
@@ -271,6 +276,7 @@ lcgs_status lcgs_set_ingest_order(lcgs_context* ctx, int order)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
     LCGS_REQUIRE(order == LCGS_ORDER_FILE || order == LCGS_ORDER_SPATIAL, "order must be LCGS_ORDER_FILE or LCGS_ORDER_SPATIAL");
+    LCGS_ENTRY(ctx);
     ctx->ingest_order = order;
     return LCGS_OK;
 }
@@ -278,6 +284,7 @@ lcgs_status lcgs_set_ingest_order(lcgs_context* ctx, int order)
 lcgs_status lcgs_scene_permutation(lcgs_context* ctx, const uint32_t** d_perm)
 {
     LCGS_REQUIRE(ctx && d_perm, "NULL argument");
+    LCGS_ENTRY(ctx);
     *d_perm = ctx->perm_valid ? ctx->scene_perm.as<uint32_t>() : nullptr;
     return LCGS_OK;
 }
@@ -286,6 +293,7 @@ lcgs_status lcgs_scene_upload(lcgs_context* ctx, int num_gaussians, int sh_degre
                               const float* h_scale, const float* h_rotq, const float* h_sh, const float* h_opacity)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
     LCGS_REQUIRE(num_gaussians >= 0 && num_gaussians < (1 << 30), "num_gaussians out of range");
     LCGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "sh_degree must be in [0,3]");
@@ -310,6 +318,7 @@ lcgs_status lcgs_scene_upload(lcgs_context* ctx, int num_gaussians, int sh_degre
 lcgs_status lcgs_scene_reorder_spatial(lcgs_context* ctx, uint32_t* d_perm)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     if (ctx->P == 0) return LCGS_OK;
     LCGS_REQUIRE(ctx->pos != nullptr, "no scene bound (call lcgs_scene_bind / lcgs_scene_upload / lcgs_scene_load_ply first)");
@@ -418,6 +427,7 @@ lcgs_status lcgs_scene_pointers(lcgs_context* ctx, int* num_gaussians, int* sh_d
                                 const float** d_scale, const float** d_rotq, const float** d_sh, const float** d_opacity)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     if (num_gaussians) *num_gaussians = ctx->P;
     if (sh_degree) *sh_degree = ctx->sh_deg;
     if (d_pos) *d_pos = ctx->pos;
@@ -431,6 +441,7 @@ lcgs_status lcgs_scene_pointers(lcgs_context* ctx, int* num_gaussians, int* sh_d
 lcgs_status lcgs_scene_use_half_sh(lcgs_context* ctx, int enable)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     if (!enable) {
         ctx->use_half_sh = false;
@@ -451,6 +462,7 @@ lcgs_status lcgs_scene_download(lcgs_context* ctx, float* h_pos, float* h_scale,
                                 float* h_opacity)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
     const size_t P    = (size_t)ctx->P;
     const RowFloats rowf  = row_floats(ctx->sh_deg);
@@ -471,6 +483,7 @@ lcgs_status lcgs_scene_load_ply(lcgs_context* ctx, const char* path, int* num_ga
 {
     LCGS_REQUIRE(ctx != nullptr && path != nullptr, "NULL argument");
     if (num_gaussians) *num_gaussians = 0;
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     PlyProbe probe;
     LCGS_TRY(ply_probe(path, &probe));

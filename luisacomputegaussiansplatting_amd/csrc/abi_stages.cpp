@@ -54,6 +54,7 @@ lcgs_status lcgs_sh_process(lcgs_context* ctx, int num_points, const float* d_po
                             const float* d_sh, float* d_color, int level, int channel)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
     LCGS_REQUIRE(num_points >= 0, "num_points < 0");
     LCGS_REQUIRE(camera != nullptr, "camera is NULL");
@@ -81,6 +82,7 @@ lcgs_status lcgs_project_forward(lcgs_context* ctx, int num_gaussians, const flo
                                  float* d_depth, const lcgs_camera* camera, int use_focal)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
     LCGS_REQUIRE(num_gaussians >= 0, "num_gaussians < 0");
     LCGS_TRY(check_camera(camera));
@@ -107,6 +109,7 @@ lcgs_status lcgs_set_stage_mode(lcgs_context* ctx, int mode)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
     LCGS_REQUIRE(mode == LCGS_STAGES_EXACT || mode == LCGS_STAGES_DEFERRED, "unknown stage mode");
+    LCGS_ENTRY(ctx);
     LCGS_TRY(lcgs_stage_flush(ctx));
     ctx->stage_mode = mode;
     return LCGS_OK;
@@ -115,6 +118,7 @@ lcgs_status lcgs_set_stage_mode(lcgs_context* ctx, int mode)
 lcgs_status lcgs_stage_flush(lcgs_context* ctx)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     if (!ctx->def_sh.pending && !ctx->def_proj.pending) return LCGS_OK;
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     LCGS_TRY(run_deferred_sh(ctx));
@@ -124,6 +128,7 @@ lcgs_status lcgs_stage_flush(lcgs_context* ctx)
 lcgs_status lcgs_inclusive_sum_u32(lcgs_context* ctx, const uint32_t* d_in, uint32_t* d_out, int64_t n)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
     LCGS_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "n out of range");
     if (n == 0) return LCGS_OK;
@@ -139,6 +144,7 @@ lcgs_status lcgs_sort_pairs_u64_u32(lcgs_context* ctx, const uint64_t* d_keys_in
                                     int end_bit)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
     LCGS_REQUIRE(n >= 0 && n < ((int64_t)1 << 30), "n out of range");
     LCGS_REQUIRE(begin_bit >= 0 && end_bit <= 64 && begin_bit <= end_bit, "bad bit range");
@@ -161,6 +167,7 @@ lcgs_status lcgs_tile_splat_forward(lcgs_context* ctx, const lcgs_tile_accel* ac
                                     const lcgs_tile_output* output, int use_focal, int* num_rendered)
 {
     LCGS_REQUIRE(ctx && accel && input && output, "NULL argument");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
     if (num_rendered) *num_rendered = 0;
     const int P = input->num_gaussians;

@@ -31,6 +31,7 @@ lcgs_status lcgs_adam_step(lcgs_context* ctx, int num_gaussians, int sh_degree, 
     LCGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "sh_degree must be in [0,3]");
     LCGS_TRY(check_adam_config(cfg));
     // (before the empty-range return: a rank whose shard is empty still belongs to a step that rewrites the arrays)
+    LCGS_ENTRY(ctx);
     scene_arrays_written(ctx, activated->pos, activated->scale, activated->rotq); // (a context-owned scene trained in place)
     if (num_gaussians == 0) return LCGS_OK;
     const lcgs_params* packs[4] = { raw, m, v, activated };
@@ -64,6 +65,7 @@ lcgs_status lcgs_fit_views(lcgs_context* ctx, int num_views, const lcgs_camera* 
     LCGS_REQUIRE(num_views >= 0, "num_views is negative");
     if (num_views == 0) return LCGS_OK;
     LCGS_REQUIRE(cameras && d_targets && grads && d_losses && bg_color, "NULL argument");
+    LCGS_ENTRY(ctx);
     LCGS_REQUIRE(ctx->P > 0 && ctx->pos != nullptr, "no scene bound");
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     const bool two = num_views > 1 && !ctx->profiling && !ctx->use_graph;
@@ -94,7 +96,7 @@ lcgs_status lcgs_fit_views(lcgs_context* ctx, int num_views, const lcgs_camera* 
         prev = c;
     }
     if (two) { // (the last view ran on ctx; the one before it on the sibling, and ctx's backward already waited for it)
-        LCGS_HIP_CHECK(hipEventRecord(ctx->ev_batch_join, ctx->twin_stream));
+        LCGS_HIP_CHECK(hipEventRecord(ctx->ev_batch_join, ctx->head_stream));
         LCGS_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_batch_join, 0));
     }
     return LCGS_OK;

@@ -47,6 +47,15 @@ CamParams make_cam_params(const lcgs_camera& cam);
 // stream of an (opaque) context, for translation units that only see the forward declaration
 hipStream_t context_stream(lcgs_context* ctx);
 int         context_device(lcgs_context* ctx);
+void        context_count_call(lcgs_context* ctx);
+// Every C ABI entry point that takes a context says LCGS_ENTRY(ctx) in front of its first use of the context (behind the
+// argument checks that refuse a call before the context is read): the per-context operation count by which a pipelined
+// forward frame knows that nothing else was asked of the context since the frame before it (context.hpp op_seq).  An entry
+// point without it could race with a chained frame's head; tests/test_abi_entry_count.py reads the sources for it.
+#define LCGS_ENTRY(ctx)                                \
+    do {                                               \
+        if (ctx) lcgs::context_count_call(ctx);        \
+    } while (0)
 
 // what the device ingest path needs to know about a PLY file (host/ply.cpp)
 struct PlyProbe {

@@ -91,7 +91,7 @@ struct lcgs_context {
 
     // workspace of the fused frame
     DeviceBuffer cull_slab, chunk_info, chunk_base; // the cull pass's per-chunk output (fused_forward.hip k_cull_compact)
-    DeviceBuffer recs, sortk[2], sortv[2], vis_index, rects, rects_sorted, pairk[2], pairv[2], zero_ws[3], counts, sort_ws,
+    DeviceBuffer recs, sortk[2], sortv[2], vis_index, rects, rects_sorted, pairk[2], pairv[3], zero_ws[3], counts, sort_ws,
         expand_ws, final_T, n_contrib, list_idx, grads2d, strip_masks, shjac, tie_ws, fused_grads, bwd_counter;
     bool         last_has_jac = false; // the last keep_state frame stored the colour Jacobian (degree 3)
     // zero_ws holds what a frame needs zeroed: the tile ranges.  Three
@@ -144,6 +144,29 @@ struct lcgs_context {
     hipEvent_t  ev_fork = nullptr, ev_join = nullptr, ev_ranges = nullptr, ev_aux_done = nullptr, ev_render = nullptr,
                 ev_counts = nullptr;
     bool        aux_pending = false, counts_pending = false;
+    hipEvent_t  aux_done_last = nullptr; // whichever of ev_aux_done / ev_pipe_aux[] the auxiliary stream recorded last
+    // Pipelined in-order frames (abi_frame.cpp enqueue_forward): forward-only, enqueue-only frames run their head
+    // -- cull, depth sort, expand, tile partition, ranges -- on head_stream, beside the PREVIOUS frame's renderer; the renderers
+    // stay on the caller's stream in call order.  What renderer k reads survives head k + 1: the records alternate between
+    // recs and recs_b, the final pair list is the one of pairv[0..2] the next head leaves alone, the renderer's two counter
+    // words travel in the frame's zeroed block, and the auxiliary job that recycles frame k - 1's zeroed block and tile
+    // schedule waits for renderer k - 1.  Events a LATER call waits for exist once per frame parity (a re-recorded event
+    // names its latest record only).
+    hipStream_t head_stream = nullptr;
+    hipEvent_t  ev_pipe_entry = nullptr;                 // the caller's stream at entry (frames that do not chain)
+    hipEvent_t  ev_pipe_render[2] = { nullptr, nullptr }; // renderer of the last pipelined frame of that parity
+    hipEvent_t  ev_pipe_aux[2]    = { nullptr, nullptr }; // ... and its auxiliary job (next schedule, cleared block)
+    DeviceBuffer recs_b;                                 // the records of odd pipelined frames
+    bool        pipeline    = true; // LCGS_PIPELINE=0: every frame in today's order (A/B and test hook)
+    uint32_t    pipe_frames = 0;    // pipelined frames so far: the parity
+    uint64_t    pipe_chained = 0, pipe_bounded = 0; // ... those that chained / rendered with the bounded grid (lcgs_debug_pipeline_counts)
+    // the renderer of a frame that chains is a bounded persistent grid of this many workgroups per CU (see persist_in_flight):
+    // measured on the bicycle stand-in at 1080p, frames/s with 2 / 3 / 4 / 6 per CU and one workgroup per tile:
+    // 1513 / 1619 / 1459 / 1357 and 1428, against 1445 in single-stream order (profiles/pipelined_frames_ab.txt)
+    int         pipe_render_wgs = 3;
+    // every C ABI entry point counts itself; a pipelined frame notes the count it left, so the next one knows whether anything
+    // else was asked of the context in between (then its head first waits for the caller's stream, which is today's order)
+    uint64_t    op_seq = 0, pipe_left_seq = ~(uint64_t)0;
     // keep_state frames clear the 2-D gradient rows on the auxiliary stream (beside the renderer) so that the backward
     // does not start with a 40 us zero-fill; consumed by the first backward of that frame
     hipEvent_t  ev_g2d_zero = nullptr;
@@ -161,7 +184,6 @@ struct lcgs_context {
     // lcgs_render_forward_batch: a sibling context (own workspace, own streams) that renders every other view, so
     // that one view's latency-bound sort chain overlaps the other's bandwidth- and VALU-bound kernels
     lcgs_context* twin         = nullptr;
-    hipStream_t   twin_stream  = nullptr; // owned
     hipEvent_t    ev_batch_fork = nullptr, ev_batch_join = nullptr;
     // lcgs_fit_views: the view's image and loss gradient (per context: two views are in flight), the order of the
     // backward passes across the two contexts

@@ -71,6 +71,7 @@ lcgs_status lcgs_grads_allreduce(lcgs_context* ctx, lcgs_comm* c, int num_gaussi
     LCGS_REQUIRE(grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh && grads->d_dL_dopacity,
                  "NULL gradient buffer");
     if (num_gaussians == 0) return LCGS_OK;
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     const AttrRows a = attr_rows(grads, sh_degree);
     const int64_t  P = num_gaussians;
@@ -152,6 +153,7 @@ lcgs_status lcgs_adam_step_sharded(lcgs_context* ctx, lcgs_comm* c, int num_gaus
     LCGS_REQUIRE(cfg->visible_only == 0, "the sharded step is dense (per-splat rows): visible_only must be 0");
     LCGS_REQUIRE(num_gaussians >= 0 && sh_degree >= 0 && sh_degree <= 3, "bad num_gaussians / sh_degree");
     if (num_gaussians == 0) return LCGS_OK;
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     const int64_t P = num_gaussians, N = c->world;
     int64_t       first = 0, count = 0;
@@ -207,6 +209,7 @@ lcgs_status lcgs_sparse_pack(lcgs_context* ctx, int sh_degree, const lcgs_grads*
 {
     LCGS_REQUIRE(ctx && grads && (count == 0 || (d_rows && d_msg)) && count >= 0 && sh_degree >= 0 && sh_degree <= 3,
                  "bad argument");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     launch_sparse_pack(attr_rows(grads, sh_degree).ptr, sh_degree, d_rows, count, d_msg, ctx->stream);
     LCGS_HIP_CHECK(hipGetLastError());
@@ -218,6 +221,7 @@ lcgs_status lcgs_sparse_accumulate(lcgs_context* ctx, int sh_degree, const lcgs_
 {
     LCGS_REQUIRE(ctx && grads && (count == 0 || d_msg) && count >= 0 && sh_degree >= 0 && sh_degree <= 3, "bad argument");
     LCGS_REQUIRE(row_first >= 0 && row_count >= 0 && row_first + row_count <= ((int64_t)1 << 30), "bad row range");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     launch_sparse_accumulate(attr_rows(grads, sh_degree).ptr, sh_degree, d_msg, count, row_first, row_count, ctx->stream);
     LCGS_HIP_CHECK(hipGetLastError());
@@ -279,6 +283,7 @@ lcgs_status lcgs_sparse_touched_rows(lcgs_context* ctx, lcgs_comm* c, int num_ga
     LCGS_REQUIRE(ctx && c && out, "NULL argument");
     LCGS_REQUIRE(c->ctx == ctx, "the communicator belongs to another context");
     LCGS_REQUIRE(num_gaussians >= 0 && world_size >= 1 && world_size <= LCGS_MAX_RANKS, "bad num_gaussians / world_size");
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     memset(out, 0, sizeof(*out));
     if (num_gaussians == 0) return LCGS_OK;
@@ -302,6 +307,7 @@ lcgs_status lcgs_adam_step_sparse(lcgs_context* ctx, lcgs_comm* c, int num_gauss
     LCGS_REQUIRE(cfg->visible_only == 0, "the sparse step keeps dense-Adam semantics (every row decays): visible_only must be 0");
     LCGS_REQUIRE(num_gaussians >= 0 && sh_degree >= 0 && sh_degree <= 3, "bad num_gaussians / sh_degree");
     if (num_gaussians == 0) return LCGS_OK;
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     const int64_t  P = num_gaussians;
     const int      N = c->world, me = c->rank;

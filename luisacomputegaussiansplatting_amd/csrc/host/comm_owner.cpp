@@ -104,6 +104,7 @@ lcgs_status lcgs_owner_step_forward(lcgs_context* ctx, lcgs_comm* c, const lcgs_
     LCGS_REQUIRE(ctx && c && cameras && bg_color && d_img, "NULL argument");
     LCGS_REQUIRE(c->ctx == ctx, "the communicator belongs to another (or a destroyed) context");
     LCGS_REQUIRE(c->world <= LCGS_MAX_OWNER_VIEWS, "world_size above LCGS_MAX_OWNER_VIEWS (one view slot per rank)");
+    LCGS_ENTRY(ctx);
     LCGS_REQUIRE(ctx->pos != nullptr && ctx->P > 0, "no scene bound");
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     const int N = c->world, me = c->rank;
@@ -241,6 +242,7 @@ lcgs_status lcgs_owner_step_backward(lcgs_context* ctx, lcgs_comm* c, const floa
         set_last_error("lcgs_owner_step_backward needs a preceding lcgs_owner_step_forward");
         return LCGS_ERR_STATE;
     }
+    LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     const int     N = c->world, me = c->rank;
     const int64_t n_all = c->own.n_all; // (a step without read-back: the padded segments' total capacity)
@@ -287,6 +289,7 @@ lcgs_status lcgs_owner_step_finish(lcgs_context* ctx, lcgs_comm* c, int* redo)
     LCGS_REQUIRE(ctx && c && redo, "NULL argument");
     LCGS_REQUIRE(c->ctx == ctx, "the communicator belongs to another (or a destroyed) context");
     *redo = 0;
+    LCGS_ENTRY(ctx);
     if (!c->own.async) return LCGS_OK; // a step that read its sizes back has nothing left to report
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     c->own.async = false;

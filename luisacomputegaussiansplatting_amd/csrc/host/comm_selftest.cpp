@@ -241,6 +241,7 @@ lcgs_status lcgs_comm_selftest(lcgs_context* ctx, lcgs_comm* c, double timeout_s
     out->rank       = c->rank;
     auto sh = std::make_shared<SelftestShared>(); // (outlives this call if a phase never returns: the worker is then detached)
     sh->rep = *out;
+    LCGS_ENTRY(ctx);
     std::thread worker([sh, ctx, c] {
         lcgs_status s = hipSetDevice(ctx->device) == hipSuccess ? LCGS_OK : LCGS_ERR_HIP;
         auto        enter = [&](int p) {

@@ -334,6 +334,7 @@ lcgs_status lcgs_comm_create(lcgs_context* ctx, const lcgs_comm_id* id, int rank
     *out = nullptr;
     LCGS_REQUIRE(world_size >= 1 && rank >= 0 && rank < world_size, "rank / world_size out of range");
     LCGS_REQUIRE(world_size <= LCGS_MAX_RANKS, "world_size above LCGS_MAX_RANKS");
+    LCGS_ENTRY(ctx);
     LCGS_REQUIRE(ctx->comm == nullptr, "the context already has a communicator attached");
     LCGS_TRY(need_rccl());
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
@@ -454,6 +455,7 @@ lcgs_status lcgs_comm_create_loopback(lcgs_context* ctx, lcgs_loopback_group* gr
     LCGS_REQUIRE(ctx && group && out, "NULL argument");
     *out = nullptr;
     LCGS_REQUIRE(rank >= 0 && rank < group->world, "rank out of range");
+    LCGS_ENTRY(ctx);
     LCGS_REQUIRE(ctx->comm == nullptr, "the context already has a communicator attached");
     {
         std::lock_guard<std::mutex> lock(group->mu);

@@ -97,6 +97,7 @@ lcgs_status lcgs_l2_loss_backward(lcgs_context* ctx, int width, int height, cons
         return LCGS_ERR_INVALID_ARG;
     }
     const int64_t n  = (int64_t)width * height * 3;
+    LCGS_ENTRY(ctx);
     hipStream_t   st = lcgs::context_stream(ctx);
     hipError_t    e  = hipSetDevice(lcgs::context_device(ctx)); // multi-GPU processes: every entry point selects its device
     if (e != hipSuccess) return lcgs::hip_fail(e, "hipSetDevice", __FILE__, __LINE__);
@@ -131,6 +132,7 @@ lcgs_status lcgs_image_to_rgb8_device(lcgs_context* ctx, int width, int height, 
         return LCGS_ERR_INVALID_ARG;
     }
     const int64_t n = (int64_t)width * height;
+    LCGS_ENTRY(ctx);
     hipLaunchKernelGGL(k_image_to_rgb8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lcgs::context_stream(ctx), width,
                        height, d_img_chw, d_rgb);
     hipError_t e = hipGetLastError();

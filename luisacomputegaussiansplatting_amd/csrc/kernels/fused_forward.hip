@@ -831,10 +831,19 @@ __global__ void __launch_bounds__(kThreads) k_expand_emit(const uint32_t* __rest
 __global__ void __launch_bounds__(kThreads) k_get_ranges_u32(uint32_t* __restrict__ d_counts, uint32_t l_cap,
                                                                const uint32_t* __restrict__ keys,
                                                                uint32_t* __restrict__ ranges,
-                                                               const uint32_t* __restrict__ scan_error_flag)
+                                                               const uint32_t* __restrict__ scan_error_flag,
+                                                               uint32_t* __restrict__ frame_words)
 {
     // (also forwards a time-out flag, if the frame has one, into the counter block the host reads back)
-    if (blockIdx.x == 0 && threadIdx.x == 0) d_counts[5] = scan_error_flag ? *scan_error_flag : 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        d_counts[5] = scan_error_flag ? *scan_error_flag : 0u;
+        // pipelined frames: the two words the renderer reads (on-screen splats, num_rendered) leave with the frame's own
+        // zeroed block -- the next frame's head rewrites the counter block while this frame's renderer runs
+        if (frame_words) {
+            frame_words[0] = d_counts[0];
+            frame_words[1] = d_counts[1];
+        }
+    }
     uint32_t g  = blockIdx.x * kThreads + threadIdx.x; // group of four keys
     uint32_t i0 = g * 4u;
     uint4    k4 = make_uint4(0, 0, 0, 0);
@@ -1143,12 +1152,12 @@ bool launch_expand(int P_cap, int64_t v_hint, int64_t l_hint, uint32_t* d_counts
 }
 
 void launch_get_ranges_u32(int64_t L_hint, uint32_t l_cap, uint32_t* d_counts, const uint32_t* keys, uint32_t* ranges,
-                           const uint32_t* scan_error_flag, hipStream_t stream, hipEvent_t done)
+                           const uint32_t* scan_error_flag, hipStream_t stream, hipEvent_t done, uint32_t* frame_words)
 {
     unsigned blocks = blocks_for((L_hint + 3) / 4); // four keys per thread
     if (blocks > 16384u) blocks = 16384u;
     hipExtLaunchKernelGGL(k_get_ranges_u32, dim3(blocks), dim3(kThreads), 0, stream, nullptr, done, 0, d_counts, l_cap, keys,
-                          ranges, scan_error_flag);
+                          ranges, scan_error_flag, frame_words);
 }
 
 // d_counts[9] accumulates the members of equal-depth runs beyond the cap (zeroed per frame by k_rowscan_first)
