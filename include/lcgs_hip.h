@@ -248,6 +248,31 @@ LCGS_API lcgs_status lcgs_render_maps(lcgs_context* ctx, int mode, float* d_dept
 LCGS_API lcgs_status lcgs_render_backward_maps(lcgs_context* ctx, const float* d_dL_dimg, int mode, const float* d_dL_ddepth,
                                                const float* d_dL_dalpha, int accumulate, const lcgs_grads* grads);
 
+/* ---- per-splat blend-weight statistics of the last lcgs_render_forward(keep_state = 1) ---- */
+/* Which splats a set of views actually uses.  w is the w_i = T_i alpha_i above: the weight pixel p gives entry i of its list, for
+ * the entries p blended (positions up to n_contrib[p] that pass the renderer's power and 1/255 tests, the 0.99 cap and the
+ * renderer's exp applied).  For every row with at least one such (pixel, entry) in the kept frame:
+ *     weight_sum += sum of w     weight_max = max(., max w)     pixels += number of such pairs     views += 1
+ * Every other row is untouched -- rows that sit on a list but that no pixel blends included.  Pixels outside the image (partial
+ * tiles) contribute nothing; a frame that drew nothing touches nothing.  Rows follow the context's row order, like
+ * lcgs_densify_accumulate.  No backward is needed.
+ * Precision: weight_max, pixels and views are exact (a max of non-negative floats and integer sums do not depend on order) and
+ * equal a binary32 CPU restatement of the frame bit for bit.  weight_sum is a binary32 sum of those bit-exact terms in an
+ * UNSPECIFIED order (float atomics across tiles): its bits may differ from run to run, within
+ *     |weight_sum - exact sum| <= gamma_n x exact sum,   gamma_n = n u / (1 - n u),  u = 2^-24,  n = the row's pixel count.
+ * Not offered: frames of the ownership step (lcgs_owner_render), a fused "score while rendering" mode, gradient-weighted scores,
+ * an lcgs-app flag. */
+typedef struct lcgs_contrib_stats { /* caller-owned, P entries each, zeroed by the caller; any member may be NULL, not all */
+    float*    weight_sum; /* sum over views and pixels of w                         */
+    float*    weight_max; /* largest w of any pixel of any view                     */
+    uint32_t* pixels;     /* number of (view, pixel) pairs that blended the row     */
+    uint32_t* views;      /* number of views in which at least one pixel blended it */
+} lcgs_contrib_stats;
+/* Enqueues on the context's stream, reads nothing back.  LCGS_ERR_STATE without a keep_state frame, or after a frame of
+ * lcgs_owner_render.  LCGS_ERR_INVALID_ARG (before any device work): NULL ctx / stats, all four members NULL, num_gaussians not
+ * the bound scene's.  Stages under lcgs_set_profiling: contrib_walk, contrib_fold. */
+LCGS_API lcgs_status lcgs_contrib_accumulate(lcgs_context* ctx, int num_gaussians, const lcgs_contrib_stats* stats);
+
 /* ---- camera gradient: the frame differentiated with respect to its camera pose ---- */
 /* Twelve floats in the order of lcgs_camera's members: position[3], front[3], up[3], right[3].  They are the gradient of the
  * scalar the LAST backward differentiated, <dL_dimg, img> + <dL_ddepth, depth> + <dL_dalpha, alpha>, the frame taken as a
@@ -368,6 +393,28 @@ LCGS_API lcgs_status lcgs_densify(lcgs_context* ctx, int num_gaussians, int sh_d
                                   const lcgs_params* out_activated, const lcgs_densify_stats* out_stats, int64_t capacity,
                                   const float* d_noise /* [P][2][3] or NULL */, uint32_t* d_src_row /* [capacity] or NULL */,
                                   int64_t* new_num_gaussians);
+/* Contribution-based pruning on the statistics of lcgs_contrib_accumulate.  A row is KEPT iff every enabled test passes:
+ * value >= minimum in binary32 (the two weights), unsigned compares (the two counts); a minimum of 0 disables its test, a
+ * non-zero minimum whose statistics member is NULL is LCGS_ERR_INVALID_ARG.  (The counts' minimums are 64-bit so that every
+ * value of a 32-bit counter can be asked for.) */
+typedef struct lcgs_prune_config {
+    float    min_weight_max; /* RadSplat: 0.01 */
+    float    min_weight_sum;
+    uint64_t min_pixels;
+    uint64_t min_views;
+} lcgs_prune_config;
+/* d_keep[i] = 1 kept, 0 dropped; P bytes on the device.  Only enqueues. */
+LCGS_API lcgs_status lcgs_contrib_keep_mask(lcgs_context* ctx, int num_gaussians, const lcgs_prune_config* cfg,
+                                            const lcgs_contrib_stats* stats, uint8_t* d_keep);
+/* lcgs_densify's rewrite with only its prune and keep actions: out of place, in source order; raw / m / v of the kept rows copied
+ * bit for bit, out_activated written with the optimiser step's activation expressions; d_src_row[r] (nullable) = source row of
+ * output row r -- any other per-row array of the caller is gathered through it.  Synchronises once (the new count).
+ * LCGS_ERR_CAPACITY: *new_num_gaussians = rows kept > capacity, no destination touched.  No row kept: LCGS_OK and 0.  The scene
+ * binding is not changed. */
+LCGS_API lcgs_status lcgs_prune(lcgs_context* ctx, int num_gaussians, int sh_degree, const lcgs_prune_config* cfg,
+                                const lcgs_contrib_stats* stats, const lcgs_params* raw, const lcgs_params* m, const lcgs_params* v,
+                                const lcgs_params* out_raw, const lcgs_params* out_m, const lcgs_params* out_v,
+                                const lcgs_params* out_activated, int64_t capacity, uint32_t* d_src_row, int64_t* new_num_gaussians);
 /* raw opacity = min(raw opacity, logit(max_opacity)), its moments zeroed, activated opacity rewritten; only the opacity
  * members of the packs are read.  Only enqueues. */
 LCGS_API lcgs_status lcgs_opacity_reset(lcgs_context* ctx, int num_gaussians, float max_opacity /* 3DGS: 0.01 */, const lcgs_params* raw,
@@ -538,6 +585,11 @@ LCGS_API lcgs_status lcgs_ply_read(const char* path, lcgs_scene_host* out);
 /* Raw (un-activated) values, INRIA property order, nx ny nz = 0 (f_dc 3P, f_rest 45P channel-major): writes the stand-ins. */
 LCGS_API lcgs_status lcgs_ply_write_raw(const char* path, int num_gaussians, const float* pos, const float* f_dc, const float* f_rest,
                                         const float* opacity_logit, const float* log_scale, const float* rot);
+/* A pruned file for a viewer: the vertex records of a binary little-endian PLY whose keep byte is non-zero, copied bit for bit
+ * in order behind the same header with the new vertex count (no activation is undone, so no bits change).  LCGS_ERR_IO: a file
+ * cannot be opened; LCGS_ERR_FORMAT: an ascii file, a vertex count other than num_rows, elements after `vertex`, a truncated
+ * payload. */
+LCGS_API lcgs_status lcgs_ply_filter_rows(const char* in_path, const char* out_path, int64_t num_rows, const uint8_t* keep);
 LCGS_API void lcgs_scene_host_free(lcgs_scene_host* scene);
 /* Deterministic stand-ins for the BASELINE scenes: kind 0 object-like, 1 unbounded-like; counter-based RNG
  * (any sub-range independently); ACTIVATED arrays, caller-allocated (count * {3, 48, 1, 3, 4} floats). */

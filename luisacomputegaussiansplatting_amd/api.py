@@ -152,6 +152,15 @@ class _DensifyConfig(C.Structure):
                 ("min_opacity", C.c_float), ("max_screen_size", C.c_int), ("seed", C.c_uint64)]
 
 
+class _ContribStats(C.Structure):
+    _fields_ = [("weight_sum", C.c_void_p), ("weight_max", C.c_void_p), ("pixels", C.c_void_p), ("views", C.c_void_p)]
+
+
+class _PruneConfig(C.Structure):
+    _fields_ = [("min_weight_max", C.c_float), ("min_weight_sum", C.c_float), ("min_pixels", C.c_uint64),
+                ("min_views", C.c_uint64)]
+
+
 class _InitConfig(C.Structure):
     _fields_ = [("initial_opacity", C.c_float), ("min_dist2", C.c_float)]
 
@@ -183,7 +192,7 @@ STRUCTS = {
     "lcgs_camera": Camera, "lcgs_tile_accel": _TileAccel, "lcgs_tile_input": _TileInput, "lcgs_tile_output": _TileOutput,
     "lcgs_stage_times": _StageTimes, "lcgs_frame_stats": _FrameStats, "lcgs_grads": _Grads, "lcgs_params": _Params,
     "lcgs_adam_config": _AdamConfig, "lcgs_densify_stats": _DensifyStats, "lcgs_densify_config": _DensifyConfig,
-    "lcgs_init_config": _InitConfig,
+    "lcgs_init_config": _InitConfig, "lcgs_contrib_stats": _ContribStats, "lcgs_prune_config": _PruneConfig,
     "lcgs_sparse_rows": _SparseRows, "lcgs_comm_stats": _CommStats, "lcgs_comm_selftest_report": _SelftestReport,
     "lcgs_scene_host": _SceneHost,
 }
@@ -202,6 +211,7 @@ def _signatures() -> dict:
     ptr = {name[len("lcgs_"):]: C.POINTER(mirror) for name, mirror in STRUCTS.items()}
     cam, grads, params, adam = ptr["camera"], ptr["grads"], ptr["params"], ptr["adam_config"]
     dstats, packs = ptr["densify_stats"], [ptr["params"]] * 4
+    cstats, prune = ptr["contrib_stats"], ptr["prune_config"]
     return {
         # library / context
         "lcgs_version": (s, []),
@@ -256,6 +266,8 @@ def _signatures() -> dict:
         # depth and alpha maps
         "lcgs_render_maps": (st, [p, i, p, p]),
         "lcgs_render_backward_maps": (st, [p, p, i, p, p, i, grads]),
+        # per-splat blend-weight statistics
+        "lcgs_contrib_accumulate": (st, [p, i, cstats]),
         # camera gradient
         "lcgs_camera_backward": (st, [p, p]),
         "lcgs_render_backward_camera": (st, [p, p, i, p, p, p]),
@@ -270,6 +282,8 @@ def _signatures() -> dict:
         # adaptive density control
         "lcgs_densify_accumulate": (st, [p, i, dstats]),
         "lcgs_densify": (st, [p, i, i, ptr["densify_config"], dstats, *packs, *packs[:3], dstats, i64, p, p, pi64]),
+        "lcgs_contrib_keep_mask": (st, [p, i, prune, cstats, p]),
+        "lcgs_prune": (st, [p, i, i, prune, cstats, *packs, *packs[:3], i64, p, pi64]),
         "lcgs_opacity_reset": (st, [p, i, f, *packs]),
         # a scene from a point cloud
         "lcgs_knn_mean_dist2": (st, [p, i64, p, p]),
@@ -312,6 +326,7 @@ def _signatures() -> dict:
         # scene ingest / image egress
         "lcgs_ply_read": (st, [s, ptr["scene_host"]]),
         "lcgs_ply_write_raw": (st, [s, i, p, p, p, p, p, p]),
+        "lcgs_ply_filter_rows": (st, [s, s, i64, p]),
         "lcgs_scene_host_free": (None, [ptr["scene_host"]]),
         "lcgs_synth_scene": (st, [i, u64, i64, i64, p, p, p, p, p]),
         "lcgs_image_to_rgb8": (None, [i, i, p, p]),
@@ -385,6 +400,22 @@ def _params(*dicts, partial: bool = False) -> list:
 
 def _densify_stats(d: dict) -> _DensifyStats:
     return _DensifyStats(_ptr(d["grad_accum"]), _ptr(d["denom"]), _ptr(d["max_radii"]))
+
+
+_CONTRIB_KEYS = ("weight_sum", "weight_max", "pixels", "views")
+
+
+def _contrib_stats(d: dict) -> _ContribStats:
+    """lcgs_contrib_stats of a dict; a missing key (or None) is a NULL member"""
+    return _ContribStats(*[_ptr(d.get(k)) for k in _CONTRIB_KEYS])
+
+
+def _contrib_rows(d: dict) -> int:
+    return next((int(d[k].shape[0]) for k in _CONTRIB_KEYS if d.get(k) is not None), 0)  # (all NULL: the library refuses)
+
+
+def _prune_config(min_weight_max: float = 0.0, min_weight_sum: float = 0.0, min_pixels: int = 0, min_views: int = 0) -> _PruneConfig:
+    return _PruneConfig(min_weight_max, min_weight_sum, int(min_pixels), int(min_views))
 
 
 def _adam_config(lr: dict, betas, eps: float, step: int, visible_only: int) -> _AdamConfig:
@@ -973,6 +1004,39 @@ class Renderer:
             raise
         return int(n.value)
 
+    # ---- contribution-based pruning
+    def contrib_accumulate(self, stats: dict):
+        """lcgs_contrib_accumulate: the last keep_state frame -> stats["weight_sum"], ["weight_max"] (float32), ["pixels"],
+        ["views"] (int32 bits of uint32 counts), device tensors of P entries zeroed by the caller; any key may be missing, not
+        all.  Only rows some pixel blended are touched.  Needs no backward; only enqueues."""
+        st = _contrib_stats(stats)
+        _check(load_library().lcgs_contrib_accumulate(self.ctx._h, _contrib_rows(stats), C.byref(st)))
+
+    def contrib_keep_mask(self, stats: dict, keep, **minimums):
+        """lcgs_contrib_keep_mask: keep[i] (uint8 device tensor of P entries) = 1 iff row i meets every given minimum
+        (min_weight_max, min_weight_sum, min_pixels, min_views; 0 or absent: not tested)."""
+        cfg, st = _prune_config(**minimums), _contrib_stats(stats)
+        _check(load_library().lcgs_contrib_keep_mask(self.ctx._h, int(keep.shape[0]), C.byref(cfg), C.byref(st), _ptr(keep)))
+
+    def prune(self, stats: dict, raw: dict, m: dict, v: dict, out_raw: dict, out_m: dict, out_v: dict, out_activated: dict,
+              src_row=None, sh_degree: int = 3, capacity: Optional[int] = None, **minimums) -> int:
+        """lcgs_prune: the rows of `raw` (with their Adam moments) that meet every given minimum (as in contrib_keep_mask), into
+        the out_* arrays -- out of place, source order kept, bit for bit -> the new row count.  Dicts as in densify; src_row:
+        optional int32 [capacity], output row -> source row.  Raises LcgsError (status 5, .needed = rows) when the kept rows do
+        not fit; nothing is written then.  Rebind out_activated and render a synchronising frame next."""
+        P = int(raw["opacity"].shape[0])
+        cap = int(out_raw["opacity"].shape[0]) if capacity is None else int(capacity)
+        cfg, st = _prune_config(**minimums), _contrib_stats(stats)
+        packs = _params(raw, m, v, out_raw, out_m, out_v, out_activated)
+        n = C.c_int64(0)
+        try:
+            _check(load_library().lcgs_prune(self.ctx._h, P, sh_degree, C.byref(cfg), C.byref(st), *map(C.byref, packs), cap,
+                                             _ptr(src_row), C.byref(n)))
+        except LcgsError as err:
+            err.needed = int(n.value)
+            raise
+        return int(n.value)
+
     def opacity_reset(self, raw: dict, m: dict, v: dict, activated: dict, max_opacity: float = 0.01):
         """lcgs_opacity_reset: raw opacity = min(raw opacity, logit(max_opacity)), its moments zeroed, activated opacity
         rewritten.  Only the "opacity" entries of the dicts are needed."""
@@ -1431,6 +1495,13 @@ def write_ply_raw(path: str, pos, f_dc, f_rest, opacity_logit, log_scale, rot):
     a = [np.ascontiguousarray(x, dtype=np.float32) for x in (pos, f_dc, f_rest, opacity_logit, log_scale, rot)]
     P = int(a[0].reshape(-1, 3).shape[0])
     _check(load_library().lcgs_ply_write_raw(path.encode(), P, *[_ptr(x) for x in a]))
+
+
+def ply_filter_rows(in_path: str, out_path: str, keep):
+    """lcgs_ply_filter_rows: the vertex records of a binary PLY whose keep entry is non-zero, bit for bit and in order, behind
+    the same header with the new count.  keep: one entry per vertex of the file (any array; compared with 0)."""
+    k = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+    _check(load_library().lcgs_ply_filter_rows(in_path.encode(), out_path.encode(), int(k.size), _ptr(k)))
 
 
 def synth_scene(kind: int, seed: int, count: int, first: int = 0) -> dict:

@@ -1,6 +1,7 @@
 // abi_backward.cpp -- the C ABI, part 5: the backward of the fused frame -- dense per-splat rows, compact
 // rows, accumulation over views, and the variant with the optimiser folded into the per-splat pass -- and the frame's depth
-// and alpha maps with their backward (kernels/maps.hip), and the camera gradient (kernels/camera_grad.hip).
+// and alpha maps with their backward (kernels/maps.hip), the per-splat blend-weight statistics of the same kept
+// lists (kernels/contrib.hip), and the camera gradient (kernels/camera_grad.hip).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -131,6 +132,37 @@ lcgs_status lcgs_render_maps(lcgs_context* ctx, int mode, float* d_depth, float*
                        ctx->n_contrib.as<uint32_t>(), kept_strip_masks(ctx), ctx->counts.as<uint32_t>(), ctx->last_tile_order,
                        mode, d_depth, d_alpha, ctx->stream);
     LCGS_HIP_CHECK(hipGetLastError());
+    return LCGS_OK;
+}
+
+lcgs_status lcgs_contrib_accumulate(lcgs_context* ctx, int num_gaussians, const lcgs_contrib_stats* stats)
+{
+    LCGS_REQUIRE(ctx && stats, "NULL argument");
+    LCGS_REQUIRE(stats->weight_sum || stats->weight_max || stats->pixels || stats->views, "all four statistics are NULL");
+    LCGS_ENTRY(ctx);
+    LCGS_REQUIRE(num_gaussians == ctx->P, "num_gaussians must be the bound scene's");
+    LCGS_TRY(check_maps_state(ctx, "lcgs_contrib_accumulate"));
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    // one slot per on-screen row; sized for the scene's rows like the frame's other per-row buffers (the count stays on the device)
+    LCGS_TRY(ctx->contrib_slab.ensure(contrib_slab_bytes((int64_t)ctx->P)));
+    hipStream_t   st   = ctx->stream;
+    const int64_t hint = ctx->hint_V > 0 ? std::min<int64_t>(ctx->hint_V, num_gaussians) : num_gaussians;
+    uint32_t*     slab = ctx->contrib_slab.as<uint32_t>();
+    ctx->n_marks       = 0;
+    LCGS_TRY(mark(ctx, "begin"));
+    launch_contrib_zero(hint, ctx->counts.as<uint32_t>(), slab, st);
+    launch_contrib_walk(ctx->last.cp, ctx->ranges, ctx->pairv[ctx->last.list_buf].as<uint32_t>(), ctx->recs.as<SplatRecord>(),
+                        ctx->n_contrib.as<uint32_t>(), kept_strip_masks(ctx), ctx->counts.as<uint32_t>(), ctx->last_tile_order,
+                        slab, st);
+    LCGS_TRY(mark(ctx, "contrib_walk"));
+    launch_contrib_fold(hint, num_gaussians, ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), slab, stats->weight_sum,
+                        stats->weight_max, stats->pixels, stats->views, st);
+    LCGS_TRY(mark(ctx, "contrib_fold"));
+    LCGS_HIP_CHECK(hipGetLastError());
+    if (ctx->profiling) {
+        LCGS_HIP_CHECK(hipStreamSynchronize(st));
+        LCGS_TRY(collect_marks(ctx));
+    }
     return LCGS_OK;
 }
 

@@ -286,6 +286,7 @@ lcgs_status lcgs_destroy(lcgs_context* ctx)
     ctx->fit_dL.release();
     ctx->loss_ws.release();
     ctx->cam_slab.release();
+    ctx->contrib_slab.release();
     if (ctx->ev_fit_bwd) (void)hipEventDestroy(ctx->ev_fit_bwd);
     ctx->frame_params.release();
     ctx->slice_bounds.release();

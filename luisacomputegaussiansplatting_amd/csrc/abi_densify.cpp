@@ -1,5 +1,6 @@
 // abi_densify.cpp -- the C ABI, part 7: adaptive density control (csrc/kernels/densify.hip) -- the statistics of a step, the
-// out-of-place clone / split / prune rewrite of raw parameters and Adam moments, and the opacity reset.
+// out-of-place clone / split / prune rewrite of raw parameters and Adam moments, the opacity reset, and contribution-based
+// pruning on the statistics of lcgs_contrib_accumulate (kernels/contrib.hip: the keep mask, and the rewrite restricted to it).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -11,6 +12,22 @@
 
 using namespace lcgs;
 using namespace lcgs::abi;
+
+namespace
+{
+// the rule of lcgs_contrib_keep_mask / lcgs_prune: an enabled (non-zero) minimum needs its statistics member
+lcgs_status check_prune_rule(const lcgs_prune_config* cfg, const lcgs_contrib_stats* stats)
+{
+    LCGS_REQUIRE((cfg->min_weight_max == 0.0f || stats->weight_max) && (cfg->min_weight_sum == 0.0f || stats->weight_sum) &&
+                     (cfg->min_pixels == 0 || stats->pixels) && (cfg->min_views == 0 || stats->views),
+                 "a non-zero minimum whose statistics member is NULL");
+    return LCGS_OK;
+}
+ContribRule prune_rule(const lcgs_prune_config* cfg)
+{
+    return { cfg->min_weight_max, cfg->min_weight_sum, cfg->min_pixels, cfg->min_views };
+}
+} // namespace
 
 extern "C" {
 
@@ -103,6 +120,72 @@ lcgs_status lcgs_densify(lcgs_context* ctx, int num_gaussians, int sh_degree, co
     LCGS_HIP_CHECK(hipMemsetAsync(out_stats->grad_accum, 0, (size_t)total * 4, st));
     LCGS_HIP_CHECK(hipMemsetAsync(out_stats->denom, 0, (size_t)total * 4, st));
     LCGS_HIP_CHECK(hipMemsetAsync(out_stats->max_radii, 0, (size_t)total * 4, st));
+    LCGS_HIP_CHECK(hipGetLastError());
+    return LCGS_OK;
+}
+
+lcgs_status lcgs_contrib_keep_mask(lcgs_context* ctx, int num_gaussians, const lcgs_prune_config* cfg,
+                                   const lcgs_contrib_stats* stats, uint8_t* d_keep)
+{
+    LCGS_REQUIRE(ctx && cfg && stats && d_keep, "NULL argument");
+    LCGS_REQUIRE(num_gaussians >= 0, "num_gaussians is negative");
+    LCGS_TRY(check_prune_rule(cfg, stats));
+    LCGS_ENTRY(ctx);
+    if (num_gaussians == 0) return LCGS_OK;
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    launch_contrib_classify(num_gaussians, prune_rule(cfg), stats->weight_sum, stats->weight_max, stats->pixels, stats->views,
+                            nullptr, d_keep, ctx->stream);
+    LCGS_HIP_CHECK(hipGetLastError());
+    return LCGS_OK;
+}
+
+lcgs_status lcgs_prune(lcgs_context* ctx, int num_gaussians, int sh_degree, const lcgs_prune_config* cfg,
+                       const lcgs_contrib_stats* stats, const lcgs_params* raw, const lcgs_params* m, const lcgs_params* v,
+                       const lcgs_params* out_raw, const lcgs_params* out_m, const lcgs_params* out_v,
+                       const lcgs_params* out_activated, int64_t capacity, uint32_t* d_src_row, int64_t* new_num_gaussians)
+{
+    LCGS_REQUIRE(ctx && cfg && stats && raw && m && v && out_raw && out_m && out_v && out_activated && new_num_gaussians,
+                 "NULL argument");
+    LCGS_REQUIRE(num_gaussians >= 0, "num_gaussians is negative");
+    LCGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "sh_degree must be in [0,3]");
+    LCGS_REQUIRE(capacity >= 0, "capacity is negative");
+    LCGS_TRY(check_prune_rule(cfg, stats));
+    *new_num_gaussians = 0;
+    if (num_gaussians == 0) return LCGS_OK;
+    const lcgs_params* packs[7] = { raw, m, v, out_raw, out_m, out_v, out_activated };
+    for (const lcgs_params* p : packs)
+        LCGS_REQUIRE(p->pos && p->scale && p->rotq && p->sh && p->opacity, "NULL device pointer in a parameter pack");
+    for (const lcgs_params* p : packs)
+        LCGS_REQUIRE((reinterpret_cast<uintptr_t>(p->rotq) & 15) == 0, "rotq arrays must be 16-byte aligned");
+    LCGS_REQUIRE(out_raw->pos != raw->pos && out_m->pos != m->pos && out_v->pos != v->pos,
+                 "the rewrite is out of place: destinations must not alias sources");
+    LCGS_ENTRY(ctx);
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t   st = ctx->stream;
+    const int64_t P  = num_gaussians;
+    LCGS_TRY(ctx->dn_emit.ensure((size_t)P * 4));
+    LCGS_TRY(ctx->dn_incl.ensure((size_t)P * 4));
+    LCGS_TRY(ctx->dn_action.ensure((size_t)P));
+    LCGS_TRY(ctx->st_scan_temp.ensure(scan_temp_bytes(P)));
+    launch_contrib_classify(P, prune_rule(cfg), stats->weight_sum, stats->weight_max, stats->pixels, stats->views,
+                            ctx->dn_emit.as<uint32_t>(), ctx->dn_action.as<uint8_t>(), st);
+    launch_inclusive_sum_u32(ctx->dn_emit.as<uint32_t>(), ctx->dn_incl.as<uint32_t>(), P, ctx->st_scan_temp.ptr, st);
+    // the call's one read-back: the new count, known before anything is scattered
+    uint32_t total = 0;
+    LCGS_HIP_CHECK(hipMemcpyAsync(&total, ctx->dn_incl.as<uint32_t>() + (P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    LCGS_HIP_CHECK(hipStreamSynchronize(st));
+    *new_num_gaussians = (int64_t)total;
+    if ((int64_t)total > capacity) {
+        set_last_error("lcgs_prune: the rewrite keeps " + std::to_string(total) + " rows, the destination arrays hold " +
+                       std::to_string((long long)capacity));
+        return LCGS_ERR_CAPACITY;
+    }
+    if (total == 0) return LCGS_OK;
+    scene_arrays_written(ctx, out_activated->pos, out_activated->scale, out_activated->rotq); // (destinations a context renders)
+    // (actions 0 and 1 only: no row splits, so neither the split's scale drop nor the sampler is reached)
+    launch_densify_scatter(P, (int)sh_floats(sh_degree), ctx->dn_action.as<uint8_t>(), ctx->dn_incl.as<uint32_t>(),
+                           adam_arrays(raw), adam_arrays(m), adam_arrays(v), adam_arrays(out_raw), adam_arrays(out_m), adam_arrays(out_v),
+                           adam_arrays(out_activated), 0.0f, nullptr, 0, d_src_row, st);
     LCGS_HIP_CHECK(hipGetLastError());
     return LCGS_OK;
 }

@@ -176,6 +176,7 @@ struct lcgs_context {
     // ... and the depth mode of the backward that wrote their value slot (kG2DValueSlot), -1: none did (lcgs_camera_backward)
     int         g2d_value_mode = -1;
     DeviceBuffer cam_slab; // lcgs_camera_backward: per-block partial sums (camera_grad_slab_bytes)
+    DeviceBuffer contrib_slab; // lcgs_contrib_accumulate: {sum, max bits, count} per on-screen row (contrib_slab_bytes)
     // lcgs_densify: emit counts, their inclusive sums, actions (one entry per source row)
     DeviceBuffer dn_emit, dn_incl, dn_action;
     // lcgs_knn_mean_dist2 / lcgs_scene_init_from_points (abi_init.cpp): Morton keys and original indices (the sort's ping-pong),

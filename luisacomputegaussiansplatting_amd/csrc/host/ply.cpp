@@ -92,9 +92,11 @@ std::vector<std::string> gs_columns()
 }
 
 // Parses the header (fp is left at the first payload byte) and looks the wanted columns (`names`) up by name.
+// elements_after (nullable): whether the header declares any element behind `vertex`.
 lcgs_status parse_header(FILE* fp, std::vector<Prop>& props, int64_t& N, size_t& stride, bool& binary,
-                         std::vector<int>& want, const std::vector<std::string>& names)
+                         std::vector<int>& want, const std::vector<std::string>& names, bool* elements_after = nullptr)
 {
+    if (elements_after) *elements_after = false;
     props.clear();
     want.clear();
     stride = 0;
@@ -140,6 +142,7 @@ lcgs_status parse_header(FILE* fp, std::vector<Prop>& props, int64_t& N, size_t&
                 if (!seen_vertex && cnt > 0) {
                         return fail(LCGS_ERR_FORMAT, "elements before `vertex` are not supported");
                 }
+                if (seen_vertex && elements_after) *elements_after = true;
                 in_vertex = false;
             }
         } else if (tok == "property") {
@@ -386,6 +389,83 @@ lcgs_status lcgs_ply_write_raw(const char* path, int num_gaussians, const float*
         }
     }
     fclose(fp);
+    return LCGS_OK;
+}
+
+// The kept vertex records of a binary file behind the same header: only the digits of the vertex count change.
+lcgs_status lcgs_ply_filter_rows(const char* in_path, const char* out_path, int64_t num_rows, const uint8_t* keep)
+{
+    if (!in_path || !out_path || num_rows < 0 || (num_rows > 0 && !keep))
+        return fail(LCGS_ERR_INVALID_ARG, "lcgs_ply_filter_rows: bad argument");
+    FILE* fp = fopen(in_path, "rb");
+    if (!fp) return fail(LCGS_ERR_IO, std::string("cannot open ") + in_path);
+    std::vector<Prop> props;
+    std::vector<int>  want;
+    int64_t           N = -1;
+    size_t            stride = 0;
+    bool              binary = false, elements_after = false;
+    lcgs_status       hs = parse_header(fp, props, N, stride, binary, want, {}, &elements_after);
+    if (hs == LCGS_OK && !binary) hs = fail(LCGS_ERR_FORMAT, "lcgs_ply_filter_rows copies binary records: the file is ascii");
+    if (hs == LCGS_OK && elements_after) hs = fail(LCGS_ERR_FORMAT, "elements after `vertex` are not supported");
+    if (hs == LCGS_OK && N != num_rows)
+        hs = fail(LCGS_ERR_FORMAT, "the file holds " + std::to_string((long long)N) + " vertices, the mask " +
+                                       std::to_string((long long)num_rows) + " rows");
+    if (hs != LCGS_OK) {
+        fclose(fp);
+        return hs;
+    }
+    const long payload = ftell(fp);
+    fseek(fp, 0, SEEK_END);
+    const long file_size = ftell(fp);
+    if (payload < 0 || (size_t)(file_size - payload) < (size_t)N * stride) {
+        fclose(fp);
+        return fail(LCGS_ERR_FORMAT, "PLY payload is truncated");
+    }
+    std::string header((size_t)payload, '\0');
+    fseek(fp, 0, SEEK_SET);
+    if (fread(&header[0], 1, header.size(), fp) != header.size()) {
+        fclose(fp);
+        return fail(LCGS_ERR_IO, "short read");
+    }
+    int64_t kept = 0;
+    for (int64_t j = 0; j < N; ++j) kept += keep[j] != 0;
+    // the `element vertex <count>` line: its digits are replaced, every other byte of the header stays
+    size_t at = header.find("element vertex");
+    while (at != std::string::npos && at != 0 && header[at - 1] != '\n') at = header.find("element vertex", at + 1);
+    if (at == std::string::npos) {
+        fclose(fp);
+        return fail(LCGS_ERR_FORMAT, "No vertex element in the ply file");
+    }
+    size_t d0 = header.find_first_of("0123456789", at), d1 = header.find_first_not_of("0123456789", d0);
+    header.replace(d0, d1 - d0, std::to_string((long long)kept));
+
+    FILE* out = fopen(out_path, "wb");
+    if (!out) {
+        fclose(fp);
+        return fail(LCGS_ERR_IO, std::string("cannot open ") + out_path + " for writing");
+    }
+    bool                       ok = fwrite(header.data(), 1, header.size(), out) == header.size();
+    constexpr int64_t          kChunk = 4096;
+    std::vector<unsigned char> rec(std::max<size_t>(stride, 1) * kChunk), sel(rec.size());
+    for (int64_t j0 = 0; j0 < N && ok && stride > 0; j0 += kChunk) {
+        const size_t rows = (size_t)std::min<int64_t>(kChunk, N - j0);
+        if (fread(rec.data(), stride, rows, fp) != rows) {
+            fclose(fp);
+            fclose(out);
+            remove(out_path);
+            return fail(LCGS_ERR_FORMAT, "PLY payload is truncated");
+        }
+        size_t n = 0;
+        for (size_t r = 0; r < rows; ++r)
+            if (keep[j0 + r]) memcpy(sel.data() + (n++) * stride, rec.data() + r * stride, stride);
+        ok = fwrite(sel.data(), stride, n, out) == n;
+    }
+    fclose(fp);
+    ok = (fclose(out) == 0) && ok;
+    if (!ok) {
+        remove(out_path);
+        return fail(LCGS_ERR_IO, "short write");
+    }
     return LCGS_OK;
 }
 

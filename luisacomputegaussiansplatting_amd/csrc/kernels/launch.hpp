@@ -380,6 +380,26 @@ void launch_render_maps_backward(const CamParams& cp, const uint32_t* ranges, co
 void launch_maps_depth_to_pos(int64_t v_hint, const CamParams& cp, const uint32_t* vis_index, const uint32_t* d_counts,
                               const SplatRecord* recs, const float* grads2d, int mode, float* dL_dpos, hipStream_t stream);
 
+// ---- contrib.hip : per-splat blend-weight statistics of the last keep-state frame, and the keep / drop rule ----
+// the context-owned slab: {sum, max bits, count} per on-screen row, indexed by the lists' on-screen indices
+size_t contrib_slab_bytes(int64_t rows);
+// clears the slots of the frame's on-screen rows (count in d_counts[0], launch sized for v_hint rows)
+void launch_contrib_zero(int64_t v_hint, const uint32_t* d_counts, uint32_t* slab, hipStream_t stream);
+// the walk of launch_render_maps, every entry reduced over the pixels that blend it; ATOMICALLY adds to the slab
+void launch_contrib_walk(const CamParams& cp, const uint32_t* ranges, const uint32_t* point_list, const SplatRecord* recs,
+                         const uint32_t* n_contrib, const uint8_t* strip_masks, const uint32_t* d_counts,
+                         const uint32_t* tile_order, uint32_t* slab, hipStream_t stream);
+// one lane per on-screen row: slots with a count fold into the caller's arrays at vis_index[row] (any of the four may be NULL)
+void launch_contrib_fold(int64_t v_hint, int64_t P, const uint32_t* vis_index, const uint32_t* d_counts, const uint32_t* slab,
+                         float* weight_sum, float* weight_max, uint32_t* pixels, uint32_t* views, hipStream_t stream);
+struct ContribRule { // a row is kept iff every enabled (non-zero) minimum is met
+    float    min_weight_max, min_weight_sum;
+    uint64_t min_pixels, min_views;
+};
+// action[i] = 1 kept / 0 dropped (lcgs_densify's actions); emit (nullable) = the same as a count, for the rewrite's prefix sums
+void launch_contrib_classify(int64_t P, const ContribRule& rule, const float* weight_sum, const float* weight_max,
+                             const uint32_t* pixels, const uint32_t* views, uint32_t* emit, uint8_t* action, hipStream_t stream);
+
 // ---- camera_grad.hip : the camera gradient of the last backward, from the 2-D rows it left ----
 // the context-owned slab: twelve doubles per block of 256 on-screen rows
 size_t camera_grad_slab_bytes(int64_t P);

@@ -292,6 +292,26 @@ public:
                            &out_activated, &out_stats, capacity, d_noise, d_src_row, &n));
         return n;
     }
+    // contribution-based pruning: per-splat blend-weight statistics of the last keep_state frame, the keep mask on them, and
+    // densify's rewrite restricted to it (rows that meet every enabled minimum, in source order) -> the new row count
+    void contrib_accumulate(int num_gaussians, const lcgs_contrib_stats& stats)
+    {
+        check(lcgs_contrib_accumulate(m_dev->ctx(), num_gaussians, &stats));
+    }
+    void contrib_keep_mask(int num_gaussians, const lcgs_prune_config& cfg, const lcgs_contrib_stats& stats, uint8_t* d_keep)
+    {
+        check(lcgs_contrib_keep_mask(m_dev->ctx(), num_gaussians, &cfg, &stats, d_keep));
+    }
+    int64_t prune(int num_gaussians, const lcgs_prune_config& cfg, const lcgs_contrib_stats& stats, const lcgs_params& raw,
+                  const lcgs_params& m, const lcgs_params& v, const lcgs_params& out_raw, const lcgs_params& out_m,
+                  const lcgs_params& out_v, const lcgs_params& out_activated, int64_t capacity, uint32_t* d_src_row = nullptr,
+                  int sh_degree = 3)
+    {
+        int64_t n = 0;
+        check(lcgs_prune(m_dev->ctx(), num_gaussians, sh_degree, &cfg, &stats, &raw, &m, &v, &out_raw, &out_m, &out_v,
+                         &out_activated, capacity, d_src_row, &n));
+        return n;
+    }
     void opacity_reset(int num_gaussians, const lcgs_params& raw, const lcgs_params& m, const lcgs_params& v,
                        const lcgs_params& activated, float max_opacity = 0.01f)
     {
