@@ -40,23 +40,22 @@ lcgs_status camera_pass(lcgs_context* ctx, float* d_dL_dcam)
                        ctx->recs.as<SplatRecord>(), ctx->g2d_value_mode, ctx->cam_slab.as<double>(), d_dL_dcam, ctx->stream);
     return LCGS_OK;
 }
-// the state both map entry points need: a keep-state frame of this context's own records, lists per tile
-lcgs_status check_maps_state(lcgs_context* ctx, const char* who)
+// the state every walk of the kept lists needs: a keep-state frame of this context's own records, lists per tile
+// (owner_frame: the whole message for a frame drawn from received records, where the caller has a better one)
+lcgs_status check_maps_state(lcgs_context* ctx, const char* who, const char* owner_frame = nullptr)
 {
     if (!ctx->frame_state_valid() || !ctx->last.has_state) {
         set_last_error((std::string(who) + " needs a preceding lcgs_render_forward(..., keep_state = 1)").c_str());
         return LCGS_ERR_STATE;
     }
     if (ctx->owner_recs) { // the last frame was lcgs_owner_render's: its records are not this context's own
-        set_last_error((std::string(who) + ": the last frame was drawn from received records (lcgs_owner_render)").c_str());
+        const std::string plain = std::string(who) + ": the last frame was drawn from received records (lcgs_owner_render)";
+        set_last_error(owner_frame ? owner_frame : plain.c_str());
         return LCGS_ERR_STATE;
     }
+    // (lcgs_render_forward never puts a frame that keeps state on per-block lists)
     LCGS_REQUIRE(ctx->last.cp.list_shift == 0u, "the kept frame lists its pairs per block: no backward walks those lists");
     return LCGS_OK;
-}
-const uint8_t* kept_strip_masks(lcgs_context* ctx)
-{
-    return render_forward_writes_strip_masks() && ctx->bwd_use_masks ? ctx->strip_masks.as<uint8_t>() : nullptr;
 }
 }
 
@@ -128,9 +127,7 @@ lcgs_status lcgs_render_maps(lcgs_context* ctx, int mode, float* d_depth, float*
     LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     LCGS_TRY(check_maps_state(ctx, "lcgs_render_maps"));
-    launch_render_maps(ctx->last.cp, ctx->ranges, ctx->pairv[ctx->last.list_buf].as<uint32_t>(), ctx->recs.as<SplatRecord>(),
-                       ctx->n_contrib.as<uint32_t>(), kept_strip_masks(ctx), ctx->counts.as<uint32_t>(), ctx->last_tile_order,
-                       mode, d_depth, d_alpha, ctx->stream);
+    launch_render_maps(kept_frame(ctx), mode, d_depth, d_alpha, ctx->stream);
     LCGS_HIP_CHECK(hipGetLastError());
     return LCGS_OK;
 }
@@ -151,9 +148,7 @@ lcgs_status lcgs_contrib_accumulate(lcgs_context* ctx, int num_gaussians, const 
     ctx->n_marks       = 0;
     LCGS_TRY(mark(ctx, "begin"));
     launch_contrib_zero(hint, ctx->counts.as<uint32_t>(), slab, st);
-    launch_contrib_walk(ctx->last.cp, ctx->ranges, ctx->pairv[ctx->last.list_buf].as<uint32_t>(), ctx->recs.as<SplatRecord>(),
-                        ctx->n_contrib.as<uint32_t>(), kept_strip_masks(ctx), ctx->counts.as<uint32_t>(), ctx->last_tile_order,
-                        slab, st);
+    launch_contrib_walk(kept_frame(ctx), slab, st);
     LCGS_TRY(mark(ctx, "contrib_walk"));
     launch_contrib_fold(hint, num_gaussians, ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), slab, stats->weight_sum,
                         stats->weight_max, stats->pixels, stats->views, st);
@@ -249,18 +244,10 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
     LCGS_REQUIRE(fused || !params || (grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh &&
                            grads->d_dL_dopacity),
                  "NULL gradient buffer");
-    if (!ctx->frame_state_valid() || !ctx->last.has_state) {
-        set_last_error("lcgs_render_backward needs a preceding lcgs_render_forward(..., keep_state = 1)");
-        return LCGS_ERR_STATE;
-    }
-    if (ctx->owner_recs) { // the last frame was lcgs_owner_render's: its records are not this context's own
-        set_last_error("the last frame was drawn from received records (lcgs_owner_render): use lcgs_owner_render_backward");
-        return LCGS_ERR_STATE;
-    }
+    LCGS_TRY(check_maps_state(ctx, "lcgs_render_backward",
+                              "the last frame was drawn from received records (lcgs_owner_render): use lcgs_owner_render_backward"));
     LCGS_REQUIRE((reinterpret_cast<uintptr_t>(grads->d_dL_drotq) & 15) == 0, "dL_drotq must be 16-byte aligned");
     if (!params) LCGS_TRY(ctx->cam_slab.ensure(camera_grad_slab_bytes((int64_t)ctx->P))); // (before any device work)
-    // (the render-backward walks per-tile lists, and lcgs_render_forward never puts a frame that keeps state on per-block ones)
-    LCGS_REQUIRE(ctx->last.cp.list_shift == 0u, "the kept frame lists its pairs per block: no backward walks those lists");
     hipStream_t  st   = ctx->stream;
     const size_t P    = (size_t)ctx->P;
     ctx->n_marks      = 0;
@@ -309,18 +296,14 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
     const int      k_bwd = ctx->persist_bwd_forced >= 0 ? ctx->persist_bwd_forced
                                                         : (ctx->frames_in_flight ? ctx->persist_bwd_in_flight : 0);
     const uint32_t bwd_wgs = (!ctx->profiling && k_bwd > 0) ? (uint32_t)(k_bwd * std::max(ctx->num_cus, 1)) : 0u;
+    const KeptFrame kept   = kept_frame(ctx);
     if (d_dL_dimg) {
-        launch_render_backward(ctx->last.cp, ctx->last.bg, ctx->ranges, ctx->pairv[ctx->last.list_buf].as<uint32_t>(),
-                               ctx->recs.as<SplatRecord>(), ctx->final_T.as<float>(), ctx->n_contrib.as<uint32_t>(),
-                               d_dL_dimg, ctx->grads2d.as<float>(), ctx->last_tile_order, st, kept_strip_masks(ctx),
-                               ctx->counts.as<uint32_t>(), ctx->bwd_counter.as<uint32_t>(), bwd_wgs, fill_in_kernel ? &fill : nullptr);
+        launch_render_backward(kept, ctx->last.bg, d_dL_dimg, ctx->grads2d.as<float>(), st, ctx->bwd_counter.as<uint32_t>(), bwd_wgs,
+                               fill_in_kernel ? &fill : nullptr);
         LCGS_TRY(mark(ctx, "render_backward"));
     }
     if (maps) { // the two map channels add to the rows the colour walk (or the zeroing alone) left
-        launch_render_maps_backward(ctx->last.cp, ctx->ranges, ctx->pairv[ctx->last.list_buf].as<uint32_t>(),
-                                    ctx->recs.as<SplatRecord>(), ctx->final_T.as<float>(), ctx->n_contrib.as<uint32_t>(),
-                                    kept_strip_masks(ctx), ctx->counts.as<uint32_t>(), ctx->last_tile_order, maps->mode,
-                                    maps->d_dL_ddepth, maps->d_dL_dalpha, ctx->grads2d.as<float>(), st);
+        launch_render_maps_backward(kept, maps->mode, maps->d_dL_ddepth, maps->d_dL_dalpha, ctx->grads2d.as<float>(), st);
         LCGS_TRY(mark(ctx, "render_maps_backward"));
     }
     if (overlap) LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_join, 0));

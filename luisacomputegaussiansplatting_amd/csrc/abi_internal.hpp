@@ -17,6 +17,7 @@
 
 #include "common.hpp"
 #include "context.hpp"
+#include "kernels/kept_walk.hpp"
 #include "kernels/launch.hpp"
 #include "kernels/tie_order.hpp"
 
@@ -149,6 +150,20 @@ struct FrameTailOptions {
 lcgs_status render_sorted_frame(lcgs_context* ctx, const CamParams& cp, const float bg[3], float* d_img, const SplatRecord* recs,
                                 const uint32_t* order, uint32_t id_mask, int64_t rows, int64_t hint_L, bool keep_state,
                                 const FrameParams* d_fp, const FrameTailOptions& opt);
+// what the walks of the last keep-state frame's kept lists read (kernels/kept_walk.hpp), this context's own records; the
+// strip masks the forward kept, unless they are switched off (LCGS_BWD_USE_MASKS=0: every walk fetches every entry)
+inline KeptFrame kept_frame(lcgs_context* ctx)
+{
+    return { ctx->last.cp,
+             ctx->ranges,
+             ctx->pairv[ctx->last.list_buf].as<uint32_t>(),
+             ctx->recs.as<SplatRecord>(),
+             ctx->final_T.as<float>(),
+             ctx->n_contrib.as<uint32_t>(),
+             ctx->bwd_use_masks ? ctx->strip_masks.as<uint8_t>() : nullptr,
+             ctx->counts.as<uint32_t>(),
+             ctx->last_tile_order };
+}
 // the kept state of the last frame that every kind of frame records
 void keep_frame_state(lcgs_context* ctx, const CamParams& cp, const float bg[3], float scale_modifier, bool has_state);
 // launch-size hints follow the live counts once those leave the [hint / 2, hint] band (inside it a captured graph stays valid)

@@ -318,9 +318,10 @@ lcgs_status lcgs::abi::owner_render_backward_into(lcgs_context* ctx, const float
     // (rows are addressed by POSITION; a frame from padded segments has positions beyond its row count: all of them are cleared)
     LCGS_HIP_CHECK(hipMemsetAsync(d_grads2d, 0, (size_t)ctx->owner_rows * LCGS_OWNER_GRAD_FLOATS * 4, st));
     LCGS_HIP_CHECK(hipMemsetAsync(ctx->bwd_counter.ptr, 0, 4, st)); // the persistent render-backward's tile counter
-    launch_render_backward(ctx->last.cp, ctx->last.bg, ctx->ranges, ctx->pairv[ctx->last.list_buf].as<uint32_t>(), ctx->owner_recs,
-                           ctx->final_T.as<float>(), ctx->n_contrib.as<uint32_t>(), d_dL_dimg, d_grads2d, ctx->last_tile_order, st,
-                           ctx->strip_masks.as<uint8_t>(), ctx->counts.as<uint32_t>(), nullptr, 0, fill);
+    KeptFrame f   = kept_frame(ctx);
+    f.recs        = ctx->owner_recs;                 // the frame was drawn from the received records
+    f.strip_masks = ctx->strip_masks.as<uint8_t>(); // (always the kept masks: the switch is the fused backward's)
+    launch_render_backward(f, ctx->last.bg, d_dL_dimg, d_grads2d, st, nullptr, 0, fill);
     LCGS_HIP_CHECK(hipGetLastError());
     return LCGS_OK;
 }

@@ -19,6 +19,7 @@
 // Thresholds are constants for the derivative: near cull, alpha < 1/255 skip, T < 1e-4 stop and power > 0 gate the
 // sums; the 0.99 alpha cap, the colour clamp and a saturated cam_clamp axis pass no gradient.
 #include "adam_rows.hpp"
+#include "kept_walk.hpp"
 #include "splat_backward.hpp"
 #include "stream_access.hpp"
 #include "tile_common.hpp"
@@ -779,24 +780,22 @@ void launch_zero_grads2d(const uint32_t* d_counts, float* grads2d, hipStream_t s
     hipLaunchKernelGGL(k_zero_grads2d, dim3(2048), dim3(256), 0, stream, d_counts, reinterpret_cast<float4*>(grads2d), bwd_counter);
 }
 
-void launch_render_backward(const CamParams& cp, const float bg[3], const uint32_t* ranges, const uint32_t* point_list,
-                            const SplatRecord* recs, const float* final_T, const uint32_t* n_contrib,
-                            const float* dL_dimg, float* grads2d, const uint32_t* tile_order, hipStream_t stream,
-                            const uint8_t* strip_masks, const uint32_t* d_counts, uint32_t* work_counter,
-                            uint32_t persistent_wgs, const DenseFill* fill_)
+void launch_render_backward(const KeptFrame& f, const float bg[3], const float* dL_dimg, float* grads2d, hipStream_t stream,
+                            uint32_t* work_counter, uint32_t persistent_wgs, const DenseFill* fill_)
 {
-    if (cp.grid_x * cp.grid_y == 0) return;
+    if (f.cp.grid_x * f.cp.grid_y == 0) return;
     const DenseFill fill = fill_ ? *fill_ : DenseFill{};
-    const uint32_t full = render_grid_size(cp.grid_x, cp.grid_y);
+    const uint32_t full = render_grid_size(f.cp.grid_x, f.cp.grid_y);
 #define LCGS_LAUNCH_BWD(KNOWN_, PERSIST_, GRID_)                                                                             \
-    hipLaunchKernelGGL((k_render_backward<KNOWN_, PERSIST_>), dim3(GRID_), dim3(256), 0, stream, cp, bg[0], bg[1], bg[2], ranges, \
-                       point_list, recs, final_T, n_contrib, dL_dimg, grads2d, tile_order, strip_masks, d_counts, work_counter, fill)
+    hipLaunchKernelGGL((k_render_backward<KNOWN_, PERSIST_>), dim3(GRID_), dim3(256), 0, stream, f.cp, bg[0], bg[1], bg[2],    \
+                       f.ranges, f.point_list, f.recs, f.final_T, f.n_contrib, dL_dimg, grads2d, f.tile_order, f.strip_masks, \
+                       f.d_counts, work_counter, fill)
     if (work_counter && persistent_wgs > 0 && persistent_wgs < full) {
-        if (strip_masks) LCGS_LAUNCH_BWD(true, true, persistent_wgs);
+        if (f.strip_masks) LCGS_LAUNCH_BWD(true, true, persistent_wgs);
         else LCGS_LAUNCH_BWD(false, true, persistent_wgs);
     } else {
         work_counter = nullptr;
-        if (strip_masks) LCGS_LAUNCH_BWD(true, false, full);
+        if (f.strip_masks) LCGS_LAUNCH_BWD(true, false, full);
         else LCGS_LAUNCH_BWD(false, false, full);
     }
 #undef LCGS_LAUNCH_BWD

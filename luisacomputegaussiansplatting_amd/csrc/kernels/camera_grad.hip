@@ -13,6 +13,7 @@
 //                         in order) and writes the twelve floats, each rounded once.  The entry count comes from d_counts[0].
 // No atomics: the summation tree depends on the number of on-screen rows only -- not on the grid, the launch hint or timing --
 // so the same 2-D rows give the same bits.
+#include "kept_walk.hpp"
 #include "splat_backward.hpp"
 
 namespace lcgs
@@ -78,14 +79,11 @@ k_camera_grad(int sh_deg, CamParams cp, float scale_modifier, const float* __res
 #pragma unroll
         for (int k = 0; k < kCamTerms; ++k) t[k] = 0.0;
         if (valid) {
-            // the depth channel's dL/dvalue reaches view z directly (maps.hip k_maps_depth_to_pos: the same expression)
+            // the depth channel's dL/dvalue reaches view z directly (as in maps.hip k_maps_depth_to_pos)
             float gz = 0.0f;
             if (depth_mode >= 0) {
                 const float gv = grads2d[(size_t)vid * kG2D + kG2DValueSlot];
-                if (gv != 0.0f) {
-                    const float z = recs[vid].depth;
-                    gz            = depth_mode == kDepthInvZ ? -gv / (z * z) : gv;
-                }
+                if (gv != 0.0f) gz = kept_walk::depth_value_backward(recs[vid].depth, depth_mode, gv);
             }
             camera_terms(cp, scale_modifier, in, gdir, gz, t);
         }

@@ -300,7 +300,6 @@ void launch_render_forward_rec(const CamParams& cp, const float bg[3], const uin
 // must be zero when the kernel starts) instead of one workgroup per tile -- caps the wave slots the renderer holds
 // strip_masks[list position] = the four per-strip reach bits of that entry (written when final_T / n_contrib are
 // kept); the backward takes them instead of repeating the tests
-bool render_forward_writes_strip_masks();
 
 // ---- comm_pack.hip : the opt-in f16 transport of the gradient all-reduce (host/comm.cpp) ----
 // |max| of n floats, atomically max-ed into *d_out_bits (float bits; zero it first)
@@ -341,12 +340,9 @@ struct DenseFill {
     float *b0 = nullptr, *b1 = nullptr, *b2 = nullptr, *b3 = nullptr, *b4 = nullptr;
     uint32_t n[5] = { 0, 0, 0, 0, 0 };
 };
-void   launch_render_backward(const CamParams& cp, const float bg[3], const uint32_t* ranges, const uint32_t* point_list,
-                              const SplatRecord* recs, const float* final_T, const uint32_t* n_contrib,
-                              const float* dL_dimg, float* grads2d, const uint32_t* tile_order, hipStream_t stream,
-                              const uint8_t* strip_masks = nullptr, const uint32_t* d_counts = nullptr,
-                              uint32_t* work_counter = nullptr, uint32_t persistent_wgs = 0,
-                              const DenseFill* fill = nullptr);
+struct KeptFrame; // kept_walk.hpp: what a walk of the last keep-state frame's kept lists reads
+void   launch_render_backward(const KeptFrame& f, const float bg[3], const float* dL_dimg, float* grads2d, hipStream_t stream,
+                              uint32_t* work_counter = nullptr, uint32_t persistent_wgs = 0, const DenseFill* fill = nullptr);
 void   launch_preprocess_backward(int64_t v_hint, int sh_deg, const CamParams& cp, float scale_modifier, const float* pos,
                                   const float* scale, const float* rotq, const float* sh, const uint32_t* vis_index,
                                   const uint32_t* d_counts, const float* grads2d, float* dL_dpos, float* dL_dscale,
@@ -367,15 +363,11 @@ void   launch_slice_bounds(const uint32_t* vis_index, const uint32_t* d_counts, 
 
 // ---- maps.hip : depth and alpha maps of the last keep-state frame and their backward ----
 constexpr int kDepthZ = 0, kDepthInvZ = 1; // = LCGS_DEPTH_Z, LCGS_DEPTH_INV_Z: a splat's value is its view z, or 1 / z
-// depth / alpha: H W floats each, either may be NULL; strip_masks NULL: every entry of the walk is fetched
-void launch_render_maps(const CamParams& cp, const uint32_t* ranges, const uint32_t* point_list, const SplatRecord* recs,
-                        const uint32_t* n_contrib, const uint8_t* strip_masks, const uint32_t* d_counts,
-                        const uint32_t* tile_order, int mode, float* depth, float* alpha, hipStream_t stream);
+// depth / alpha: H W floats each, either may be NULL; f.strip_masks NULL: every entry of the walk is fetched
+void launch_render_maps(const KeptFrame& f, int mode, float* depth, float* alpha, hipStream_t stream);
 // ADDS the sums of the two map channels to grads2d slots 0-5 and kG2DValueSlot (dL_ddepth / dL_dalpha: either may be NULL)
-void launch_render_maps_backward(const CamParams& cp, const uint32_t* ranges, const uint32_t* point_list,
-                                 const SplatRecord* recs, const float* final_T, const uint32_t* n_contrib,
-                                 const uint8_t* strip_masks, const uint32_t* d_counts, const uint32_t* tile_order, int mode,
-                                 const float* dL_ddepth, const float* dL_dalpha, float* grads2d, hipStream_t stream);
+void launch_render_maps_backward(const KeptFrame& f, int mode, const float* dL_ddepth, const float* dL_dalpha, float* grads2d,
+                                 hipStream_t stream);
 // one lane per on-screen row: dL_dpos[row] += grads2d slot kG2DValueSlot x dvalue/dz x front (behind the preprocess-backward)
 void launch_maps_depth_to_pos(int64_t v_hint, const CamParams& cp, const uint32_t* vis_index, const uint32_t* d_counts,
                               const SplatRecord* recs, const float* grads2d, int mode, float* dL_dpos, hipStream_t stream);
@@ -386,9 +378,7 @@ size_t contrib_slab_bytes(int64_t rows);
 // clears the slots of the frame's on-screen rows (count in d_counts[0], launch sized for v_hint rows)
 void launch_contrib_zero(int64_t v_hint, const uint32_t* d_counts, uint32_t* slab, hipStream_t stream);
 // the walk of launch_render_maps, every entry reduced over the pixels that blend it; ATOMICALLY adds to the slab
-void launch_contrib_walk(const CamParams& cp, const uint32_t* ranges, const uint32_t* point_list, const SplatRecord* recs,
-                         const uint32_t* n_contrib, const uint8_t* strip_masks, const uint32_t* d_counts,
-                         const uint32_t* tile_order, uint32_t* slab, hipStream_t stream);
+void launch_contrib_walk(const KeptFrame& f, uint32_t* slab, hipStream_t stream);
 // one lane per on-screen row: slots with a count fold into the caller's arrays at vis_index[row] (any of the four may be NULL)
 void launch_contrib_fold(int64_t v_hint, int64_t P, const uint32_t* vis_index, const uint32_t* d_counts, const uint32_t* slab,
                          float* weight_sum, float* weight_max, uint32_t* pixels, uint32_t* views, hipStream_t stream);

@@ -532,7 +532,4 @@ void launch_render_forward_rec(const CamParams& cp, const float bg[3], const uin
                   stream, strip_masks, done, work_counter, persistent_wgs, g2d_zero, bwd_counters);
 }
 
-// the forward renderer fills strip_masks whenever it keeps backward state
-bool render_forward_writes_strip_masks() { return true; }
-
 } // namespace lcgs
