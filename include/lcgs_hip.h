@@ -210,6 +210,10 @@ LCGS_API lcgs_status lcgs_debug_blend_exp(lcgs_context* ctx, const float* d_x, f
 /* Debug/test hook: forward frames of this context whose cull and sort chain ran on the head stream (enqueue-only frames of a
  * context-owned scene), those of them that chained behind the frame before, and those that rendered with the bounded grid. */
 LCGS_API lcgs_status lcgs_debug_pipeline_counts(lcgs_context* ctx, uint64_t* piped, uint64_t* chained, uint64_t* bounded);
+/* Debug/test hook: chained frames of this context whose cull pass ran one slot ahead, on the cull stream beside the previous
+ * frame's sort chain: the frames that chained while the GPU was behind the host (none if LCGS_EARLY_CULL=0 was set when the
+ * context was created). */
+LCGS_API lcgs_status lcgs_debug_early_cull_count(lcgs_context* ctx, uint64_t* early);
 
 /* ---- backward of the last lcgs_render_forward(keep_state = 1) (no reference counterpart, README.md:70) ---- */
 /* Outputs w.r.t. the ACTIVATED inputs: dL/dpos[3P], dL/dscale[3P], dL/drotq[4P] (as stored; 16-byte aligned),

@@ -258,6 +258,7 @@ def _signatures() -> dict:
         "lcgs_debug_last_state": (st, [p, p, p]),
         "lcgs_debug_blend_exp": (st, [p, p, p, i64]),
         "lcgs_debug_pipeline_counts": (st, [p, p, p, p]),
+        "lcgs_debug_early_cull_count": (st, [p, p]),
         # backward
         "lcgs_render_backward": (st, [p, p, grads]),
         "lcgs_render_backward_accumulate": (st, [p, p, grads]),
@@ -941,6 +942,13 @@ class Renderer:
         a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(load_library().lcgs_debug_pipeline_counts(self.ctx._h, C.byref(a), C.byref(b), C.byref(c)))
         return {"piped": a.value, "chained": b.value, "bounded": c.value}
+
+    def early_cull_count(self) -> int:
+        """lcgs_debug_early_cull_count: frames whose cull pass ran one slot ahead on the cull stream (those that chained while
+        the GPU was behind the host)"""
+        a = C.c_uint64(0)
+        _check(load_library().lcgs_debug_early_cull_count(self.ctx._h, C.byref(a)))
+        return a.value
 
     def set_list_policy(self, policy: str):
         """lcgs_set_list_policy: "tile" (the reference's per-tile lists), "block" (per 2 x 2 tiles), "auto" (default)"""

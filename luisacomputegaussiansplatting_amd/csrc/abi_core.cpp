@@ -169,6 +169,13 @@ const char* lcgs_last_error(void) { return g_last_error.c_str(); }
 
 lcgs_status lcgs_create(int device_id, void* stream, lcgs_context** out_ctx)
 {
+    return abi::create_context(device_id, stream, nullptr, out_ctx);
+}
+
+} // extern "C"
+
+lcgs_status lcgs::abi::create_context(int device_id, void* stream, hipStream_t borrowed_aux, lcgs_context** out_ctx)
+{
     LCGS_REQUIRE(out_ctx != nullptr, "out_ctx is NULL");
     *out_ctx  = nullptr;
     int count = 0;
@@ -202,11 +209,15 @@ lcgs_status lcgs_create(int device_id, void* stream, lcgs_context** out_ctx)
     if (const char* e = getenv("LCGS_COARSE_LISTS")) ctx->coarse_mode = e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2); // A/B / test hook
     if (const char* e = getenv("LCGS_BWD_USE_MASKS")) ctx->bwd_use_masks = e[0] != '0';      // test hook: the launcher's mask-less form
     if (const char* e = getenv("LCGS_PIPELINE")) ctx->pipeline = e[0] != '0'; // A/B and test hook: 0 = every frame in single-stream order
+    if (const char* e = getenv("LCGS_EARLY_CULL")) ctx->early_cull = e[0] != '0'; // A/B and test hook: 0 = chained frames cull on the head stream
     if (const char* e = getenv("LCGS_STAGE_SORT")) ctx->stage_sort = e[0] == 'l' ? 1 : (e[0] == 's' ? 2 : 0); // test hook
     // The auxiliary stream has the LOWEST dispatch priority: its bandwidth-bound workgroups fill the gaps the main
     // stream's short, latency-bound kernels leave instead of competing with them.
-    hipError_t se;
-    {
+    hipError_t se = hipSuccess;
+    if (borrowed_aux) {
+        ctx->aux_stream   = borrowed_aux;
+        ctx->aux_borrowed = true;
+    } else {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi); // lo = numerically greatest = lowest priority
         se = hipStreamCreateWithPriority(&ctx->aux_stream, hipStreamNonBlocking, lo);
@@ -214,7 +225,7 @@ lcgs_status lcgs_create(int device_id, void* stream, lcgs_context** out_ctx)
     }
     for (hipEvent_t* ev : { &ctx->ev_fork, &ctx->ev_join, &ctx->ev_ranges, &ctx->ev_aux_done, &ctx->ev_render, &ctx->ev_counts,
                             &ctx->ev_g2d_zero, &ctx->ev_pipe_entry, &ctx->ev_pipe_render[0], &ctx->ev_pipe_render[1],
-                            &ctx->ev_pipe_aux[0], &ctx->ev_pipe_aux[1] })
+                            &ctx->ev_pipe_aux[0], &ctx->ev_pipe_aux[1], &ctx->ev_cull })
         if (se == hipSuccess) se = hipEventCreateWithFlags(ev, hipEventDisableTiming);
     if (se != hipSuccess) {
         lcgs_status s = hip_fail(se, "aux stream / events", __FILE__, __LINE__);
@@ -225,6 +236,8 @@ lcgs_status lcgs_create(int device_id, void* stream, lcgs_context** out_ctx)
     *out_ctx    = ctx;
     return LCGS_OK;
 }
+
+extern "C" {
 
 lcgs_status lcgs_destroy(lcgs_context* ctx)
 {
@@ -247,8 +260,9 @@ lcgs_status lcgs_destroy(lcgs_context* ctx)
         if (ev) (void)hipEventDestroy(ev);
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->head_stream) (void)hipStreamSynchronize(ctx->head_stream);
+    if (ctx->cull_stream) (void)hipStreamSynchronize(ctx->cull_stream);
     if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
-    DeviceBuffer* bufs[] = { &ctx->recs, &ctx->recs_b, &ctx->pairv[2], &ctx->sortk[0], &ctx->sortk[1], &ctx->sortv[0], &ctx->sortv[1], &ctx->vis_index,
+    DeviceBuffer* bufs[] = { &ctx->recs, &ctx->recs_b, &ctx->cull_counts, &ctx->pairv[2], &ctx->sortk[0], &ctx->sortk[1], &ctx->sortv[0], &ctx->sortv[1], &ctx->vis_index,
                              &ctx->rects, &ctx->rects_sorted, &ctx->cull_slab, &ctx->chunk_info, &ctx->chunk_base, &ctx->pairk[0], &ctx->pairk[1], &ctx->pairv[0],
                              &ctx->pairv[1], &ctx->zero_ws[0], &ctx->zero_ws[1], &ctx->zero_ws[2], &ctx->counts, &ctx->sort_ws,
                              &ctx->expand_ws, &ctx->final_T, &ctx->n_contrib, &ctx->list_idx, &ctx->grads2d, &ctx->tile_order[0], &ctx->tile_order[1], &ctx->st_keys_tmp,
@@ -275,12 +289,13 @@ lcgs_status lcgs_destroy(lcgs_context* ctx)
     if (ctx->graph_exec) (void)hipGraphExecDestroy(ctx->graph_exec);
     if (ctx->aux_stream) {
         (void)hipStreamSynchronize(ctx->aux_stream);
-        (void)hipStreamDestroy(ctx->aux_stream);
+        if (!ctx->aux_borrowed) (void)hipStreamDestroy(ctx->aux_stream);
     }
-    if (ctx->head_stream) (void)hipStreamDestroy(ctx->head_stream); // (synchronised above, with the other two)
+    if (ctx->head_stream) (void)hipStreamDestroy(ctx->head_stream); // (synchronised above, with the others)
+    if (ctx->cull_stream) (void)hipStreamDestroy(ctx->cull_stream);
     for (hipEvent_t ev : { ctx->ev_fork, ctx->ev_join, ctx->ev_ranges, ctx->ev_aux_done, ctx->ev_render, ctx->ev_counts,
                            ctx->ev_g2d_zero, ctx->ev_pipe_entry, ctx->ev_pipe_render[0], ctx->ev_pipe_render[1],
-                           ctx->ev_pipe_aux[0], ctx->ev_pipe_aux[1] })
+                           ctx->ev_pipe_aux[0], ctx->ev_pipe_aux[1], ctx->ev_cull })
         if (ev) (void)hipEventDestroy(ev);
     ctx->fit_img.release();
     ctx->fit_dL.release();
@@ -422,6 +437,15 @@ lcgs_status lcgs_debug_pipeline_counts(lcgs_context* ctx, uint64_t* piped, uint6
     *piped   = ctx->pipe_frames;
     *chained = ctx->pipe_chained;
     *bounded = ctx->pipe_bounded;
+    return LCGS_OK;
+}
+
+// Debug/test hook: how many chained frames of this context ran their cull pass ahead, on the cull stream
+lcgs_status lcgs_debug_early_cull_count(lcgs_context* ctx, uint64_t* early)
+{
+    LCGS_REQUIRE(ctx && early, "NULL argument");
+    LCGS_ENTRY(ctx);
+    *early = ctx->pipe_early;
     return LCGS_OK;
 }
 

@@ -30,6 +30,9 @@ lcgs_status ensure_fused_workspace(lcgs_context* ctx, const CamParams& cp, bool 
         LCGS_TRY(ctx->cull_slab.ensure(chunks * 2048 * 16));
         LCGS_TRY(ctx->chunk_info.ensure(chunks * 8));
         LCGS_TRY(ctx->chunk_base.ensure(chunks * 4));
+        // the cull pass's digit counts, apart from sort_ws: a chained frame's cull pass writes them while the previous head's
+        // later passes and tile partition still count in that workspace (context.hpp cull_stream)
+        LCGS_TRY(ctx->cull_counts.ensure(depth_sort_first_counts_bytes((int64_t)P)));
     }
     LCGS_TRY(ctx->vis_index.ensure(P * 4));
     LCGS_TRY(ctx->rects.ensure(P * 8));
@@ -92,6 +95,20 @@ lcgs_status ensure_fused_workspace(lcgs_context* ctx, const CamParams& cp, bool 
 lcgs_status ensure_head_stream(lcgs_context* ctx)
 {
     if (!ctx->head_stream) LCGS_HIP_CHECK(hipStreamCreateWithFlags(&ctx->head_stream, hipStreamNonBlocking));
+    return LCGS_OK;
+}
+
+// The cull stream exists from the first frame that culls early, or from the first batch, whose sibling context takes it for
+// its auxiliary stream (context.hpp cull_stream): one stream for both, with the auxiliary stream's lowest priority.
+static lcgs_status ensure_cull_stream(lcgs_context* ctx)
+{
+    if (ctx->cull_stream) return LCGS_OK;
+    int lo = 0, hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+    if (hipStreamCreateWithPriority(&ctx->cull_stream, hipStreamNonBlocking, lo) != hipSuccess) {
+        (void)hipGetLastError();
+        LCGS_HIP_CHECK(hipStreamCreateWithFlags(&ctx->cull_stream, hipStreamNonBlocking));
+    }
     return LCGS_OK;
 }
 
@@ -323,9 +340,35 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
         LCGS_HIP_CHECK(hipStreamWaitEvent(hs, ctx->ev_join, 0));
     }
     LCGS_TRY(use_zero_block(ctx, zb, deferred && ctx->zero_ready[zb], hs));
-    const DepthSortFirstPass dfirst = depth_sort_first_pass(P, ctx->sort_ws.ptr);
+    // a frame that chains culls one slot ahead, on the cull stream beside the previous head's sort chain (context.hpp
+    // cull_stream): the pass depends on nothing that head produces.  Only while the GPU is BEHIND the host -- the previous frame's renderer has not finished when this frame is enqueued (one
+    // hipEventQuery, which also gates the bounded grid below): then the previous head is still running and the pass has a
+    // chain to run beside.  A viewer paced below the GPU's speed would only pay for the two cross-stream waits.
+    bool behind = false;
+    if (pipe == Pipe::Chained) {
+        behind = hipEventQuery(ctx->ev_pipe_render[par ^ 1]) == hipErrorNotReady;
+        (void)hipGetLastError();
+    }
+    const bool        early = behind && ctx->early_cull;
+    const hipStream_t cs    = early ? ctx->cull_stream : hs;
+    if (early) {
+        // the previous frame's first scatter has read the slabs, chunk_info and cull_counts this pass rewrites: ev_fork names
+        // its latest record, the one that scatter's dispatch carried (k_rowscan_first and k_scatter_first are their only
+        // readers).  It does NOT wait for ev_join, ev_pipe_render[] or ev_pipe_aux[]: it writes none of what those guard --
+        // vis_index, d_counts, the records, the pair buffers, the zeroed blocks -- and the scene it reads is the context's own,
+        // which only entry points that break the chain write
+        LCGS_HIP_CHECK(hipStreamWaitEvent(cs, ctx->ev_fork, 0));
+    }
+    const DepthSortFirstPass dfirst = depth_sort_first_pass(P, ctx->cull_counts.ptr);
     launch_cull_compact(P, cp, scale_modifier, d_fp, ctx->pos, ctx->scale, ctx->rotq, ctx->opacity, d_radii,
-                        ctx->cull_slab.as<uint4>(), ctx->chunk_info.as<uint2>(), dfirst, hs, ctx->cull_rows());
+                        ctx->cull_slab.as<uint4>(), ctx->chunk_info.as<uint2>(), dfirst, cs, ctx->cull_rows());
+    if (early) {
+        // the head joins it in front of k_rowscan_first; the caller's stream, which waits for this head's ev_ranges, is thereby
+        // behind every early cull pass, so whatever follows the burst on that stream is too
+        LCGS_HIP_CHECK(hipEventRecord(ctx->ev_cull, cs));
+        LCGS_HIP_CHECK(hipStreamWaitEvent(hs, ctx->ev_cull, 0));
+        ctx->pipe_early++;
+    }
     LCGS_TRY(mark(ctx, "cull_compact"));
     const int64_t hint_V = ctx->hint_V > 0 ? ctx->hint_V : P;
     // (per-tile and per-block frames of one context keep a launch-size hint each: their pair counts differ by up to 3 x, and a
@@ -342,7 +385,8 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
                                   ctx->chunk_base.as<uint32_t>(), ctx->sortk[0].as<uint32_t>(), ctx->sortk[1].as<uint32_t>(),
                                   ctx->sortv[0].as<uint32_t>(), ctx->sortv[1].as<uint32_t>(), ctx->vis_index.as<uint32_t>(),
                                   ctx->rects.as<uint2>(), d_counts, ctx->sort_ws.ptr, hs,
-                                  (overlap && !in_capture) ? ctx->ev_fork : nullptr, ft.on ? &ft.tie : nullptr);
+                                  (overlap && !in_capture) ? ctx->ev_fork : nullptr, ft.on ? &ft.tie : nullptr,
+                                  /*first_pass_only=*/false, dfirst.counts);
     LCGS_TRY(mark(ctx, "depth_sort"));
     // Record building (SH fetch + colour: bandwidth-bound) is independent of the rest of the sort chain (latency-bound
     // short kernels): fork it onto the auxiliary stream so the two overlap; the renderer joins.
@@ -375,9 +419,7 @@ lcgs_status enqueue_forward(lcgs_context* ctx, const CamParams& cp, const float 
     // overlaps on the GPU; alone, the bounded grid is the slower renderer (REJECTED.md), and such a frame keeps the full one.
     if (pipe == Pipe::Chained) {
         ctx->pipe_chained++;
-        const bool behind = hipEventQuery(ctx->ev_pipe_render[par ^ 1]) == hipErrorNotReady;
-        (void)hipGetLastError();
-        if (behind && ctx->persist_forced < 0) {
+        if (behind && ctx->persist_forced < 0) { // (the query in front of the cull pass)
             opt.persist_wgs = (uint32_t)(ctx->pipe_render_wgs * std::max(ctx->num_cus, 1));
             ctx->pipe_bounded++;
         }
@@ -493,6 +535,7 @@ lcgs_status lcgs_render_forward(lcgs_context* ctx, const lcgs_camera* camera, co
                 LCGS_TRY(ensure_head_stream(ctx));
                 LCGS_TRY(ctx->recs_b.ensure((size_t)ctx->P * sizeof(SplatRecord)));
                 LCGS_TRY(ctx->pairv[2].ensure((size_t)ctx->pair_capacity * 4));
+                if (pipe == Pipe::Chained && ctx->early_cull) LCGS_TRY(ensure_cull_stream(ctx));
             }
             LCGS_TRY(enqueue_forward(ctx, cp, bg_color, scale_modifier, d_img, d_radii, keep_state != 0, nullptr,
                                      /*in_capture=*/false, pipe));
@@ -597,7 +640,8 @@ lcgs_status prepare_twin(lcgs_context* ctx)
         LCGS_TRY(ensure_head_stream(ctx));
         LCGS_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_batch_fork, hipEventDisableTiming));
         LCGS_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_batch_join, hipEventDisableTiming));
-        LCGS_TRY(lcgs_create(ctx->device, ctx->head_stream, &ctx->twin));
+        LCGS_TRY(ensure_cull_stream(ctx));
+        LCGS_TRY(create_context(ctx->device, ctx->head_stream, ctx->cull_stream, &ctx->twin));
     }
     {
         lcgs_context* t = ctx->twin;

@@ -121,6 +121,8 @@ lcgs_status ensure_fused_workspace(lcgs_context* ctx, const CamParams& cp, bool 
 // a pipelined frame of the context may still be using the workspace through the auxiliary stream: ctx->stream waits for it
 lcgs_status join_aux_stream(lcgs_context* ctx);
 lcgs_status ensure_head_stream(lcgs_context* ctx); // created on first use; also the stream of the batch sibling
+// lcgs_create with the auxiliary stream given (borrowed: synchronised but not destroyed with the context) instead of created
+lcgs_status create_context(int device_id, void* stream, hipStream_t borrowed_aux, lcgs_context** out_ctx);
 // a frame's zeroed block (tile ranges + the persistent renderers' counters) is copy `zb`; cleared on `st` unless it already is
 lcgs_status use_zero_block(lcgs_context* ctx, int zb, bool cleared, hipStream_t st);
 // what the depth sort of a re-ordered scene needs to blend equal depths in FILE order (kernels/tie_order.hpp), and the bits

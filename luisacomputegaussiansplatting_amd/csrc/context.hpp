@@ -141,6 +141,7 @@ struct lcgs_context {
     bool use_graph = false; // opt-in (LCGS_GRAPH=1): measured no gain on MI355X, the short kernels are GPU-latency-bound
     // second stream: work that is independent of the sort chain (record building; gradient zero-fill) overlaps it
     hipStream_t aux_stream = nullptr;
+    bool        aux_borrowed = false; // the batch sibling's: its parent's cull_stream, not destroyed with the sibling
     hipEvent_t  ev_fork = nullptr, ev_join = nullptr, ev_ranges = nullptr, ev_aux_done = nullptr, ev_render = nullptr,
                 ev_counts = nullptr;
     bool        aux_pending = false, counts_pending = false;
@@ -157,6 +158,19 @@ struct lcgs_context {
     hipEvent_t  ev_pipe_render[2] = { nullptr, nullptr }; // renderer of the last pipelined frame of that parity
     hipEvent_t  ev_pipe_aux[2]    = { nullptr, nullptr }; // ... and its auxiliary job (next schedule, cleared block)
     DeviceBuffer recs_b;                                 // the records of odd pipelined frames
+    // A frame that CHAINS runs its cull pass one slot ahead, on cull_stream beside the previous head's sort chain: the pass reads
+    // the call's camera and the context's own scene (which nothing writes while frames chain) and writes the chunk slabs,
+    // chunk_info and cull_counts, whose last readers are the previous head's k_rowscan_first / k_scatter_first -- it waits for
+    // that scatter (ev_fork) and for nothing else; the head waits for ev_cull in front of its k_rowscan_first.  Only while the
+    // GPU is behind the host (the query that gates the bounded grid): a paced frame has nothing to run beside and would only
+    // pay for the cross-stream waits.  The stream has the auxiliary stream's lowest priority and is ALSO the auxiliary stream
+    // of the batch sibling (aux_borrowed): the two uses never coincide, and the process stays at four streams -- a fifth
+    // shares a hardware queue with the caller's stream and costs the camera batch 12 % (profiles/early_cull_ab.txt).
+    hipStream_t cull_stream = nullptr;
+    hipEvent_t  ev_cull     = nullptr;
+    DeviceBuffer cull_counts; // the cull pass's counts[digit][chunk], apart from sort_ws (which the previous head's passes still use)
+    bool        early_cull  = true; // LCGS_EARLY_CULL=0: a chained frame's cull pass stays on the head stream (A/B and test hook)
+    uint64_t    pipe_early  = 0;    // frames that culled early (lcgs_debug_early_cull_count)
     bool        pipeline    = true; // LCGS_PIPELINE=0: every frame in today's order (A/B and test hook)
     uint32_t    pipe_frames = 0;    // pipelined frames so far: the parity
     uint64_t    pipe_chained = 0, pipe_bounded = 0; // ... those that chained / rendered with the bounded grid (lcgs_debug_pipeline_counts)

@@ -90,7 +90,10 @@ struct DepthSortFirstPass {
     uint32_t  row_stride; // counts[digit * row_stride + chunk]
     uint32_t* counts;
 };
-DepthSortFirstPass depth_sort_first_pass(int64_t P, void* sort_ws);
+// table: the start of the sort's workspace, or a table of depth_sort_first_counts_bytes(P) that only the cull pass and the
+// sort's first pass touch (launch_depth_sort_from_chunks first_counts) -- a cull pass may then run beside the later passes
+DepthSortFirstPass depth_sort_first_pass(int64_t P, void* table);
+size_t depth_sort_first_counts_bytes(int64_t P);
 int    cull_chunk_count(int P); // 2048-splat chunks: slab = 2048 x 16 B per chunk, chunk_info / chunk_base one entry each
 void launch_set_frame_params(const FrameParams& fp, FrameParams* d_fp, hipStream_t stream);
 // d_fp (nullable): when non-NULL the kernels take camera / bg / scale_modifier from device memory (graph replay)
@@ -117,7 +120,9 @@ void launch_depth_sort_from_chunks(int64_t P, int64_t v_hint, const uint4* slab,
                                    // values then carry a file-index tag above their id_bits -- readers mask it off
                                    const TieOrder* tie = nullptr,
                                    // first_pass_only: stop behind the compaction (vis_index, rects, V, num_rendered)
-                                   bool first_pass_only = false);
+                                   bool first_pass_only = false,
+                                   // the cull pass's digit counts when they are not at the start of sort_ws
+                                   uint32_t* first_counts = nullptr);
 void launch_fix_equal_depth_order(uint32_t* keys, uint32_t* vals, uint32_t* scratch_k, uint32_t* scratch_v, int64_t n_cap,
                                   int64_t v_hint, const TieOrder& tie, hipStream_t stream);
 // ---- splat ownership: a frame from RECEIVED records instead of the context's own cull pass

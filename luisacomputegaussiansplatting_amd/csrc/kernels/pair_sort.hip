@@ -769,14 +769,18 @@ PairSortFirstPass pair_sort_first_pass(int64_t n_cap, int64_t grid_hint, int beg
 }
 
 // The depth sort fed by the cull pass's chunk slabs (see k_scatter_first).  Chunks are the cull pass's 2048 splats.
-DepthSortFirstPass depth_sort_first_pass(int64_t P, void* ws)
+// table: where the cull pass leaves counts[digit][chunk] -- the start of the sort's workspace, or a table of the caller's own
+// (depth_sort_first_counts_bytes) that launch_depth_sort_from_chunks is then given as first_counts
+DepthSortFirstPass depth_sort_first_pass(int64_t P, void* table)
 {
     DepthSortFirstPass fp;
     fp.mask       = 0xFFu; // 32 key bits in 4 passes of 8
     fp.row_stride = (uint32_t)row_stride_for(P, 8);
-    fp.counts     = reinterpret_cast<uint32_t*>(ws);
+    fp.counts     = reinterpret_cast<uint32_t*>(table);
     return fp;
 }
+
+size_t depth_sort_first_counts_bytes(int64_t P) { return (size_t)(row_stride_for(P, 8) * kRadix) * sizeof(uint32_t); }
 
 namespace
 {
@@ -849,15 +853,17 @@ int launch_pair_sort_u32(uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a, u
 void launch_depth_sort_from_chunks(int64_t P, int64_t v_hint, const uint4* slab, const uint2* chunk_info,
                                    uint32_t* chunk_base, uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a,
                                    uint32_t* vals_b, uint32_t* vis_index, uint2* rects, uint32_t* d_counts, void* ws_,
-                                   hipStream_t stream, hipEvent_t fork, const TieOrder* tie, bool first_pass_only)
+                                   hipStream_t stream, hipEvent_t fork, const TieOrder* tie, bool first_pass_only,
+                                   uint32_t* first_counts)
 {
     if (P <= 0) return;
     constexpr int  kItems = 8;
     static_assert(kThreads * kItems == kCullChunkSplats, "one workgroup of the first pass per cull chunk");
     const uint32_t nb     = (uint32_t)((P + kThreads * kItems - 1) / (kThreads * kItems));
     const uint32_t stride = (uint32_t)row_stride_for(P, kItems);
-    uint32_t*      counts = reinterpret_cast<uint32_t*>(ws_);
-    uint32_t*      totals = counts + (size_t)stride * kRadix;
+    // the cull pass's table: scanned in place and read by this pass alone (the digit totals stay in the workspace)
+    uint32_t*      counts = first_counts ? first_counts : reinterpret_cast<uint32_t*>(ws_);
+    uint32_t*      totals = reinterpret_cast<uint32_t*>(ws_) + (size_t)stride * kRadix;
     hipLaunchKernelGGL(k_rowscan_first, dim3(kRadix + 1), dim3(kThreads), 0, stream, counts, nb, totals, stride, chunk_info,
                        chunk_base, d_counts);
     hipExtLaunchKernelGGL(k_scatter_first<kItems>, dim3(nb), dim3(kThreads), 0, stream, nullptr, fork, 0, slab, chunk_info,
