@@ -424,6 +424,82 @@ LCGS_API lcgs_status lcgs_prune(lcgs_context* ctx, int num_gaussians, int sh_deg
 LCGS_API lcgs_status lcgs_opacity_reset(lcgs_context* ctx, int num_gaussians, float max_opacity /* 3DGS: 0.01 */, const lcgs_params* raw,
                                         const lcgs_params* m, const lcgs_params* v, const lcgs_params* activated);
 
+/* ---- 3DGS-MCMC density control (Kheradmand et al., NeurIPS 2024; no reference counterpart) ------------------- */
+/* The other density control in general use: a fixed splat budget and no clone / split thresholds.  Everything is IN PLACE on the
+ * caller's raw / m / v / activated arrays (activated pos / sh may alias raw's); none of the calls changes the scene binding --
+ * rebind, or call lcgs_scene_modified, before the next frame.
+ *   dead        o = 1 / (1 + exp(-raw opacity)) in binary32 (the optimiser step's expression); a row is dead iff !(o > min_opacity):
+ *               a NaN opacity is dead, o == min_opacity is dead
+ *   weight      w_i = dead ? 0 : (uint32_t)(o * 2^24) -- exact in binary32, a pure function of the row; sums of w in u64 are
+ *               exact and order free, so the sampler is reproducible bit for bit anywhere
+ *   cdf         cdf_i = w_0 + ... + w_i (u64), T = cdf_{P-1}; the scan works in blocks of 512 rows
+ *   draw j      c = Philox4x32-10(key = seed, counter = (j low, j high, tag, 0)); u = c[0] | (uint64_t)c[1] << 32;
+ *               t = the high 64 bits of u * T; src_j = the smallest i with cdf_i > t.  tag = 0x4D430001 (relocate), 0x4D430002 (add);
+ *               the SGLD normals below use 0x4D430003 -- all unlike lcgs_densify's counters (row low, row high, child 0 | 1, 0)
+ *   count       count_i = draws with src_j == i
+ *   values      for a source with original raw opacity x and n = min(count + 1, n_max), in BINARY64 from the binary32 inputs,
+ *               each result rounded once to binary32:
+ *                 o = 1 / (1 + exp(-x)), q = 1 / (1 + exp(x)) (= 1 - o without its rounding), o' = 1 - q^(1/n)
+ *                 D = sum_{i=1..n} sum_{k=0..i-1} C(i-1, k) (-1)^k o'^(k+1) / sqrt(k+1)   (i outer, k inner, summed in that order)
+ *                 new raw scale = old raw scale + log(o / D) per component (no exp / log round trip)
+ *                 o^ = min(max(o', min_opacity), 1 - 2^-23), new raw opacity = log(o^) - log1p(-o^)
+ *               liveness: where that binary32 raw opacity is dead by the rule above (o' <= min_opacity was clamped TO min_opacity,
+ *               and the rounding fell at or below it), it is replaced by the next binary32 values up until it is live (at most
+ *               64 steps; one step at min_opacity = 0.005) -- no row is dead right after a relocation.  gsplat leaves such a row
+ *               at min_opacity, to be relocated again the next time.
+ *   destination (a dead row, or an appended one) raw pos / rotq / sh of the source bit for bit, the source's new scale and opacity
+ *               (computed from its ORIGINAL values), ZERO Adam moments in every group, activated values by the optimiser step's
+ *               expressions
+ *   source      (count > 0) the same new scale and opacity -- the same bits as its copies --, its Adam moments zeroed in every
+ *               group, activated scale and opacity rewritten
+ * Zeroing the DESTINATION's moments too departs from gsplat's MCMCStrategy, which leaves a relocated row the moments of the dead
+ * splat that used to live there. */
+typedef struct lcgs_mcmc_config {
+    float    min_opacity; /* 0.005 */
+    int      n_max;       /* 1..51; 51 */
+    uint64_t seed;        /* built-in sampler, used when d_src_in is NULL */
+} lcgs_mcmc_config;
+/* Every dead row, in ascending row order (draw j fills the j-th dead row), becomes a copy of a live row.  d_src_in (nullable):
+ * [#dead] sources to use instead of the built-in sampler; an entry >= num_gaussians or naming a dead row is
+ * LCGS_ERR_INVALID_ARG, found on the device and reported with the count's read-back, nothing of the scene written.  d_src_row
+ * (nullable, [P], written whenever the call gets past its argument checks): the source of a relocated row, its own index for
+ * every other row.  *num_relocated = rows relocated; no dead row, or no live row (T == 0): 0 and nothing written.
+ * Synchronises once (the count). */
+LCGS_API lcgs_status lcgs_mcmc_relocate(lcgs_context* ctx, int num_gaussians, int sh_degree, const lcgs_mcmc_config* cfg,
+                                        const lcgs_params* raw, const lcgs_params* m, const lcgs_params* v,
+                                        const lcgs_params* activated, const uint32_t* d_src_in, uint32_t* d_src_row,
+                                        int64_t* num_relocated);
+/* Rows [num_gaussians, num_gaussians + num_new) of the caller's arrays (which hold `capacity` rows) become copies of live rows:
+ * the same weights, dead rule, draws (tag 0x4D430002) and values as lcgs_mcmc_relocate.  d_src_in (nullable): [num_new] sources;
+ * d_src_row (nullable): [num_new], the source of row num_gaussians + j.  num_gaussians + num_new > capacity: LCGS_ERR_CAPACITY,
+ * before any device work; num_new == 0: nothing happens; no live row: LCGS_ERR_STATE; a bad entry of d_src_in:
+ * LCGS_ERR_INVALID_ARG -- the last two are found on the device: the call reads one status word back (one synchronisation) and
+ * has written nothing of the scene when it reports them. */
+LCGS_API lcgs_status lcgs_mcmc_add(lcgs_context* ctx, int num_gaussians, int sh_degree, const lcgs_mcmc_config* cfg,
+                                   const lcgs_params* raw, const lcgs_params* m, const lcgs_params* v, const lcgs_params* activated,
+                                   int64_t num_new, int64_t capacity, const uint32_t* d_src_in, uint32_t* d_src_row);
+typedef struct lcgs_mcmc_noise_config {
+    float    noise_lr /* 5e5 */, lr_pos /* the step's position learning rate */, k /* 100 */, x0 /* 0.995 */;
+    uint64_t seed;
+    int      step; /* word 3 of the built-in sampler's counter */
+} lcgs_mcmc_noise_config;
+/* SGLD noise, binary32, in place on raw pos (and on activated pos when that is another array); moments untouched:
+ *   o = 1 / (1 + exp(-raw opacity)), g = 1 / (1 + exp(-k ((1 - o) - x0))), a = (noise_lr * lr_pos) * g
+ *   s = exp(raw scale), R = the rotation of rotq / |rotq|, t_j = (sum_r R_rj eps_r) * (s_j * s_j), d_c = sum_j R_cj t_j  (= R S^2 R^T eps)
+ *   pos_c += a * d_c
+ * eps = d_noise[i][0..2], or (NULL) three standard normals: Box-Muller on Philox4x32-10(seed; row low, row high, 0x4D430003, step)
+ * with lcgs_densify's (0, 1) mapping ((x >> 8) + 0.5) / 2^24: (r0 cos t0, r0 sin t0, r1 cos t1), r = sqrt(-2 ln u), t = 2 pi u'.
+ * Only enqueues. */
+LCGS_API lcgs_status lcgs_mcmc_noise(lcgs_context* ctx, int num_gaussians, const lcgs_mcmc_noise_config* cfg, const lcgs_params* raw,
+                                     const lcgs_params* activated, const float* d_noise);
+/* grads.d_dL_dopacity[i] += (float)(lambda_opacity / P), grads.d_dL_dscale[i][c] += (float)(lambda_scale / (3 P)), the quotients
+ * formed in binary64: the gradients of lambda_opacity mean(o) + lambda_scale mean(s) with respect to the ACTIVATED values, what
+ * lcgs_adam_step consumes (3DGS-MCMC: 0.01 each).  Call it between the backward and the optimiser step.  The on-screen-only
+ * modes of lcgs_adam_step (visible_only 1 with per-splat rows) apply it to on-screen rows only; compact rows (visible_only 2)
+ * are not indexed by splat and must not be passed.  Only the opacity and scale members are read.  Only enqueues. */
+LCGS_API lcgs_status lcgs_mcmc_regularize(lcgs_context* ctx, int num_gaussians, float lambda_opacity, float lambda_scale,
+                                          const lcgs_grads* grads);
+
 /* ---- a scene from a point cloud (no reference counterpart: app/gaussians.cpp only loads trained PLYs) -------- */
 /* The mean squared distance to the three nearest neighbours, of n points p_i (binary32, AoS xyz xyz ...):
  *   valid       a point is valid if all three coordinates are finite; an invalid point is nobody's neighbour

@@ -37,6 +37,7 @@ from .api import (  # noqa: F401
     library_path,
     load_library,
     local_to_world_matrix,
+    mcmc_num_new,
     ply_filter_rows,
     projection_matrix,
     read_gs_ply,

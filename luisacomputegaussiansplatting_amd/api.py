@@ -152,6 +152,15 @@ class _DensifyConfig(C.Structure):
                 ("min_opacity", C.c_float), ("max_screen_size", C.c_int), ("seed", C.c_uint64)]
 
 
+class _McmcConfig(C.Structure):
+    _fields_ = [("min_opacity", C.c_float), ("n_max", C.c_int), ("seed", C.c_uint64)]
+
+
+class _McmcNoiseConfig(C.Structure):
+    _fields_ = [("noise_lr", C.c_float), ("lr_pos", C.c_float), ("k", C.c_float), ("x0", C.c_float), ("seed", C.c_uint64),
+                ("step", C.c_int)]
+
+
 class _ContribStats(C.Structure):
     _fields_ = [("weight_sum", C.c_void_p), ("weight_max", C.c_void_p), ("pixels", C.c_void_p), ("views", C.c_void_p)]
 
@@ -192,6 +201,7 @@ STRUCTS = {
     "lcgs_camera": Camera, "lcgs_tile_accel": _TileAccel, "lcgs_tile_input": _TileInput, "lcgs_tile_output": _TileOutput,
     "lcgs_stage_times": _StageTimes, "lcgs_frame_stats": _FrameStats, "lcgs_grads": _Grads, "lcgs_params": _Params,
     "lcgs_adam_config": _AdamConfig, "lcgs_densify_stats": _DensifyStats, "lcgs_densify_config": _DensifyConfig,
+    "lcgs_mcmc_config": _McmcConfig, "lcgs_mcmc_noise_config": _McmcNoiseConfig,
     "lcgs_init_config": _InitConfig, "lcgs_contrib_stats": _ContribStats, "lcgs_prune_config": _PruneConfig,
     "lcgs_sparse_rows": _SparseRows, "lcgs_comm_stats": _CommStats, "lcgs_comm_selftest_report": _SelftestReport,
     "lcgs_scene_host": _SceneHost,
@@ -286,6 +296,11 @@ def _signatures() -> dict:
         "lcgs_contrib_keep_mask": (st, [p, i, prune, cstats, p]),
         "lcgs_prune": (st, [p, i, i, prune, cstats, *packs, *packs[:3], i64, p, pi64]),
         "lcgs_opacity_reset": (st, [p, i, f, *packs]),
+        # 3DGS-MCMC density control
+        "lcgs_mcmc_relocate": (st, [p, i, i, ptr["mcmc_config"], *packs, p, p, pi64]),
+        "lcgs_mcmc_add": (st, [p, i, i, ptr["mcmc_config"], *packs, i64, i64, p, p]),
+        "lcgs_mcmc_noise": (st, [p, i, ptr["mcmc_noise_config"], *packs[:2], p]),
+        "lcgs_mcmc_regularize": (st, [p, i, f, f, grads]),
         # a scene from a point cloud
         "lcgs_knn_mean_dist2": (st, [p, i64, p, p]),
         "lcgs_scene_init_from_points": (st, [p, i, i, p, p, ptr["init_config"], *packs[:2]]),
@@ -1052,6 +1067,49 @@ class Renderer:
         packs = _params(raw, m, v, activated, partial=True)
         _check(load_library().lcgs_opacity_reset(self.ctx._h, P, max_opacity, *map(C.byref, packs)))
 
+    # ---- 3DGS-MCMC density control
+    def mcmc_relocate(self, raw: dict, m: dict, v: dict, activated: dict, min_opacity: float = 0.005, n_max: int = 51,
+                      seed: int = 0, src_in=None, src_row=None, sh_degree: int = 3) -> int:
+        """lcgs_mcmc_relocate: every dead row (opacity <= min_opacity) becomes a copy of a live row drawn with probability
+        proportional to opacity; source and copies get the corrected opacity and scale, zero Adam moments -> rows relocated.  In
+        place; dicts as in adam_step.  src_in: optional int32 [#dead] sources instead of the built-in sampler keyed by seed.
+        src_row: optional int32 [P], the source of a relocated row, its own index otherwise.  Synchronises once.  Rebind (or
+        scene_modified) before the next frame."""
+        P = int(raw["opacity"].shape[0])
+        cfg, packs, n = _McmcConfig(min_opacity, int(n_max), int(seed)), _params(raw, m, v, activated), C.c_int64(0)
+        _check(load_library().lcgs_mcmc_relocate(self.ctx._h, P, sh_degree, C.byref(cfg), *map(C.byref, packs), _ptr(src_in),
+                                                 _ptr(src_row), C.byref(n)))
+        return int(n.value)
+
+    def mcmc_add(self, num_gaussians: int, num_new: int, raw: dict, m: dict, v: dict, activated: dict, min_opacity: float = 0.005,
+                 n_max: int = 51, seed: int = 0, src_in=None, src_row=None, sh_degree: int = 3, capacity: Optional[int] = None):
+        """lcgs_mcmc_add: rows [num_gaussians, num_gaussians + num_new) of the tensors (which hold `capacity` rows, default
+        raw["opacity"]'s length) become copies of live rows among the first num_gaussians, drawn and corrected as in
+        mcmc_relocate.  src_in / src_row: optional int32 [num_new].  Raises LcgsError: status 5 when the rows do not fit (nothing
+        is touched), 8 when no row is live, 1 for a bad entry of src_in."""
+        cap = int(raw["opacity"].shape[0]) if capacity is None else int(capacity)
+        cfg, packs = _McmcConfig(min_opacity, int(n_max), int(seed)), _params(raw, m, v, activated)
+        _check(load_library().lcgs_mcmc_add(self.ctx._h, int(num_gaussians), sh_degree, C.byref(cfg), *map(C.byref, packs),
+                                            int(num_new), cap, _ptr(src_in), _ptr(src_row)))
+
+    def mcmc_noise(self, raw: dict, activated: dict, lr_pos: float, step: int, noise_lr: float = 5e5, k: float = 100.0,
+                   x0: float = 0.995, seed: int = 0, noise=None):
+        """lcgs_mcmc_noise: pos += (noise_lr lr_pos g(opacity)) Sigma eps in place on raw["pos"] (and activated["pos"] when it is
+        another tensor); g is ~0 for opaque splats.  noise: optional [P, 3] normals, None: the built-in sampler keyed by
+        (seed, row, step).  Needs raw pos / scale / rotq / opacity and activated pos.  Only enqueues."""
+        P = int(raw["opacity"].shape[0])
+        cfg = _McmcNoiseConfig(noise_lr, lr_pos, k, x0, int(seed), int(step))
+        packs = _params(raw, activated, partial=True)
+        _check(load_library().lcgs_mcmc_noise(self.ctx._h, P, C.byref(cfg), *map(C.byref, packs), _ptr(noise)))
+
+    def mcmc_regularize(self, grads: dict, lambda_opacity: float = 0.01, lambda_scale: float = 0.01):
+        """lcgs_mcmc_regularize: grads["opacity"] += lambda_opacity / P, grads["scale"] += lambda_scale / (3 P) -- the gradients of
+        lambda_opacity mean(opacity) + lambda_scale mean(scale) w.r.t. the activated values; call it before adam_step (whose
+        on-screen-only mode then applies it to on-screen rows only).  Only enqueues."""
+        P = int(grads["opacity"].shape[0])
+        g = _Grads(None, _ptr(grads["scale"]), None, None, _ptr(grads["opacity"]))
+        _check(load_library().lcgs_mcmc_regularize(self.ctx._h, P, lambda_opacity, lambda_scale, C.byref(g)))
+
 
     # ---- a scene from a point cloud (DESIGN.md 9)
     def init_from_points(self, pos, rgb, sh_degree: int = 3, initial_opacity: float = 0.1, min_dist2: float = 1e-7):
@@ -1093,6 +1151,11 @@ def scene_extent(cameras):
     center, radius = np.zeros(3, np.float32), np.zeros(1, np.float32)
     _check(load_library().lcgs_scene_extent(n, (Camera * max(n, 1))(*cameras), _ptr(center), _ptr(radius)))
     return center, float(radius[0])
+
+
+def mcmc_num_new(P: int, cap_max: int, growth: float = 1.05) -> int:
+    """3DGS-MCMC's growth step: the rows Renderer.mcmc_add appends to a scene of P rows -- 5 % at a time up to cap_max"""
+    return max(0, min(int(cap_max), int(growth * P)) - int(P))
 
 
 def read_points_ply(path: str) -> dict:

@@ -269,6 +269,7 @@ lcgs_status lcgs_destroy(lcgs_context* ctx)
                              &ctx->st_vals_tmp, &ctx->st_sort_temp, &ctx->st_scan_temp, &ctx->st_scalar, &ctx->sh_half, &ctx->strip_masks, &ctx->shjac, &ctx->tie_ws, &ctx->fused_grads, &ctx->bwd_counter, &ctx->st_flags, &ctx->st_keys_exp, &ctx->st_vals_exp,
                              &ctx->st_u32[0], &ctx->st_u32[1], &ctx->st_u32[2], &ctx->st_u32[3], &ctx->st_u32[4], &ctx->st_u32[5], &ctx->st_u32[6], &ctx->st_u32[7],
                              &ctx->cull_bound_buf, &ctx->verify_ws, &ctx->st_win, &ctx->st_win2, &ctx->st_offs, &ctx->dn_emit, &ctx->dn_incl, &ctx->dn_action,
+                             &ctx->mc_w, &ctx->mc_dead, &ctx->mc_dead_incl, &ctx->mc_cdf, &ctx->mc_count, &ctx->mc_dead_list, &ctx->mc_draw, &ctx->mc_scan_temp, &ctx->mc_status,
                              &ctx->knn_keys[0], &ctx->knn_keys[1], &ctx->knn_vals[0], &ctx->knn_vals[1], &ctx->knn_sort_ws, &ctx->knn_sorted,
                              &ctx->knn_boxes, &ctx->knn_grid, &ctx->knn_dist2 };
     for (DeviceBuffer* b : bufs) b->release();

@@ -2,7 +2,7 @@
 //   lcgs-app --ply <path> [--res WxH] [--out dir] [--world colmap|blender] [--exp_N N] [--backend hip]
 //            [--path fused|stage|deferred] [--synth kind:count:seed] [--ingest device|host] [--cameras file]
 //            [--order file|spatial] [--pose garden|lego] [--gpus N] [--backward [--owner] [--comm-selftest]] [--fit K]
-//            [--fused-adam] [--loss l2|photometric] [--lambda-dssim f]
+//            [--fused-adam] [--loss l2|photometric] [--lambda-dssim f] [--density mcmc --cap-max N]
 // Same flags (app/main.cpp:52-124; `--key=value` and `--key value`, app/command_parser.hpp:5-79), the same
 // hard-coded look-at camera (app/main.cpp:191-207), the same frame loop (:266-308), the same output:
 // <out>/<ply stem>_<backend>.png, CHW float -> vertically flipped RGB8 with a truncating *255 (:323-339).
@@ -76,6 +76,10 @@ void usage(const char* argv0)
     printf("  --loss <l2|photometric>  With --fit: mean squared error (default) or the 3DGS training loss\n"
            "                           (1 - lambda) L1 + lambda (1 - SSIM) (lcgs_photometric_loss_backward)\n");
     printf("  --lambda-dssim <f>       With --loss photometric: the weight of the 1 - SSIM term, in [0,1] (default: 0.2)\n");
+    printf("  --density <none|mcmc>    With --fit: 3DGS-MCMC density control with the paper's schedule -- every parameter is\n"
+           "                           optimised, the L1 regulariser (0.01 each) before and SGLD noise after every Adam step, dead\n"
+           "                           splats relocated and the set grown by 5 %% every 100 steps from step 500\n");
+    printf("  --cap-max <N>            With --density mcmc: the splat budget the set grows to (default: the scene's count)\n");
     printf("  --display                Not supported (headless)\n");
 }
 
@@ -93,6 +97,8 @@ int main(int argc, char** argv)
     unsigned    W = 1600, H = 1063; // app/main.cpp:38
     std::string ply_path = "gsplat.ply", backend = "hip", out_dir = "out", world = "colmap", path = "fused", synth;
     std::string ingest = "device", cameras_file, order = "auto", pose = "garden", loss_kind = "l2";
+    std::string density = "none";
+    long long   cap_max = 0;
     float       lambda_dssim = 0.2f;
     int         exp_N = 1, gpus = 1, fit_steps = 0;
     bool        backward = false, fused_adam = false, owner = false, comm_selftest = false;
@@ -165,6 +171,14 @@ int main(int argc, char** argv)
             lambda_dssim = value.empty() ? -1.0f : std::strtof(value.c_str(), &end);
             if (value.empty() || *end != '\0' || !(lambda_dssim >= 0.0f && lambda_dssim <= 1.0f))
                 die("--lambda-dssim must be a number in [0,1]");
+        }
+        else if (key == "density") {
+            if (value != "none" && value != "mcmc") die("Invalid density control: '" + value + "'. Expected none or mcmc");
+            density = value;
+        } else if (key == "cap-max" || key == "cap_max") {
+            if (value.empty()) die("--cap-max requires a value");
+            cap_max = std::stoll(value);
+            if (cap_max < 1 || cap_max > 0x7fffffff) die("--cap-max out of range");
         }
         else if (key == "display") die("--display needs a GUI; this build is headless");
         else die("unknown option --" + key);
@@ -390,24 +404,44 @@ int main(int argc, char** argv)
             }
             for (int i = 0; i < P; ++i)
                 for (int c = 0; c < 3; ++c) h_sh[(size_t)i * 48 + c] += 0.3f * ((float)((i * 3 + c) % 7) / 3.0f - 1.0f);
-            lcgs::Buffer<float> a_pos = upload(h_pos.data(), n3), a_scale = upload(h_scale.data(), n3),
-                                a_rotq = upload(h_rotq.data(), n4), a_sh = upload(h_sh.data(), n48), a_op = upload(h_op.data(), (size_t)P);
-            lcgs::Buffer<float> w_scale = upload(r_scale.data(), n3), w_rotq = upload(h_rotq.data(), n4), w_op = upload(r_op.data(), (size_t)P);
+            // --density mcmc: the arrays hold --cap-max rows, the scene grows into them in place
+            const bool   mcmc = density == "mcmc";
+            const size_t cap  = mcmc ? std::max<size_t>((size_t)cap_max, (size_t)P) : (size_t)P;
+            if (mcmc && fused_adam) die("--density mcmc needs the gradient arrays (omit --fused-adam)");
             auto zeros = [&](size_t n) {
                 lcgs::Buffer<float> b(n);
                 if (hipMemset(b.data(), 0, n * sizeof(float)) != hipSuccess) die("memset failed");
                 return b;
             };
-            lcgs::Buffer<float> g[5] = { zeros(n3), zeros(n3), zeros(n4), zeros(n48), zeros((size_t)P) };
-            lcgs::Buffer<float> m[5] = { zeros(n3), zeros(n3), zeros(n4), zeros(n48), zeros((size_t)P) };
-            lcgs::Buffer<float> v[5] = { zeros(n3), zeros(n3), zeros(n4), zeros(n48), zeros((size_t)P) };
-            scene.bind(P, a_pos, a_scale, a_rotq, a_sh, a_op);
+            auto rows = [&](const float* h, size_t row_floats) { // P rows uploaded into a zeroed array of `cap` rows
+                lcgs::Buffer<float> b = zeros(cap * row_floats);
+                if (hipMemcpy(b.data(), h, (size_t)P * row_floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) die("H2D copy failed");
+                return b;
+            };
+            lcgs::Buffer<float> a_pos = rows(h_pos.data(), 3), a_scale = rows(h_scale.data(), 3), a_rotq = rows(h_rotq.data(), 4),
+                                a_sh = rows(h_sh.data(), 48), a_op = rows(h_op.data(), 1);
+            lcgs::Buffer<float> w_scale = rows(r_scale.data(), 3), w_rotq = rows(h_rotq.data(), 4), w_op = rows(r_op.data(), 1);
+            lcgs::Buffer<float> g[5] = { zeros(cap * 3), zeros(cap * 3), zeros(cap * 4), zeros(cap * 48), zeros(cap) };
+            lcgs::Buffer<float> m[5] = { zeros(cap * 3), zeros(cap * 3), zeros(cap * 4), zeros(cap * 48), zeros(cap) };
+            lcgs::Buffer<float> v[5] = { zeros(cap * 3), zeros(cap * 3), zeros(cap * 4), zeros(cap * 48), zeros(cap) };
+            int       rows_now = P; // the scene's row count: grows under --density mcmc
+            long long relocated = 0;
+            auto      bind_rows = [&]() {
+                scene.bind(rows_now, lcgs::BufferView<float>(a_pos.data(), (size_t)rows_now * 3),
+                           lcgs::BufferView<float>(a_scale.data(), (size_t)rows_now * 3),
+                           lcgs::BufferView<float>(a_rotq.data(), (size_t)rows_now * 4),
+                           lcgs::BufferView<float>(a_sh.data(), (size_t)rows_now * 48),
+                           lcgs::BufferView<float>(a_op.data(), (size_t)rows_now));
+            };
+            bind_rows();
             const lcgs_grads  grads = { g[0].data(), g[1].data(), g[2].data(), g[3].data(), g[4].data() };
             const lcgs_params raw = { a_pos.data(), w_scale.data(), w_rotq.data(), a_sh.data(), w_op.data() }; // pos / sh: raw == activated
             const lcgs_params act = { a_pos.data(), a_scale.data(), a_rotq.data(), a_sh.data(), a_op.data() };
             const lcgs_params mm = { m[0].data(), m[1].data(), m[2].data(), m[3].data(), m[4].data() };
             const lcgs_params vv = { v[0].data(), v[1].data(), v[2].data(), v[3].data(), v[4].data() };
             lcgs_adam_config cfg = { 0.0f, 2.5e-2f, 0.0f, 5e-2f, 0.0f, 0.0f, 0.9f, 0.999f, 1e-15f, 1, 0 }; // opacity + dc only
+            if (mcmc) cfg = { 1.6e-4f, 2.5e-3f, 1.25e-4f, 5e-2f, 5e-3f, 1e-3f, 0.9f, 0.999f, 1e-15f, 1, 0 }; // 3DGS's rates, every parameter
+            const lcgs_mcmc_config mcfg = { 0.005f, 51, 0x4c434753ull };
             auto t0 = std::chrono::steady_clock::now();
             float first_loss = 0.0f, loss = 0.0f;
             if (fused_adam && nv != 1) die("--fused-adam differentiates one view per step (omit --cameras)");
@@ -425,7 +459,22 @@ int main(int argc, char** argv)
                     lcgs::check(lcgs_render_backward_adam(device.ctx(), d_dL.data(), P, 3, &cfg, &raw, &mm, &vv, &act));
                 } else {
                     scene.fit_views(cams, target_ptrs, grads, d_loss.data(), bg);
-                    lcgs::check(lcgs_adam_step(device.ctx(), P, 3, &cfg, &grads, &raw, &mm, &vv, &act));
+                    if (mcmc) scene.mcmc_regularize(rows_now, grads); // 0.01 mean(opacity) + 0.01 mean(scale)
+                    lcgs::check(lcgs_adam_step(device.ctx(), rows_now, 3, &cfg, &grads, &raw, &mm, &vv, &act));
+                }
+                if (mcmc) {
+                    const lcgs_mcmc_noise_config ncfg = { 5e5f, cfg.lr_pos, 100.0f, 0.995f, mcfg.seed, it + 1 };
+                    scene.mcmc_noise(rows_now, ncfg, raw, act);
+                    if (it + 1 >= 500 && (it + 1) % 100 == 0) { // relocate the dead, then grow by 5 % towards the cap
+                        lcgs_mcmc_config step_cfg = mcfg;
+                        step_cfg.seed += (uint64_t)(it + 1);
+                        relocated += scene.mcmc_relocate(rows_now, step_cfg, raw, mm, vv, act);
+                        const long long grown   = std::min<long long>((long long)cap, (long long)(1.05 * rows_now));
+                        const long long num_new = std::max<long long>(0, grown - rows_now);
+                        scene.mcmc_add(rows_now, step_cfg, raw, mm, vv, act, num_new, (int64_t)cap);
+                        rows_now += (int)num_new;
+                        bind_rows();
+                    }
                 }
                 device.synchronize();
                 if (hipMemcpy(h_loss.data(), d_loss.data(), sizeof(float) * nv, hipMemcpyDeviceToHost) != hipSuccess) die("D2H copy failed");
@@ -437,6 +486,8 @@ int main(int argc, char** argv)
             double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             printf("fit: loss %.6e -> %.6e in %d steps of %d view(s) (%.3f ms per step)\n", first_loss, loss, fit_steps, nv,
                    ms / fit_steps);
+            if (mcmc)
+                printf("fit: mcmc density control: %d -> %d splats (cap %zu), %lld rows relocated\n", P, rows_now, cap, relocated);
             scene.render(cam, d_img, bg);
             save_view(d_img.data(), 0);
             views.clear(); // done

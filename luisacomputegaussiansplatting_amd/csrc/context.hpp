@@ -193,6 +193,10 @@ struct lcgs_context {
     DeviceBuffer contrib_slab; // lcgs_contrib_accumulate: {sum, max bits, count} per on-screen row (contrib_slab_bytes)
     // lcgs_densify: emit counts, their inclusive sums, actions (one entry per source row)
     DeviceBuffer dn_emit, dn_incl, dn_action;
+    // lcgs_mcmc_relocate / lcgs_mcmc_add (abi_mcmc.cpp): per row the weight, the dead flag, its inclusive sums, the u64 sums of
+    // the weights and the draws that landed on the row; per draw the dead row it fills and its source; the u64 scan's block
+    // sums; one status word (kernels/launch.hpp launch_mcmc_draw)
+    DeviceBuffer mc_w, mc_dead, mc_dead_incl, mc_cdf, mc_count, mc_dead_list, mc_draw, mc_scan_temp, mc_status;
     // lcgs_knn_mean_dist2 / lcgs_scene_init_from_points (abi_init.cpp): Morton keys and original indices (the sort's ping-pong),
     // the sort's workspace, the sorted points, the per-chunk boxes, the box partials + grid, the init call's dist2
     DeviceBuffer knn_keys[2], knn_vals[2], knn_sort_ws, knn_sorted, knn_boxes, knn_grid, knn_dist2;

@@ -12,6 +12,7 @@
 // written here instead of by a memset over the whole array.  64-bit element indices throughout.
 #include "activations.hpp" // train.hip's exact expression sequences (the values equal what an Adam step writes)
 #include "launch.hpp"
+#include "philox.hpp"
 #include "stream_access.hpp"
 
 namespace lcgs
@@ -125,33 +126,13 @@ __global__ void __launch_bounds__(256) k_densify_rows(int64_t P, const uint8_t* 
     }
 }
 
-// Philox4x32-10 (Salmon et al., SC'11): the built-in sampler's counter-based generator.  key = the seed, counter = (row, child):
-// a child's three normals depend on nothing else -- not the launch shape, not P.
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
-        const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0;
-        c[1] = lo1;
-        c[2] = n2;
-        c[3] = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-__device__ __forceinline__ float unit_open(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); } // (0, 1)
-__device__ __forceinline__ void  child_normals(uint64_t seed, int64_t row, int child, float n[3])
+// The built-in sampler (philox.hpp): key = the seed, counter = (row, child): a child's three normals depend on nothing else --
+// not the launch shape, not P.
+__device__ __forceinline__ void child_normals(uint64_t seed, int64_t row, int child, float n[3])
 {
     uint32_t c[4] = { (uint32_t)row, (uint32_t)((uint64_t)row >> 32), (uint32_t)child, 0u };
     philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const float r0 = sqrtf(-2.0f * logf(unit_open(c[0]))), t0 = 6.28318530717958647692f * unit_open(c[1]);
-    const float r1 = sqrtf(-2.0f * logf(unit_open(c[2]))), t1 = 6.28318530717958647692f * unit_open(c[3]);
-    n[0] = r0 * cosf(t0); // Box-Muller
-    n[1] = r0 * sinf(t0);
-    n[2] = r1 * cosf(t1);
+    box_muller3(c, n);
 }
 
 // ---- positions: one thread per source row (a split row's children need its scale and rotation)

@@ -235,6 +235,47 @@ void launch_densify_scatter(int64_t P, int sh_floats, const uint8_t* action, con
                             uint32_t* src_row, hipStream_t stream);
 // raw = min(raw, ceiling), m = v = 0, act = sigmoid(raw)
 void launch_opacity_reset(int64_t P, float ceiling, float* raw, float* m, float* v, float* act, hipStream_t stream);
+// ---- mcmc.hip : 3DGS-MCMC density control (relocation, growth, SGLD noise, the L1 regulariser) ----
+constexpr int      kMcmcScanTile    = 512;         // elements per workgroup of the u64 scan (256 lanes x 2), and its block-sums step
+constexpr int      kMcmcMaxN        = 51;          // the binomial table's rows: n_max <= 51
+constexpr uint32_t kMcmcTagRelocate = 0x4D430001u; // word 2 of the Philox counters (philox.hpp)
+constexpr uint32_t kMcmcTagAdd      = 0x4D430002u;
+constexpr uint32_t kMcmcTagNoise    = 0x4D430003u;
+// w[i] = dead ? 0 : (uint32_t)(sigmoid(raw opacity) * 2^24), dead = !(sigmoid > min_opacity); dead (nullable) = 0 | 1;
+// src_row (nullable) = i
+void launch_mcmc_weights(int64_t P, float min_opacity, const float* raw_opacity, uint32_t* w, uint32_t* dead, uint32_t* src_row,
+                         hipStream_t stream);
+// dead_list[dead_incl[i] - 1] = i for every dead row (dead_incl: inclusive sums of dead)
+void   launch_mcmc_dead_list(int64_t P, const uint32_t* dead, const uint32_t* dead_incl, uint32_t* dead_list, hipStream_t stream);
+size_t mcmc_scan_temp_bytes(int64_t n);
+// cdf[i] = w[0] + ... + w[i] in u64 (reduce / block sums / final, like scan.hip)
+void launch_mcmc_inclusive_sum_u64(const uint32_t* w, uint64_t* cdf, int64_t n, void* temp, hipStream_t stream);
+// draws 0 .. D - 1 (D = *d_n if d_n, else n_host; the launch is sized for n_launch): draw_src[j] = src_in ? src_in[j] : the
+// smallest i with cdf[i] > mulhi64(u_j, T), u_j = Philox(seed; j low, j high, tag, 0) words 0 | 1 << 32, T = cdf[P - 1];
+// count[draw_src[j]] += 1.  status[0] |= 1: an entry of src_in is >= P or has weight 0 (the draw is skipped); |= 2: T == 0
+// (no draw is made)
+void launch_mcmc_draw(int64_t P, int64_t n_launch, int64_t n_host, const uint32_t* d_n, const uint64_t* cdf, const uint32_t* w,
+                      const uint32_t* src_in, uint64_t seed, uint32_t tag, uint32_t* draw_src, uint32_t* count, uint32_t* status,
+                      hipStream_t stream);
+struct McmcRule {
+    float min_opacity;
+    int   n_max;
+};
+// K1: draw j writes row dst = dead_list ? dead_list[j] : dst_first + j from source draw_src[j]; src_row (nullable)
+// [dead_list ? dst : j] = the source.  K2: every row with count > 0, in place.  Run K1 first: it reads the sources' ORIGINAL
+// scale and opacity.
+void launch_mcmc_place(int64_t D, int sh_floats, const uint32_t* dead_list, int64_t dst_first, const uint32_t* draw_src,
+                       const uint32_t* count, const McmcRule& rule, const AdamArrays& raw, const AdamArrays& m, const AdamArrays& v,
+                       const AdamArrays& act, uint32_t* src_row, hipStream_t stream);
+void launch_mcmc_sources(int64_t P, int sh_floats, const uint32_t* count, const McmcRule& rule, const AdamArrays& raw,
+                         const AdamArrays& m, const AdamArrays& v, const AdamArrays& act, hipStream_t stream);
+// pos += (gain * g(o)) * Sigma eps in place (act_pos too when it is another array); noise: [P][3] or NULL (Philox keyed by seed,
+// row, step)
+void launch_mcmc_noise(int64_t P, float gain, float k, float x0, const float* raw_opacity, const float* raw_scale,
+                       const float* raw_rotq, const float* noise, uint64_t seed, uint32_t step, float* raw_pos, float* act_pos,
+                       hipStream_t stream);
+// d_opacity[i] += add_opacity, d_scale[i][c] += add_scale
+void launch_mcmc_regularize(int64_t P, float add_opacity, float add_scale, float* d_opacity, float* d_scale, hipStream_t stream);
 // ---- loss.hip : the 3DGS photometric loss, (1 - lambda) L1 + lambda (1 - SSIM), and its gradient ----
 // Both passes tile a channel into 32 x 16 outputs, one workgroup each; partial sums are indexed by workgroup.
 int64_t photometric_workgroups(int W, int H);

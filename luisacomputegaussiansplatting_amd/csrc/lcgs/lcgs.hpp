@@ -317,6 +317,33 @@ public:
     {
         check(lcgs_opacity_reset(m_dev->ctx(), num_gaussians, max_opacity, &raw, &m, &v, &activated));
     }
+    // 3DGS-MCMC density control (no reference counterpart), all in place: dead rows relocated onto live ones -> rows relocated;
+    // num_new rows appended behind num_gaussians (throws Error(LCGS_ERR_CAPACITY) when they do not fit); SGLD noise on the
+    // positions; the L1 regulariser's gradients.  Bind again (or lcgs_scene_modified) before the next frame.
+    int64_t mcmc_relocate(int num_gaussians, const lcgs_mcmc_config& cfg, const lcgs_params& raw, const lcgs_params& m,
+                          const lcgs_params& v, const lcgs_params& activated, const uint32_t* d_src_in = nullptr,
+                          uint32_t* d_src_row = nullptr, int sh_degree = 3)
+    {
+        int64_t n = 0;
+        check(lcgs_mcmc_relocate(m_dev->ctx(), num_gaussians, sh_degree, &cfg, &raw, &m, &v, &activated, d_src_in, d_src_row, &n));
+        return n;
+    }
+    void mcmc_add(int num_gaussians, const lcgs_mcmc_config& cfg, const lcgs_params& raw, const lcgs_params& m, const lcgs_params& v,
+                  const lcgs_params& activated, int64_t num_new, int64_t capacity, const uint32_t* d_src_in = nullptr,
+                  uint32_t* d_src_row = nullptr, int sh_degree = 3)
+    {
+        check(lcgs_mcmc_add(m_dev->ctx(), num_gaussians, sh_degree, &cfg, &raw, &m, &v, &activated, num_new, capacity, d_src_in,
+                            d_src_row));
+    }
+    void mcmc_noise(int num_gaussians, const lcgs_mcmc_noise_config& cfg, const lcgs_params& raw, const lcgs_params& activated,
+                    const float* d_noise = nullptr)
+    {
+        check(lcgs_mcmc_noise(m_dev->ctx(), num_gaussians, &cfg, &raw, &activated, d_noise));
+    }
+    void mcmc_regularize(int num_gaussians, const lcgs_grads& grads, float lambda_opacity = 0.01f, float lambda_scale = 0.01f)
+    {
+        check(lcgs_mcmc_regularize(m_dev->ctx(), num_gaussians, lambda_opacity, lambda_scale, &grads));
+    }
     // a scene from a point cloud (3DGS's create_from_pcd; no reference counterpart): the exact mean squared distance to the three
     // nearest neighbours, and the initial raw / activated rows built from it (nothing is bound; moments are the caller's to zero)
     void knn_mean_dist2(int64_t num_points, const float* d_pos, float* d_dist2)
