@@ -278,7 +278,7 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
     if (sliced) {
         LCGS_TRY(ctx->slice_bounds.ensure((lcgs::kMaxGradSlices + 1) * sizeof(uint32_t)));
         for (int k = 0; k < ctx->grad_slices; ++k)
-            if (!ctx->ev_slice[k]) LCGS_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_slice[k], hipEventDisableTiming));
+            LCGS_TRY(ctx->ev_slice[k].ensure());
         launch_slice_bounds(ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), (int64_t)P, ctx->grad_slices,
                             ctx->slice_bounds.as<uint32_t>(), zs); // (before the fill: ev_join / stream order covers it)
     }

@@ -1,4 +1,4 @@
-// abi_core.cpp -- the C ABI of liblcgs_hip.so (include/lcgs_hip.h), part 1: errors, device buffers, the context and its
+// abi_core.cpp -- the C ABI of liblcgs_hip.so (include/lcgs_hip.h), part 1: errors, the context and its
 // streams.  No compute happens on the host; if there is no GPU lcgs_create fails with LCGS_ERR_NO_DEVICE -- there is no CPU
 // fallback.  (The other parts: abi_internal.hpp.)
 #include <math.h>
@@ -30,36 +30,6 @@ lcgs_status hip_fail(hipError_t e, const char* what, const char* file, int line)
     return LCGS_ERR_HIP;
 }
 
-lcgs_status DeviceBuffer::ensure(size_t need)
-{
-    if (need <= bytes) return LCGS_OK;
-    // geometric growth, like ensure_*_temp_buffer (lcgs/src/gs_tile_splatter/impl.cpp:38-41)
-    size_t new_bytes = bytes == 0 ? need : std::max(need, bytes * 2);
-    new_bytes        = (new_bytes + 255) & ~(size_t)255;
-    if (ptr) {
-        LCGS_HIP_CHECK(hipFree(ptr));
-        ptr   = nullptr;
-        bytes = 0;
-    }
-    LCGS_HIP_CHECK(hipMalloc(&ptr, new_bytes));
-    bytes = new_bytes;
-    // test hook: fresh workspace starts as garbage instead of whatever the allocator hands out (usually zeros), so
-    // that a kernel reading what no kernel wrote shows up in the parity tests
-    static const bool poison = getenv("LCGS_POISON") != nullptr;
-    if (poison) {
-        LCGS_HIP_CHECK(hipMemset(ptr, 0xA5, new_bytes)); // (legacy stream: not ordered against non-blocking streams,
-        LCGS_HIP_CHECK(hipDeviceSynchronize());          //  so finish it before anybody writes real data)
-    }
-    return LCGS_OK;
-}
-
-void DeviceBuffer::release()
-{
-    if (ptr) (void)hipFree(ptr);
-    ptr   = nullptr;
-    bytes = 0;
-}
-
 } // namespace lcgs
 
 using namespace lcgs;
@@ -87,11 +57,8 @@ lcgs_status mark(lcgs_context* ctx, const char* name)
         fprintf(stderr, "[lcgs %p] %s done\n", (void*)ctx, name);
     }
     if (!ctx->profiling) return LCGS_OK;
-    if (!ctx->events_created) {
-        for (int i = 0; i < kMaxEvents; ++i) LCGS_HIP_CHECK(hipEventCreate(&ctx->events[i]));
-        ctx->events_created = true;
-    }
     if (ctx->n_marks >= kMaxEvents) return LCGS_OK;
+    LCGS_TRY(ctx->events[ctx->n_marks].ensure(0)); // (the timing kind)
     ctx->mark_names[ctx->n_marks] = name;
     LCGS_HIP_CHECK(hipEventRecord(ctx->events[ctx->n_marks], ctx->stream));
     ctx->n_marks++;
@@ -213,24 +180,21 @@ lcgs_status lcgs::abi::create_context(int device_id, void* stream, hipStream_t b
     if (const char* e = getenv("LCGS_STAGE_SORT")) ctx->stage_sort = e[0] == 'l' ? 1 : (e[0] == 's' ? 2 : 0); // test hook
     // The auxiliary stream has the LOWEST dispatch priority: its bandwidth-bound workgroups fill the gaps the main
     // stream's short, latency-bound kernels leave instead of competing with them.
-    hipError_t se = hipSuccess;
+    lcgs_status made = LCGS_OK;
     if (borrowed_aux) {
-        ctx->aux_stream   = borrowed_aux;
-        ctx->aux_borrowed = true;
+        ctx->aux_stream.borrow(borrowed_aux);
     } else {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi); // lo = numerically greatest = lowest priority
-        se = hipStreamCreateWithPriority(&ctx->aux_stream, hipStreamNonBlocking, lo);
-        if (se != hipSuccess) se = hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking);
+        made = ctx->aux_stream.ensure_priority(lo);
     }
-    for (hipEvent_t* ev : { &ctx->ev_fork, &ctx->ev_join, &ctx->ev_ranges, &ctx->ev_aux_done, &ctx->ev_render, &ctx->ev_counts,
-                            &ctx->ev_g2d_zero, &ctx->ev_pipe_entry, &ctx->ev_pipe_render[0], &ctx->ev_pipe_render[1],
-                            &ctx->ev_pipe_aux[0], &ctx->ev_pipe_aux[1], &ctx->ev_cull })
-        if (se == hipSuccess) se = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-    if (se != hipSuccess) {
-        lcgs_status s = hip_fail(se, "aux stream / events", __FILE__, __LINE__);
-        (void)lcgs_destroy(ctx); // releases whichever of the stream / events were created
-        return s;
+    for (Event* ev : { &ctx->ev_fork, &ctx->ev_join, &ctx->ev_ranges, &ctx->ev_aux_done, &ctx->ev_render, &ctx->ev_counts,
+                       &ctx->ev_pipe_entry, &ctx->ev_pipe_render[0], &ctx->ev_pipe_render[1], &ctx->ev_pipe_aux[0],
+                       &ctx->ev_pipe_aux[1], &ctx->ev_cull })
+        if (made == LCGS_OK) made = ev->ensure();
+    if (made != LCGS_OK) {
+        delete ctx;
+        return made;
     }
     abi::registry_add(ctx);
     *out_ctx    = ctx;
@@ -251,69 +215,16 @@ lcgs_status lcgs_destroy(lcgs_context* ctx)
         ctx->comm = nullptr;
     }
     if (ctx->twin) {
-        ctx->twin->sh_half.ptr    = nullptr; // borrowed from this context
-        ctx->twin->scene_perm.ptr = nullptr; // likewise
         (void)lcgs_destroy(ctx->twin);
         ctx->twin = nullptr;
     }
-    for (hipEvent_t ev : { ctx->ev_batch_fork, ctx->ev_batch_join })
-        if (ev) (void)hipEventDestroy(ev);
+    // every stream first, then the members free themselves
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->head_stream) (void)hipStreamSynchronize(ctx->head_stream);
-    if (ctx->cull_stream) (void)hipStreamSynchronize(ctx->cull_stream);
-    if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
-    DeviceBuffer* bufs[] = { &ctx->recs, &ctx->recs_b, &ctx->cull_counts, &ctx->pairv[2], &ctx->sortk[0], &ctx->sortk[1], &ctx->sortv[0], &ctx->sortv[1], &ctx->vis_index,
-                             &ctx->rects, &ctx->rects_sorted, &ctx->cull_slab, &ctx->chunk_info, &ctx->chunk_base, &ctx->pairk[0], &ctx->pairk[1], &ctx->pairv[0],
-                             &ctx->pairv[1], &ctx->zero_ws[0], &ctx->zero_ws[1], &ctx->zero_ws[2], &ctx->counts, &ctx->sort_ws,
-                             &ctx->expand_ws, &ctx->final_T, &ctx->n_contrib, &ctx->list_idx, &ctx->grads2d, &ctx->tile_order[0], &ctx->tile_order[1], &ctx->st_keys_tmp,
-                             &ctx->st_vals_tmp, &ctx->st_sort_temp, &ctx->st_scan_temp, &ctx->st_scalar, &ctx->sh_half, &ctx->strip_masks, &ctx->shjac, &ctx->tie_ws, &ctx->fused_grads, &ctx->bwd_counter, &ctx->st_flags, &ctx->st_keys_exp, &ctx->st_vals_exp,
-                             &ctx->st_u32[0], &ctx->st_u32[1], &ctx->st_u32[2], &ctx->st_u32[3], &ctx->st_u32[4], &ctx->st_u32[5], &ctx->st_u32[6], &ctx->st_u32[7],
-                             &ctx->cull_bound_buf, &ctx->verify_ws, &ctx->st_win, &ctx->st_win2, &ctx->st_offs, &ctx->dn_emit, &ctx->dn_incl, &ctx->dn_action,
-                             &ctx->mc_w, &ctx->mc_dead, &ctx->mc_dead_incl, &ctx->mc_cdf, &ctx->mc_count, &ctx->mc_dead_list, &ctx->mc_draw, &ctx->mc_scan_temp, &ctx->mc_status,
-                             &ctx->knn_keys[0], &ctx->knn_keys[1], &ctx->knn_vals[0], &ctx->knn_vals[1], &ctx->knn_sort_ws, &ctx->knn_sorted,
-                             &ctx->knn_boxes, &ctx->knn_grid, &ctx->knn_dist2 };
-    for (DeviceBuffer* b : bufs) b->release();
-    for (auto& s : ctx->owner)
-        for (DeviceBuffer* b : { &s.vis, &s.shjac, &s.counts }) b->release();
-    for (auto& l : ctx->owner_lane) {
-        if (l.stream) {
-            (void)hipStreamSynchronize(l.stream);
-            (void)hipStreamDestroy(l.stream);
-        }
-        if (l.done) (void)hipEventDestroy(l.done);
-        for (DeviceBuffer* b : { &l.slab, &l.chunk_info, &l.chunk_base, &l.sortk[0], &l.sortk[1], &l.sortv[0], &l.sortv[1], &l.rects,
-                                 &l.sort_ws })
-            b->release();
-    }
-    if (ctx->ev_owner_fork) (void)hipEventDestroy(ctx->ev_owner_fork);
-    for (auto& b : ctx->owned) b.release();
+    for (const Stream* st : { &ctx->head_stream, &ctx->cull_stream, &ctx->aux_stream })
+        if (*st) (void)hipStreamSynchronize(*st);
+    for (const auto& l : ctx->owner_lane)
+        if (l.stream) (void)hipStreamSynchronize(l.stream);
     if (ctx->graph_exec) (void)hipGraphExecDestroy(ctx->graph_exec);
-    if (ctx->aux_stream) {
-        (void)hipStreamSynchronize(ctx->aux_stream);
-        if (!ctx->aux_borrowed) (void)hipStreamDestroy(ctx->aux_stream);
-    }
-    if (ctx->head_stream) (void)hipStreamDestroy(ctx->head_stream); // (synchronised above, with the others)
-    if (ctx->cull_stream) (void)hipStreamDestroy(ctx->cull_stream);
-    for (hipEvent_t ev : { ctx->ev_fork, ctx->ev_join, ctx->ev_ranges, ctx->ev_aux_done, ctx->ev_render, ctx->ev_counts,
-                           ctx->ev_g2d_zero, ctx->ev_pipe_entry, ctx->ev_pipe_render[0], ctx->ev_pipe_render[1],
-                           ctx->ev_pipe_aux[0], ctx->ev_pipe_aux[1], ctx->ev_cull })
-        if (ev) (void)hipEventDestroy(ev);
-    ctx->fit_img.release();
-    ctx->fit_dL.release();
-    ctx->loss_ws.release();
-    ctx->cam_slab.release();
-    ctx->contrib_slab.release();
-    if (ctx->ev_fit_bwd) (void)hipEventDestroy(ctx->ev_fit_bwd);
-    ctx->frame_params.release();
-    ctx->slice_bounds.release();
-    ctx->scene_perm.release();
-    for (hipEvent_t ev : ctx->ev_slice)
-        if (ev) (void)hipEventDestroy(ev);
-    if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);
-    if (ctx->h_owner_counts) (void)hipHostFree(ctx->h_owner_counts);
-    if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-    if (ctx->events_created)
-        for (auto& ev : ctx->events) (void)hipEventDestroy(ev);
     delete ctx;
     return LCGS_OK;
 }

@@ -51,20 +51,18 @@ lcgs_status ensure_fused_workspace(lcgs_context* ctx, const CamParams& cp, bool 
     }
     const size_t G = (size_t)cp.grid_x * cp.grid_y;
     auto         al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // (b0: the chained scan's state block, gone with the scan; b1: the tile ranges + the persistent renderers' tile counters)
-    const size_t b0 = 0, b1 = al(G * 2 * 4) + 256;
+    const size_t b1 = al(G * 2 * 4) + 256; // the tile ranges + the persistent renderers' tile counters
     for (int i = 0; i < 3; ++i) {
         const void* before = ctx->zero_ws[i].ptr;
-        LCGS_TRY(ctx->zero_ws[i].ensure(b0 + b1));
-        if (ctx->zero_ws[i].ptr != before || ctx->zero_bytes != b0 + b1) ctx->zero_ready[i] = false;
+        LCGS_TRY(ctx->zero_ws[i].ensure(b1));
+        if (ctx->zero_ws[i].ptr != before || ctx->zero_bytes != b1) ctx->zero_ready[i] = false;
     }
     for (int i = 0; i < 2; ++i) {
         const void* before = ctx->tile_order[i].ptr;
         LCGS_TRY(ctx->tile_order[i].ensure(G * 8)); // (G slots + the sorted blocks of a per-block schedule: render.hip k_tile_order)
         if (ctx->tile_order[i].ptr != before) ctx->order_G = 0;
     }
-    ctx->zero_scan_bytes = b0;
-    ctx->zero_bytes      = b0 + b1;
+    ctx->zero_bytes = b1;
     {
         // the counter block starts zeroed: words [6] / [7] (overflow since the last read-back) are only ever added to
         const void* before = ctx->counts.ptr;
@@ -84,8 +82,7 @@ lcgs_status ensure_fused_workspace(lcgs_context* ctx, const CamParams& cp, bool 
             LCGS_HIP_CHECK(hipMemsetAsync(ctx->bwd_counter.ptr, 0, 256, ctx->stream));
         }
     }
-    if (!ctx->h_counts) LCGS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_counts), 64, hipHostMallocDefault));
-    return LCGS_OK;
+    return ctx->h_counts.ensure(64);
 }
 
 // The head stream exists from the first frame that needs it -- a pipelined frame, or a batch: the SIBLING context of camera
@@ -94,8 +91,7 @@ lcgs_status ensure_fused_workspace(lcgs_context* ctx, const CamParams& cp, bool 
 // camera batch lost 12 % (profiles/pipelined_frames_ab.txt).  Default priority (the highest was measured: inside the noise).
 lcgs_status ensure_head_stream(lcgs_context* ctx)
 {
-    if (!ctx->head_stream) LCGS_HIP_CHECK(hipStreamCreateWithFlags(&ctx->head_stream, hipStreamNonBlocking));
-    return LCGS_OK;
+    return ctx->head_stream.ensure();
 }
 
 // The cull stream exists from the first frame that culls early, or from the first batch, whose sibling context takes it for
@@ -105,11 +101,7 @@ static lcgs_status ensure_cull_stream(lcgs_context* ctx)
     if (ctx->cull_stream) return LCGS_OK;
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (hipStreamCreateWithPriority(&ctx->cull_stream, hipStreamNonBlocking, lo) != hipSuccess) {
-        (void)hipGetLastError();
-        LCGS_HIP_CHECK(hipStreamCreateWithFlags(&ctx->cull_stream, hipStreamNonBlocking));
-    }
-    return LCGS_OK;
+    return ctx->cull_stream.ensure_priority(lo);
 }
 
 lcgs_status join_aux_stream(lcgs_context* ctx)
@@ -124,7 +116,7 @@ lcgs_status use_zero_block(lcgs_context* ctx, int zb, bool cleared, hipStream_t 
 {
     if (!cleared) LCGS_HIP_CHECK(hipMemsetAsync(ctx->zero_ws[zb].ptr, 0, ctx->zero_bytes, st));
     ctx->zero_ready[zb] = false;
-    ctx->ranges         = reinterpret_cast<uint32_t*>(ctx->zero_ws[zb].as<char>() + ctx->zero_scan_bytes);
+    ctx->ranges         = ctx->zero_ws[zb].as<uint32_t>();
     ctx->work_counters  = reinterpret_cast<uint32_t*>(ctx->zero_ws[zb].as<char>() + ctx->zero_bytes - 256);
     return LCGS_OK;
 }
@@ -638,8 +630,8 @@ lcgs_status prepare_twin(lcgs_context* ctx)
 {
     if (!ctx->twin) {
         LCGS_TRY(ensure_head_stream(ctx));
-        LCGS_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_batch_fork, hipEventDisableTiming));
-        LCGS_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_batch_join, hipEventDisableTiming));
+        LCGS_TRY(ctx->ev_batch_fork.ensure());
+        LCGS_TRY(ctx->ev_batch_join.ensure());
         LCGS_TRY(ensure_cull_stream(ctx));
         LCGS_TRY(create_context(ctx->device, ctx->head_stream, ctx->cull_stream, &ctx->twin));
     }
@@ -663,13 +655,11 @@ lcgs_status prepare_twin(lcgs_context* ctx)
         t->foreign_writes.fetch_and(~lcgs_context::kRowsStale, std::memory_order_acq_rel);
         registry_publish(t);
         // the sibling renders the same (possibly re-ordered) arrays: it borrows their permutation for the order of equal depths
-        t->scene_perm.ptr   = ctx->scene_perm.ptr;
-        t->scene_perm.bytes = 0;
-        t->perm_valid       = ctx->perm_valid;
-        if (ctx->use_half_sh) { // the sibling reads the same f16 copy (not owned: never grown or freed through it)
-            t->sh_half.ptr   = ctx->sh_half.ptr;
-            t->sh_half.bytes = 0;
-            t->use_half_sh   = true;
+        t->scene_perm.borrow(ctx->scene_perm);
+        t->perm_valid = ctx->perm_valid;
+        if (ctx->use_half_sh) { // the sibling reads the same f16 copy
+            t->sh_half.borrow(ctx->sh_half);
+            t->use_half_sh = true;
         }
         // launch sizes and pair capacity learnt by the synchronised frames of this context serve the sibling too
         t->hint_V        = std::max(t->hint_V, ctx->hint_V);

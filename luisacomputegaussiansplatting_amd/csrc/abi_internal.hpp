@@ -1,7 +1,8 @@
 // abi_internal.hpp -- what the translation units behind the C ABI share: the context (context.hpp), the small helpers of
 // abi_core.cpp and the frame / sibling plumbing of abi_frame.cpp.  The C ABI itself is split by subject (round 4; one
 // 1 700-line file until then), every exported symbol unchanged:
-//   abi_core.cpp      errors, device buffers, context create / destroy, stream, synchronise, profiling, stats, debug hooks
+//   abi_core.cpp      errors, context create / destroy, stream, synchronise, profiling, stats, debug hooks
+//   device_owned.cpp  the owning types of common.hpp (device buffer, event, stream, pinned block): nothing else frees
 //   abi_stages.cpp    the reference's three operators + the two lcpp primitives (stage level), deferred stage mode
 //   abi_scene.cpp     scene bind / upload / download / PLY ingest / spatial re-order / f16 SH / LOD
 //   abi_frame.cpp     the fused frame: workspace, enqueue, lcgs_render_forward, camera batches, the sibling context

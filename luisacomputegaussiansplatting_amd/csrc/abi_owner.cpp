@@ -140,12 +140,12 @@ lcgs_status lcgs_owner_project_views(lcgs_context* ctx, int first_slot, int num_
     // lanes: scratch sized by the row range, a stream and an event each; every lane starts behind what the context's stream
     // holds now (the caller's writes to the scene, an optimiser step) and the context's stream continues behind every lane
     const size_t n = (size_t)row_count, chunks = (size_t)cull_chunk_count(row_count);
-    if (!ctx->ev_owner_fork) LCGS_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_owner_fork, hipEventDisableTiming));
+    LCGS_TRY(ctx->ev_owner_fork.ensure());
     LCGS_HIP_CHECK(hipEventRecord(ctx->ev_owner_fork, ctx->stream));
     for (int l = 0; l < lanes; ++l) {
         auto& L = ctx->owner_lane[l];
-        if (!L.stream) LCGS_HIP_CHECK(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-        if (!L.done) LCGS_HIP_CHECK(hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
+        LCGS_TRY(L.stream.ensure());
+        LCGS_TRY(L.done.ensure());
         LCGS_TRY(L.slab.ensure(chunks * 2048 * 16));
         LCGS_TRY(L.chunk_info.ensure(chunks * 8));
         LCGS_TRY(L.chunk_base.ensure(chunks * 4));
@@ -177,8 +177,7 @@ lcgs_status lcgs_owner_counts(lcgs_context* ctx, int first_slot, int num_slots, 
     LCGS_REQUIRE(first_slot >= 0 && num_slots >= 0 && first_slot + num_slots <= LCGS_MAX_OWNER_VIEWS, "slots out of range");
     LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
-    if (!ctx->h_owner_counts)
-        LCGS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_owner_counts), LCGS_MAX_OWNER_VIEWS * 4, hipHostMallocDefault));
+    LCGS_TRY(ctx->h_owner_counts.ensure(LCGS_MAX_OWNER_VIEWS * 4));
     bool pending = false;
     for (int k = 0; k < num_slots; ++k) {
         auto& s = ctx->owner[first_slot + k];

@@ -15,6 +15,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "abi_internal.hpp"
@@ -327,15 +328,15 @@ lcgs_status lcgs_scene_reorder_spatial(lcgs_context* ctx, uint32_t* d_perm)
     hipStream_t   st = ctx->stream;
     const int64_t P  = ctx->P;
     // ---- the box: mean +- 4 sigma per axis (finite positions only), 1024 cells per axis
-    DeviceBuffer partial;
-    const int    nb = pos_moment_blocks();
-    LCGS_TRY(partial.ensure((size_t)nb * 7 * sizeof(double)));
-    launch_pos_moments(P, ctx->pos, partial.as<double>(), st);
+    const int           nb = pos_moment_blocks();
     std::vector<double> h((size_t)nb * 7);
-    hipError_t          e = hipMemcpyAsync(h.data(), partial.ptr, h.size() * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    partial.release();
-    LCGS_HIP_CHECK(e);
+    {
+        DeviceBuffer partial;
+        LCGS_TRY(partial.ensure((size_t)nb * 7 * sizeof(double)));
+        launch_pos_moments(P, ctx->pos, partial.as<double>(), st);
+        LCGS_HIP_CHECK(hipMemcpyAsync(h.data(), partial.ptr, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        LCGS_HIP_CHECK(hipStreamSynchronize(st));
+    }
     double acc[7] = { 0, 0, 0, 0, 0, 0, 0 };
     for (int b = 0; b < nb; ++b)
         for (int k = 0; k < 7; ++k) acc[k] += h[(size_t)b * 7 + k];
@@ -347,76 +348,43 @@ lcgs_status lcgs_scene_reorder_spatial(lcgs_context* ctx, uint32_t* d_perm)
         lo[a]    = (float)(mean - half);
         cells[a] = (float)(1024.0 / (2.0 * half));
     }
-    // ---- keys, stable sort, gather
-    DeviceBuffer keys[2], vals[2], ws, fresh[5];
-    auto         drop = [&]() {
-        for (int i = 0; i < 2; ++i) {
-            keys[i].release();
-            vals[i].release();
-        }
-        ws.release();
-    };
-    lcgs_status s = LCGS_OK;
-    for (int i = 0; i < 2 && s == LCGS_OK; ++i) {
-        s = keys[i].ensure((size_t)P * 4);
-        if (s == LCGS_OK) s = vals[i].ensure((size_t)P * 4);
-    }
-    if (s == LCGS_OK) s = ws.ensure(pair_sort_ws_bytes(P));
+    // ---- keys, stable sort, gather (a failed call frees what it allocated: HIP drains the device before it frees)
+    DeviceBuffer    fresh[5], kept_perm;
     const RowFloats rowf = row_floats(ctx->sh_deg);
-    for (int i = 0; i < 5 && s == LCGS_OK; ++i) s = fresh[i].ensure(std::max<size_t>((size_t)P * rowf[i] * 4, 16));
-    if (s != LCGS_OK) {
-        drop();
-        for (DeviceBuffer& b : fresh) b.release();
-        return s;
-    }
-    launch_morton_keys(P, ctx->pos, lo, cells, keys[0].as<uint32_t>(), vals[0].as<uint32_t>(), st);
-    const int where = launch_pair_sort_u32(keys[0].as<uint32_t>(), keys[1].as<uint32_t>(), vals[0].as<uint32_t>(),
-                                           vals[1].as<uint32_t>(), nullptr, P, P, 0, 30, ws.ptr, st);
-    const uint32_t* perm   = vals[where].as<uint32_t>();
-    const float*    src[5] = { ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->opacity };
-    for (int i = 0; i < 5; ++i) launch_gather_rows(P, (int)rowf[i], perm, src[i], fresh[i].as<float>(), st);
-    e = hipGetLastError();
-    DeviceBuffer kept_perm;
-    if (e == hipSuccess && kept_perm.ensure((size_t)P * 4) != LCGS_OK) e = hipErrorOutOfMemory;
-    if (e == hipSuccess) e = hipMemcpyAsync(kept_perm.ptr, perm, (size_t)P * 4, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && d_perm) e = hipMemcpyAsync(d_perm, perm, (size_t)P * 4, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    drop();
-    if (e != hipSuccess) {
-        for (DeviceBuffer& b : fresh) b.release();
-        kept_perm.release();
-        LCGS_HIP_CHECK(e);
+    {
+        DeviceBuffer keys[2], vals[2], ws; // (gone before the composed permutation below is allocated)
+        for (int i = 0; i < 2; ++i) {
+            LCGS_TRY(keys[i].ensure((size_t)P * 4));
+            LCGS_TRY(vals[i].ensure((size_t)P * 4));
+        }
+        LCGS_TRY(ws.ensure(pair_sort_ws_bytes(P)));
+        for (int i = 0; i < 5; ++i) LCGS_TRY(fresh[i].ensure(std::max<size_t>((size_t)P * rowf[i] * 4, 16)));
+        launch_morton_keys(P, ctx->pos, lo, cells, keys[0].as<uint32_t>(), vals[0].as<uint32_t>(), st);
+        const int where = launch_pair_sort_u32(keys[0].as<uint32_t>(), keys[1].as<uint32_t>(), vals[0].as<uint32_t>(),
+                                               vals[1].as<uint32_t>(), nullptr, P, P, 0, 30, ws.ptr, st);
+        const uint32_t* perm   = vals[where].as<uint32_t>();
+        const float*    src[5] = { ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->opacity };
+        for (int i = 0; i < 5; ++i) launch_gather_rows(P, (int)rowf[i], perm, src[i], fresh[i].as<float>(), st);
+        LCGS_HIP_CHECK(hipGetLastError());
+        LCGS_TRY(kept_perm.ensure((size_t)P * 4));
+        LCGS_HIP_CHECK(hipMemcpyAsync(kept_perm.ptr, perm, (size_t)P * 4, hipMemcpyDeviceToDevice, st));
+        if (d_perm) LCGS_HIP_CHECK(hipMemcpyAsync(d_perm, perm, (size_t)P * 4, hipMemcpyDeviceToDevice, st));
+        LCGS_HIP_CHECK(hipStreamSynchronize(st));
     }
     // ---- the context now owns (and renders from) the re-ordered copy
     const bool half = ctx->use_half_sh, had_perm = ctx->perm_valid;
-    for (int i = 0; i < 5; ++i) {
-        ctx->owned[i].release();
-        ctx->owned[i] = fresh[i];
-    }
+    for (int i = 0; i < 5; ++i) ctx->owned[i] = std::move(fresh[i]);
     LCGS_TRY(lcgs_scene_bind(ctx, ctx->P, ctx->sh_deg, ctx->owned[0].as<float>(), ctx->owned[1].as<float>(),
                              ctx->owned[2].as<float>(), ctx->owned[3].as<float>(), ctx->owned[4].as<float>()));
     // the permutation stays with the context (composed with an earlier one: file index of every row)
     if (had_perm) {
         DeviceBuffer composed;
-        lcgs_status  cs = composed.ensure((size_t)P * 4);
-        if (cs == LCGS_OK) {
-            launch_gather_rows(P, 1, kept_perm.as<uint32_t>(), ctx->scene_perm.as<float>(), composed.as<float>(), st);
-            hipError_t ce = hipStreamSynchronize(st);
-            kept_perm.release();
-            if (ce != hipSuccess) {
-                composed.release();
-                LCGS_HIP_CHECK(ce);
-            }
-            ctx->scene_perm.release();
-            ctx->scene_perm = composed;
-        } else {
-            kept_perm.release();
-            return cs;
-        }
-    } else {
-        ctx->scene_perm.release();
-        ctx->scene_perm = kept_perm;
+        LCGS_TRY(composed.ensure((size_t)P * 4));
+        launch_gather_rows(P, 1, kept_perm.as<uint32_t>(), ctx->scene_perm.as<float>(), composed.as<float>(), st);
+        LCGS_HIP_CHECK(hipStreamSynchronize(st));
+        kept_perm = std::move(composed);
     }
+    ctx->scene_perm     = std::move(kept_perm);
     ctx->perm_valid     = true;
     ctx->perm_for_owned = true;
     if (half) LCGS_TRY(lcgs_scene_use_half_sh(ctx, 1)); // the f16 copy follows the new order
@@ -513,58 +481,48 @@ lcgs_status lcgs_scene_load_ply(lcgs_context* ctx, const char* path, int* num_ga
             set_last_error(std::string("cannot map ") + path);
             return LCGS_ERR_IO;
         }
+        struct Unmap {
+            void*  p;
+            size_t n;
+            ~Unmap() { munmap(p, n); }
+        } unmap{ map, map_bytes };
         (void)madvise(map, map_bytes, MADV_SEQUENTIAL);
         const unsigned char* payload = static_cast<const unsigned char*>(map) + probe.payload_offset;
         const int64_t        chunk   = std::max<int64_t>(1, ((int64_t)64 << 20) / (int64_t)probe.stride); // records
         const size_t         cbytes  = (size_t)chunk * probe.stride;
-        unsigned char*       pinned[2] = { nullptr, nullptr };
-        hipEvent_t           done[2]   = { nullptr, nullptr };
-        DeviceBuffer         d_raw[2];
-        lcgs_status          st = LCGS_OK;
-        auto                 cleanup = [&]() {
-            for (int i = 0; i < 2; ++i) {
-                if (pinned[i]) (void)hipHostFree(pinned[i]);
-                if (done[i]) (void)hipEventDestroy(done[i]);
-                d_raw[i].release();
-            }
-            munmap(map, map_bytes);
-        };
-        for (int i = 0; i < 2 && st == LCGS_OK; ++i) {
-            if (hipHostMalloc(reinterpret_cast<void**>(&pinned[i]), cbytes, hipHostMallocDefault) != hipSuccess ||
-                hipEventCreateWithFlags(&done[i], hipEventDisableTiming) != hipSuccess)
-                st = LCGS_ERR_OUT_OF_MEMORY;
-            else
-                st = d_raw[i].ensure(cbytes);
+        // (a failed call below frees these with copies still in flight: HIP drains the device before it frees)
+        Pinned<unsigned char> pinned[2];
+        Event                 done[2];
+        DeviceBuffer          d_raw[2];
+        for (int i = 0; i < 2; ++i) {
+            LCGS_TRY(pinned[i].ensure(cbytes));
+            LCGS_TRY(done[i].ensure());
+            LCGS_TRY(d_raw[i].ensure(cbytes));
         }
         PlyColumns cols;
         for (int w = 0; w < 59; ++w) cols.offset[w] = probe.column_offset[w];
         int b = 0;
-        for (int64_t first = 0; first < N && st == LCGS_OK; first += chunk, b ^= 1) {
+        for (int64_t first = 0; first < N; first += chunk, b ^= 1) {
             const int64_t count = std::min<int64_t>(chunk, N - first);
             const size_t  bytes = (size_t)count * probe.stride;
-            if (first >= 2 * chunk && hipEventSynchronize(done[b]) != hipSuccess) st = LCGS_ERR_HIP; // buffer b is free again
-            if (st != LCGS_OK) break;
+            if (first >= 2 * chunk) LCGS_HIP_CHECK(hipEventSynchronize(done[b])); // buffer b is free again
             // page cache -> pinned memory with a few threads (one memcpy stream tops out well below PCIe rate)
             const unsigned char* src = payload + (size_t)first * probe.stride;
+            unsigned char*       dst = pinned[b];
             const int            nt  = 8;
             std::vector<std::thread> th;
             for (int t = 0; t < nt; ++t) {
                 const size_t a = bytes * t / nt, e = bytes * (t + 1) / nt;
-                th.emplace_back([=] { memcpy(pinned[b] + a, src + a, e - a); });
+                th.emplace_back([=] { memcpy(dst + a, src + a, e - a); });
             }
             for (auto& x : th) x.join();
-            if (hipMemcpyAsync(d_raw[b].ptr, pinned[b], bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) st = LCGS_ERR_HIP;
+            LCGS_HIP_CHECK(hipMemcpyAsync(d_raw[b].ptr, dst, bytes, hipMemcpyHostToDevice, ctx->stream));
             launch_ply_activate(d_raw[b].as<unsigned char>(), first, count, (uint32_t)probe.stride, cols,
                                 ctx->owned[0].as<float>(), ctx->owned[1].as<float>(), ctx->owned[2].as<float>(),
                                 ctx->owned[3].as<float>(), ctx->owned[4].as<float>(), ctx->stream);
-            if (hipEventRecord(done[b], ctx->stream) != hipSuccess) st = LCGS_ERR_HIP;
+            LCGS_HIP_CHECK(hipEventRecord(done[b], ctx->stream));
         }
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess && st == LCGS_OK) st = LCGS_ERR_HIP;
-        cleanup();
-        if (st != LCGS_OK) {
-            if (st == LCGS_ERR_HIP) set_last_error("device ingest of the PLY payload failed");
-            return st;
-        }
+        LCGS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
     if (num_gaussians) *num_gaussians = (int)N;
     LCGS_TRY(lcgs_scene_bind(ctx, (int)N, 3, ctx->owned[0].as<float>(), ctx->owned[1].as<float>(), ctx->owned[2].as<float>(),

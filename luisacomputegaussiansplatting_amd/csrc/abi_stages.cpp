@@ -251,7 +251,7 @@ lcgs_status lcgs_tile_splat_forward(lcgs_context* ctx, const lcgs_tile_accel* ac
     if (!ctx->h_stage) {
         // (coherent + mapped, asked for explicitly: the host polls this block while the stream that posts to it is still
         // running -- the hand-off must not depend on what HIP_HOST_COHERENT makes of a default allocation)
-        LCGS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_stage), 16, hipHostMallocCoherent | hipHostMallocMapped));
+        LCGS_TRY(ctx->h_stage.ensure(16, hipHostMallocCoherent | hipHostMallocMapped));
         memset(ctx->h_stage, 0, 16);
         if (hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->h_stage_dev), ctx->h_stage, 0) != hipSuccess) {
             (void)hipGetLastError();

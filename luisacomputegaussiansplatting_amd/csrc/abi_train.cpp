@@ -80,7 +80,7 @@ lcgs_status lcgs_fit_views(lcgs_context* ctx, int num_views, const lcgs_camera* 
         const size_t img_bytes = (size_t)cameras[j].width * cameras[j].height * 3 * sizeof(float);
         LCGS_TRY(c->fit_img.ensure(img_bytes));
         LCGS_TRY(c->fit_dL.ensure(img_bytes));
-        if (!c->ev_fit_bwd) LCGS_HIP_CHECK(hipEventCreateWithFlags(&c->ev_fit_bwd, hipEventDisableTiming));
+        LCGS_TRY(c->ev_fit_bwd.ensure());
         LCGS_TRY(lcgs_render_forward(c, &cameras[j], bg_color, scale_modifier, c->fit_img.as<float>(), nullptr, 1, nullptr));
         if (ctx->fit_loss == LCGS_LOSS_PHOTOMETRIC)
             LCGS_TRY(lcgs_photometric_loss_backward(c, cameras[j].width, cameras[j].height, c->fit_img.as<float>(), d_targets[j],

@@ -30,15 +30,98 @@ lcgs_status hip_fail(hipError_t e, const char* what, const char* file, int line)
         }                                                        \
     } while (0)
 
+// The one ownership rule of the host code: a member or local that owns a device resource releases it in its destructor.
+// The owning types below are move-only (a move leaves the source empty); one that BORROWS somebody else's resource never
+// releases it.  None may live at namespace scope: their destructors call into the HIP runtime.  (Bodies: device_owned.cpp.)
+
 // A device allocation that only ever grows (geometric growth, like the reference's
 // ensure_*_temp_buffer, lcgs/src/gs_tile_splatter/impl.cpp:31-61).
 struct DeviceBuffer {
     void*  ptr   = nullptr;
     size_t bytes = 0;
-    lcgs_status ensure(size_t need);
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer&& o) noexcept : ptr(o.ptr), bytes(o.bytes), borrowed(o.borrowed) { o.forget(); }
+    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept
+    {
+        if (this != &o) {
+            release();
+            ptr = o.ptr, bytes = o.bytes, borrowed = o.borrowed;
+            o.forget();
+        }
+        return *this;
+    }
+    DeviceBuffer(const DeviceBuffer&)            = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() { release(); }
+    lcgs_status ensure(size_t need); // (on a borrowed buffer: LCGS_ERR_STATE, the lender's memory is not touched)
     void        release();
+    // reads the lender's memory where it lies now: never grown or freed through this buffer
+    void borrow(const DeviceBuffer& lender)
+    {
+        release();
+        ptr = lender.ptr, bytes = lender.bytes, borrowed = true;
+    }
     template <typename T>
     T* as() const { return reinterpret_cast<T*>(ptr); }
+
+private:
+    bool borrowed = false;
+    void forget() { ptr = nullptr, bytes = 0, borrowed = false; }
+};
+
+// An event, a stream or a pinned host block: owned (made by ensure()) or borrowed; converts to the raw handle for the HIP calls.
+template <typename H, void (*Drop)(H)>
+struct Handle {
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h(o.h), borrowed(o.borrowed) { o.forget(); }
+    Handle& operator=(Handle&& o) noexcept
+    {
+        if (this != &o) {
+            release();
+            h = o.h, borrowed = o.borrowed;
+            o.forget();
+        }
+        return *this;
+    }
+    Handle(const Handle&)            = delete;
+    Handle& operator=(const Handle&) = delete;
+    ~Handle() { release(); }
+    void release()
+    {
+        if (h && !borrowed) Drop(h);
+        forget();
+    }
+    void borrow(H other)
+    {
+        release();
+        h = other, borrowed = true;
+    }
+    operator H() const { return h; }
+
+protected:
+    H    h        = nullptr;
+    bool borrowed = false;
+    void forget() { h = nullptr, borrowed = false; }
+};
+void drop_event(hipEvent_t ev);
+void drop_stream(hipStream_t st);
+void drop_pinned(void* p);
+struct Event : Handle<hipEvent_t, drop_event> {
+    lcgs_status ensure(unsigned flags = hipEventDisableTiming); // (the profiling marks ask for the timing kind: 0)
+};
+struct Stream : Handle<hipStream_t, drop_stream> {
+    lcgs_status ensure();                      // non-blocking, default priority
+    lcgs_status ensure_priority(int priority); // ... with this priority where the device grants it
+};
+lcgs_status ensure_pinned(void** p, size_t bytes, unsigned flags);
+template <typename T>
+void drop_pinned_as(T* p) { drop_pinned(p); }
+template <typename T>
+struct Pinned : Handle<T*, drop_pinned_as<T>> { // a block of fixed size
+    lcgs_status ensure(size_t bytes, unsigned flags = hipHostMallocDefault)
+    {
+        return ensure_pinned(reinterpret_cast<void**>(&this->h), bytes, flags);
+    }
 };
 
 // host camera -> kernel constants (lcgs/src/gs_projector/impl.cpp:34-42, util/camera.h:38-72)

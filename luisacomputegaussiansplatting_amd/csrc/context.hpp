@@ -28,6 +28,9 @@ void scene_arrays_written(lcgs_context* ctx, const float* pos, const float* scal
 
 using lcgs::CamParams;
 using lcgs::DeviceBuffer;
+using lcgs::Event;
+using lcgs::Pinned;
+using lcgs::Stream;
 
 struct lcgs_context {
     int         device = 0;
@@ -92,14 +95,14 @@ struct lcgs_context {
     // workspace of the fused frame
     DeviceBuffer cull_slab, chunk_info, chunk_base; // the cull pass's per-chunk output (fused_forward.hip k_cull_compact)
     DeviceBuffer recs, sortk[2], sortv[2], vis_index, rects, rects_sorted, pairk[2], pairv[3], zero_ws[3], counts, sort_ws,
-        expand_ws, final_T, n_contrib, list_idx, grads2d, strip_masks, shjac, tie_ws, fused_grads, bwd_counter;
+        expand_ws, final_T, n_contrib, grads2d, strip_masks, shjac, tie_ws, fused_grads, bwd_counter;
     bool         last_has_jac = false; // the last keep_state frame stored the colour Jacobian (degree 3)
     // zero_ws holds what a frame needs zeroed: the tile ranges.  Three
     // copies rotate: while frame N runs, the auxiliary stream clears the copy of frame N + 2.  Two frames ahead, not
     // one, so that no wait is needed when a frame starts: the fill issued during frame N - 1 sits on the auxiliary
     // stream in front of frame N's record builder, whose completion frame N's renderer waited for -- and frame N + 1
     // starts behind that renderer.
-    size_t    zero_scan_bytes = 0, zero_bytes = 0;
+    size_t    zero_bytes      = 0;
     int       zero_cur        = 0;
     bool      zero_ready[3]   = { false, false, false };
     uint32_t* ranges          = nullptr; // tile ranges of the last frame (inside zero_ws[...])
@@ -140,10 +143,8 @@ struct lcgs_context {
     uint32_t* work_counters = nullptr; // [0] forward renderer, [1] render-backward: inside the frame's zeroed block
     bool use_graph = false; // opt-in (LCGS_GRAPH=1): measured no gain on MI355X, the short kernels are GPU-latency-bound
     // second stream: work that is independent of the sort chain (record building; gradient zero-fill) overlaps it
-    hipStream_t aux_stream = nullptr;
-    bool        aux_borrowed = false; // the batch sibling's: its parent's cull_stream, not destroyed with the sibling
-    hipEvent_t  ev_fork = nullptr, ev_join = nullptr, ev_ranges = nullptr, ev_aux_done = nullptr, ev_render = nullptr,
-                ev_counts = nullptr;
+    Stream      aux_stream; // (the batch sibling's: borrowed, its parent's cull_stream)
+    Event       ev_fork, ev_join, ev_ranges, ev_aux_done, ev_render, ev_counts;
     bool        aux_pending = false, counts_pending = false;
     hipEvent_t  aux_done_last = nullptr; // whichever of ev_aux_done / ev_pipe_aux[] the auxiliary stream recorded last
     // Pipelined in-order frames (abi_frame.cpp enqueue_forward): forward-only, enqueue-only frames run their head
@@ -153,10 +154,10 @@ struct lcgs_context {
     // words travel in the frame's zeroed block, and the auxiliary job that recycles frame k - 1's zeroed block and tile
     // schedule waits for renderer k - 1.  Events a LATER call waits for exist once per frame parity (a re-recorded event
     // names its latest record only).
-    hipStream_t head_stream = nullptr;
-    hipEvent_t  ev_pipe_entry = nullptr;                 // the caller's stream at entry (frames that do not chain)
-    hipEvent_t  ev_pipe_render[2] = { nullptr, nullptr }; // renderer of the last pipelined frame of that parity
-    hipEvent_t  ev_pipe_aux[2]    = { nullptr, nullptr }; // ... and its auxiliary job (next schedule, cleared block)
+    Stream      head_stream;
+    Event       ev_pipe_entry;     // the caller's stream at entry (frames that do not chain)
+    Event       ev_pipe_render[2]; // renderer of the last pipelined frame of that parity
+    Event       ev_pipe_aux[2];    // ... and its auxiliary job (next schedule, cleared block)
     DeviceBuffer recs_b;                                 // the records of odd pipelined frames
     // A frame that CHAINS runs its cull pass one slot ahead, on cull_stream beside the previous head's sort chain: the pass reads
     // the call's camera and the context's own scene (which nothing writes while frames chain) and writes the chunk slabs,
@@ -164,10 +165,10 @@ struct lcgs_context {
     // that scatter (ev_fork) and for nothing else; the head waits for ev_cull in front of its k_rowscan_first.  Only while the
     // GPU is behind the host (the query that gates the bounded grid): a paced frame has nothing to run beside and would only
     // pay for the cross-stream waits.  The stream has the auxiliary stream's lowest priority and is ALSO the auxiliary stream
-    // of the batch sibling (aux_borrowed): the two uses never coincide, and the process stays at four streams -- a fifth
+    // of the batch sibling (which borrows it): the two uses never coincide, and the process stays at four streams -- a fifth
     // shares a hardware queue with the caller's stream and costs the camera batch 12 % (profiles/early_cull_ab.txt).
-    hipStream_t cull_stream = nullptr;
-    hipEvent_t  ev_cull     = nullptr;
+    Stream      cull_stream;
+    Event       ev_cull;
     DeviceBuffer cull_counts; // the cull pass's counts[digit][chunk], apart from sort_ws (which the previous head's passes still use)
     bool        early_cull  = true; // LCGS_EARLY_CULL=0: a chained frame's cull pass stays on the head stream (A/B and test hook)
     uint64_t    pipe_early  = 0;    // frames that culled early (lcgs_debug_early_cull_count)
@@ -183,7 +184,6 @@ struct lcgs_context {
     uint64_t    op_seq = 0, pipe_left_seq = ~(uint64_t)0;
     // keep_state frames clear the 2-D gradient rows on the auxiliary stream (beside the renderer) so that the backward
     // does not start with a 40 us zero-fill; consumed by the first backward of that frame
-    hipEvent_t  ev_g2d_zero = nullptr;
     bool        g2d_zeroed  = false;
     // a backward has run on the last keep-state frame: until then its 2-D gradient rows are only zeros (lcgs_densify_accumulate)
     bool        g2d_backward_done = false;
@@ -203,7 +203,7 @@ struct lcgs_context {
     // lcgs_render_forward_batch: a sibling context (own workspace, own streams) that renders every other view, so
     // that one view's latency-bound sort chain overlaps the other's bandwidth- and VALU-bound kernels
     lcgs_context* twin         = nullptr;
-    hipEvent_t    ev_batch_fork = nullptr, ev_batch_join = nullptr;
+    Event         ev_batch_fork, ev_batch_join;
     // lcgs_fit_views: the view's image and loss gradient (per context: two views are in flight), the order of the
     // backward passes across the two contexts
     DeviceBuffer fit_img, fit_dL;
@@ -212,7 +212,7 @@ struct lcgs_context {
     DeviceBuffer loss_ws;
     int          fit_loss   = LCGS_LOSS_L2;
     float        fit_lambda = 0.2f;
-    hipEvent_t   ev_fit_bwd = nullptr;
+    Event        ev_fit_bwd;
     // launch-size hints from the last synchronised frame (live counts stay on the device; larger counts are
     // still handled correctly by chunk striding)
     int64_t hint_V = 0, hint_L = 0, hint_Lb = 0; // (hint_L: frames with per-tile lists; hint_Lb: per 2 x 2-tile block)
@@ -221,8 +221,8 @@ struct lcgs_context {
     DeviceBuffer st_flags, st_u32[8], st_keys_exp, st_vals_exp; // the splatter's sort-before-duplicate (lcgs_tile_splat_forward)
     DeviceBuffer st_win, st_win2, st_offs; // ... and the output-balanced pair copies' window table (one word per 1024 pairs) and offsets
     uint32_t     pair_capacity = 0;
-    uint32_t*    h_counts      = nullptr; // pinned, 8 x u32
-    uint32_t*    h_stage       = nullptr; // pinned, 4 x u32: the stage-level splatter's one read-back (num_rendered & co.)
+    Pinned<uint32_t> h_counts;            // 16 x u32
+    Pinned<uint32_t> h_stage;             // 4 x u32, coherent and mapped: the stage-level splatter's one read-back (num_rendered & co.)
     uint32_t*    h_stage_dev   = nullptr; // the same words as the device sees them (posted by the compaction's scan launch)
 
     // state of the last forward (for backward and stats)
@@ -242,7 +242,7 @@ struct lcgs_context {
     lcgs_comm*   comm = nullptr;        // attached by lcgs_comm_create (not owned)
     int          grad_slices = 1;       // > 1: slice the dense preprocess-backward
     DeviceBuffer slice_bounds;          // (grad_slices + 1) x u32, dense-id boundaries of the slices (device)
-    hipEvent_t   ev_slice[lcgs::kMaxGradSlices]{};
+    Event        ev_slice[lcgs::kMaxGradSlices];
     int          slices_recorded = 0;   // slices of the last dense backward whose events are valid (0: not sliced)
     const void*  slices_of = nullptr;   // the dL_dpos array those events belong to
 
@@ -289,24 +289,23 @@ struct lcgs_context {
         int          row_first = 0, row_count = 0, num = 0;
         DeviceBuffer vis, shjac, counts;
     } owner[LCGS_MAX_OWNER_VIEWS];
-    uint32_t*                h_owner_counts = nullptr; // pinned, LCGS_MAX_OWNER_VIEWS words (lcgs_owner_counts)
+    Pinned<uint32_t>         h_owner_counts; // LCGS_MAX_OWNER_VIEWS words (lcgs_owner_counts)
     // lcgs_owner_project_views: the N views of a step are N INDEPENDENT short pipelines over the rank's P / N rows (five launches
     // of a few hundred workgroups each); they run side by side on kOwnerLanes streams at most (two by default), each lane with its own scratch of
     // the cull / first-sort-pass stages (sized by the row range), joined on the context's stream at the end of the call
     static constexpr int kOwnerLanes = 4;
     struct OwnerLane {
         DeviceBuffer slab, chunk_info, chunk_base, sortk[2], sortv[2], rects, sort_ws;
-        hipStream_t  stream = nullptr;
-        hipEvent_t   done   = nullptr;
+        Stream       stream;
+        Event        done;
     } owner_lane[kOwnerLanes];
-    hipEvent_t               ev_owner_fork = nullptr;
+    Event                    ev_owner_fork;
     const lcgs::SplatRecord* owner_recs = nullptr;
     int                      owner_rows = 0;
 
     // per-stage timing
     bool             profiling = false;
-    hipEvent_t       events[lcgs::kMaxEvents]{};
-    bool             events_created = false;
+    Event            events[lcgs::kMaxEvents]; // (the timing kind, made by the first mark that records them)
     int              n_marks        = 0;
     const char*      mark_names[lcgs::kMaxEvents]{};
     lcgs_stage_times times{};

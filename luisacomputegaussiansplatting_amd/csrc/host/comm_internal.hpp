@@ -106,21 +106,17 @@ struct lcgs_loopback_group {
     struct Msg {
         const void* ptr;
         size_t      bytes;
-        hipEvent_t  ready; // recorded on the sender's stream behind the data
+        Event       ready; // recorded on the sender's stream behind the data
     };
     std::vector<std::deque<Msg>> box;  // box[dst * world + src]: the sends posted in the open group, in order
-    std::vector<hipEvent_t>      done; // per rank: behind the copies of its receives of the last group
+    std::vector<Event>           done; // per rank: behind the copies of its receives of the last group
     int                          members = 0;
     int                          device  = -1;  // every member's device (one GPU: that is the point)
     std::vector<char>            taken;         // ranks that have a communicator
-    // messages nobody received (a member gave up mid-group): their events are not leaked
+    // messages nobody received (a member gave up mid-group)
     void drop_unconsumed()
     {
-        for (auto& q : box) {
-            for (Msg& m : q)
-                if (m.ready) (void)hipEventDestroy(m.ready);
-            q.clear();
-        }
+        for (auto& q : box) q.clear();
     }
     // collectives of the open group (all-reduce / reduce-scatter / all-gather): what every rank passed, op by op
     struct CollArgs {
@@ -129,7 +125,7 @@ struct lcgs_loopback_group {
     };
     std::vector<std::vector<CollArgs>> coll;    // coll[op][rank]
     std::vector<float*>                scratch; // per rank: where it leaves its reduced slices (phase 1 of an all-reduce)
-    std::vector<hipEvent_t>            ready, reduced; // per rank: inputs complete / phase 1 complete
+    std::vector<Event>                 ready, reduced; // per rank: inputs complete / phase 1 complete
 
     bool barrier() // false: the group failed
     {
@@ -158,8 +154,8 @@ struct lcgs_comm {
     lcgs_context* ctx    = nullptr;
     ncclComm_t    comm   = nullptr;
     int           rank   = 0, world = 1;
-    hipStream_t   stream = nullptr; // the collectives' own stream: they overlap the compute stream's tail
-    hipEvent_t    ev_in = nullptr, ev_out = nullptr;
+    Stream        stream; // the collectives' own stream: they overlap the compute stream's tail
+    Event         ev_in, ev_out;
     // The two plain hand-offs between the context's stream (compute) and this one.  A place that orders the streams in any
     // other way -- the chunked all-reduce's per-slice waits, the async ownership step's ev_checked -- writes it out.
     lcgs_status compute_to_comm() // what comes next on the communicator's stream runs behind the context's stream as it stands
@@ -182,12 +178,8 @@ struct lcgs_comm {
     bool         track_rows = false;
     int64_t      flags_P    = 0;     // rows the flag array covers
     DeviceBuffer flags, chunk_ws, rows, bounds, matrix, sendbuf, recvbuf; // bounds: [world + 2] positions + [1] total
-    uint32_t*    h_matrix = nullptr; // pinned: world x (world + 2) positions (row r = rank r's owner bounds)
-    lcgs_status  ensure_h_matrix()
-    {
-        if (!h_matrix) LCGS_HIP_CHECK(hipHostMalloc((void**)&h_matrix, (size_t)LCGS_MAX_RANKS * (LCGS_MAX_RANKS + 2) * 4, 0));
-        return LCGS_OK;
-    }
+    Pinned<uint32_t> h_matrix; // world x (world + 2) positions (row r = rank r's owner bounds)
+    lcgs_status      ensure_h_matrix() { return h_matrix.ensure((size_t)LCGS_MAX_RANKS * (LCGS_MAX_RANKS + 2) * 4); }
     lcgs_comm_stats stats{};
     // splat-ownership step (lcgs_owner_step_forward / _backward): my rows' records for every view of the step, what I
     // received for my view (owner order), its 2-D gradients, and the 2-D gradients of my rows that came back
@@ -213,9 +205,9 @@ struct lcgs_comm {
         int64_t               P = 0;
         std::vector<uint32_t> table; // [o * N + v]: rows of owner o on view v's screen, last step
     } prev;
-    uint32_t*    h_next = nullptr;   // pinned: the table of the step in flight [N x N] + the reduced flag [1]
+    Pinned<uint32_t> h_next;     // the table of the step in flight [N x N] + the reduced flag [1]
     DeviceBuffer flag_dev;           // u32: bit 0 a message was clipped, bit 1 a frame's pairs were truncated (any rank)
-    hipEvent_t   ev_checked = nullptr; // behind the flag's reduction and the copies to h_next
+    Event        ev_checked; // behind the flag's reduction and the copies to h_next
     struct {
         bool     valid = false;
         bool     async = false;                 // the step in flight used padded messages (sizes below)

@@ -162,8 +162,8 @@ lcgs_status lcgs_owner_step_forward(lcgs_context* ctx, lcgs_comm* c, const lcgs_
     c->force_sync_once = false;
 
     if (async) {
-        if (!c->h_next) LCGS_HIP_CHECK(hipHostMalloc((void**)&c->h_next, ((size_t)LCGS_MAX_RANKS * LCGS_MAX_RANKS + 4) * 4, 0));
-        if (!c->ev_checked) LCGS_HIP_CHECK(hipEventCreateWithFlags(&c->ev_checked, hipEventDisableTiming));
+        LCGS_TRY(c->h_next.ensure(((size_t)LCGS_MAX_RANKS * LCGS_MAX_RANKS + 4) * 4));
+        LCGS_TRY(c->ev_checked.ensure());
         LCGS_TRY(c->flag_dev.ensure(16));
         LCGS_HIP_CHECK(hipMemsetAsync(c->flag_dev.ptr, 0, 16, ctx->stream));
         LCGS_TRY(c->compute_to_comm());
@@ -219,7 +219,7 @@ lcgs_status lcgs_owner_step_forward(lcgs_context* ctx, lcgs_comm* c, const lcgs_
         if (ctx->owner[v].valid && ctx->owner[v].row_count > 0) ctx->owner[v].num = (int)table(me, v);
     }
     // (what the next step sizes its padded messages from, if it runs without a read-back)
-    c->prev.table.assign(c->h_matrix, c->h_matrix + (size_t)N * N);
+    c->prev.table.assign(c->h_matrix + 0, c->h_matrix + (size_t)N * N);
     c->prev.have = true, c->prev.world = N, c->prev.P = ctx->P;
     // ---- 3. the records travel: mine to every view's rank, every owner's to me (owner order = ascending rows)
     LCGS_TRY(exchange_records(c, wire, count, n_in, n_out, /*alias=*/false));
@@ -297,7 +297,7 @@ lcgs_status lcgs_owner_step_finish(lcgs_context* ctx, lcgs_comm* c, int* redo)
     // backward's messages on the communicator's stream): by now the device is normally far into the backward
     LCGS_HIP_CHECK(hipEventSynchronize(c->ev_checked));
     const int N = c->world, me = c->rank;
-    c->prev.table.assign(c->h_next, c->h_next + (size_t)N * N);
+    c->prev.table.assign(c->h_next + 0, c->h_next + (size_t)N * N);
     c->prev.have = true, c->prev.world = N, c->prev.P = ctx->P;
     abi::owner_frame_settle(ctx);
     int64_t rows = 0;

@@ -32,34 +32,19 @@ struct SelftestShared {
 };
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-struct DevArr {
-    void* p = nullptr;
-    ~DevArr()
-    {
-        if (p) (void)hipFree(p);
-    }
-    lcgs_status alloc(size_t bytes)
-    {
-        LCGS_HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16)));
-        return LCGS_OK;
-    }
-    template <class T>
-    T* as() const { return static_cast<T*>(p); }
-};
-
 lcgs_status selftest_allreduce(lcgs_comm* c, lcgs_comm_selftest_report* rep)
 {
     const int N = c->world;
-    DevArr    buf;
-    LCGS_TRY(buf.alloc(1024));
+    DeviceBuffer    buf;
+    LCGS_TRY(buf.ensure(1024));
     std::vector<float> h(256, (float)(c->rank + 1));
-    LCGS_HIP_CHECK(hipMemcpyAsync(buf.p, h.data(), 1024, hipMemcpyHostToDevice, c->stream));
+    LCGS_HIP_CHECK(hipMemcpyAsync(buf.ptr, h.data(), 1024, hipMemcpyHostToDevice, c->stream));
     Wire         wire{ c };
     const double t0 = now_s();
     LCGS_TRY(wire.group_begin());
     LCGS_TRY(wire.allreduce_sum(buf.as<float>(), 256));
     LCGS_TRY(wire.group_end());
-    LCGS_HIP_CHECK(hipMemcpyAsync(h.data(), buf.p, 1024, hipMemcpyDeviceToHost, c->stream));
+    LCGS_HIP_CHECK(hipMemcpyAsync(h.data(), buf.ptr, 1024, hipMemcpyDeviceToHost, c->stream));
     LCGS_HIP_CHECK(hipStreamSynchronize(c->stream));
     rep->allreduce_ms = (now_s() - t0) * 1e3;
     const float want = 0.5f * (float)N * (float)(N + 1);
@@ -72,25 +57,25 @@ lcgs_status selftest_allreduce(lcgs_comm* c, lcgs_comm_selftest_report* rep)
 lcgs_status selftest_p2p(lcgs_comm* c, lcgs_comm_selftest_report* rep)
 {
     const int N = c->world, me = c->rank;
-    DevArr    out, in;
-    LCGS_TRY(out.alloc(16));
-    LCGS_TRY(in.alloc((size_t)N + 16));
+    DeviceBuffer    out, in;
+    LCGS_TRY(out.ensure(16));
+    LCGS_TRY(in.ensure((size_t)N + 16));
     const unsigned char mine = (unsigned char)(me + 1);
-    LCGS_HIP_CHECK(hipMemcpyAsync(out.p, &mine, 1, hipMemcpyHostToDevice, c->stream));
-    LCGS_HIP_CHECK(hipMemsetAsync(in.p, 0, (size_t)N + 16, c->stream));
+    LCGS_HIP_CHECK(hipMemcpyAsync(out.ptr, &mine, 1, hipMemcpyHostToDevice, c->stream));
+    LCGS_HIP_CHECK(hipMemsetAsync(in.ptr, 0, (size_t)N + 16, c->stream));
     Wire         wire{ c };
     const double t0 = now_s();
     LCGS_TRY(wire.group_begin());
     for (int p = 0; p < N; ++p) {
         if (N > 1 && p == me) continue; // (one rank: the messages go to itself)
-        LCGS_TRY(wire.send(out.p, 0, p));
-        LCGS_TRY(wire.send(out.p, 1, p));
+        LCGS_TRY(wire.send(out.ptr, 0, p));
+        LCGS_TRY(wire.send(out.ptr, 1, p));
         LCGS_TRY(wire.recv(in.as<unsigned char>() + p, 0, p));
         LCGS_TRY(wire.recv(in.as<unsigned char>() + p, 1, p));
     }
     LCGS_TRY(wire.group_end());
     std::vector<unsigned char> h((size_t)N);
-    LCGS_HIP_CHECK(hipMemcpyAsync(h.data(), in.p, (size_t)N, hipMemcpyDeviceToHost, c->stream));
+    LCGS_HIP_CHECK(hipMemcpyAsync(h.data(), in.ptr, (size_t)N, hipMemcpyDeviceToHost, c->stream));
     LCGS_HIP_CHECK(hipStreamSynchronize(c->stream));
     rep->p2p_ms = (now_s() - t0) * 1e3;
     rep->p2p_ok = 1;
@@ -108,7 +93,7 @@ void fill_loss_gradient(uint32_t seed, std::vector<float>& h)
         v = ((float)(x >> 8) / 16777216.0f) - 0.5f;
     }
 }
-lcgs_grads grads_of(const DevArr (&g)[5])
+lcgs_grads grads_of(const DeviceBuffer (&g)[5])
 {
     return { g[0].as<float>(), g[1].as<float>(), g[2].as<float>(), g[3].as<float>(), g[4].as<float>() };
 }
@@ -124,21 +109,21 @@ lcgs_status selftest_owner_step(lcgs_context* ctx, lcgs_comm* c, lcgs_comm_selft
     LCGS_TRY(lcgs_synth_scene(0, 4242u, 0, P, h_pos.data(), h_sh.data(), h_op.data(), h_scale.data(), h_rotq.data()));
     const size_t widths[5] = { 3, 3, 4, (size_t)feat, 1 };
     const float* host[5]   = { h_pos.data(), h_scale.data(), h_rotq.data(), h_sh.data(), h_op.data() };
-    DevArr       act[5], g_ref[5], g_own[5], img_ref, img_own, dL;
+    DeviceBuffer       act[5], g_ref[5], g_own[5], img_ref, img_own, dL;
     for (int a = 0; a < 5; ++a) {
-        LCGS_TRY(act[a].alloc((size_t)P * widths[a] * 4));
-        LCGS_TRY(g_ref[a].alloc((size_t)P * widths[a] * 4));
-        LCGS_TRY(g_own[a].alloc((size_t)P * widths[a] * 4));
-        LCGS_HIP_CHECK(hipMemcpy(act[a].p, host[a], (size_t)P * widths[a] * 4, hipMemcpyHostToDevice));
+        LCGS_TRY(act[a].ensure((size_t)P * widths[a] * 4));
+        LCGS_TRY(g_ref[a].ensure((size_t)P * widths[a] * 4));
+        LCGS_TRY(g_own[a].ensure((size_t)P * widths[a] * 4));
+        LCGS_HIP_CHECK(hipMemcpy(act[a].ptr, host[a], (size_t)P * widths[a] * 4, hipMemcpyHostToDevice));
     }
     const size_t img_bytes = (size_t)3 * W * H * 4;
-    LCGS_TRY(img_ref.alloc(img_bytes));
-    LCGS_TRY(img_own.alloc(img_bytes));
-    LCGS_TRY(dL.alloc(img_bytes));
+    LCGS_TRY(img_ref.ensure(img_bytes));
+    LCGS_TRY(img_own.ensure(img_bytes));
+    LCGS_TRY(dL.ensure(img_bytes));
     {
         std::vector<float> h((size_t)3 * W * H);
         fill_loss_gradient(12345u + (uint32_t)me * 977u, h); // (every rank differentiates its own view with its own loss gradient)
-        LCGS_HIP_CHECK(hipMemcpy(dL.p, h.data(), img_bytes, hipMemcpyHostToDevice));
+        LCGS_HIP_CHECK(hipMemcpy(dL.ptr, h.data(), img_bytes, hipMemcpyHostToDevice));
     }
     std::vector<lcgs_camera> cams((size_t)N);
     for (int v = 0; v < N; ++v) {
@@ -164,18 +149,18 @@ lcgs_status selftest_owner_step(lcgs_context* ctx, lcgs_comm* c, lcgs_comm_selft
     // ---- what the step must reproduce: my view's fused frame; my rows' gradients = the sum of every view's ordinary backward
     // (every view differentiated with ITS rank's loss gradient: regenerate those)
     lcgs_grads gr = grads_of(g_ref);
-    DevArr     dLv, scratch;
-    LCGS_TRY(dLv.alloc(img_bytes));
-    LCGS_TRY(scratch.alloc(img_bytes));
+    DeviceBuffer     dLv, scratch;
+    LCGS_TRY(dLv.ensure(img_bytes));
+    LCGS_TRY(scratch.ensure(img_bytes));
     for (int v = 0; v < N; ++v) {
         std::vector<float> h((size_t)3 * W * H);
         fill_loss_gradient(12345u + (uint32_t)v * 977u, h);
-        LCGS_HIP_CHECK(hipMemcpy(dLv.p, h.data(), img_bytes, hipMemcpyHostToDevice));
+        LCGS_HIP_CHECK(hipMemcpy(dLv.ptr, h.data(), img_bytes, hipMemcpyHostToDevice));
         int n = 0;
         LCGS_TRY(lcgs_render_forward(ctx, &cams[(size_t)v], bg, 1.0f, v == me ? img_ref.as<float>() : scratch.as<float>(), nullptr, 1, &n));
         if (n > 0) LCGS_TRY(v == 0 ? lcgs_render_backward(ctx, dLv.as<float>(), &gr) : lcgs_render_backward_accumulate(ctx, dLv.as<float>(), &gr));
         else if (v == 0)
-            for (int a = 0; a < 5; ++a) LCGS_HIP_CHECK(hipMemsetAsync(g_ref[a].p, 0, (size_t)P * widths[a] * 4, ctx->stream));
+            for (int a = 0; a < 5; ++a) LCGS_HIP_CHECK(hipMemsetAsync(g_ref[a].ptr, 0, (size_t)P * widths[a] * 4, ctx->stream));
         LCGS_TRY(lcgs_synchronize(ctx)); // (dLv is rewritten by a blocking copy at the top of the loop: the backward must be through)
     }
     // (known and kept: an early LCGS_HIP_CHECK return below leaves owner_async and prev.have as the scratch scene set them)
@@ -190,7 +175,7 @@ lcgs_status selftest_owner_step(lcgs_context* ctx, lcgs_comm* c, lcgs_comm_selft
     lcgs_status  st = LCGS_OK;
     for (int round = 0; round < 3 && st == LCGS_OK; ++round) {
         c->owner_async = round > 0;
-        LCGS_HIP_CHECK(hipMemsetAsync(img_own.p, 0, img_bytes, ctx->stream));
+        LCGS_HIP_CHECK(hipMemsetAsync(img_own.ptr, 0, img_bytes, ctx->stream));
         for (int attempt = 0; attempt < 3 && st == LCGS_OK; ++attempt) {
             st = lcgs_owner_step_forward(ctx, c, cams.data(), bg, 1.0f, img_own.as<float>());
             if (st == LCGS_OK) st = lcgs_owner_step_backward(ctx, c, dL.as<float>(), &go);
@@ -201,8 +186,8 @@ lcgs_status selftest_owner_step(lcgs_context* ctx, lcgs_comm* c, lcgs_comm_selft
         if (st != LCGS_OK) break;
         if (lcgs_synchronize(ctx) != LCGS_OK) st = LCGS_ERR_HIP;
         std::vector<float> a((size_t)3 * W * H), b((size_t)3 * W * H);
-        LCGS_HIP_CHECK(hipMemcpy(a.data(), img_own.p, img_bytes, hipMemcpyDeviceToHost));
-        LCGS_HIP_CHECK(hipMemcpy(b.data(), img_ref.p, img_bytes, hipMemcpyDeviceToHost));
+        LCGS_HIP_CHECK(hipMemcpy(a.data(), img_own.ptr, img_bytes, hipMemcpyDeviceToHost));
+        LCGS_HIP_CHECK(hipMemcpy(b.data(), img_ref.ptr, img_bytes, hipMemcpyDeviceToHost));
         if (memcmp(a.data(), b.data(), img_bytes) != 0) image_ok = false;
         for (int k = 0; k < 5; ++k) {
             const size_t       n = (size_t)count * widths[k];

@@ -115,11 +115,11 @@ lcgs_status Wire::allgather(const float* send, float* recv, size_t count_per_ran
 lcgs_status Wire::send(const void* d_buf, size_t bytes, int peer)
 {
     if (!c->loop) return rccl_call(rccl().Send(d_buf, bytes, ncclUint8, peer, c->comm, c->stream), "ncclSend", __FILE__, __LINE__);
-    lcgs_loopback_group::Msg m{ d_buf, bytes, nullptr };
-    LCGS_HIP_CHECK(hipEventCreateWithFlags(&m.ready, hipEventDisableTiming));
+    lcgs_loopback_group::Msg m{ d_buf, bytes, {} };
+    LCGS_TRY(m.ready.ensure());
     LCGS_HIP_CHECK(hipEventRecord(m.ready, c->stream));
     std::lock_guard<std::mutex> lock(c->loop->mu);
-    c->loop->box[(size_t)peer * c->loop->world + c->rank].push_back(m);
+    c->loop->box[(size_t)peer * c->loop->world + c->rank].push_back(std::move(m));
     return LCGS_OK;
 }
 lcgs_status Wire::recv(void* d_buf, size_t bytes, int peer)
@@ -165,11 +165,9 @@ lcgs_status Wire::allreduce_max_u32(uint32_t* d_buf, size_t count)
     const int N = c->loop->world;
     DeviceBuffer all;
     LCGS_TRY(all.ensure((size_t)N * count * 4));
-    lcgs_status s = allgather_u32(d_buf, all.as<uint32_t>(), count); // (the loopback's rendezvous is host-side anyway)
-    uint32_t    h[8 * LCGS_MAX_RANKS], m[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    if (s == LCGS_OK && hipMemcpy(h, all.ptr, (size_t)N * count * 4, hipMemcpyDeviceToHost) != hipSuccess) s = LCGS_ERR_HIP;
-    all.release();
-    LCGS_TRY(s);
+    LCGS_TRY(allgather_u32(d_buf, all.as<uint32_t>(), count)); // (the loopback's rendezvous is host-side anyway)
+    uint32_t h[8 * LCGS_MAX_RANKS], m[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    LCGS_HIP_CHECK(hipMemcpy(h, all.ptr, (size_t)N * count * 4, hipMemcpyDeviceToHost));
     for (int r = 0; r < N; ++r)
         for (size_t k = 0; k < count; ++k) m[k] = std::max(m[k], h[(size_t)r * count + k]);
     LCGS_HIP_CHECK(hipMemcpyAsync(d_buf, m, count * 4, hipMemcpyHostToDevice, c->stream));
@@ -204,7 +202,7 @@ lcgs_status Wire::group_end()
     for (int r = 0; r < N; ++r)
         if (r != me) LCGS_HIP_CHECK(hipStreamWaitEvent(st, g->ready[r], 0));
     // ---- point-to-point: copy what was sent to me
-    std::vector<hipEvent_t> consumed;
+    std::vector<Event> consumed; // (alive until everybody's copies have been waited for)
     for (auto& r : c->own.recvs) {
         lcgs_loopback_group::Msg m{};
         {
@@ -216,12 +214,12 @@ lcgs_status Wire::group_end()
                 set_last_error("loopback: a receive has no matching send of the same size (ranks disagree on the message table)");
                 return LCGS_ERR_STATE;
             }
-            m = q.front();
+            m = std::move(q.front());
             q.pop_front();
         }
         LCGS_HIP_CHECK(hipStreamWaitEvent(st, m.ready, 0));
         if (m.bytes) LCGS_HIP_CHECK(hipMemcpyAsync(r.first, m.ptr, m.bytes, hipMemcpyDeviceToDevice, st));
-        consumed.push_back(m.ready);
+        consumed.push_back(std::move(m.ready));
     }
     // ---- collectives, phase 1: reductions that only READ the other ranks' buffers (sums in rank order)
     std::vector<lcgs_loopback_group::CollArgs> args; // (a private copy: the shared table is re-used by the next group)
@@ -280,7 +278,6 @@ lcgs_status Wire::group_end()
     if (!g->barrier()) return loop_failed(); // every copy out of my buffers / scratch has been enqueued
     for (int p = 0; p < N; ++p)               // ... and has run before I touch them again
         if (p != me) LCGS_HIP_CHECK(hipStreamWaitEvent(st, g->done[p], 0));
-    for (hipEvent_t e : consumed) (void)hipEventDestroy(e);
     if (!g->barrier()) return loop_failed(); // (the shared events are not re-recorded before everybody has waited on them)
     return LCGS_OK;
 }
@@ -292,18 +289,13 @@ namespace
 // What both constructors give a communicator: its own stream and the two events of the hand-offs.  highest_priority: the
 // collective's workgroups should get their slots as soon as a chunk is ready, not queue behind the backward's remaining
 // slices (the auxiliary stream of the context has the LOWEST, for the opposite reason); the loopback asks for none.
-hipError_t create_stream_and_events(lcgs_comm* c, bool highest_priority)
+lcgs_status create_stream_and_events(lcgs_comm* c, bool highest_priority)
 {
-    hipError_t e = hipErrorUnknown;
-    if (highest_priority) {
-        int lo = 0, hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&lo, &hi); // hi = numerically smallest = highest priority
-        e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi);
-    }
-    if (e != hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming);
-    return e;
+    int lo = 0, hi = 0;
+    if (highest_priority) (void)hipDeviceGetStreamPriorityRange(&lo, &hi); // hi = numerically smallest = highest priority
+    LCGS_TRY(highest_priority ? c->stream.ensure_priority(hi) : c->stream.ensure());
+    LCGS_TRY(c->ev_in.ensure());
+    return c->ev_out.ensure();
 }
 
 // chunked all-reduce: the dense backward slices its preprocess pass (tuning hook LCGS_GRAD_SLICES; 1 = one chunk)
@@ -344,10 +336,9 @@ lcgs_status lcgs_comm_create(lcgs_context* ctx, const lcgs_comm_id* id, int rank
     c->device = ctx->device;
     c->rank   = rank;
     c->world = world_size;
-    const hipError_t e = create_stream_and_events(c, /*highest_priority=*/true);
-    if (e != hipSuccess) {
+    if (const lcgs_status s = create_stream_and_events(c, /*highest_priority=*/true); s != LCGS_OK) {
         (void)lcgs_comm_destroy(c);
-        LCGS_HIP_CHECK(e);
+        return s;
     }
     ncclUniqueId nid;
     memcpy(nid.internal, id->bytes, sizeof(nid.internal));
@@ -381,19 +372,7 @@ lcgs_status lcgs_comm_destroy(lcgs_comm* c)
         --c->loop->members;
         if (c->rank >= 0 && (size_t)c->rank < c->loop->taken.size()) c->loop->taken[(size_t)c->rank] = 0;
     }
-    c->packed.release();
-    c->scales.release();
-    for (DeviceBuffer* b : { &c->flags, &c->chunk_ws, &c->rows, &c->bounds, &c->matrix, &c->sendbuf, &c->recvbuf, &c->own_rows,
-                             &c->own_recs, &c->in_rows, &c->in_recs, &c->g2d_all, &c->g_in, &c->loop_scratch })
-        b->release();
-    if (c->h_matrix) (void)hipHostFree(c->h_matrix);
-    if (c->h_next) (void)hipHostFree(c->h_next);
-    c->flag_dev.release();
-    if (c->ev_checked) (void)hipEventDestroy(c->ev_checked);
-    if (c->ev_in) (void)hipEventDestroy(c->ev_in);
-    if (c->ev_out) (void)hipEventDestroy(c->ev_out);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c; // (its buffers, events, pinned blocks and stream free themselves)
     return LCGS_OK;
 }
 
@@ -429,9 +408,9 @@ lcgs_status lcgs_loopback_group_create(int world_size, lcgs_loopback_group** out
     if (!g) return LCGS_ERR_OUT_OF_MEMORY;
     g->world = world_size;
     g->box.resize((size_t)world_size * world_size);
-    g->done.assign(world_size, nullptr);
-    g->ready.assign(world_size, nullptr);
-    g->reduced.assign(world_size, nullptr);
+    g->done.resize(world_size);
+    g->ready.resize(world_size);
+    g->reduced.resize(world_size);
     g->scratch.assign(world_size, nullptr);
     g->taken.assign(world_size, 0);
     *out = g;
@@ -442,10 +421,6 @@ lcgs_status lcgs_loopback_group_destroy(lcgs_loopback_group* g)
 {
     if (!g) return LCGS_OK;
     LCGS_REQUIRE(g->members == 0, "communicators of this group are still alive");
-    g->drop_unconsumed();
-    for (auto* evs : { &g->done, &g->ready, &g->reduced })
-        for (hipEvent_t e : *evs)
-            if (e) (void)hipEventDestroy(e);
     delete g;
     return LCGS_OK;
 }
@@ -468,21 +443,21 @@ lcgs_status lcgs_comm_create_loopback(lcgs_context* ctx, lcgs_loopback_group* gr
     lcgs_comm* c = new (std::nothrow) lcgs_comm();
     if (!c) return LCGS_ERR_OUT_OF_MEMORY;
     c->ctx = ctx, c->device = ctx->device, c->rank = rank, c->world = group->world, c->loop = group;
-    hipError_t e = create_stream_and_events(c, /*highest_priority=*/false);
+    lcgs_status s = create_stream_and_events(c, /*highest_priority=*/false);
     {
         std::lock_guard<std::mutex> lock(group->mu);
         for (auto* evs : { &group->done, &group->ready, &group->reduced })
-            if (e == hipSuccess && !(*evs)[rank]) e = hipEventCreateWithFlags(&(*evs)[rank], hipEventDisableTiming);
-        if (e == hipSuccess) ++group->members;
+            if (s == LCGS_OK) s = (*evs)[rank].ensure();
+        if (s == LCGS_OK) ++group->members;
     }
-    if (e != hipSuccess) {
+    if (s != LCGS_OK) {
         {
             std::lock_guard<std::mutex> lock(group->mu);
             group->taken[(size_t)rank] = 0;
         }
         c->loop = nullptr;
         (void)lcgs_comm_destroy(c);
-        LCGS_HIP_CHECK(e);
+        return s;
     }
     ctx->comm = c; // (kept as it is: the test hook LCGS_OWNER_SELF_P2P is lcgs_comm_create's alone and is not read here)
     set_grad_slices(ctx);

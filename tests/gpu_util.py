@@ -16,6 +16,20 @@ def upload_scene(scene):
     return {k: dev(scene[k]) for k in ("pos", "scale", "rotq", "sh", "opacity")}
 
 
+def device_bytes_lost(once, rounds=4):
+    """Free device memory before minus after `rounds` calls of once(), following one warm-up call (the first use pays for
+    one-off allocations of the runtime): what create / use / close rounds did not give back."""
+    once()
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(rounds):
+        once()
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    return free0 - torch.cuda.mem_get_info()[0]
+
+
 def assert_image_parity(gpu_img, orc, **_legacy):
     """The HIP frame must equal the oracle's BIT FOR BIT -- every pixel, no tolerance, no exempt pixels.
 

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from conftest import make_scene
-from gpu_util import DEV, upload_scene
+from gpu_util import DEV, dev, device_bytes_lost, upload_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -435,6 +435,87 @@ def test_destroy_returns_every_byte(lcgs):
     torch.cuda.empty_cache()
     free1 = torch.cuda.mem_get_info()[0]
     assert free0 - free1 < (2 << 20), f"{(free0 - free1) / 2**20:.1f} MiB lost over four create/destroy rounds (16 B x P = {16 * P / 2**20:.1f} MiB a round)"
+
+
+def test_destroy_returns_every_features_scratch(lcgs):
+    """The same measurement and bar with every feature that keeps scratch in the context used once per round: the re-ordered
+    upload, the f16 coefficients, a kept frame with its backward, maps, contribution and densify statistics, densify, prune,
+    MCMC relocation and growth, the point-cloud initialiser, the photometric loss, a camera batch (sibling context, head and cull
+    streams), a burst of enqueue-only frames (the pipelined frames' second set of buffers), fit_views, the three stage
+    operators, the ownership projection (alone and on the lanes) and a frame from its records.  The smallest per-row scratch
+    (4 B x P) would lose 6.4 MB over four rounds, three times the bar."""
+    rng = np.random.default_rng(48)
+    P = 400_000
+    scene = make_scene(rng, P)
+    W, H = 640, 360
+    cam = lcgs.get_lookat_cam([-3.0, 0.2, 1.0], [0, 0, 0.5], [0, 0, 1], width=W, height=H)
+    cam2 = lcgs.get_lookat_cam([2.5, 1.5, 1.0], [0, 0, 0.5], [0, 0, 1], width=W, height=H)
+    points, rgb = dev(scene["pos"]), dev(rng.uniform(0, 1, (P, 3)).astype(np.float32))
+    keys = ("pos", "scale", "rotq", "sh", "opacity")
+
+    def once():
+        r = lcgs.Renderer(lcgs.Context(0))
+        r.upload_scene(scene, order="spatial")
+        r.use_half_sh(True)
+        img, img2, dL = (torch.zeros(3, H, W, device=DEV) for _ in range(3))
+        g = {k: torch.zeros_like(t) for k, t in r.scene_tensors().items()}
+        # a kept frame, its backward, and what reads the kept state
+        n_rendered = r.forward(cam, img, keep_state=True, sync=True)
+        assert n_rendered > 0
+        r.backward(dL, *[g[k] for k in keys])
+        r.render_maps(torch.zeros(H, W, device=DEV), torch.zeros(H, W, device=DEV))
+        contrib = {k: torch.zeros(P, dtype=torch.float32 if k.startswith("weight") else torch.int32, device=DEV)
+                   for k in ("weight_sum", "weight_max", "pixels", "views")}
+        r.contrib_accumulate(contrib)
+        new_stats = lambda: {"grad_accum": torch.zeros(P, device=DEV), "denom": torch.zeros(P, dtype=torch.int32, device=DEV),
+                             "max_radii": torch.zeros(P, dtype=torch.int32, device=DEV)}
+        stats = new_stats()
+        r.densify_accumulate(stats)
+        # a trainable scene of P rows from the point-cloud initialiser; the rewrites go out of place into a second set
+        raw, act = r.init_from_points(points, rgb)
+        m, v = ({k: torch.zeros_like(raw[k]) for k in keys} for _ in range(2))
+        outs = [{k: torch.zeros_like(raw[k]) for k in keys} for _ in range(4)]
+        assert 0 < r.densify(stats, raw, m, v, *outs, new_stats(), grad_threshold=1e30) <= P  # (nothing cloned or split)
+        assert r.prune(contrib, raw, m, v, *outs, min_pixels=1) >= 0
+        raw["opacity"][: P // 8], act["opacity"][: P // 8] = -20.0, float(torch.sigmoid(torch.tensor(-20.0)))  # dead rows
+        assert r.mcmc_relocate(raw, m, v, act) > 0
+        r.mcmc_add(P - 1000, 1000, raw, m, v, act)
+        loss = torch.zeros(1, device=DEV)
+        r.photometric_loss_backward(img, img2, dL, loss)
+        # two frames in flight (the sibling context), then a burst of enqueue-only frames, then two views of a fit
+        r.forward_batch([cam, cam2], [img, img2])
+        r.ctx.synchronize()
+        for _ in range(4):
+            r.forward(cam, img, sync=False)
+        r.ctx.synchronize()
+        r.fit_views([cam, cam2], [img, img2], *[g[k] for k in keys], torch.zeros(2, device=DEV))
+        r.ctx.synchronize()
+        # the stage operators on the same context
+        sh, pr, ts = lcgs.SHProcessor(), lcgs.GSProjector(), lcgs.GSTileSplatter()
+        for op in (sh, pr, ts):
+            op.create(r.ctx)
+        d = r.scene_tensors()
+        color, means, covs, depth = (torch.zeros(P, c, device=DEV) for c in (3, 2, 3, 1))
+        sh.process(lcgs.GPUPointsProxy(P, 3, d["pos"]), cam, d["sh"], color, 3, 3)
+        pr.forward(lcgs.GSProjectorInputProxy(P, d["pos"], d["scale"], d["rotq"], 1.0),
+                   lcgs.GSProjectorOutputProxy(means, covs, depth), cam, True)
+        cap, G = 2 * n_rendered + 7, ((W + 15) // 16) * ((H + 15) // 16)
+        i64 = lambda n: torch.zeros(n, dtype=torch.int64, device=DEV)
+        i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=DEV)
+        accel = lcgs.GSTileSplatterAccelProxy(i32(P), i32(P), i64(cap), i32(cap), i64(cap), i32(cap), i32(2 * G))
+        out = lcgs.GSSplatForwardOutputProxy(H, W, img2, i32(P), torch.zeros(H, W, device=DEV), i32(H * W))
+        assert ts.forward(accel, lcgs.GSTileSplatterInputProxy(P, (0.0, 0.0, 0.0), means, depth, covs, color, d["opacity"]), out,
+                          True) > 0
+        # splat ownership: the per-splat half alone and on the lanes, and a frame from its records
+        rows, recs = r.owner_project(0, cam, 0, P)
+        r.owner_project_all([cam, cam2], 0, P)
+        r.owner_render(cam, rows, recs, img)
+        r.ctx.synchronize()
+        r.ctx.close()
+
+    lost = device_bytes_lost(once)
+    print(f"[scratch] {lost / 2**20:.2f} MiB lost over four rounds")
+    assert lost < (2 << 20), f"{lost / 2**20:.1f} MiB lost over four create/use/close rounds (4 B x P = {4 * P / 2**20:.1f} MiB a round)"
 
 
 def test_empty_frame_still_clears_what_the_backward_relies_on(lcgs):
