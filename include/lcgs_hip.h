@@ -161,6 +161,20 @@ LCGS_API lcgs_status lcgs_scene_use_half_sh(lcgs_context* ctx, int enable);
 /* Opt-in footprint cull: splats whose reference radius (pixels, gs_tile_splatter/shader.cpp:145-148) is below
  * min_radius_px touch no tile.  Changes the image; never the default; 0 = off.  Stage-level operators ignore it. */
 LCGS_API lcgs_status lcgs_set_lod(lcgs_context* ctx, int min_radius_px);
+/* Opt-in antialiased frame (the 2-D filter of Mip-Splatting, Yu et al. CVPR 2024; gsplat's rasterize_mode="antialiased"): the
+ * 0.3 px^2 dilation of the projected covariance stays, and the frame blends with opacity * rho,
+ * rho = sqrt(max(0, det cov2d / det(cov2d + 0.3 I))), so the dilated splat carries the energy of the undilated one.  radii,
+ * num_rendered, depths and the order of the lists are the classic frame's; the image changes; never the default.  A kept frame
+ * remembers the mode it was rendered in: every backward, lcgs_render_maps, lcgs_contrib_accumulate and the camera gradient work
+ * on that frame, whatever the context's mode is by then; dL/dopacity is with respect to the splat's own opacity, and the
+ * position / scale / rotation / camera gradients carry d rho.  lcgs_fit_views and batches follow the context's mode.
+ * NOT offered: the stage-level operators (lcgs_sh_process / lcgs_project_forward / lcgs_tile_splat_forward, deferred mode
+ * included) and the ownership step (lcgs_owner_*, lcgs_owner_step_*) ignore the mode and render and differentiate the classic
+ * frame consistently; Mip-Splatting's 3-D smoothing filter (it needs per-splat sampling rates over the training views); a
+ * per-call mode argument.  Any other value: LCGS_ERR_INVALID_ARG. */
+#define LCGS_RASTER_CLASSIC     0   /* default: the reference's frame, unchanged */
+#define LCGS_RASTER_ANTIALIASED 1
+LCGS_API lcgs_status lcgs_set_raster_mode(lcgs_context* ctx, int mode);
 /* Bound scene -> host arrays sized like lcgs_scene_upload's inputs (NULL outputs skipped).  Synchronises. */
 LCGS_API lcgs_status lcgs_scene_download(lcgs_context* ctx, float* h_pos, float* h_scale, float* h_rotq, float* h_sh, float* h_opacity);
 

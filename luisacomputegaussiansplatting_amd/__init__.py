@@ -26,6 +26,8 @@ from .api import (  # noqa: F401
     LOSS_L2,
     LOSS_PHOTOMETRIC,
     LcgsError,
+    RASTER_ANTIALIASED,
+    RASTER_CLASSIC,
     Renderer,
     SHProcessor,
     build_library,

@@ -56,6 +56,9 @@ _DEPTH_MODES = {"z": DEPTH_Z, "inv_z": DEPTH_INV_Z}
 LCGS_KNN_CHUNK = 256  # sorted points per query workgroup of the nearest-neighbour search (sizes around its multiples are edge cases)
 # lcgs_set_fit_loss kinds (LCGS_LOSS_* in include/lcgs_hip.h)
 LOSS_L2, LOSS_PHOTOMETRIC = 0, 1
+# lcgs_set_raster_mode modes (LCGS_RASTER_* in include/lcgs_hip.h)
+RASTER_CLASSIC, RASTER_ANTIALIASED = 0, 1
+_RASTER_MODES = {"classic": RASTER_CLASSIC, "antialiased": RASTER_ANTIALIASED}
 
 _KEYS = ("pos", "scale", "rotq", "sh", "opacity")
 
@@ -256,6 +259,7 @@ def _signatures() -> dict:
         "lcgs_scene_declare_static": (st, [p, i, p, p, p]),
         "lcgs_scene_use_half_sh": (st, [p, i]),
         "lcgs_set_lod": (st, [p, i]),
+        "lcgs_set_raster_mode": (st, [p, i]),
         "lcgs_scene_download": (st, [p, p, p, p, p, p]),
         # the fused frame
         "lcgs_render_forward": (st, [p, cam, p, f, p, p, i, pi]),
@@ -770,6 +774,15 @@ class Renderer:
         """lcgs_set_lod: opt-in footprint cull (0 = off): splats whose reference radius is below min_radius_px pixels are
         dropped from the fused frame.  Changes the image; never the default."""
         _check(load_library().lcgs_set_lod(self.ctx._h, int(min_radius_px)))
+
+    def set_raster_mode(self, mode: str):
+        """lcgs_set_raster_mode: "classic" (default: the reference's frame) or "antialiased" (every splat's opacity times
+        rho = sqrt(det cov2d / det(cov2d + 0.3 I)), the 2-D filter of Mip-Splatting; same radii and num_rendered).  A kept
+        frame remembers its mode: backward, maps, contrib and the camera gradient follow the frame, not the context.  The
+        stage-level operators and the ownership step ignore it."""
+        if mode not in _RASTER_MODES:
+            raise ValueError(f"raster mode must be one of {sorted(_RASTER_MODES)}, not {mode!r}")
+        _check(load_library().lcgs_set_raster_mode(self.ctx._h, _RASTER_MODES[mode]))
 
     def download_scene(self) -> dict:
         """Host copies of the bound scene (same keys and shapes as read_gs_ply)."""

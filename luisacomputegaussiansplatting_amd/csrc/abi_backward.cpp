@@ -37,7 +37,8 @@ lcgs_status camera_pass(lcgs_context* ctx, float* d_dL_dcam)
     launch_camera_grad(ctx->hint_V > 0 ? ctx->hint_V : (int64_t)ctx->P, ctx->sh_deg, ctx->last.cp, ctx->last.scale_modifier,
                        ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(),
                        ctx->grads2d.as<float>(), ctx->last_has_jac ? ctx->shjac.as<float4>() : nullptr,
-                       ctx->recs.as<SplatRecord>(), ctx->g2d_value_mode, ctx->cam_slab.as<double>(), d_dL_dcam, ctx->stream);
+                       ctx->recs.as<SplatRecord>(), ctx->g2d_value_mode, ctx->cam_slab.as<double>(), d_dL_dcam, ctx->stream,
+                       ctx->opacity);
     return LCGS_OK;
 }
 // the state every walk of the kept lists needs: a keep-state frame of this context's own records, lists per tile
@@ -310,7 +311,7 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
     const int slices = (fused || !params) ? 0 : (sliced ? ctx->grad_slices : 1);
     if (fused) // (compact, unsliced: the update is applied where the gradients are formed; nothing is written out)
         launch_preprocess_backward_adam(ctx->hint_V > 0 ? ctx->hint_V : (int64_t)P, ctx->last.cp, ctx->last.scale_modifier,
-                                        ctx->pos, ctx->scale, ctx->rotq, ctx->vis_index.as<uint32_t>(),
+                                        ctx->pos, ctx->scale, ctx->rotq, ctx->opacity, ctx->vis_index.as<uint32_t>(),
                                         ctx->counts.as<uint32_t>(), ctx->grads2d.as<float>(), ctx->shjac.as<float4>(),
                                         fused->raw, fused->m, fused->v, fused->act, fused->lr, fused->step, st);
     for (int k = 0; k < slices; ++k) {
@@ -319,7 +320,7 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
                                    ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), ctx->grads2d.as<float>(),
                                    grads->d_dL_dpos, grads->d_dL_dscale, grads->d_dL_drotq, grads->d_dL_dsh,
                                    grads->d_dL_dopacity, st, ctx->last_has_jac ? ctx->shjac.as<float4>() : nullptr, compact,
-                                   sliced ? ctx->slice_bounds.as<uint32_t>() : nullptr, k, slices, accumulate);
+                                   sliced ? ctx->slice_bounds.as<uint32_t>() : nullptr, k, slices, accumulate, ctx->opacity);
         if (sliced) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_slice[k], st));
     }
     if (params && maps && maps->d_dL_ddepth) // view z = front . pos + tz: the depth channel's dL/dvalue reaches the position rows directly

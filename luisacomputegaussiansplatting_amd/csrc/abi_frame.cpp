@@ -474,6 +474,7 @@ lcgs_status lcgs_render_forward(lcgs_context* ctx, const lcgs_camera* camera, co
     LCGS_REQUIRE(ctx->pos != nullptr, "no scene bound (call lcgs_scene_bind / lcgs_scene_upload first)");
     CamParams cp      = make_cam_params(*camera);
     cp.lod_min_radius = ctx->lod_min_radius;
+    cp.raster_mode    = ctx->raster_mode;
     // (frames that keep backward state stay per tile: letting them follow was built in round 6 and lost 1.1 % -- REJECTED.md)
     cp.list_shift     = (!keep_state && (ctx->coarse_mode == 1 || (ctx->coarse_mode == 2 && ctx->coarse_on))) ? 1u : 0u;
     ctx->owner_recs   = nullptr; // (an ordinary frame: its backward is lcgs_render_backward again)
@@ -641,6 +642,7 @@ lcgs_status prepare_twin(lcgs_context* ctx)
             LCGS_TRY(lcgs_scene_bind(t, ctx->P, ctx->sh_deg, ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->opacity));
         t->use_half_sh    = false;
         t->lod_min_radius = ctx->lod_min_radius;
+        t->raster_mode    = ctx->raster_mode;
         t->fit_loss       = ctx->fit_loss;
         t->fit_lambda     = ctx->fit_lambda;
         t->coarse_mode    = ctx->coarse_mode;

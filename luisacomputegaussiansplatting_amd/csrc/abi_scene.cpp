@@ -273,6 +273,17 @@ lcgs_status lcgs_set_lod(lcgs_context* ctx, int min_radius_px)
     return LCGS_OK;
 }
 
+lcgs_status lcgs_set_raster_mode(lcgs_context* ctx, int mode)
+{
+    LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    LCGS_REQUIRE(mode == LCGS_RASTER_CLASSIC || mode == LCGS_RASTER_ANTIALIASED,
+                 "mode must be LCGS_RASTER_CLASSIC or LCGS_RASTER_ANTIALIASED");
+    LCGS_ENTRY(ctx);
+    ctx->raster_mode = mode;
+    if (ctx->twin) ctx->twin->raster_mode = mode;
+    return LCGS_OK;
+}
+
 lcgs_status lcgs_set_ingest_order(lcgs_context* ctx, int order)
 {
     LCGS_REQUIRE(ctx != nullptr, "ctx is NULL");

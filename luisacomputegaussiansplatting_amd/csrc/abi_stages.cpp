@@ -192,6 +192,7 @@ lcgs_status lcgs_tile_splat_forward(lcgs_context* ctx, const lcgs_tile_accel* ac
             b.means == input->means_2d && b.covs == input->conic && b.depth == input->depth_features && same_cam &&
             b.use_focal != 0 && use_focal != 0 && a.level >= 0 && a.level <= 3 && b.cam.width == output->width &&
             b.cam.height == output->height && !output->final_T && !output->n_contrib && ctx->lod_min_radius == 0 &&
+            ctx->raster_mode == LCGS_RASTER_CLASSIC &&
             (reinterpret_cast<uintptr_t>(b.rotq) & 15) == 0 && P < (1 << 30);
         if (match) {
             // the recorded arrays stand in for the context's scene for this one frame

@@ -80,6 +80,8 @@ void usage(const char* argv0)
            "                           optimised, the L1 regulariser (0.01 each) before and SGLD noise after every Adam step, dead\n"
            "                           splats relocated and the set grown by 5 %% every 100 steps from step 500\n");
     printf("  --cap-max <N>            With --density mcmc: the splat budget the set grows to (default: the scene's count)\n");
+    printf("  --antialiased            Render (and --fit) the antialiased frame: every splat's opacity times\n"
+           "                           sqrt(det cov / det(cov + 0.3 I)) (lcgs_set_raster_mode; --path fused, not with --owner)\n");
     printf("  --display                Not supported (headless)\n");
 }
 
@@ -101,7 +103,7 @@ int main(int argc, char** argv)
     long long   cap_max = 0;
     float       lambda_dssim = 0.2f;
     int         exp_N = 1, gpus = 1, fit_steps = 0;
-    bool        backward = false, fused_adam = false, owner = false, comm_selftest = false;
+    bool        backward = false, fused_adam = false, owner = false, comm_selftest = false, antialiased = false;
     // parse_command (app/command_parser.hpp:5-79): strip leading dashes, `key=value` or `key value`
     for (int i = 1; i < argc; ++i) {
         std::string arg = argv[i];
@@ -180,9 +182,12 @@ int main(int argc, char** argv)
             cap_max = std::stoll(value);
             if (cap_max < 1 || cap_max > 0x7fffffff) die("--cap-max out of range");
         }
+        else if (key == "antialiased") antialiased = true;
         else if (key == "display") die("--display needs a GUI; this build is headless");
         else die("unknown option --" + key);
     }
+    if (antialiased && (path != "fused" || owner))
+        die("--antialiased is a mode of the fused frame (--path fused, without --owner)");
     // ply stem (app/main.cpp:126-148)
     std::string ply_name = ply_path;
     size_t      sp       = ply_name.find_last_of("/\\");
@@ -246,6 +251,7 @@ int main(int argc, char** argv)
 
     try {
         lcgs::Device device(rank);
+        if (antialiased) device.set_raster_mode(LCGS_RASTER_ANTIALIASED);
         // ---- scene: read_gs_ply (app/main.cpp:165-167) or a synthetic stand-in
         lcgs_scene_host sc{};
         std::vector<float> spos, sfeat, sop, sscale, srot;

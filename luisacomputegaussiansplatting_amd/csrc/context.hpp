@@ -43,6 +43,7 @@ struct lcgs_context {
     // Splat order of a context-owned scene: lcgs_scene_load_ply re-orders along a Morton curve unless told otherwise
     // (lcgs_set_ingest_order); scene_perm[r] = file index of splat r while perm_valid (lcgs_scene_permutation)
     int          lod_min_radius = 0; // lcgs_set_lod: opt-in footprint cull of the fused frame (0 = off)
+    int          raster_mode = 0;    // lcgs_set_raster_mode: LCGS_RASTER_CLASSIC, or the opacity-compensated frame (a kept frame remembers its own: last.cp)
     int          ingest_order = 1; // LCGS_ORDER_SPATIAL
     DeviceBuffer scene_perm;
     bool         perm_valid = false;      // the BOUND arrays are owned[] in the order scene_perm describes

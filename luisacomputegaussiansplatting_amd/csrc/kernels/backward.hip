@@ -505,13 +505,14 @@ __device__ __forceinline__ void store_geometry_rows(size_t orow, bool accumulate
     }
 }
 
+template <bool AA>
 __global__ void __launch_bounds__(256)
 k_preprocess_backward(int sh_deg, CamParams cp, float scale_modifier, const float* __restrict__ pos,
                       const float* __restrict__ scale, const float* __restrict__ rotq, const float* __restrict__ sh,
                       const uint32_t* __restrict__ vis_index, const uint32_t* __restrict__ d_counts,
                       const float* __restrict__ grads2d, float* __restrict__ dL_dpos, float* __restrict__ dL_dscale,
                       float* __restrict__ dL_drotq, float* __restrict__ dL_dsh, float* __restrict__ dL_dopacity,
-                      int mode, const uint32_t* __restrict__ slice_bounds, int slice)
+                      int mode, const uint32_t* __restrict__ slice_bounds, int slice, const float* __restrict__ opacity)
 {
     __shared__ float4 s_sh[4][64 * 13];
     const bool compact = (mode & 1) != 0, accumulate = (mode & 2) != 0; // (see launch_preprocess_backward)
@@ -529,7 +530,7 @@ k_preprocess_backward(int sh_deg, CamParams cp, float scale_modifier, const floa
         const uint32_t wave_first = v0 + blk * 256u + wave * 64u;
         const uint32_t nvalid     = wave_first < V ? ((V - wave_first) < 64u ? (V - wave_first) : 64u) : 0u;
         float*         row = reinterpret_cast<float*>(&s_sh[wave][lane * 13]); // this lane's 48 floats (+4 pad)
-        const SplatOperands in = load_splat_operands(valid ? vid : V - 1, idx, grads2d, pos, scale, rotq); // (with the SH rows below)
+        const SplatOperands in = load_splat_operands<AA>(valid ? vid : V - 1, idx, grads2d, pos, scale, rotq, opacity); // (with the SH rows below)
 
         // ---- stage the SH rows (coalesced), or fetch them lane-wise for other degrees
         __syncthreads();
@@ -553,12 +554,12 @@ k_preprocess_backward(int sh_deg, CamParams cp, float scale_modifier, const floa
             // ---- colour -> SH coefficients and position (through the view direction)
             sh_colour_step<true>(cp, in, feat, row, gp);
 
-            float  gs[3];
+            float  gs[3], gop;
             float4 gq;
-            geom_backward(cp, scale_modifier, in, gp, gs, gq);
+            geom_backward<AA>(cp, scale_modifier, in, gp, gs, gq, gop);
 
             const size_t orow = compact ? (size_t)vid : (size_t)idx; // compact: row = dense id (see launch.hpp)
-            store_geometry_rows(orow, accumulate, gp, gs, gq, in.gop, dL_dpos, dL_dscale, dL_drotq, dL_dopacity);
+            store_geometry_rows(orow, accumulate, gp, gs, gq, gop, dL_dpos, dL_dscale, dL_drotq, dL_dopacity);
         }
 
         // ---- SH gradient rows: 12 consecutive lanes write one splat's 192 contiguous bytes
@@ -607,6 +608,7 @@ __device__ __forceinline__ float4 jac_outer_part(const float* slot, uint32_t par
     return make_float4(v[0], v[1], v[2], v[3]);
 }
 
+template <bool AA>
 __global__ void __launch_bounds__(256)
 k_preprocess_backward_jac(CamParams cp, float scale_modifier, const float* __restrict__ pos,
                           const float* __restrict__ scale, const float* __restrict__ rotq,
@@ -614,7 +616,7 @@ k_preprocess_backward_jac(CamParams cp, float scale_modifier, const float* __res
                           const float* __restrict__ grads2d, const float4* __restrict__ shjac,
                           float* __restrict__ dL_dpos, float* __restrict__ dL_dscale, float* __restrict__ dL_drotq,
                           float* __restrict__ dL_dsh, float* __restrict__ dL_dopacity, int mode,
-                          const uint32_t* __restrict__ slice_bounds, int slice)
+                          const uint32_t* __restrict__ slice_bounds, int slice, const float* __restrict__ opacity)
 {
     __shared__ float s_outer[4][64 * kJacPitch];
     const bool compact = (mode & 1) != 0, accumulate = (mode & 2) != 0;
@@ -628,15 +630,15 @@ k_preprocess_backward_jac(CamParams cp, float scale_modifier, const float* __res
         const int      idx   = (int)vis_index[vsafe];
         const uint32_t wave_first = v0 + blk * 256u + wave * 64u;
         const uint32_t nvalid     = wave_first < V ? ((V - wave_first) < 64u ? (V - wave_first) : 64u) : 0u;
-        const SplatOperands in = load_splat_operands(vsafe, idx, grads2d, pos, scale, rotq);
+        const SplatOperands in = load_splat_operands<AA>(vsafe, idx, grads2d, pos, scale, rotq, opacity);
         const float4 j0 = shjac[(size_t)vsafe * 3 + 0], j1 = shjac[(size_t)vsafe * 3 + 1], j2 = shjac[(size_t)vsafe * 3 + 2];
         if (valid) {
-            float  gp[3], gs[3];
+            float  gp[3], gs[3], gop;
             float4 gq;
             jac_colour_step(cp, in, j0, j1, j2, &s_outer[wave][lane * kJacPitch], gp);
-            geom_backward(cp, scale_modifier, in, gp, gs, gq);
+            geom_backward<AA>(cp, scale_modifier, in, gp, gs, gq, gop);
             const size_t orow = compact ? (size_t)vid : (size_t)idx; // compact: row = dense id (see launch.hpp)
-            store_geometry_rows(orow, accumulate, gp, gs, gq, in.gop, dL_dpos, dL_dscale, dL_drotq, dL_dopacity);
+            store_geometry_rows(orow, accumulate, gp, gs, gq, gop, dL_dpos, dL_dscale, dL_drotq, dL_dopacity);
         }
         __syncthreads();
         // ---- SH gradient rows: 12 consecutive lanes write one splat's 192 contiguous bytes
@@ -670,8 +672,10 @@ k_preprocess_backward_jac(CamParams cp, float scale_modifier, const float* __res
 // bicycle stand-in).  Each lane owns its splat's rows in raw / m / v / activated: read, updated, written by the same lane,
 // so the in-place update of the arrays this very kernel reads (the activated pos / scale / rotq are the renderer's scene
 // arrays) needs no synchronisation.
+template <bool AA>
 __global__ void __launch_bounds__(256)
 k_preprocess_backward_adam(CamParams cp, float scale_modifier, const float* pos, const float* scale, const float* rotq,
+                           const float* opacity,
                            const uint32_t* __restrict__ vis_index, const uint32_t* __restrict__ d_counts,
                            const float* __restrict__ grads2d, const float4* __restrict__ shjac, AdamArrays raw, AdamArrays am,
                            AdamArrays av, AdamArrays act, AdamRates lr, AdamStep a)
@@ -686,13 +690,14 @@ k_preprocess_backward_adam(CamParams cp, float scale_modifier, const float* pos,
         const int      idx   = (int)vis_index[vsafe];
         const uint32_t wave_first = blk * 256u + wave * 64u;
         const uint32_t nvalid     = wave_first < V ? ((V - wave_first) < 64u ? (V - wave_first) : 64u) : 0u;
-        const SplatOperands in = load_splat_operands(vsafe, idx, grads2d, pos, scale, rotq);
+        // (an antialiased frame's raw opacity is read here, before this lane's update of the activated row below)
+        const SplatOperands in = load_splat_operands<AA>(vsafe, idx, grads2d, pos, scale, rotq, opacity);
         const float4 j0 = shjac[(size_t)vsafe * 3 + 0], j1 = shjac[(size_t)vsafe * 3 + 1], j2 = shjac[(size_t)vsafe * 3 + 2];
         if (valid) {
-            float  gp[3], gs[3];
+            float  gp[3], gs[3], gop;
             float4 gq;
             jac_colour_step(cp, in, j0, j1, j2, &s_outer[wave][lane * kJacPitch], gp);
-            geom_backward(cp, scale_modifier, in, gp, gs, gq);
+            geom_backward<AA>(cp, scale_modifier, in, gp, gs, gq, gop);
             // ---- Adam on this splat's geometry rows (train.hip: k_adam_rows<3,0>, <3,1>, k_adam_rot, <1,2>)
             const size_t i3 = 3 * (size_t)idx;
 #pragma unroll
@@ -727,7 +732,7 @@ k_preprocess_backward_adam(CamParams cp, float scale_modifier, const float* pos,
             }
             {
                 float x = raw.opacity[idx], mm = am.opacity[idx], vv = av.opacity[idx], o = act.opacity[idx];
-                adam_opacity(in.gop, x, mm, vv, o, lr.opacity, a);
+                adam_opacity(gop, x, mm, vv, o, lr.opacity, a);
                 am.opacity[idx]  = mm;
                 av.opacity[idx]  = vv;
                 raw.opacity[idx] = x;
@@ -835,30 +840,44 @@ void launch_preprocess_backward(int64_t v_hint, int sh_deg, const CamParams& cp,
                                 const uint32_t* d_counts, const float* grads2d, float* dL_dpos, float* dL_dscale,
                                 float* dL_drotq, float* dL_dsh, float* dL_dopacity, hipStream_t stream,
                                 const float4* shjac, bool compact, const uint32_t* slice_bounds, int slice, int slices,
-                                bool accumulate)
+                                bool accumulate, const float* opacity)
 {
     const int mode = (compact ? 1 : 0) | (accumulate ? 2 : 0);
     // (a slice's launch is sized for its share of the hint; larger live counts are strided)
     const unsigned blocks = grid_256(v_hint / (slice_bounds ? slices : 1));
+    const bool aa = cp.raster_mode != 0; // (one instantiation per raster mode: the classic pass carries none of the other's code)
     if (shjac && sh_deg == 3 && (reinterpret_cast<uintptr_t>(dL_dsh) & 15) == 0) {
-        hipLaunchKernelGGL(k_preprocess_backward_jac, dim3(blocks), dim3(256), 0, stream, cp, scale_modifier, pos,
-                           scale, rotq, vis_index, d_counts, grads2d, shjac, dL_dpos, dL_dscale, dL_drotq, dL_dsh,
-                           dL_dopacity, mode, slice_bounds, slice);
+#define LCGS_LAUNCH_JAC(AA_)                                                                                                   \
+    hipLaunchKernelGGL((k_preprocess_backward_jac<AA_>), dim3(blocks), dim3(256), 0, stream, cp, scale_modifier, pos, scale, rotq,  \
+                       vis_index, d_counts, grads2d, shjac, dL_dpos, dL_dscale, dL_drotq, dL_dsh, dL_dopacity, mode, slice_bounds, \
+                       slice, opacity)
+        if (aa) LCGS_LAUNCH_JAC(true);
+        else LCGS_LAUNCH_JAC(false);
+#undef LCGS_LAUNCH_JAC
         return;
     }
-    hipLaunchKernelGGL(k_preprocess_backward, dim3(blocks), dim3(256), 0, stream, sh_deg, cp, scale_modifier,
-                       pos, scale, rotq, sh, vis_index, d_counts, grads2d, dL_dpos, dL_dscale, dL_drotq, dL_dsh,
-                       dL_dopacity, mode, slice_bounds, slice);
+#define LCGS_LAUNCH_ROWS(AA_)                                                                                                  \
+    hipLaunchKernelGGL((k_preprocess_backward<AA_>), dim3(blocks), dim3(256), 0, stream, sh_deg, cp, scale_modifier, pos, scale,  \
+                       rotq, sh, vis_index, d_counts, grads2d, dL_dpos, dL_dscale, dL_drotq, dL_dsh, dL_dopacity, mode,        \
+                       slice_bounds, slice, opacity)
+    if (aa) LCGS_LAUNCH_ROWS(true);
+    else LCGS_LAUNCH_ROWS(false);
+#undef LCGS_LAUNCH_ROWS
 }
 
 void launch_preprocess_backward_adam(int64_t v_hint, const CamParams& cp, float scale_modifier, const float* pos,
-                                     const float* scale, const float* rotq, const uint32_t* vis_index, const uint32_t* d_counts,
+                                     const float* scale, const float* rotq, const float* opacity, const uint32_t* vis_index,
+                                     const uint32_t* d_counts,
                                      const float* grads2d, const float4* shjac, const AdamArrays& raw, const AdamArrays& m,
                                      const AdamArrays& v, const AdamArrays& act, const AdamRates& lr, const AdamStep& a,
                                      hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_preprocess_backward_adam, dim3(grid_256(v_hint)), dim3(256), 0, stream, cp, scale_modifier, pos, scale,
-                       rotq, vis_index, d_counts, grads2d, shjac, raw, m, v, act, lr, a);
+#define LCGS_LAUNCH_ADAM(AA_)                                                                                                  \
+    hipLaunchKernelGGL((k_preprocess_backward_adam<AA_>), dim3(grid_256(v_hint)), dim3(256), 0, stream, cp, scale_modifier, pos,   \
+                       scale, rotq, opacity, vis_index, d_counts, grads2d, shjac, raw, m, v, act, lr, a)
+    if (cp.raster_mode != 0) LCGS_LAUNCH_ADAM(true);
+    else LCGS_LAUNCH_ADAM(false);
+#undef LCGS_LAUNCH_ADAM
 }
 
 } // namespace lcgs

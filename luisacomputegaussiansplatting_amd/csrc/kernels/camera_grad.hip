@@ -30,12 +30,12 @@ __device__ __forceinline__ double wave_sum(double x)
     return x;
 }
 
-template <bool JAC>
+template <bool JAC, bool AA>
 __global__ void __launch_bounds__(256)
 k_camera_grad(int sh_deg, CamParams cp, float scale_modifier, const float* __restrict__ pos, const float* __restrict__ scale,
               const float* __restrict__ rotq, const float* __restrict__ sh, const uint32_t* __restrict__ vis_index,
               const uint32_t* __restrict__ d_counts, const float* __restrict__ grads2d, const float4* __restrict__ shjac,
-              const SplatRecord* __restrict__ recs, int depth_mode, double* __restrict__ slab)
+              const SplatRecord* __restrict__ recs, int depth_mode, double* __restrict__ slab, const float* __restrict__ opacity)
 {
     __shared__ float4 s_sh[JAC ? 1 : 4][JAC ? 1 : 64 * 13]; // (the coefficient rows' slab: the SH-row path only)
     __shared__ double s_part[4][kCamTerms];
@@ -48,7 +48,7 @@ k_camera_grad(int sh_deg, CamParams cp, float scale_modifier, const float* __res
         const bool     valid = vid < V;
         const uint32_t vsafe = valid ? vid : V - 1;
         const int      idx   = (int)vis_index[vsafe];
-        const SplatOperands in = load_splat_operands(vsafe, idx, grads2d, pos, scale, rotq);
+        const SplatOperands in = load_splat_operands<AA>(vsafe, idx, grads2d, pos, scale, rotq, opacity);
         float gdir[3] = { 0.0f, 0.0f, 0.0f };
         if constexpr (JAC) {
             const float4 j0 = shjac[(size_t)vsafe * 3 + 0], j1 = shjac[(size_t)vsafe * 3 + 1], j2 = shjac[(size_t)vsafe * 3 + 2];
@@ -85,7 +85,7 @@ k_camera_grad(int sh_deg, CamParams cp, float scale_modifier, const float* __res
                 const float gv = grads2d[(size_t)vid * kG2D + kG2DValueSlot];
                 if (gv != 0.0f) gz = kept_walk::depth_value_backward(recs[vid].depth, depth_mode, gv);
             }
-            camera_terms(cp, scale_modifier, in, gdir, gz, t);
+            camera_terms<AA>(cp, scale_modifier, in, gdir, gz, t);
         }
         // ---- the block's twelve sums: butterfly over the wave, then the four waves in order
 #pragma unroll
@@ -129,15 +129,19 @@ size_t camera_grad_slab_bytes(int64_t P) { return (size_t)((P + 255) / 256) * kC
 void launch_camera_grad(int64_t v_hint, int sh_deg, const CamParams& cp, float scale_modifier, const float* pos, const float* scale,
                         const float* rotq, const float* sh, const uint32_t* vis_index, const uint32_t* d_counts,
                         const float* grads2d, const float4* shjac, const SplatRecord* recs, int depth_mode, double* slab,
-                        float* dL_dcam, hipStream_t stream)
+                        float* dL_dcam, hipStream_t stream, const float* opacity)
 {
     const unsigned blocks = grid_256(v_hint);
-    if (shjac && sh_deg == 3)
-        hipLaunchKernelGGL(k_camera_grad<true>, dim3(blocks), dim3(256), 0, stream, sh_deg, cp, scale_modifier, pos, scale, rotq, sh,
-                           vis_index, d_counts, grads2d, shjac, recs, depth_mode, slab);
-    else
-        hipLaunchKernelGGL(k_camera_grad<false>, dim3(blocks), dim3(256), 0, stream, sh_deg, cp, scale_modifier, pos, scale, rotq, sh,
-                           vis_index, d_counts, grads2d, shjac, recs, depth_mode, slab);
+    // (one instantiation per raster mode, like the preprocess-backward's: the classic pass carries none of the other's code)
+#define LCGS_LAUNCH_CAM(JAC_, AA_)                                                                                             \
+    hipLaunchKernelGGL((k_camera_grad<JAC_, AA_>), dim3(blocks), dim3(256), 0, stream, sh_deg, cp, scale_modifier, pos, scale,   \
+                       rotq, sh, vis_index, d_counts, grads2d, shjac, recs, depth_mode, slab, opacity)
+    const bool jac = shjac && sh_deg == 3, aa = cp.raster_mode != 0;
+    if (jac && aa) LCGS_LAUNCH_CAM(true, true);
+    else if (jac) LCGS_LAUNCH_CAM(true, false);
+    else if (aa) LCGS_LAUNCH_CAM(false, true);
+    else LCGS_LAUNCH_CAM(false, false);
+#undef LCGS_LAUNCH_CAM
     hipLaunchKernelGGL(k_camera_grad_finish, dim3(1), dim3(256), 0, stream, d_counts, slab, dL_dcam);
 }
 

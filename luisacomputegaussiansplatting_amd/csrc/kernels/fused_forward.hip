@@ -62,6 +62,7 @@ struct Projected {
     float    pix_x, pix_y, depth, conic[3];
     uint32_t rmin[2], rw, rh; // pruned rect: origin + size in LIST BLOCKS (= tiles unless CamParams::list_shift)
     uint32_t trect_xy, trect_wh; // the same rect in tiles, packed like SplatRecord::rect_xy / rect_wh
+    float    opac;      // the opacity the frame blends with: the splat's own, x rho in an antialiased frame (gs_math.hpp aa_compensation)
 };
 
 // One splat's inputs, loaded before any of the arithmetic so that all of a lane's loads are in flight together.
@@ -96,6 +97,7 @@ __device__ __forceinline__ Projected project_splat(const CamParams& cp, float sc
     r.conic[0] = r.conic[1] = r.conic[2] = 0.0f;
     r.rmin[0] = r.rmin[1] = r.rw = r.rh = 0;
     r.trect_xy = r.trect_wh = 0;
+    r.opac     = opac;
     float v[3], ndc[2];
     view_transform(cp, px, py, pz, v);
     if (v[2] < 0.2f) return r; // gs_projector/shader.cpp:121
@@ -119,7 +121,10 @@ __device__ __forceinline__ Projected project_splat(const CamParams& cp, float sc
     r.ref_tiles = (fmax[0] - fmin[0]) * (fmax[1] - fmin[1]);
     if (r.radius <= 0) r.ref_tiles = 0; // radius <= 0 never emits pairs (gs_tile_splatter/shader.cpp:41-42)
     if (r.ref_tiles == 0) return r;
-    tight_rect(r.pix_x, r.pix_y, filt[0], filt[1], filt[2], opac, fmin, fmax, tmin, tmax);
+    // opt-in antialiased frame (lcgs_set_raster_mode; never taken at the default): the cull pass and the record builder both
+    // come through here, so the pruned rect and the record agree on the compensated opacity
+    if (cp.raster_mode != 0) r.opac = opac * aa_compensation(cov2d, filt);
+    tight_rect(r.pix_x, r.pix_y, filt[0], filt[1], filt[2], r.opac, fmin, fmax, tmin, tmax);
     r.trect_xy = tmin[0] | (tmin[1] << 16);
     r.trect_wh = (tmax[0] - tmin[0]) | ((tmax[1] - tmin[1]) << 16);
     if (cp.list_shift != 0u && tmax[0] > tmin[0] && tmax[1] > tmin[1]) { // the same rect in list blocks (half-open)
@@ -561,7 +566,7 @@ k_build_records(int sh_deg, CamParams cp, float scale_modifier, const FrameParam
     const Projected pr = project_splat(cp, scale_modifier, in, opacity[idx]);
     float4* out = reinterpret_cast<float4*>(recs + vid);
     out[0]      = make_float4(pr.pix_x, pr.pix_y, pr.conic[0], pr.conic[1]);
-    out[1]      = make_float4(pr.conic[2], opacity[idx], clamp_(raw[0], 0.0f, 1.0f), clamp_(raw[1], 0.0f, 1.0f));
+    out[1]      = make_float4(pr.conic[2], pr.opac, clamp_(raw[0], 0.0f, 1.0f), clamp_(raw[1], 0.0f, 1.0f));
     out[2]      = make_float4(clamp_(raw[2], 0.0f, 1.0f), pr.depth, __uint_as_float(pr.trect_xy), __uint_as_float(pr.trect_wh));
     if (JAC) {
         // last, with the record gone from the registers; the coefficients are read from the LDS row once more

@@ -59,6 +59,10 @@ struct CamParams {
     // own one 16 x 16 tile each and walk their block's list -- the reach masks of their staging drop what belongs to the block's
     // other tiles.  Frames that keep backward state use 0 (the backward walks per-tile lists).
     uint32_t list_shift;
+    // opt-in antialiased frame (lcgs_set_raster_mode; 0 = classic = the reference's behaviour): the splat's opacity is
+    // multiplied by rho = sqrt(det cov2d / det(cov2d + 0.3 I)) (aa_compensation below), so the dilated splat carries the
+    // energy of the undilated one.  Radius, rect, depth and keys are the classic frame's.
+    int32_t raster_mode;
 };
 LCGS_HD uint32_t list_grid_x(const CamParams& cp) { return (cp.grid_x + (1u << cp.list_shift) - 1u) >> cp.list_shift; }
 LCGS_HD uint32_t list_grid_y(const CamParams& cp) { return (cp.grid_y + (1u << cp.list_shift) - 1u) >> cp.list_shift; }
@@ -368,6 +372,17 @@ LCGS_HD void conic_and_radius(float cx, float cy, float cz, bool use_focal, uint
     float lambda1 = mid + sqrtf(fmax_(0.1f, mid * mid - det));
     float lambda2 = mid - sqrtf(fmax_(0.1f, mid * mid - det));
     radius        = f2i_sat(ceilf(3.0f * sqrtf(fmax_(lambda1, lambda2))));
+}
+
+// Opacity compensation of the antialiased frame (NOT in the reference; the 2-D filter of Mip-Splatting, Yu et al. CVPR 2024):
+// rho = sqrt(max(0, det cov / det filtered)) from the projector's raw covariance and conic_and_radius' `filtered`.  d1 has the
+// bits of conic_and_radius' det before its + 1e-6; IEEE division and square root; a NaN quotient gives 0.
+LCGS_HD float aa_compensation(const float cov[3], const float filtered[3])
+{
+    const float d0 = cov[0] * cov[2] - cov[1] * cov[1];
+    const float d1 = filtered[0] * filtered[2] - filtered[1] * filtered[1];
+    const float q  = d0 / d1;
+    return q > 0.0f ? sqrtf(q) : 0.0f;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -293,7 +293,8 @@ void launch_photometric_finish(int W, int H, const double* partials, float lambd
 // backward.hip: the per-splat half of the backward with the on-screen-only Adam update applied where the gradients are
 // formed (degree 3, frames that kept the colour Jacobian): no gradient rows are written at all
 void launch_preprocess_backward_adam(int64_t v_hint, const CamParams& cp, float scale_modifier, const float* pos,
-                                     const float* scale, const float* rotq, const uint32_t* vis_index, const uint32_t* d_counts,
+                                     const float* scale, const float* rotq, const float* opacity /* read for an antialiased frame */,
+                                     const uint32_t* vis_index, const uint32_t* d_counts,
                                      const float* grads2d, const float4* shjac, const AdamArrays& raw, const AdamArrays& m,
                                      const AdamArrays& v, const AdamArrays& act, const AdamRates& lr, const AdamStep& a,
                                      hipStream_t stream);
@@ -402,7 +403,9 @@ void   launch_preprocess_backward(int64_t v_hint, int sh_deg, const CamParams& c
                                   // (a splat-range slice, see launch_slice_bounds; `slices` sizes the launch)
                                   const uint32_t* slice_bounds = nullptr, int slice = 0, int slices = 1,
                                   // accumulate: ADD the rows to what the arrays hold (dense rows of a further view)
-                                  bool accumulate = false);
+                                  bool accumulate = false,
+                                  // the scene's opacity rows: read only for a row of an antialiased frame (cp.raster_mode)
+                                  const float* opacity = nullptr);
 // bounds[0 .. slices]: dense-id boundaries of the splat-index ranges [k P / slices, (k + 1) P / slices), k < slices <= 63
 void   launch_slice_bounds(const uint32_t* vis_index, const uint32_t* d_counts, int64_t P, int slices, uint32_t* bounds,
                            hipStream_t stream);
@@ -445,6 +448,7 @@ size_t camera_grad_slab_bytes(int64_t P);
 void launch_camera_grad(int64_t v_hint, int sh_deg, const CamParams& cp, float scale_modifier, const float* pos, const float* scale,
                         const float* rotq, const float* sh, const uint32_t* vis_index, const uint32_t* d_counts,
                         const float* grads2d, const float4* shjac, const SplatRecord* recs, int depth_mode, double* slab,
-                        float* dL_dcam, hipStream_t stream);
+                        float* dL_dcam, hipStream_t stream,
+                        const float* opacity = nullptr); // the scene's opacity rows: read only for an antialiased frame (cp.raster_mode)
 
 } // namespace lcgs

@@ -24,10 +24,15 @@ struct GeomCameraTerms {
 // dL/d{pixel mean (gmx, gmy), conic (gA, gB, gC)} -> dL/d{pos (gp), scale (gs), rotq (gq: r,x,y,z)} through the EWA
 // projection, in precision R.  The forward quantities are recomputed (the order of gs_math.hpp is irrelevant for the
 // derivative).  cov_trace = a + c of the filtered 2-D covariance (>= its larger eigenvalue: the splat's footprint).
+// aa_rho != NULL: a row of an antialiased frame (CamParams::raster_mode).  The frame blended with o' = opacity * rho,
+// rho = sqrt(max(0, d0 / d1)), d0 = a0 c0 - b^2 of the raw and d1 = a c - b^2 of the filtered covariance (the unfloored d1, not
+// D = d1 + 1e-6); aa_go = dL/do' * opacity.  rho is returned through aa_rho (dL/dopacity = dL/do' * rho is the caller's) and
+// aa_go * drho/d(a, b, c) joins g00 / g01 / g11, so the parameter gradients and the camera terms carry it with no further code.
 template <typename FP>
 __device__ __forceinline__ void geom_backward_t(const CamParams& cp, FP scale_modifier, FP px, FP py, FP pz, FP sc0, FP sc1, FP sc2,
                                                 FP qw_, FP qx_, FP qy_, FP qz_, FP gmx, FP gmy, FP gA, FP gB, FP gC, FP gp[3], FP gs[3],
-                                                FP gq[4], FP& cov_trace, GeomCameraTerms<FP>* cam_terms = nullptr)
+                                                FP gq[4], FP& cov_trace, GeomCameraTerms<FP>* cam_terms = nullptr,
+                                                FP aa_go = FP(0.0), FP* aa_rho = nullptr)
 {
     // ---- geometry: recompute the forward quantities (gs_math.hpp order is irrelevant for the derivative)
     FP v[3];
@@ -69,14 +74,27 @@ __device__ __forceinline__ void geom_backward_t(const CamParams& cp, FP scale_mo
         ST0[r] = Sig[r][0] * T0[0] + Sig[r][1] * T0[1] + Sig[r][2] * T0[2];
         ST1[r] = Sig[r][0] * T1[0] + Sig[r][1] * T1[1] + Sig[r][2] * T1[2];
     }
-    const FP a = T0[0] * ST0[0] + T0[1] * ST0[1] + T0[2] * ST0[2] + FP(0.3);
+    const FP a0 = T0[0] * ST0[0] + T0[1] * ST0[1] + T0[2] * ST0[2];
     const FP b = T1[0] * ST0[0] + T1[1] * ST0[1] + T1[2] * ST0[2];
-    const FP c = T1[0] * ST1[0] + T1[1] * ST1[1] + T1[2] * ST1[2] + FP(0.3);
+    const FP c0 = T1[0] * ST1[0] + T1[1] * ST1[1] + T1[2] * ST1[2];
+    const FP a = a0 + FP(0.3), c = c0 + FP(0.3);
     const FP D = a * c - b * b + FP(1e-6);
     const FP iD2 = FP(1.0) / (D * D);
-    const FP g00 = (-c * c * gA + b * c * gB + (D - a * c) * gC) * iD2;
-    const FP g11 = ((D - a * c) * gA + a * b * gB - a * a * gC) * iD2;
-    const FP g01 = (FP(2.0) * b * c * gA - (D + FP(2.0) * b * b) * gB + FP(2.0) * a * b * gC) * iD2;
+    FP g00 = (-c * c * gA + b * c * gB + (D - a * c) * gC) * iD2;
+    FP g11 = ((D - a * c) * gA + a * b * gB - a * a * gC) * iD2;
+    FP g01 = (FP(2.0) * b * c * gA - (D + FP(2.0) * b * b) * gB + FP(2.0) * a * b * gC) * iD2;
+    if (aa_rho) { // (a row of an antialiased frame; a compile-time NULL in the classic frame's kernels)
+        const FP d0 = a0 * c0 - b * b, d1 = a * c - b * b;
+        const FP q   = d0 / d1;
+        const FP rho = q > FP(0.0) ? FP(sqrt(q)) : FP(0.0); // (a NaN quotient gives 0, like the forward)
+        *aa_rho      = rho;
+        if (rho > FP(0.0)) {
+            const FP k = aa_go / (FP(2.0) * rho * (d1 * d1));
+            g00 += k * (c0 * d1 - d0 * c);
+            g11 += k * (a0 * d1 - d0 * a);
+            g01 += k * (FP(2.0) * b * (d0 - d1));
+        }
+    }
     FP Gm[3][3], dT0[3], dT1[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r)
@@ -140,9 +158,13 @@ struct SplatOperands {
     float  gmx, gmy, gA, gB, gC, gop, gcol[3]; // dL/d{pixel mean, conic, opacity, colour}
     float  px, py, pz, sc0, sc1, sc2;
     float4 q; // (r,x,y,z)
+    float  opac; // the splat's own opacity: loaded for a row of an antialiased frame only (0 otherwise, never read)
 };
+// AA: a row of an antialiased frame (CamParams::raster_mode; the kernels are compiled once per mode, so the classic frame's
+// pass is the code it was before the mode existed); opacity: the scene's rows, read only then
+template <bool AA>
 __device__ __forceinline__ SplatOperands load_splat_operands(uint32_t vsafe, int idx, const float* grads2d, const float* pos,
-                                                             const float* scale, const float* rotq)
+                                                             const float* scale, const float* rotq, const float* opacity)
 {
     const float4* g2 = reinterpret_cast<const float4*>(grads2d + (size_t)vsafe * kG2D);
     const float4  q0 = g2[0], q1 = g2[1];
@@ -153,6 +175,7 @@ __device__ __forceinline__ SplatOperands load_splat_operands(uint32_t vsafe, int
     in.q = *reinterpret_cast<const float4*>(rotq + 4 * (size_t)idx);
     in.gmx = q0.x, in.gmy = q0.y, in.gA = q0.z, in.gB = q0.w, in.gC = q1.x, in.gop = q1.y;
     in.gcol[0] = q1.z, in.gcol[1] = q1.w, in.gcol[2] = gcol2;
+    in.opac = AA ? opacity[idx] : 0.0f;
     return in;
 }
 
@@ -167,16 +190,21 @@ constexpr float kGiantCovTrace = 455.0f;
 // terms, and ANY f32 evaluation loses them (the f32 CPU restatement is off by up to 1.7e-1 on such rows; the 2-D gradients
 // feeding this step are good to ~1e-4: profiles/r04_gradient_error_survey.txt).  0.4 % of the on-screen splats of the
 // bicycle stand-in qualify; the kernels calling this are HBM-bound, the divergent f64 pass hides under their stores.
+// gop: dL/dopacity of the row -- in.gop, times rho for a row of an antialiased frame (whose in.gop is dL/d(opacity rho)).
+template <bool AA>
 __device__ __forceinline__ void geom_backward(const CamParams& cp, float scale_modifier, const SplatOperands& in, float gp[3],
-                                              float gs[3], float4& gq)
+                                              float gs[3], float4& gq, float& gop)
 {
-    float dp[3], q4[4], tr;
+    constexpr bool aa = AA;
+    float dp[3], q4[4], tr, rho = 1.0f;
     geom_backward_t<float>(cp, scale_modifier, in.px, in.py, in.pz, in.sc0, in.sc1, in.sc2, in.q.x, in.q.y, in.q.z, in.q.w, in.gmx,
-                           in.gmy, in.gA, in.gB, in.gC, dp, gs, q4, tr);
+                           in.gmy, in.gA, in.gB, in.gC, dp, gs, q4, tr, nullptr, in.gop * in.opac, aa ? &rho : nullptr);
     if (tr > kGiantCovTrace) {
-        double dpd[3], gsd[3], q4d[4], trd;
+        double dpd[3], gsd[3], q4d[4], trd, rhod = 1.0;
         geom_backward_t<double>(cp, scale_modifier, in.px, in.py, in.pz, in.sc0, in.sc1, in.sc2, in.q.x, in.q.y, in.q.z, in.q.w,
-                                in.gmx, in.gmy, in.gA, in.gB, in.gC, dpd, gsd, q4d, trd);
+                                in.gmx, in.gmy, in.gA, in.gB, in.gC, dpd, gsd, q4d, trd, nullptr, (double)in.gop * (double)in.opac,
+                                aa ? &rhod : nullptr);
+        rho = (float)rhod;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             dp[i] = (float)dpd[i];
@@ -187,7 +215,8 @@ __device__ __forceinline__ void geom_backward(const CamParams& cp, float scale_m
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) gp[i] += dp[i];
-    gq = make_float4(q4[0], q4[1], q4[2], q4[3]);
+    gq  = make_float4(q4[0], q4[1], q4[2], q4[3]);
+    gop = aa ? in.gop * rho : in.gop;
 }
 
 // The colour step of that path for one splat: parks the 16 basis values of its view direction and its 3 clamp-masked
@@ -286,18 +315,21 @@ __device__ __forceinline__ void camera_terms_t(const CamParams& cp, const SplatO
     }
 }
 // ... in the precision geom_backward takes for this splat: binary32, binary64 for a screen-filling footprint
+template <bool AA>
 __device__ __forceinline__ void camera_terms(const CamParams& cp, float scale_modifier, const SplatOperands& in,
                                              const float gdir[3], float gz, double out[12])
 {
-    float                  dp[3], gs[3], q4[4], tr;
+    constexpr bool         aa = AA; // (an antialiased frame: the compensation's covariance term, as geom_backward)
+    float                  dp[3], gs[3], q4[4], tr, rho;
     GeomCameraTerms<float> t;
     geom_backward_t<float>(cp, scale_modifier, in.px, in.py, in.pz, in.sc0, in.sc1, in.sc2, in.q.x, in.q.y, in.q.z, in.q.w, in.gmx,
-                           in.gmy, in.gA, in.gB, in.gC, dp, gs, q4, tr, &t);
+                           in.gmy, in.gA, in.gB, in.gC, dp, gs, q4, tr, &t, in.gop * in.opac, aa ? &rho : nullptr);
     if (tr > kGiantCovTrace) {
-        double                  dpd[3], gsd[3], q4d[4], trd;
+        double                  dpd[3], gsd[3], q4d[4], trd, rhod;
         GeomCameraTerms<double> td;
         geom_backward_t<double>(cp, scale_modifier, in.px, in.py, in.pz, in.sc0, in.sc1, in.sc2, in.q.x, in.q.y, in.q.z, in.q.w,
-                                in.gmx, in.gmy, in.gA, in.gB, in.gC, dpd, gsd, q4d, trd, &td);
+                                in.gmx, in.gmy, in.gA, in.gB, in.gC, dpd, gsd, q4d, trd, &td, (double)in.gop * (double)in.opac,
+                                aa ? &rhod : nullptr);
         camera_terms_t<double>(cp, in, td, gdir, gz, out);
     } else {
         camera_terms_t<float>(cp, in, t, gdir, gz, out);

@@ -107,6 +107,8 @@ public:
     }
     // the loss Scene::fit_views applies: LCGS_LOSS_L2 (default) or LCGS_LOSS_PHOTOMETRIC
     void set_fit_loss(int kind, float lambda_dssim = 0.2f) { check(lcgs_set_fit_loss(m_ctx, kind, lambda_dssim)); }
+    // LCGS_RASTER_CLASSIC (default) or LCGS_RASTER_ANTIALIASED: the fused frame's opacity compensation (lcgs_set_raster_mode)
+    void set_raster_mode(int mode) { check(lcgs_set_raster_mode(m_ctx, mode)); }
     // the camera gradient (12 device floats: position, front, up, right) of the last backward of the kept frame
     void camera_backward(float* d_dL_dcam) { check(lcgs_camera_backward(m_ctx, d_dL_dcam)); }
     // walks + camera pass without parameter gradients; any of the three incoming gradients may be NULL, not all
