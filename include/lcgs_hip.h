@@ -266,6 +266,40 @@ LCGS_API lcgs_status lcgs_render_maps(lcgs_context* ctx, int mode, float* d_dept
 LCGS_API lcgs_status lcgs_render_backward_maps(lcgs_context* ctx, const float* d_dL_dimg, int mode, const float* d_dL_ddepth,
                                                const float* d_dL_dalpha, int accumulate, const lcgs_grads* grads);
 
+/* ---- depth-distortion map of the last lcgs_render_forward(keep_state = 1), and its backward ---- */
+/* The Mip-NeRF 360 distortion loss in the squared form that 2DGS, GOF and RaDe-GS rasterise: it pulls the blend weights of a
+ * ray together in depth.  With the entries i, the weights w_i, the value v_i of `mode` and the list order of the maps above,
+ * u_i = fl(v_i - center), s_i = fl(u_i u_i):
+ *     A = sum_i w_i      M1 = sum_i fl(w_i u_i)      M2 = sum_i fl(w_i s_i)          (binary32, list order, from 0)
+ *     dist[p] = fl( fl(A M2) - fl(M1 M1) )       ( = sum_{i<j} w_i w_j (v_i - v_j)^2 in exact arithmetic )
+ * The closed form, not 2DGS's running form: three accumulated channels, which a CPU restatement of the frame composites bit
+ * for bit as the per-splat colour (u, 1, u u).  `center` is any finite float, 0 included: in exact arithmetic the term does not
+ * depend on it; it is there to cut the cancellation between A M2 and M1 M1, which grows with the square of the distance
+ * between the values and the centre.  Pass a typical depth of the scene (in inverse-depth mode its reciprocal), e.g. the
+ * distance from the camera to the scene's centre.
+ * The map is NOT normalised (divide by alpha^2 for the normalised term), NO background is blended in and it is NOT clamped:
+ * rounding may leave a pixel with one blended entry a few ulps from 0, on either side.  A pixel outside every list, and every
+ * pixel of a frame that drew nothing, is 0.
+ * The backward treats thresholds, the 0.99 cap and saturation as lcgs_render_backward does.  With g = dL/ddist[p] and the
+ * pixel's own A, M1, M2:
+ *     d dist / d w_i = M2 + u_i (A u_i - 2 M1)          d dist / d u_i = 2 w_i (A u_i - M1)
+ * the first taken through the blend like a per-pixel value of entry i, the second reaching the position through dv/dz.  The
+ * backward re-derives A, M1, M2 itself, with the forward's bits: it needs no preceding lcgs_render_distortion and no map as input.
+ * Not offered: a distortion channel in lcgs_render_backward_camera, in lcgs_fit_views, in the ownership step, or as an lcgs-app flag. */
+/* d_dist: H*W floats.  Enqueues on the context's stream, reads nothing back. */
+LCGS_API lcgs_status lcgs_render_distortion(lcgs_context* ctx, int mode, float center, float* d_dist);
+/* lcgs_render_backward_maps with one more channel: the gradient of <dL_dimg, img> + <dL_ddepth, depth> + <dL_dalpha, alpha> +
+ * <dL_ddist, dist>, dense rows overwritten (accumulate = 0) or added to.  Any of the four incoming gradients may be NULL, not
+ * all four; `mode` holds for the depth and the distortion channel, `center` as above; the three map channels share one walk of
+ * the lists.  With d_dL_ddist NULL the call is lcgs_render_backward_maps.  lcgs_densify_accumulate and lcgs_camera_backward work
+ * behind it and see the combined gradient.
+ * Both calls: LCGS_ERR_STATE without a keep_state frame, or after a frame of lcgs_owner_render.  LCGS_ERR_INVALID_ARG (before
+ * any device work): a mode that is neither constant, a non-finite center, a NULL output, all four gradients NULL, a NULL
+ * gradient buffer. */
+LCGS_API lcgs_status lcgs_render_backward_distortion(lcgs_context* ctx, const float* d_dL_dimg, int mode, float center,
+                                                     const float* d_dL_ddepth, const float* d_dL_dalpha, const float* d_dL_ddist,
+                                                     int accumulate, const lcgs_grads* grads);
+
 /* ---- per-splat blend-weight statistics of the last lcgs_render_forward(keep_state = 1) ---- */
 /* Which splats a set of views actually uses.  w is the w_i = T_i alpha_i above: the weight pixel p gives entry i of its list, for
  * the entries p blended (positions up to n_contrib[p] that pass the renderer's power and 1/255 tests, the 0.99 cap and the
@@ -313,8 +347,8 @@ LCGS_API lcgs_status lcgs_contrib_accumulate(lcgs_context* ctx, int num_gaussian
  * (behind lcgs_render_backward_adam it sees the updated scene).
  * Not offered: gradients w.r.t. fov / aspect_ratio, frames of the ownership step, pose gradients inside lcgs_fit_views. */
 /* The camera gradient of the last backward of the kept frame (any of lcgs_render_backward, _accumulate, _compact,
- * lcgs_render_backward_maps, lcgs_render_backward_adam, lcgs_render_backward_camera), from the 2-D rows the context still
- * holds.  d_dL_dcam: 12 floats, device, overwritten.  Enqueues on the context's stream, reads nothing back.
+ * lcgs_render_backward_maps, lcgs_render_backward_distortion, lcgs_render_backward_adam, lcgs_render_backward_camera), from
+ * the 2-D rows the context still holds (behind lcgs_render_backward_distortion the distortion channel's dL/dz is part of dv).  d_dL_dcam: 12 floats, device, overwritten.  Enqueues on the context's stream, reads nothing back.
  * LCGS_ERR_STATE: no keep_state frame, a frame of lcgs_owner_render, or no backward of the frame yet. */
 LCGS_API lcgs_status lcgs_camera_backward(lcgs_context* ctx, float* d_dL_dcam);
 /* Walks + camera pass, NO parameter gradients: the 2-D rows zeroed, the colour walk (d_dL_dimg), the maps walk (d_dL_ddepth /
@@ -386,7 +420,8 @@ typedef struct lcgs_densify_stats {
 /* The context's last keep_state lcgs_render_forward and the backward that followed it (any variant): for every on-screen row,
  * grad_accum += |(gx W/2, gy H/2)| of its pixel-space mean gradient, denom += 1, max_radii = max(., reference radius,
  * gs_tile_splatter/shader.cpp:145-148).  Other rows untouched; the context's row order.  LCGS_ERR_STATE: no such frame, no
- * backward on it yet, or a frame of lcgs_owner_render.  Only enqueues. */
+ * backward on it yet, or a frame of lcgs_owner_render.  Only enqueues.  Behind lcgs_render_backward_maps or
+ * lcgs_render_backward_distortion the mean gradient is the combined one of every channel that call was given. */
 LCGS_API lcgs_status lcgs_densify_accumulate(lcgs_context* ctx, int num_gaussians, const lcgs_densify_stats* stats);
 typedef struct lcgs_densify_config {
     float    grad_threshold;  /* 3DGS: 2e-4 */

@@ -46,6 +46,7 @@ from .api import (  # noqa: F401
     read_points_ply,
     render_autograd,
     render_autograd_camera,
+    render_autograd_distortion,
     render_autograd_maps,
     scene_extent,
     shard_rows,

@@ -281,6 +281,9 @@ def _signatures() -> dict:
         # depth and alpha maps
         "lcgs_render_maps": (st, [p, i, p, p]),
         "lcgs_render_backward_maps": (st, [p, p, i, p, p, i, grads]),
+        # depth-distortion map
+        "lcgs_render_distortion": (st, [p, i, f, p]),
+        "lcgs_render_backward_distortion": (st, [p, p, i, f, p, p, p, i, grads]),
         # per-splat blend-weight statistics
         "lcgs_contrib_accumulate": (st, [p, i, cstats]),
         # camera gradient
@@ -834,6 +837,21 @@ class Renderer:
         g = _grads((dpos, dscale, drotq, dsh, dopacity))
         _check(load_library().lcgs_render_backward_maps(self.ctx._h, _ptr(dL_dimg), _DEPTH_MODES[mode], _ptr(dL_ddepth),
                                                         _ptr(dL_dalpha), bool(accumulate), C.byref(g)))
+
+    def render_distortion(self, dist, mode: str = "z", center: float = 0.0):
+        """lcgs_render_distortion: the depth-distortion map of the last keep_state frame, H x W floats --
+        sum_{i<j} w_i w_j (v_i - v_j)^2 per pixel in the closed form A M2 - M1^2 about `center` (any finite float; a typical
+        depth of the scene cuts the cancellation).  Not normalised, not clamped, no background.  Enqueues only."""
+        _check(load_library().lcgs_render_distortion(self.ctx._h, _DEPTH_MODES[mode], float(center), _ptr(dist)))
+
+    def backward_distortion(self, dL_dimg, dL_ddepth, dL_dalpha, dL_ddist, dpos, dscale, drotq, dsh, dopacity, mode: str = "z",
+                            center: float = 0.0, accumulate: bool = False):
+        """lcgs_render_backward_distortion: backward_maps with the distortion map's incoming gradient as a fourth channel; any
+        of the four may be None (not all).  With dL_ddist None it is backward_maps."""
+        g = _grads((dpos, dscale, drotq, dsh, dopacity))
+        _check(load_library().lcgs_render_backward_distortion(self.ctx._h, _ptr(dL_dimg), _DEPTH_MODES[mode], float(center),
+                                                              _ptr(dL_ddepth), _ptr(dL_dalpha), _ptr(dL_ddist),
+                                                              bool(accumulate), C.byref(g)))
 
     def camera_backward(self, out12):
         """lcgs_camera_backward: the camera gradient of the last backward of the kept frame -- 12 floats on the device in the
@@ -1467,6 +1485,52 @@ def render_autograd_maps(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh
                     renderer.forward(cam, scratch, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
                     ctx.generation = renderer._generation
                 renderer.backward_maps(*incoming, *grads, mode=depth_mode)
+            return tuple(g.view(s) for g, s in zip(grads, ctx.shapes))
+
+    return _Fn.apply(pos, scale, rotq, sh, opacity)
+
+
+def render_autograd_distortion(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh, opacity, bg=(0.0, 0.0, 0.0),
+                               depth_mode: str = "z", center: float = 0.0, scale_modifier: float = 1.0):
+    """render_autograd_maps with the frame's depth-distortion map: returns (img [3, H, W], depth [H, W], alpha [H, W],
+    dist [H, W]) as include/lcgs_hip.h defines them (dist = sum_{i<j} w_i w_j (v_i - v_j)^2, evaluated about `center`; not
+    normalised, not clamped).  The backward runs lcgs_render_backward_distortion with the four incoming gradients; an output
+    the loss does not use arrives as None (or zero-shaped) and is passed as NULL.  Like render_autograd it re-renders its own
+    view when the renderer's generation has moved."""
+    import torch
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, pos, scale, rotq, sh, opacity):
+            args = [t.detach().contiguous() for t in (pos, scale, rotq, sh, opacity)]
+            renderer.bind_scene(*args)
+            dev = args[0].device
+            img = torch.empty(3, cam.height, cam.width, device=dev, dtype=torch.float32)
+            depth, alpha, dist = (torch.empty(cam.height, cam.width, device=dev, dtype=torch.float32) for _ in range(3))
+            n = renderer.forward(cam, img, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
+            if n == 0:
+                img[:] = torch.tensor(bg, device=dev).view(3, 1, 1)  # nothing drawn: the image is the background
+            renderer.render_maps(depth, alpha, mode=depth_mode)
+            renderer.render_distortion(dist, mode=depth_mode, center=center)
+            ctx.shapes = [t.shape for t in (pos, scale, rotq, sh, opacity)]
+            ctx.empty = n == 0
+            ctx.generation = renderer._generation
+            ctx.save_for_backward(*args)
+            ctx.set_materialize_grads(False)
+            return img, depth, alpha, dist
+
+        @staticmethod
+        def backward(ctx, dL_dimg, dL_ddepth, dL_dalpha, dL_ddist):
+            args = ctx.saved_tensors
+            grads = [torch.zeros_like(t) for t in args]
+            incoming = [None if g is None or g.numel() == 0 else g.contiguous() for g in (dL_dimg, dL_ddepth, dL_dalpha, dL_ddist)]
+            if not ctx.empty and any(g is not None for g in incoming):
+                if renderer._generation != ctx.generation:  # the renderer's frame state is no longer this frame's
+                    renderer.bind_scene(*args)
+                    scratch = torch.empty(3, cam.height, cam.width, device=args[0].device, dtype=torch.float32)
+                    renderer.forward(cam, scratch, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
+                    ctx.generation = renderer._generation
+                renderer.backward_distortion(*incoming, *grads, mode=depth_mode, center=center)
             return tuple(g.view(s) for g, s in zip(grads, ctx.shapes))
 
     return _Fn.apply(pos, scale, rotq, sh, opacity)

@@ -1,6 +1,6 @@
 // abi_backward.cpp -- the C ABI, part 5: the backward of the fused frame -- dense per-splat rows, compact
 // rows, accumulation over views, and the variant with the optimiser folded into the per-splat pass -- and the frame's depth
-// and alpha maps with their backward (kernels/maps.hip), the per-splat blend-weight statistics of the same kept
+// alpha and depth-distortion maps with their backward (kernels/maps.hip), the per-splat blend-weight statistics of the same kept
 // lists (kernels/contrib.hip), and the camera gradient (kernels/camera_grad.hip).
 #include <math.h>
 #include <stdio.h>
@@ -22,10 +22,14 @@ struct FusedAdam {
     AdamRates  lr;
     AdamStep   step;
 };
-// the incoming gradients of the depth and alpha maps (lcgs_render_backward_maps): either pointer may be NULL
+// the incoming gradients of the depth and alpha maps (lcgs_render_backward_maps) and of the distortion map about `center`
+// (lcgs_render_backward_distortion): any pointer may be NULL
 struct MapGrads {
     int          mode;
     const float *d_dL_ddepth, *d_dL_dalpha;
+    float        center     = 0.0f;
+    const float* d_dL_ddist = nullptr;
+    bool value_channel() const { return d_dL_ddepth || d_dL_ddist; } // something arrives in the rows' value slot
 };
 lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcgs_grads* grads, bool compact,
                             bool accumulate = false, const FusedAdam* fused = nullptr, const MapGrads* maps = nullptr,
@@ -133,6 +137,19 @@ lcgs_status lcgs_render_maps(lcgs_context* ctx, int mode, float* d_depth, float*
     return LCGS_OK;
 }
 
+lcgs_status lcgs_render_distortion(lcgs_context* ctx, int mode, float center, float* d_dist)
+{
+    LCGS_REQUIRE(ctx && d_dist, "NULL argument");
+    LCGS_REQUIRE(mode == LCGS_DEPTH_Z || mode == LCGS_DEPTH_INV_Z, "mode must be LCGS_DEPTH_Z or LCGS_DEPTH_INV_Z");
+    LCGS_REQUIRE(isfinite(center), "center must be finite");
+    LCGS_ENTRY(ctx);
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    LCGS_TRY(check_maps_state(ctx, "lcgs_render_distortion"));
+    launch_render_distortion(kept_frame(ctx), mode, center, d_dist, ctx->stream);
+    LCGS_HIP_CHECK(hipGetLastError());
+    return LCGS_OK;
+}
+
 lcgs_status lcgs_contrib_accumulate(lcgs_context* ctx, int num_gaussians, const lcgs_contrib_stats* stats)
 {
     LCGS_REQUIRE(ctx && stats, "NULL argument");
@@ -174,6 +191,24 @@ lcgs_status lcgs_render_backward_maps(lcgs_context* ctx, const float* d_dL_dimg,
     LCGS_ENTRY(ctx);
     return render_backward(ctx, d_dL_dimg, grads, /*compact=*/false, accumulate != 0, nullptr,
                            (d_dL_ddepth || d_dL_dalpha) ? &maps : nullptr);
+}
+
+lcgs_status lcgs_render_backward_distortion(lcgs_context* ctx, const float* d_dL_dimg, int mode, float center,
+                                            const float* d_dL_ddepth, const float* d_dL_dalpha, const float* d_dL_ddist,
+                                            int accumulate, const lcgs_grads* grads)
+{
+    LCGS_REQUIRE(ctx && grads, "NULL argument");
+    LCGS_REQUIRE(mode == LCGS_DEPTH_Z || mode == LCGS_DEPTH_INV_Z, "mode must be LCGS_DEPTH_Z or LCGS_DEPTH_INV_Z");
+    LCGS_REQUIRE(isfinite(center), "center must be finite");
+    LCGS_REQUIRE(d_dL_dimg || d_dL_ddepth || d_dL_dalpha || d_dL_ddist, "all four incoming gradients are NULL");
+    LCGS_REQUIRE(grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh && grads->d_dL_dopacity,
+                 "NULL gradient buffer");
+    MapGrads maps   = { mode, d_dL_ddepth, d_dL_dalpha };
+    maps.center     = center;
+    maps.d_dL_ddist = d_dL_ddist;
+    LCGS_ENTRY(ctx);
+    return render_backward(ctx, d_dL_dimg, grads, /*compact=*/false, accumulate != 0, nullptr,
+                           (d_dL_ddepth || d_dL_dalpha || d_dL_ddist) ? &maps : nullptr);
 }
 
 lcgs_status lcgs_camera_backward(lcgs_context* ctx, float* d_dL_dcam)
@@ -303,8 +338,9 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
                                fill_in_kernel ? &fill : nullptr);
         LCGS_TRY(mark(ctx, "render_backward"));
     }
-    if (maps) { // the two map channels add to the rows the colour walk (or the zeroing alone) left
-        launch_render_maps_backward(kept, maps->mode, maps->d_dL_ddepth, maps->d_dL_dalpha, ctx->grads2d.as<float>(), st);
+    if (maps) { // the map channels add to the rows the colour walk (or the zeroing alone) left: one walk for all of them
+        launch_render_maps_backward(kept, maps->mode, maps->d_dL_ddepth, maps->d_dL_dalpha, ctx->grads2d.as<float>(), st,
+                                    maps->center, maps->d_dL_ddist);
         LCGS_TRY(mark(ctx, "render_maps_backward"));
     }
     if (overlap) LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_join, 0));
@@ -323,7 +359,7 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
                                    sliced ? ctx->slice_bounds.as<uint32_t>() : nullptr, k, slices, accumulate, ctx->opacity);
         if (sliced) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_slice[k], st));
     }
-    if (params && maps && maps->d_dL_ddepth) // view z = front . pos + tz: the depth channel's dL/dvalue reaches the position rows directly
+    if (params && maps && maps->value_channel()) // view z = front . pos + tz: the depth and distortion channels' dL/dvalue reaches the position rows directly
         launch_maps_depth_to_pos(ctx->hint_V > 0 ? ctx->hint_V : (int64_t)P, ctx->last.cp, ctx->vis_index.as<uint32_t>(),
                                  ctx->counts.as<uint32_t>(), ctx->recs.as<SplatRecord>(), ctx->grads2d.as<float>(), maps->mode,
                                  grads->d_dL_dpos, st);
@@ -334,7 +370,7 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
         LCGS_TRY(lcgs::comm_mark_touched(ctx->comm, ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), (int64_t)P,
                                          ctx->hint_V, accumulate, st));
     ctx->g2d_backward_done = true; // the frame's 2-D gradient rows now hold a backward's sums (lcgs_densify_accumulate)
-    ctx->g2d_value_mode    = (maps && maps->d_dL_ddepth) ? maps->mode : -1; // (every backward starts from zeroed rows)
+    ctx->g2d_value_mode    = (maps && maps->value_channel()) ? maps->mode : -1; // (every backward starts from zeroed rows)
     if (!params) LCGS_TRY(camera_pass(ctx, d_camera_only));
     LCGS_TRY(mark(ctx, "preprocess_backward"));
     LCGS_HIP_CHECK(hipGetLastError());

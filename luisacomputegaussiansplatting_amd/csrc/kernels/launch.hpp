@@ -414,9 +414,13 @@ void   launch_slice_bounds(const uint32_t* vis_index, const uint32_t* d_counts, 
 constexpr int kDepthZ = 0, kDepthInvZ = 1; // = LCGS_DEPTH_Z, LCGS_DEPTH_INV_Z: a splat's value is its view z, or 1 / z
 // depth / alpha: H W floats each, either may be NULL; f.strip_masks NULL: every entry of the walk is fetched
 void launch_render_maps(const KeptFrame& f, int mode, float* depth, float* alpha, hipStream_t stream);
-// ADDS the sums of the two map channels to grads2d slots 0-5 and kG2DValueSlot (dL_ddepth / dL_dalpha: either may be NULL)
+// the depth-distortion map, H W floats: fl(fl(A M2) - fl(M1 M1)) of the three channels accumulated with u = fl(value - center)
+void launch_render_distortion(const KeptFrame& f, int mode, float center, float* dist, hipStream_t stream);
+// ADDS the sums of the map channels to grads2d slots 0-5 and kG2DValueSlot (dL_ddepth / dL_dalpha / dL_ddist: any may be NULL).
+// dL_ddist != NULL: the distortion channel about `center`, its three per-pixel sums re-derived by a pre-walk inside the kernel;
+// NULL: the two-channel kernel
 void launch_render_maps_backward(const KeptFrame& f, int mode, const float* dL_ddepth, const float* dL_dalpha, float* grads2d,
-                                 hipStream_t stream);
+                                 hipStream_t stream, float center = 0.0f, const float* dL_ddist = nullptr);
 // one lane per on-screen row: dL_dpos[row] += grads2d slot kG2DValueSlot x dvalue/dz x front (behind the preprocess-backward)
 void launch_maps_depth_to_pos(int64_t v_hint, const CamParams& cp, const uint32_t* vis_index, const uint32_t* d_counts,
                               const SplatRecord* recs, const float* grads2d, int mode, float* dL_dpos, hipStream_t stream);

@@ -1,19 +1,29 @@
-// maps.hip -- depth and alpha maps of the last keep-state frame, and their backward (the contract is in
-// include/lcgs_hip.h).  Neither map exists in the reference: its renderer composites colour only.
+// maps.hip -- depth, alpha and depth-distortion maps of the last keep-state frame, and their backward (the
+// contract is in include/lcgs_hip.h).  None of the maps exists in the reference: its renderer composites colour only.
 //
-// Both walk kernels are kept_walk.hpp's walk -- one workgroup per 16x16 tile in the renderer's schedule, wave k = the tile's
+// The walk kernels are kept_walk.hpp's walk -- one workgroup per 16x16 tile in the renderer's schedule, wave k = the tile's
 // 8x8 quadrant k, one pixel per lane, the KEPT per-tile list in rounds of 256 staged entries up to the tile's largest n_contrib
 // -- with their own accumulators, per-entry body and flush:
 //   k_render_maps           front to back.  A pixel takes entries up to its own n_contrib, so the forward's saturation test is
 //                           not repeated (the saturating entry lies past it); power, alpha and the two skips are the walk's
 //                           restatement of the forward's, and the T update is its expression too (-ffp-contract=off), which
 //                           makes alpha = sum w and depth = sum fl(w v) the tests' binary32 CPU restatement's bit for bit.
+//   k_render_distortion     the same walk with three accumulators: with u = fl(v - center), A = sum w, M1 = sum fl(w u),
+//                           M2 = sum fl(w fl(u u)) and one store fl(fl(A M2) - fl(M1 M1)) per pixel -- the closed form of
+//                           sum_{i<j} w_i w_j (v_i - v_j)^2, three accumulated channels the CPU restatement composites as the
+//                           colour (u, 1, u u).
 //   k_render_maps_backward  back to front like k_render_backward, with the two channels (v, dL/dD) and (1, dL/dA) folded into
 //                           one per-entry scalar.  Seven per-pixel terms per entry (q dx, q dy, q dx dx, q dx dy, q dy dy, q,
 //                           w dL/dD) are summed over the strip's 64 lanes -- four DPP butterfly steps inside each 16-lane row,
 //                           then one LDS add per row -- and over the four waves in a per-round LDS accumulator; the round's
 //                           totals leave as at most seven global float atomics per (tile, splat), eight consecutive lanes per
 //                           splat row.  It ADDS to grads2d slots 0-5 and 9.
+//                           DIST = true adds the distortion channel: the pixel's A, M1, M2 are first re-derived in registers
+//                           by the forward's own front-to-back walk over the same LDS (walk_distortion_sums: the forward's
+//                           bits, nothing cached, nothing taken as input), then d dist / d w_i = M2 + u_i (A u_i - 2 M1) joins
+//                           the per-entry scalar as a third per-pixel "value" and 2 w_i (A u_i - M1) dL/ddist joins the
+//                           w dL/dD sum.  Still seven sums per (tile, splat) and the same flush.  DIST = false is the
+//                           two-channel kernel, operation for operation.
 //   k_maps_depth_to_pos     one lane per on-screen row: dL/dpos += slot 9 x dv/dz x front.
 // Thresholds are constants for the derivative, exactly as in backward.hip: the 0.99 cap passes nothing, a saturated pixel stops.
 #include "kept_walk.hpp"
@@ -52,8 +62,45 @@ __global__ void __launch_bounds__(256) k_render_maps(KeptFrame f, int mode, floa
     }
 }
 
-__global__ void __launch_bounds__(256) k_render_maps_backward(KeptFrame f, int mode, const float* __restrict__ dL_ddepth,
-                                                              const float* __restrict__ dL_dalpha, float* __restrict__ grads2d)
+// the distortion map's three accumulated channels of the lane's pixel, front to back in list order from 0 (k_render_maps'
+// walk); ONE statement of them for the forward and for the backward's pre-walk, which must reproduce the forward's bits
+__device__ __forceinline__ void walk_distortion_sums(const KeptFrame& f, WalkShared& s_walk, const TileWalk& t, int mode,
+                                                     float center, float& A, float& M1, float& M2)
+{
+    float T = 1.0f, a0 = 0.0f, m1 = 0.0f, m2 = 0.0f;
+    walk_rounds<false>(
+        f, s_walk, t, mode, [](uint32_t) {},
+        [&](uint32_t, uint32_t pos, const float4& ea, const float4& eb) {
+            const EntryEval v = eval_entry(ea, eb, t.pxf, t.pyf, pos, t.last);
+            if (__builtin_amdgcn_ballot_w64(v.cand) == 0ull) return;
+            const EntryBlend b = blend_entry(eb, v);
+            if (b.blended) {
+                const float wgt = T * b.alpha, u = eb.w - center;
+                a0              = a0 + wgt;
+                m1              = m1 + wgt * u;
+                m2              = m2 + wgt * (u * u);
+                T               = T * (1.0f - b.alpha);
+            }
+        },
+        [] {});
+    A = a0, M1 = m1, M2 = m2;
+}
+
+__global__ void __launch_bounds__(256) k_render_distortion(KeptFrame f, int mode, float center, float* __restrict__ dist_map)
+{
+    __shared__ WalkShared s_walk;
+    TileWalk              t;
+    if (!tile_prologue(f, s_walk, t)) return; // (a frame that drew nothing walks nothing: the map is zero)
+    float A, M1, M2;
+    walk_distortion_sums(f, s_walk, t, mode, center, A, M1, M2);
+    if (t.inside) dist_map[t.pix] = A * M2 - M1 * M1;
+}
+
+template <bool DIST>
+__global__ void __launch_bounds__(256) k_render_maps_backward(KeptFrame f, int mode, float center,
+                                                              const float* __restrict__ dL_ddepth,
+                                                              const float* __restrict__ dL_dalpha,
+                                                              const float* __restrict__ dL_ddist, float* __restrict__ grads2d)
 {
     constexpr int         kSums = 7;
     __shared__ WalkShared s_walk;
@@ -66,6 +113,12 @@ __global__ void __launch_bounds__(256) k_render_maps_backward(KeptFrame f, int m
     const float T_final = t.inside ? f.final_T[t.pix] : 0.0f;
     const float gd = (t.inside && dL_ddepth) ? dL_ddepth[t.pix] : 0.0f;
     const float ga = (t.inside && dL_dalpha) ? dL_dalpha[t.pix] : 0.0f;
+    // the distortion channel: the pixel's own sums, as the forward accumulated them, before anything is walked backwards
+    float gq = 0.0f, dA = 0.0f, dM1 = 0.0f, dM2 = 0.0f;
+    if constexpr (DIST) {
+        gq = (t.inside && dL_ddist) ? dL_ddist[t.pix] : 0.0f;
+        walk_distortion_sums(f, s_walk, t, mode, center, dA, dM1, dM2);
+    }
 
     // per-pixel recurrences, back to front (backward.hip): Qr = prod (1 - alpha) over the entries walked so far, over T_final;
     // Bd = (value composited behind the current splat) . dL/dpixel over the two channels -- nothing lies behind the last entry
@@ -89,7 +142,13 @@ __global__ void __launch_bounds__(256) k_render_maps_backward(KeptFrame f, int m
             Qr = Qr * (1.0f - a);
             const float Tn  = __builtin_amdgcn_rcpf(Qr);
             const float wgt = a * Tn;
-            const float d   = __builtin_fmaf(eb.w, gd, ga) - Bd; // (value - what lies behind) . dL/dpixel
+            float       val = __builtin_fmaf(eb.w, gd, ga), gv = wgt * gd; // value . dL/dpixel; dL/dvalue
+            if constexpr (DIST) { // d dist / d w_i as a third per-pixel value, d dist / d u_i beside w dL/dD
+                const float u = eb.w - center, au = dA * u;
+                val = val + gq * (dM2 + u * (au - 2.0f * dM1));
+                gv  = gv + (2.0f * gq) * (wgt * (au - dM1));
+            }
+            const float d   = val - Bd; // (value - what lies behind) . dL/dpixel
             const float dLa = d * Tn;
             Bd              = __builtin_fmaf(a, d, Bd);
             // the 0.99 cap passes no gradient; selected behind the product (G is arbitrary bits off the candidate lanes)
@@ -101,7 +160,7 @@ __global__ void __launch_bounds__(256) k_render_maps_backward(KeptFrame f, int m
             s[3] = s[0] * v.dy;
             s[4] = s[1] * v.dy;
             s[5] = q;
-            s[6] = wgt * gd; // dL/dvalue
+            s[6] = gv;
 #pragma unroll
             for (int g = 0; g < kSums; ++g) s[g] = row16_sum(s[g]);
             if (row_head) {
@@ -165,12 +224,23 @@ void launch_render_maps(const KeptFrame& f, int mode, float* depth, float* alpha
     hipLaunchKernelGGL(k_render_maps, dim3(maps_grid(f.cp, f.tile_order)), dim3(256), 0, stream, f, mode, depth, alpha);
 }
 
-void launch_render_maps_backward(const KeptFrame& f, int mode, const float* dL_ddepth, const float* dL_dalpha, float* grads2d,
-                                 hipStream_t stream)
+void launch_render_distortion(const KeptFrame& f, int mode, float center, float* dist, hipStream_t stream)
 {
     if (f.cp.grid_x * f.cp.grid_y == 0) return;
-    hipLaunchKernelGGL(k_render_maps_backward, dim3(maps_grid(f.cp, f.tile_order)), dim3(256), 0, stream, f, mode, dL_ddepth,
-                       dL_dalpha, grads2d);
+    hipLaunchKernelGGL(k_render_distortion, dim3(maps_grid(f.cp, f.tile_order)), dim3(256), 0, stream, f, mode, center, dist);
+}
+
+void launch_render_maps_backward(const KeptFrame& f, int mode, const float* dL_ddepth, const float* dL_dalpha, float* grads2d,
+                                 hipStream_t stream, float center, const float* dL_ddist)
+{
+    if (f.cp.grid_x * f.cp.grid_y == 0) return;
+    const dim3 grid(maps_grid(f.cp, f.tile_order));
+    if (dL_ddist)
+        hipLaunchKernelGGL(k_render_maps_backward<true>, grid, dim3(256), 0, stream, f, mode, center, dL_ddepth, dL_dalpha,
+                           dL_ddist, grads2d);
+    else // (the two-channel kernel: no pre-walk, lcgs_render_backward_maps' arithmetic)
+        hipLaunchKernelGGL(k_render_maps_backward<false>, grid, dim3(256), 0, stream, f, mode, 0.0f, dL_ddepth, dL_dalpha,
+                           nullptr, grads2d);
 }
 
 void launch_maps_depth_to_pos(int64_t v_hint, const CamParams& cp, const uint32_t* vis_index, const uint32_t* d_counts,
