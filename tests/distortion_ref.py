@@ -54,28 +54,35 @@ def _walk_inputs(o, st, cam, v, center, dL_ddist):
     return _colour(o, v, center)[1], np.stack([-(two * g * M1), g * M2, g * A]).astype(o.dtype)
 
 
-def backward(o, scene, cam, dL_ddist, dL_ddepth=None, dL_dalpha=None, mode="z", center=0.0, scale_modifier=1.0, sh_deg=3):
-    """attribute -> gradient of <dL_ddist, dist> + <dL_ddepth, depth> + <dL_dalpha, alpha> in oracle build `o` (its own forward)"""
+def backward(o, scene, cam, dL_ddist, dL_ddepth=None, dL_dalpha=None, mode="z", center=0.0, scale_modifier=1.0, sh_deg=3,
+             frame=maps_ref.Classic, walk=None):
+    """attribute -> gradient of <dL_ddist, dist> + <dL_ddepth, depth> + <dL_dalpha, alpha> in oracle build `o` (its own forward);
+    frame: maps_ref.Classic, or another raster mode's state and augmentation; walk: a dict that receives the distortion walk's
+    own dL/dopacity row ("go")"""
     W, H = cam.width, cam.height
-    st = o.forward_state(scene, cam, scale_modifier=scale_modifier, sh_deg=sh_deg)
+    st = frame.state(o, scene, cam, scale_modifier, sh_deg)
     v, dv = maps_ref._value(o, scene, cam, mode, scale_modifier)
     u = _colour(o, v, center)[0]
     col, dl3 = _walk_inputs(o, st, cam, v, center, dL_ddist)
     gm, gc, go, gcol = o.render_backward(W, H, np.zeros(3), st["ranges"], st["point_list"], st["means"], st["conic"],
                                          st["opacity"], col, st["final_T"], st["n_contrib"], dl3)
+    if walk is not None:
+        walk["go"] = go
+    gc, go = frame.augment(o, st, gc, go)
     g = o.preprocess_backward(scene, cam, st["radii"], gm, gc, np.zeros_like(gcol), scale_modifier=scale_modifier, sh_deg=sh_deg)
     gu = gcol[:, 0] + o.dtype(2.0) * u * gcol[:, 2]
     g["pos"] = g["pos"] + (gu * dv)[:, None] * np.asarray(cam.front[:], o.dtype)[None, :]
     g["opacity"] = go
     g["sh"] = np.zeros_like(g["sh"])
     if dL_ddepth is not None or dL_dalpha is not None:
-        gm_ = maps_ref.backward(o, scene, cam, dL_ddepth, dL_dalpha, mode=mode, scale_modifier=scale_modifier, sh_deg=sh_deg)
+        gm_ = maps_ref.backward(o, scene, cam, dL_ddepth, dL_dalpha, mode=mode, scale_modifier=scale_modifier, sh_deg=sh_deg,
+                                frame=frame)
         g = {k: g[k] + gm_[k] for k in g}
     return g
 
 
 def row_bound(scene, ocam, dL_ddist, dL_ddepth=None, dL_dalpha=None, mode="z", center=0.0, scale_modifier=1.0, sh_deg=3,
-              maps_bound=None):
+              maps_bound=None, frame=maps_ref.Classic):
     """(per attribute [P, n] bound, f64 reference) for a distortion backward without an image gradient.  maps_bound: the
     (bound, reference) of maps_ref.row_bound for the same dL_ddepth / dL_dalpha, where the caller has it."""
     from oracle import abs_jacobian_apply
@@ -83,18 +90,20 @@ def row_bound(scene, ocam, dL_ddist, dL_ddepth=None, dL_dalpha=None, mode="z", c
     o32, o64, o32c = _oracles()
     ocam = o32.convert_camera(ocam)
     cam64 = o64.convert_camera(ocam)
-    kw = dict(mode=mode, center=center, scale_modifier=scale_modifier, sh_deg=sh_deg)
+    kw = dict(mode=mode, center=center, scale_modifier=scale_modifier, sh_deg=sh_deg, frame=frame)
     r32 = backward(o32, scene, ocam, dL_ddist, **kw)
-    r64 = backward(o64, scene, cam64, dL_ddist, **kw)
+    walk64 = {}
+    r64 = backward(o64, scene, cam64, dL_ddist, walk=walk64, **kw)
     r32c = backward(o32c, scene, o32c.convert_camera(ocam), dL_ddist, **kw)
     # the rounding budget of the walk, over the binary32 state and the binary32 maps the kernels produce bit for bit
     W, H = ocam.width, ocam.height
-    st = o32.forward_state(scene, ocam, scale_modifier=scale_modifier, sh_deg=sh_deg)
+    st = frame.state(o32, scene, ocam, scale_modifier, sh_deg)
     v, dv = maps_ref._value(o32, scene, ocam, mode, scale_modifier)
     u = _colour(o32, v, center)[0]
     col, dl3 = _walk_inputs(o32, st, ocam, v, center, dL_ddist)
     A, F = o64.render_backward_bound(W, H, np.zeros(3, np.float32), st["ranges"], st["point_list"], st["means"], st["conic"],
                                      st["opacity"], col, st["final_T"], st["n_contrib"], dl3)
+    A, F = (frame.augment_budget(o64, scene, cam64, st, X, scale_modifier) for X in (A, F))
     Az, Fz = A.copy(), F.copy()
     Az[:, 6:9] = 0.0
     Fz[:, 6:9] = 0.0
@@ -105,6 +114,7 @@ def row_bound(scene, ocam, dL_ddist, dL_ddepth=None, dL_dalpha=None, mode="z", c
     JA["pos"] = JA["pos"] + ((A[:, 6] + au2 * A[:, 8]) * adv)[:, None] * front
     JF["pos"] = JF["pos"] + ((F[:, 6] + au2 * F[:, 8]) * adv)[:, None] * front
     P = np.asarray(scene["pos"]).reshape(-1, 3).shape[0]
+    extra = frame.conditioning(o64, scene, cam64, st["radii"], walk64["go"], scale_modifier, sh_deg)
     B, R = {}, {}
     for k in KEYS:
         b64 = r64[k].astype(np.float64).reshape(P, -1)
@@ -112,10 +122,12 @@ def row_bound(scene, ocam, dL_ddist, dL_ddepth=None, dL_dalpha=None, mode="z", c
                            np.abs(r32c[k].astype(np.float64).reshape(P, -1) - b64))
         ja, jf = JA[k].reshape(P, -1), JF[k].reshape(P, -1)
         B[k] = GRAD_ROW_K * noise + GRAD_ROW_CU * U32 * ja + jf + GRAD_ROW_FLOOR * ja
+        if extra is not None:
+            B[k] = B[k] + extra[k].reshape(P, -1)
         R[k] = b64
     if dL_ddepth is not None or dL_dalpha is not None:
         if maps_bound is None:
-            maps_bound = maps_ref.row_bound(scene, ocam, dL_ddepth, dL_dalpha, mode, scale_modifier, sh_deg)
+            maps_bound = maps_ref.row_bound(scene, ocam, dL_ddepth, dL_dalpha, mode, scale_modifier, sh_deg, frame=frame)
         return sum_row_bounds([(B, R), maps_bound])
     return B, R
 
