@@ -1400,6 +1400,77 @@ def sparse_message_words(count: int, sh_degree: int = 3) -> int:
     return count * (1 + 3 + 3 + 4 + (sh_degree + 1) ** 2 * 3 + 1)
 
 
+def _autograd_frame(renderer: "Renderer", view: Camera, scene, bg, scale_modifier: float, outputs: str = "image",
+                    depth_mode: str = "z", center: float = 0.0, cam12=None):
+    """The one differentiable frame behind render_autograd and its variants: binds the scene, renders `view` with keep_state,
+    renders the maps `outputs` asks for ("image": the image alone; "maps": plus depth and alpha; "distortion": plus the
+    distortion map about `center`) and, on backward, differentiates that frame -- after binding its saved scene and rendering
+    its view again when the renderer's generation has moved -- through the one Renderer backward that fits.  cam12 (a tensor
+    or None): the pose is an input too, in front of the five scene tensors, and gets the camera gradient."""
+    import torch
+
+    maps, dist, pose = outputs != "image", outputs == "distortion", cam12 is not None
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, *inputs):
+            params = inputs[1:] if pose else inputs
+            args = [t.detach().contiguous() for t in params]
+            renderer.bind_scene(*args)
+            dev = args[0].device
+            img = torch.empty(3, view.height, view.width, device=dev, dtype=torch.float32)
+            extra = [torch.empty(view.height, view.width, device=dev, dtype=torch.float32) for _ in range(3 if dist else 2 if maps else 0)]
+            n = renderer.forward(view, img, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
+            if n == 0:
+                img[:] = torch.tensor(bg, device=dev).view(3, 1, 1)  # nothing drawn: the image is the background
+            if maps:
+                renderer.render_maps(extra[0], extra[1], mode=depth_mode)
+            if dist:
+                renderer.render_distortion(extra[2], mode=depth_mode, center=center)
+            ctx.shapes = [t.shape for t in params]
+            if pose:
+                ctx.cam_like = (inputs[0].shape, inputs[0].device)
+            ctx.empty = n == 0
+            ctx.generation = renderer._generation
+            ctx.save_for_backward(*args)
+            if not maps:
+                return img  # (its single gradient arrives materialised)
+            ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None and is passed as NULL
+            return (img, *extra)
+
+        @staticmethod
+        def backward(ctx, *incoming):
+            args = ctx.saved_tensors
+            want_cam = pose and ctx.needs_input_grad[0]
+            want_scene = not pose or any(ctx.needs_input_grad[1:])
+            g12 = torch.zeros(12, device=args[0].device, dtype=torch.float32) if pose else None
+            grads = [torch.zeros_like(t) for t in args] if want_scene else None  # (the pose alone: no parameter rows)
+            incoming = [None if g is None or g.numel() == 0 else g.contiguous() for g in incoming]
+            if not ctx.empty and any(g is not None for g in incoming):
+                if renderer._generation != ctx.generation:  # the renderer's frame state is no longer this frame's
+                    renderer.bind_scene(*args)
+                    scratch = torch.empty(3, view.height, view.width, device=args[0].device, dtype=torch.float32)
+                    renderer.forward(view, scratch, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
+                    ctx.generation = renderer._generation
+                if not want_scene:
+                    renderer.backward_camera(*incoming, g12, mode=depth_mode)
+                elif dist:
+                    renderer.backward_distortion(*incoming, *grads, mode=depth_mode, center=center)
+                elif maps:
+                    renderer.backward_maps(*incoming, *grads, mode=depth_mode)
+                else:
+                    renderer.backward(*incoming, *grads)
+                if want_scene and want_cam:
+                    renderer.camera_backward(g12)
+            out = tuple(g.view(s) for g, s in zip(grads, ctx.shapes)) if want_scene else (None,) * 5
+            if pose:
+                shape, dev = ctx.cam_like
+                out = (g12.to(dev).view(shape) if want_cam else None,) + out
+            return out
+
+    return _Fn.apply(*((cam12,) if pose else ()), *scene)
+
+
 def render_autograd(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh, opacity, bg=(0.0, 0.0, 0.0),
                     scale_modifier: float = 1.0):
     """Differentiable frame for torch: `img = render_autograd(r, cam, pos, scale, rotq, sh, opacity)` (activated
@@ -1411,37 +1482,7 @@ def render_autograd(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh, opa
     frame's forward and its backward: the backward notices (the renderer's generation counter has moved), binds its own
     saved scene again and re-renders its own view with keep_state before differentiating -- the cost of one extra
     forward instead of gradients silently computed from another view's lists."""
-    import torch
-
-    class _Fn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, pos, scale, rotq, sh, opacity):
-            args = [t.detach().contiguous() for t in (pos, scale, rotq, sh, opacity)]
-            renderer.bind_scene(*args)
-            img = torch.empty(3, cam.height, cam.width, device=args[0].device, dtype=torch.float32)
-            n = renderer.forward(cam, img, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
-            if n == 0:
-                img[:] = torch.tensor(bg, device=img.device).view(3, 1, 1)  # nothing drawn: the image is the background
-            ctx.shapes = [t.shape for t in (pos, scale, rotq, sh, opacity)]
-            ctx.empty = n == 0
-            ctx.generation = renderer._generation
-            ctx.save_for_backward(*args)
-            return img
-
-        @staticmethod
-        def backward(ctx, dL_dimg):
-            args = ctx.saved_tensors
-            grads = [torch.zeros_like(t) for t in args]
-            if not ctx.empty:
-                if renderer._generation != ctx.generation:  # the renderer's frame state is no longer this frame's
-                    renderer.bind_scene(*args)
-                    scratch = torch.empty(3, cam.height, cam.width, device=args[0].device, dtype=torch.float32)
-                    renderer.forward(cam, scratch, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
-                    ctx.generation = renderer._generation
-                renderer.backward(dL_dimg.contiguous(), *grads)
-            return tuple(g.view(s) for g, s in zip(grads, ctx.shapes))
-
-    return _Fn.apply(pos, scale, rotq, sh, opacity)
+    return _autograd_frame(renderer, cam, (pos, scale, rotq, sh, opacity), bg, scale_modifier)
 
 
 def render_autograd_maps(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh, opacity, bg=(0.0, 0.0, 0.0),
@@ -1451,43 +1492,7 @@ def render_autograd_maps(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh
     background in the maps).  The backward runs lcgs_render_backward_maps with the three incoming gradients; an output the loss
     does not use arrives as None (or zero-shaped) and is passed as NULL.  Like render_autograd it re-renders its own view
     when the renderer's generation has moved."""
-    import torch
-
-    class _Fn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, pos, scale, rotq, sh, opacity):
-            args = [t.detach().contiguous() for t in (pos, scale, rotq, sh, opacity)]
-            renderer.bind_scene(*args)
-            dev = args[0].device
-            img = torch.empty(3, cam.height, cam.width, device=dev, dtype=torch.float32)
-            depth = torch.empty(cam.height, cam.width, device=dev, dtype=torch.float32)
-            alpha = torch.empty(cam.height, cam.width, device=dev, dtype=torch.float32)
-            n = renderer.forward(cam, img, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
-            if n == 0:
-                img[:] = torch.tensor(bg, device=dev).view(3, 1, 1)  # nothing drawn: the image is the background
-            renderer.render_maps(depth, alpha, mode=depth_mode)
-            ctx.shapes = [t.shape for t in (pos, scale, rotq, sh, opacity)]
-            ctx.empty = n == 0
-            ctx.generation = renderer._generation
-            ctx.save_for_backward(*args)
-            ctx.set_materialize_grads(False)
-            return img, depth, alpha
-
-        @staticmethod
-        def backward(ctx, dL_dimg, dL_ddepth, dL_dalpha):
-            args = ctx.saved_tensors
-            grads = [torch.zeros_like(t) for t in args]
-            incoming = [None if g is None or g.numel() == 0 else g.contiguous() for g in (dL_dimg, dL_ddepth, dL_dalpha)]
-            if not ctx.empty and any(g is not None for g in incoming):
-                if renderer._generation != ctx.generation:  # the renderer's frame state is no longer this frame's
-                    renderer.bind_scene(*args)
-                    scratch = torch.empty(3, cam.height, cam.width, device=args[0].device, dtype=torch.float32)
-                    renderer.forward(cam, scratch, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
-                    ctx.generation = renderer._generation
-                renderer.backward_maps(*incoming, *grads, mode=depth_mode)
-            return tuple(g.view(s) for g, s in zip(grads, ctx.shapes))
-
-    return _Fn.apply(pos, scale, rotq, sh, opacity)
+    return _autograd_frame(renderer, cam, (pos, scale, rotq, sh, opacity), bg, scale_modifier, "maps", depth_mode)
 
 
 def render_autograd_distortion(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh, opacity, bg=(0.0, 0.0, 0.0),
@@ -1497,43 +1502,7 @@ def render_autograd_distortion(renderer: "Renderer", cam: Camera, pos, scale, ro
     normalised, not clamped).  The backward runs lcgs_render_backward_distortion with the four incoming gradients; an output
     the loss does not use arrives as None (or zero-shaped) and is passed as NULL.  Like render_autograd it re-renders its own
     view when the renderer's generation has moved."""
-    import torch
-
-    class _Fn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, pos, scale, rotq, sh, opacity):
-            args = [t.detach().contiguous() for t in (pos, scale, rotq, sh, opacity)]
-            renderer.bind_scene(*args)
-            dev = args[0].device
-            img = torch.empty(3, cam.height, cam.width, device=dev, dtype=torch.float32)
-            depth, alpha, dist = (torch.empty(cam.height, cam.width, device=dev, dtype=torch.float32) for _ in range(3))
-            n = renderer.forward(cam, img, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
-            if n == 0:
-                img[:] = torch.tensor(bg, device=dev).view(3, 1, 1)  # nothing drawn: the image is the background
-            renderer.render_maps(depth, alpha, mode=depth_mode)
-            renderer.render_distortion(dist, mode=depth_mode, center=center)
-            ctx.shapes = [t.shape for t in (pos, scale, rotq, sh, opacity)]
-            ctx.empty = n == 0
-            ctx.generation = renderer._generation
-            ctx.save_for_backward(*args)
-            ctx.set_materialize_grads(False)
-            return img, depth, alpha, dist
-
-        @staticmethod
-        def backward(ctx, dL_dimg, dL_ddepth, dL_dalpha, dL_ddist):
-            args = ctx.saved_tensors
-            grads = [torch.zeros_like(t) for t in args]
-            incoming = [None if g is None or g.numel() == 0 else g.contiguous() for g in (dL_dimg, dL_ddepth, dL_dalpha, dL_ddist)]
-            if not ctx.empty and any(g is not None for g in incoming):
-                if renderer._generation != ctx.generation:  # the renderer's frame state is no longer this frame's
-                    renderer.bind_scene(*args)
-                    scratch = torch.empty(3, cam.height, cam.width, device=args[0].device, dtype=torch.float32)
-                    renderer.forward(cam, scratch, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
-                    ctx.generation = renderer._generation
-                renderer.backward_distortion(*incoming, *grads, mode=depth_mode, center=center)
-            return tuple(g.view(s) for g, s in zip(grads, ctx.shapes))
-
-    return _Fn.apply(pos, scale, rotq, sh, opacity)
+    return _autograd_frame(renderer, cam, (pos, scale, rotq, sh, opacity), bg, scale_modifier, "distortion", depth_mode, center)
 
 
 CAM12_FIELDS = ("position", "front", "up", "right")  # the camera gradient's order: Camera's first four members
@@ -1565,55 +1534,8 @@ def render_autograd_camera(renderer: "Renderer", cam: Camera, cam12, pos, scale,
     and size are cam's).  The backward returns the camera gradient for cam12 (the twelve numbers as independent variables:
     chain a pose parameterisation onto them, e.g. camera_grad_to_twist) plus the scene gradients.  When no scene tensor
     requires grad it runs lcgs_render_backward_camera and allocates no parameter rows."""
-    import torch
-
     view = camera_with_vectors(cam, cam12.detach().cpu().numpy())
-
-    class _Fn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, cam12, pos, scale, rotq, sh, opacity):
-            args = [t.detach().contiguous() for t in (pos, scale, rotq, sh, opacity)]
-            renderer.bind_scene(*args)
-            dev = args[0].device
-            img = torch.empty(3, view.height, view.width, device=dev, dtype=torch.float32)
-            depth = torch.empty(view.height, view.width, device=dev, dtype=torch.float32)
-            alpha = torch.empty(view.height, view.width, device=dev, dtype=torch.float32)
-            n = renderer.forward(view, img, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
-            if n == 0:
-                img[:] = torch.tensor(bg, device=dev).view(3, 1, 1)  # nothing drawn: the image is the background
-            renderer.render_maps(depth, alpha, mode=mode)
-            ctx.shapes = [t.shape for t in (pos, scale, rotq, sh, opacity)]
-            ctx.cam_like = (cam12.shape, cam12.device)
-            ctx.empty = n == 0
-            ctx.generation = renderer._generation
-            ctx.save_for_backward(*args)
-            ctx.set_materialize_grads(False)
-            return img, depth, alpha
-
-        @staticmethod
-        def backward(ctx, dL_dimg, dL_ddepth, dL_dalpha):
-            args = ctx.saved_tensors
-            want_cam, want_scene = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:])
-            g12 = torch.zeros(12, device=args[0].device, dtype=torch.float32)
-            grads = [torch.zeros_like(t) for t in args] if want_scene else None
-            incoming = [None if g is None or g.numel() == 0 else g.contiguous() for g in (dL_dimg, dL_ddepth, dL_dalpha)]
-            if not ctx.empty and any(g is not None for g in incoming):
-                if renderer._generation != ctx.generation:  # the renderer's frame state is no longer this frame's
-                    renderer.bind_scene(*args)
-                    scratch = torch.empty(3, view.height, view.width, device=args[0].device, dtype=torch.float32)
-                    renderer.forward(view, scratch, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
-                    ctx.generation = renderer._generation
-                if want_scene:
-                    renderer.backward_maps(*incoming, *grads, mode=mode)
-                    if want_cam:
-                        renderer.camera_backward(g12)
-                else:
-                    renderer.backward_camera(*incoming, g12, mode=mode)
-            shape, dev = ctx.cam_like
-            scene = tuple(g.view(s) for g, s in zip(grads, ctx.shapes)) if want_scene else (None,) * 5
-            return (g12.to(dev).view(shape) if want_cam else None,) + scene
-
-    return _Fn.apply(cam12, pos, scale, rotq, sh, opacity)
+    return _autograd_frame(renderer, view, (pos, scale, rotq, sh, opacity), bg, scale_modifier, "maps", mode, cam12=cam12)
 
 
 # ---------------------------------------------------------------------------------------------- host io

@@ -16,41 +16,47 @@ using namespace lcgs::abi;
 
 namespace
 {
-// the optimiser folded into the per-splat pass (lcgs_render_backward_adam): no gradient arrays at all
-struct FusedAdam {
-    AdamArrays raw, m, v, act;
-    AdamRates  lr;
-    AdamStep   step;
-};
-// the incoming gradients of the depth and alpha maps (lcgs_render_backward_maps) and of the distortion map about `center`
-// (lcgs_render_backward_distortion): any pointer may be NULL
-struct MapGrads {
-    int          mode;
-    const float *d_dL_ddepth, *d_dL_dalpha;
-    float        center     = 0.0f;
-    const float* d_dL_ddist = nullptr;
+// What a backward of the last keep-state frame is asked for: the incoming gradients, and where the result goes.
+struct BackwardRequest {
+    // the incoming gradients of the image, of the depth and alpha maps (about depth mode `mode`) and of the distortion map
+    // (about `center`): any may be NULL, not all
+    const float *d_dL_dimg = nullptr, *d_dL_ddepth = nullptr, *d_dL_dalpha = nullptr, *d_dL_ddist = nullptr;
+    int          mode   = kDepthZ;
+    float        center = 0.0f;
+    // exactly one destination: per-splat rows in `grads` (dense, dense added to what the arrays hold, or compact), the
+    // optimiser folded into the per-splat pass (no gradient arrays at all), or the camera's twelve numbers alone
+    enum Dest { Dense, DenseAccumulate, Compact, FusedAdam, CameraOnly } dest = Dense;
+    const lcgs_grads* grads = nullptr;   // Dense, DenseAccumulate, Compact
+    AdamArrays        raw{}, m{}, v{}, act{}; // FusedAdam
+    AdamRates         lr{};
+    AdamStep          step{};
+    float*            d_dL_dcam = nullptr; // CameraOnly
+
+    bool maps() const { return d_dL_ddepth || d_dL_dalpha || d_dL_ddist; }
     bool value_channel() const { return d_dL_ddepth || d_dL_ddist; } // something arrives in the rows' value slot
+    bool rows() const { return dest == Dense || dest == DenseAccumulate || dest == Compact; }
 };
-lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcgs_grads* grads, bool compact,
-                            bool accumulate = false, const FusedAdam* fused = nullptr, const MapGrads* maps = nullptr,
-                            float* d_camera_only = nullptr);
+lcgs_status render_backward(lcgs_context* ctx, const BackwardRequest& req);
 // the camera pass over the 2-D rows the context holds (kernels/camera_grad.hip)
 lcgs_status camera_pass(lcgs_context* ctx, float* d_dL_dcam)
 {
     LCGS_TRY(ctx->cam_slab.ensure(camera_grad_slab_bytes((int64_t)ctx->P)));
-    launch_camera_grad(ctx->hint_V > 0 ? ctx->hint_V : (int64_t)ctx->P, ctx->sh_deg, ctx->last.cp, ctx->last.scale_modifier,
-                       ctx->pos, ctx->scale, ctx->rotq, ctx->sh, ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(),
-                       ctx->grads2d.as<float>(), ctx->last_has_jac ? ctx->shjac.as<float4>() : nullptr,
-                       ctx->recs.as<SplatRecord>(), ctx->g2d_value_mode, ctx->cam_slab.as<double>(), d_dL_dcam, ctx->stream,
-                       ctx->opacity);
+    launch_camera_grad(kept_rows(ctx), ctx->g2d_value_mode, ctx->cam_slab.as<double>(), d_dL_dcam, ctx->stream);
     return LCGS_OK;
 }
-// the state every walk of the kept lists needs: a keep-state frame of this context's own records, lists per tile
-// (owner_frame: the whole message for a frame drawn from received records, where the caller has a better one)
-lcgs_status check_maps_state(lcgs_context* ctx, const char* who, const char* owner_frame = nullptr)
+BackwardRequest rows_request(const float* d_dL_dimg, const lcgs_grads* grads, BackwardRequest::Dest dest)
+{
+    BackwardRequest req;
+    req.d_dL_dimg = d_dL_dimg, req.grads = grads, req.dest = dest;
+    return req;
+}
+}
+
+lcgs_status lcgs::abi::check_own_kept_frame(lcgs_context* ctx, const char* who, const char* owner_frame, const char* no_frame)
 {
     if (!ctx->frame_state_valid() || !ctx->last.has_state) {
-        set_last_error((std::string(who) + " needs a preceding lcgs_render_forward(..., keep_state = 1)").c_str());
+        const std::string plain = std::string(who) + " needs a preceding lcgs_render_forward(..., keep_state = 1)";
+        set_last_error(no_frame ? no_frame : plain.c_str());
         return LCGS_ERR_STATE;
     }
     if (ctx->owner_recs) { // the last frame was lcgs_owner_render's: its records are not this context's own
@@ -62,26 +68,25 @@ lcgs_status check_maps_state(lcgs_context* ctx, const char* who, const char* own
     LCGS_REQUIRE(ctx->last.cp.list_shift == 0u, "the kept frame lists its pairs per block: no backward walks those lists");
     return LCGS_OK;
 }
-}
 
 extern "C" {
 
 lcgs_status lcgs_render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcgs_grads* grads)
 {
     LCGS_ENTRY(ctx);
-    return render_backward(ctx, d_dL_dimg, grads, /*compact=*/false);
+    return render_backward(ctx, rows_request(d_dL_dimg, grads, BackwardRequest::Dense));
 }
 
 lcgs_status lcgs_render_backward_compact(lcgs_context* ctx, const float* d_dL_dimg, const lcgs_grads* grads)
 {
     LCGS_ENTRY(ctx);
-    return render_backward(ctx, d_dL_dimg, grads, /*compact=*/true);
+    return render_backward(ctx, rows_request(d_dL_dimg, grads, BackwardRequest::Compact));
 }
 
 lcgs_status lcgs_render_backward_accumulate(lcgs_context* ctx, const float* d_dL_dimg, const lcgs_grads* grads)
 {
     LCGS_ENTRY(ctx);
-    return render_backward(ctx, d_dL_dimg, grads, /*compact=*/false, /*accumulate=*/true);
+    return render_backward(ctx, rows_request(d_dL_dimg, grads, BackwardRequest::DenseAccumulate));
 }
 
 lcgs_status lcgs_render_backward_adam(lcgs_context* ctx, const float* d_dL_dimg, int num_gaussians, int sh_degree,
@@ -112,16 +117,17 @@ lcgs_status lcgs_render_backward_adam(lcgs_context* ctx, const float* d_dL_dimg,
         LCGS_TRY(ctx->fused_grads.ensure((o_op + rows) * 4));
         float*     g  = ctx->fused_grads.as<float>();
         lcgs_grads gr = { g, g + o_scale, g + o_rotq, g + o_sh, g + o_op };
-        LCGS_TRY(render_backward(ctx, d_dL_dimg, &gr, /*compact=*/true));
+        LCGS_TRY(render_backward(ctx, rows_request(d_dL_dimg, &gr, BackwardRequest::Compact)));
         lcgs_adam_config c2 = *cfg;
         c2.visible_only     = 2;
         return lcgs_adam_step(ctx, num_gaussians, sh_degree, &c2, &gr, raw, m, v, activated);
     }
     scene_arrays_written(ctx, activated->pos, activated->scale, activated->rotq); // (a context-owned scene trained in place)
-    FusedAdam fa = { adam_arrays(raw), adam_arrays(m), adam_arrays(v), adam_arrays(activated), adam_rates(cfg),
-                     make_adam_step(cfg->beta1, cfg->beta2, cfg->eps, cfg->step) };
-    lcgs_grads none{};
-    return render_backward(ctx, d_dL_dimg, &none, /*compact=*/true, /*accumulate=*/false, &fa);
+    BackwardRequest req;
+    req.d_dL_dimg = d_dL_dimg, req.dest = BackwardRequest::FusedAdam;
+    req.raw = adam_arrays(raw), req.m = adam_arrays(m), req.v = adam_arrays(v), req.act = adam_arrays(activated);
+    req.lr = adam_rates(cfg), req.step = make_adam_step(cfg->beta1, cfg->beta2, cfg->eps, cfg->step);
+    return render_backward(ctx, req);
 }
 
 lcgs_status lcgs_render_maps(lcgs_context* ctx, int mode, float* d_depth, float* d_alpha)
@@ -131,7 +137,7 @@ lcgs_status lcgs_render_maps(lcgs_context* ctx, int mode, float* d_depth, float*
     LCGS_REQUIRE(d_depth || d_alpha, "both outputs are NULL");
     LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
-    LCGS_TRY(check_maps_state(ctx, "lcgs_render_maps"));
+    LCGS_TRY(check_own_kept_frame(ctx, "lcgs_render_maps"));
     launch_render_maps(kept_frame(ctx), mode, d_depth, d_alpha, ctx->stream);
     LCGS_HIP_CHECK(hipGetLastError());
     return LCGS_OK;
@@ -144,7 +150,7 @@ lcgs_status lcgs_render_distortion(lcgs_context* ctx, int mode, float center, fl
     LCGS_REQUIRE(isfinite(center), "center must be finite");
     LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
-    LCGS_TRY(check_maps_state(ctx, "lcgs_render_distortion"));
+    LCGS_TRY(check_own_kept_frame(ctx, "lcgs_render_distortion"));
     launch_render_distortion(kept_frame(ctx), mode, center, d_dist, ctx->stream);
     LCGS_HIP_CHECK(hipGetLastError());
     return LCGS_OK;
@@ -156,20 +162,19 @@ lcgs_status lcgs_contrib_accumulate(lcgs_context* ctx, int num_gaussians, const 
     LCGS_REQUIRE(stats->weight_sum || stats->weight_max || stats->pixels || stats->views, "all four statistics are NULL");
     LCGS_ENTRY(ctx);
     LCGS_REQUIRE(num_gaussians == ctx->P, "num_gaussians must be the bound scene's");
-    LCGS_TRY(check_maps_state(ctx, "lcgs_contrib_accumulate"));
+    LCGS_TRY(check_own_kept_frame(ctx, "lcgs_contrib_accumulate"));
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     // one slot per on-screen row; sized for the scene's rows like the frame's other per-row buffers (the count stays on the device)
     LCGS_TRY(ctx->contrib_slab.ensure(contrib_slab_bytes((int64_t)ctx->P)));
-    hipStream_t   st   = ctx->stream;
-    const int64_t hint = ctx->hint_V > 0 ? std::min<int64_t>(ctx->hint_V, num_gaussians) : num_gaussians;
-    uint32_t*     slab = ctx->contrib_slab.as<uint32_t>();
-    ctx->n_marks       = 0;
+    hipStream_t    st   = ctx->stream;
+    const KeptRows rows = kept_rows(ctx);
+    uint32_t*      slab = ctx->contrib_slab.as<uint32_t>();
+    ctx->n_marks        = 0;
     LCGS_TRY(mark(ctx, "begin"));
-    launch_contrib_zero(hint, ctx->counts.as<uint32_t>(), slab, st);
+    launch_contrib_zero(rows, slab, st);
     launch_contrib_walk(kept_frame(ctx), slab, st);
     LCGS_TRY(mark(ctx, "contrib_walk"));
-    launch_contrib_fold(hint, num_gaussians, ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), slab, stats->weight_sum,
-                        stats->weight_max, stats->pixels, stats->views, st);
+    launch_contrib_fold(rows, slab, stats->weight_sum, stats->weight_max, stats->pixels, stats->views, st);
     LCGS_TRY(mark(ctx, "contrib_fold"));
     LCGS_HIP_CHECK(hipGetLastError());
     if (ctx->profiling) {
@@ -187,10 +192,10 @@ lcgs_status lcgs_render_backward_maps(lcgs_context* ctx, const float* d_dL_dimg,
     LCGS_REQUIRE(d_dL_dimg || d_dL_ddepth || d_dL_dalpha, "all three incoming gradients are NULL");
     LCGS_REQUIRE(grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh && grads->d_dL_dopacity,
                  "NULL gradient buffer");
-    const MapGrads maps = { mode, d_dL_ddepth, d_dL_dalpha };
+    BackwardRequest req = rows_request(d_dL_dimg, grads, accumulate ? BackwardRequest::DenseAccumulate : BackwardRequest::Dense);
+    req.mode = mode, req.d_dL_ddepth = d_dL_ddepth, req.d_dL_dalpha = d_dL_dalpha;
     LCGS_ENTRY(ctx);
-    return render_backward(ctx, d_dL_dimg, grads, /*compact=*/false, accumulate != 0, nullptr,
-                           (d_dL_ddepth || d_dL_dalpha) ? &maps : nullptr);
+    return render_backward(ctx, req);
 }
 
 lcgs_status lcgs_render_backward_distortion(lcgs_context* ctx, const float* d_dL_dimg, int mode, float center,
@@ -203,19 +208,18 @@ lcgs_status lcgs_render_backward_distortion(lcgs_context* ctx, const float* d_dL
     LCGS_REQUIRE(d_dL_dimg || d_dL_ddepth || d_dL_dalpha || d_dL_ddist, "all four incoming gradients are NULL");
     LCGS_REQUIRE(grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh && grads->d_dL_dopacity,
                  "NULL gradient buffer");
-    MapGrads maps   = { mode, d_dL_ddepth, d_dL_dalpha };
-    maps.center     = center;
-    maps.d_dL_ddist = d_dL_ddist;
+    BackwardRequest req = rows_request(d_dL_dimg, grads, accumulate ? BackwardRequest::DenseAccumulate : BackwardRequest::Dense);
+    req.mode = mode, req.center = center;
+    req.d_dL_ddepth = d_dL_ddepth, req.d_dL_dalpha = d_dL_dalpha, req.d_dL_ddist = d_dL_ddist;
     LCGS_ENTRY(ctx);
-    return render_backward(ctx, d_dL_dimg, grads, /*compact=*/false, accumulate != 0, nullptr,
-                           (d_dL_ddepth || d_dL_dalpha || d_dL_ddist) ? &maps : nullptr);
+    return render_backward(ctx, req);
 }
 
 lcgs_status lcgs_camera_backward(lcgs_context* ctx, float* d_dL_dcam)
 {
     LCGS_REQUIRE(ctx && d_dL_dcam, "NULL argument");
     LCGS_ENTRY(ctx);
-    LCGS_TRY(check_maps_state(ctx, "lcgs_camera_backward"));
+    LCGS_TRY(check_own_kept_frame(ctx, "lcgs_camera_backward"));
     if (!ctx->g2d_backward_done) {
         set_last_error("lcgs_camera_backward needs a backward of the last frame (its 2-D gradient rows are only zeros until then)");
         return LCGS_ERR_STATE;
@@ -232,11 +236,11 @@ lcgs_status lcgs_render_backward_camera(lcgs_context* ctx, const float* d_dL_dim
     LCGS_REQUIRE(ctx && d_dL_dcam, "NULL argument");
     LCGS_REQUIRE(mode == LCGS_DEPTH_Z || mode == LCGS_DEPTH_INV_Z, "mode must be LCGS_DEPTH_Z or LCGS_DEPTH_INV_Z");
     LCGS_REQUIRE(d_dL_dimg || d_dL_ddepth || d_dL_dalpha, "all three incoming gradients are NULL");
-    const MapGrads maps = { mode, d_dL_ddepth, d_dL_dalpha };
-    lcgs_grads     none{};
+    BackwardRequest req;
+    req.d_dL_dimg = d_dL_dimg, req.mode = mode, req.d_dL_ddepth = d_dL_ddepth, req.d_dL_dalpha = d_dL_dalpha;
+    req.dest = BackwardRequest::CameraOnly, req.d_dL_dcam = d_dL_dcam;
     LCGS_ENTRY(ctx);
-    return render_backward(ctx, d_dL_dimg, &none, /*compact=*/true, /*accumulate=*/false, nullptr,
-                           (d_dL_ddepth || d_dL_dalpha) ? &maps : nullptr, d_dL_dcam);
+    return render_backward(ctx, req);
 }
 
 lcgs_status lcgs_camera_grad_to_twist(const lcgs_camera* cam, const float dL_dcam[12], float dL_dxi[6])
@@ -271,19 +275,23 @@ lcgs_status lcgs_visible_rows(lcgs_context* ctx, const uint32_t** d_rows, const 
 
 namespace
 {
-lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcgs_grads* grads, bool compact,
-                            bool accumulate, const FusedAdam* fused, const MapGrads* maps, float* d_camera_only)
+lcgs_status render_backward(lcgs_context* ctx, const BackwardRequest& req)
 {
-    const bool params = !d_camera_only; // (lcgs_render_backward_camera: the walks and the camera pass, no per-splat rows)
-    LCGS_REQUIRE(ctx && (d_dL_dimg || maps) && grads, "NULL argument");
+    using Dest = BackwardRequest::Dest;
+    const float* const      d_dL_dimg = req.d_dL_dimg;
+    const lcgs_grads* const grads     = req.grads; // (non-NULL behind the first check when the request has rows)
+    const bool maps = req.maps(), rows_out = req.rows(); // (rows_out: gradient arrays are written; else the optimiser's or the camera's)
+    const bool camera_only = req.dest == Dest::CameraOnly; // (lcgs_render_backward_camera: the walks and the camera pass, no per-splat pass)
+    const bool accumulate = req.dest == Dest::DenseAccumulate, compact = !accumulate && req.dest != Dest::Dense;
+    LCGS_REQUIRE(ctx && (d_dL_dimg || maps) && (grads || !rows_out), "NULL argument");
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
-    LCGS_REQUIRE(fused || !params || (grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh &&
-                           grads->d_dL_dopacity),
+    LCGS_REQUIRE(!rows_out || (grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh &&
+                               grads->d_dL_dopacity),
                  "NULL gradient buffer");
-    LCGS_TRY(check_maps_state(ctx, "lcgs_render_backward",
+    LCGS_TRY(check_own_kept_frame(ctx, "lcgs_render_backward",
                               "the last frame was drawn from received records (lcgs_owner_render): use lcgs_owner_render_backward"));
-    LCGS_REQUIRE((reinterpret_cast<uintptr_t>(grads->d_dL_drotq) & 15) == 0, "dL_drotq must be 16-byte aligned");
-    if (!params) LCGS_TRY(ctx->cam_slab.ensure(camera_grad_slab_bytes((int64_t)ctx->P))); // (before any device work)
+    LCGS_REQUIRE(!rows_out || (reinterpret_cast<uintptr_t>(grads->d_dL_drotq) & 15) == 0, "dL_drotq must be 16-byte aligned");
+    if (camera_only) LCGS_TRY(ctx->cam_slab.ensure(camera_grad_slab_bytes((int64_t)ctx->P))); // (before any device work)
     hipStream_t  st   = ctx->stream;
     const size_t P    = (size_t)ctx->P;
     ctx->n_marks      = 0;
@@ -315,8 +323,7 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
         LCGS_TRY(ctx->slice_bounds.ensure((lcgs::kMaxGradSlices + 1) * sizeof(uint32_t)));
         for (int k = 0; k < ctx->grad_slices; ++k)
             LCGS_TRY(ctx->ev_slice[k].ensure());
-        launch_slice_bounds(ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), (int64_t)P, ctx->grad_slices,
-                            ctx->slice_bounds.as<uint32_t>(), zs); // (before the fill: ev_join / stream order covers it)
+        launch_slice_bounds(kept_rows(ctx), ctx->grad_slices, ctx->slice_bounds.as<uint32_t>(), zs); // (before the fill: ev_join / stream order covers it)
     }
     if (dense_fill && !fill_in_kernel) LCGS_TRY(zero_grad_rows(*grads, ctx->sh_deg, P, zs));
     if (overlap) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->aux_stream));
@@ -333,45 +340,37 @@ lcgs_status render_backward(lcgs_context* ctx, const float* d_dL_dimg, const lcg
                                                         : (ctx->frames_in_flight ? ctx->persist_bwd_in_flight : 0);
     const uint32_t bwd_wgs = (!ctx->profiling && k_bwd > 0) ? (uint32_t)(k_bwd * std::max(ctx->num_cus, 1)) : 0u;
     const KeptFrame kept   = kept_frame(ctx);
+    const KeptRows  rows   = kept_rows(ctx); // (behind the 2-D rows' ensure above)
     if (d_dL_dimg) {
         launch_render_backward(kept, ctx->last.bg, d_dL_dimg, ctx->grads2d.as<float>(), st, ctx->bwd_counter.as<uint32_t>(), bwd_wgs,
                                fill_in_kernel ? &fill : nullptr);
         LCGS_TRY(mark(ctx, "render_backward"));
     }
     if (maps) { // the map channels add to the rows the colour walk (or the zeroing alone) left: one walk for all of them
-        launch_render_maps_backward(kept, maps->mode, maps->d_dL_ddepth, maps->d_dL_dalpha, ctx->grads2d.as<float>(), st,
-                                    maps->center, maps->d_dL_ddist);
+        launch_render_maps_backward(kept, req.mode, req.d_dL_ddepth, req.d_dL_dalpha, ctx->grads2d.as<float>(), st, req.center,
+                                    req.d_dL_ddist);
         LCGS_TRY(mark(ctx, "render_maps_backward"));
     }
     if (overlap) LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_join, 0));
-    const int slices = (fused || !params) ? 0 : (sliced ? ctx->grad_slices : 1);
-    if (fused) // (compact, unsliced: the update is applied where the gradients are formed; nothing is written out)
-        launch_preprocess_backward_adam(ctx->hint_V > 0 ? ctx->hint_V : (int64_t)P, ctx->last.cp, ctx->last.scale_modifier,
-                                        ctx->pos, ctx->scale, ctx->rotq, ctx->opacity, ctx->vis_index.as<uint32_t>(),
-                                        ctx->counts.as<uint32_t>(), ctx->grads2d.as<float>(), ctx->shjac.as<float4>(),
-                                        fused->raw, fused->m, fused->v, fused->act, fused->lr, fused->step, st);
+    const int slices = rows_out ? (sliced ? ctx->grad_slices : 1) : 0;
+    if (req.dest == Dest::FusedAdam) // (compact, unsliced: the update is applied where the gradients are formed; nothing is written out)
+        launch_preprocess_backward_adam(rows, req.raw, req.m, req.v, req.act, req.lr, req.step, st);
     for (int k = 0; k < slices; ++k) {
-        launch_preprocess_backward(ctx->hint_V > 0 ? ctx->hint_V : (int64_t)P, ctx->sh_deg, ctx->last.cp,
-                                   ctx->last.scale_modifier, ctx->pos, ctx->scale, ctx->rotq, ctx->sh,
-                                   ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), ctx->grads2d.as<float>(),
-                                   grads->d_dL_dpos, grads->d_dL_dscale, grads->d_dL_drotq, grads->d_dL_dsh,
-                                   grads->d_dL_dopacity, st, ctx->last_has_jac ? ctx->shjac.as<float4>() : nullptr, compact,
-                                   sliced ? ctx->slice_bounds.as<uint32_t>() : nullptr, k, slices, accumulate, ctx->opacity);
+        launch_preprocess_backward(rows, grads->d_dL_dpos, grads->d_dL_dscale, grads->d_dL_drotq, grads->d_dL_dsh,
+                                   grads->d_dL_dopacity,
+                                   RowsOut{ compact, accumulate, sliced ? ctx->slice_bounds.as<uint32_t>() : nullptr, k, slices }, st);
         if (sliced) LCGS_HIP_CHECK(hipEventRecord(ctx->ev_slice[k], st));
     }
-    if (params && maps && maps->value_channel()) // view z = front . pos + tz: the depth and distortion channels' dL/dvalue reaches the position rows directly
-        launch_maps_depth_to_pos(ctx->hint_V > 0 ? ctx->hint_V : (int64_t)P, ctx->last.cp, ctx->vis_index.as<uint32_t>(),
-                                 ctx->counts.as<uint32_t>(), ctx->recs.as<SplatRecord>(), ctx->grads2d.as<float>(), maps->mode,
-                                 grads->d_dL_dpos, st);
+    if (rows_out && req.value_channel()) // view z = front . pos + tz: the depth and distortion channels' dL/dvalue reaches the position rows directly
+        launch_maps_depth_to_pos(rows, req.mode, grads->d_dL_dpos, st);
     ctx->slices_recorded = sliced ? slices : 0;
     ctx->slices_of       = sliced ? grads->d_dL_dpos : nullptr;
     // sparse exchange (opt-in, lcgs_comm_track_touched_rows): the rows this frame wrote join the step's touched set
-    if (params && !compact && !fused && ctx->comm)
-        LCGS_TRY(lcgs::comm_mark_touched(ctx->comm, ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), (int64_t)P,
-                                         ctx->hint_V, accumulate, st));
+    if (rows_out && !compact && ctx->comm)
+        LCGS_TRY(lcgs::comm_mark_touched(ctx->comm, rows, accumulate, st));
     ctx->g2d_backward_done = true; // the frame's 2-D gradient rows now hold a backward's sums (lcgs_densify_accumulate)
-    ctx->g2d_value_mode    = (maps && maps->value_channel()) ? maps->mode : -1; // (every backward starts from zeroed rows)
-    if (!params) LCGS_TRY(camera_pass(ctx, d_camera_only));
+    ctx->g2d_value_mode    = req.value_channel() ? req.mode : -1; // (every backward starts from zeroed rows)
+    if (camera_only) LCGS_TRY(camera_pass(ctx, req.d_dL_dcam));
     LCGS_TRY(mark(ctx, "preprocess_backward"));
     LCGS_HIP_CHECK(hipGetLastError());
     if (ctx->profiling) {

@@ -36,24 +36,17 @@ lcgs_status lcgs_densify_accumulate(lcgs_context* ctx, int num_gaussians, const 
     LCGS_REQUIRE(ctx && stats, "NULL argument");
     LCGS_REQUIRE(stats->grad_accum && stats->denom && stats->max_radii, "NULL device pointer in the statistics");
     LCGS_ENTRY(ctx);
-    if (!ctx->frame_state_valid() || !ctx->last.has_state) {
-        set_last_error("lcgs_densify_accumulate needs a preceding lcgs_render_forward(..., keep_state = 1) of this scene");
-        return LCGS_ERR_STATE;
-    }
-    if (ctx->owner_recs) { // an ownership-step frame: its rows are the received records', not this context's scene's
-        set_last_error("the last frame was drawn from received records (lcgs_owner_render): no statistics for it");
-        return LCGS_ERR_STATE;
-    }
+    // (an ownership-step frame: its rows are the received records', not this context's scene's)
+    LCGS_TRY(check_own_kept_frame(ctx, "lcgs_densify_accumulate",
+                                  "the last frame was drawn from received records (lcgs_owner_render): no statistics for it",
+                                  "lcgs_densify_accumulate needs a preceding lcgs_render_forward(..., keep_state = 1) of this scene"));
     if (!ctx->g2d_backward_done) {
         set_last_error("lcgs_densify_accumulate needs a backward of the last frame (its 2-D gradient rows are only zeros until then)");
         return LCGS_ERR_STATE;
     }
     LCGS_REQUIRE(num_gaussians == ctx->P, "num_gaussians must be the bound scene's");
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
-    const int64_t hint = ctx->hint_V > 0 ? std::min<int64_t>(ctx->hint_V, num_gaussians) : num_gaussians;
-    launch_densify_stats(hint, num_gaussians, ctx->last.cp, ctx->last.scale_modifier, ctx->pos, ctx->scale, ctx->rotq,
-                         ctx->vis_index.as<uint32_t>(), ctx->counts.as<uint32_t>(), ctx->grads2d.as<float>(), stats->grad_accum,
-                         stats->denom, stats->max_radii, ctx->stream);
+    launch_densify_stats(kept_rows(ctx), stats->grad_accum, stats->denom, stats->max_radii, ctx->stream);
     LCGS_HIP_CHECK(hipGetLastError());
     return LCGS_OK;
 }

@@ -6,7 +6,8 @@
 //   abi_stages.cpp    the reference's three operators + the two lcpp primitives (stage level), deferred stage mode
 //   abi_scene.cpp     scene bind / upload / download / PLY ingest / spatial re-order / f16 SH / LOD
 //   abi_frame.cpp     the fused frame: workspace, enqueue, lcgs_render_forward, camera batches, the sibling context
-//   abi_backward.cpp  lcgs_render_backward and its variants (compact rows, accumulate, fused Adam)
+//   abi_backward.cpp  lcgs_render_backward and its variants (compact rows, accumulate, fused Adam, maps, distortion, camera): one
+//                     request (BackwardRequest) behind all of them; lcgs_render_maps / _distortion, lcgs_contrib_accumulate
 //   abi_train.cpp     lcgs_adam_step, lcgs_fit_views
 //   abi_densify.cpp   adaptive density control: lcgs_densify_accumulate, lcgs_densify, lcgs_opacity_reset; lcgs_contrib_keep_mask, lcgs_prune
 //   abi_mcmc.cpp      3DGS-MCMC density control: lcgs_mcmc_relocate, lcgs_mcmc_add, lcgs_mcmc_noise, lcgs_mcmc_regularize
@@ -19,6 +20,7 @@
 
 #include "common.hpp"
 #include "context.hpp"
+#include "kernels/kept_rows.hpp"
 #include "kernels/kept_walk.hpp"
 #include "kernels/launch.hpp"
 #include "kernels/tie_order.hpp"
@@ -168,6 +170,54 @@ inline KeptFrame kept_frame(lcgs_context* ctx)
              ctx->counts.as<uint32_t>(),
              ctx->last_tile_order };
 }
+// the launch size of a pass with one lane per on-screen row: the hint the frames keep, never more than the scene's rows
+inline int64_t rows_hint(const lcgs_context* ctx) { return ctx->hint_V > 0 ? std::min<int64_t>(ctx->hint_V, ctx->P) : ctx->P; }
+// what such a pass over the last keep-state frame reads (kernels/kept_rows.hpp), this context's own records and 2-D rows
+inline KeptRows kept_rows(lcgs_context* ctx)
+{
+    return { ctx->last.cp,
+             ctx->last.scale_modifier,
+             ctx->sh_deg,
+             ctx->pos,
+             ctx->scale,
+             ctx->rotq,
+             ctx->sh,
+             ctx->opacity,
+             ctx->vis_index.as<uint32_t>(),
+             ctx->counts.as<uint32_t>(),
+             ctx->grads2d.as<float>(),
+             ctx->last_has_jac ? ctx->shjac.as<float4>() : nullptr,
+             ctx->recs.as<SplatRecord>(),
+             (int64_t)ctx->P,
+             rows_hint(ctx) };
+}
+// ... and a view of an ownership step (abi_owner.cpp): the slot's row range of the scene, its rows and counts, the caller's
+// 2-D rows; the launch is sized by the slot's known row count
+inline KeptRows owner_slot_rows(lcgs_context* ctx, int slot, const float* d_grads2d)
+{
+    auto&           s = ctx->owner[slot];
+    const SceneRows r = rows_from(scene_rows(ctx), ctx->sh_deg, (size_t)s.row_first);
+    return { s.cp,
+             s.scale_modifier,
+             ctx->sh_deg,
+             r.pos,
+             r.scale,
+             r.rotq,
+             r.sh,
+             r.opacity, // (s.cp.raster_mode is 0: the classic instantiation runs and reads none of it)
+             s.vis.as<uint32_t>(),
+             s.counts.as<uint32_t>(),
+             d_grads2d,
+             s.has_jac ? s.shjac.as<float4>() : nullptr,
+             nullptr,
+             (int64_t)s.row_count,
+             (int64_t)s.num };
+}
+// The state every pass over a kept frame needs: a keep-state frame of this context's own records, lists per tile.  Both
+// overrides are whole messages for callers that have a better one: no_frame, and owner_frame for a frame drawn from
+// received records.  (abi_backward.cpp)
+lcgs_status check_own_kept_frame(lcgs_context* ctx, const char* who, const char* owner_frame = nullptr,
+                                 const char* no_frame = nullptr);
 // the kept state of the last frame that every kind of frame records
 void keep_frame_state(lcgs_context* ctx, const CamParams& cp, const float bg[3], float scale_modifier, bool has_state);
 // launch-size hints follow the live counts once those leave the [hint / 2, hint] band (inside it a captured graph stays valid)

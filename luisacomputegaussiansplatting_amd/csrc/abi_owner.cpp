@@ -363,11 +363,8 @@ lcgs_status lcgs::abi::owner_backward_rows(lcgs_context* ctx, int slot, const fl
     }
     if (s.num == 0) return LCGS_OK;
     LCGS_REQUIRE(d_grads2d != nullptr, "NULL 2-D gradients");
-    const SceneRows r = rows_from(scene_rows(ctx), ctx->sh_deg, (size_t)s.row_first);
-    launch_preprocess_backward(s.num, ctx->sh_deg, s.cp, s.scale_modifier, r.pos, r.scale, r.rotq, r.sh, s.vis.as<uint32_t>(),
-                               s.counts.as<uint32_t>(), d_grads2d, g.d_dL_dpos, g.d_dL_dscale, g.d_dL_drotq, g.d_dL_dsh,
-                               g.d_dL_dopacity, st, s.has_jac ? s.shjac.as<float4>() : nullptr, /*compact=*/false, nullptr, 0, 1,
-                               /*accumulate=*/mode == 1);
+    launch_preprocess_backward(owner_slot_rows(ctx, slot, d_grads2d), g.d_dL_dpos, g.d_dL_dscale, g.d_dL_drotq, g.d_dL_dsh,
+                               g.d_dL_dopacity, RowsOut{ /*compact=*/false, /*accumulate=*/mode == 1, nullptr, 0, 1 }, st);
     LCGS_HIP_CHECK(hipGetLastError());
     return LCGS_OK;
 }

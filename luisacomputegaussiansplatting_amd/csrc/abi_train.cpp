@@ -48,7 +48,7 @@ lcgs_status lcgs_adam_step(lcgs_context* ctx, int num_gaussians, int sh_degree, 
                      "visible_only needs a forward frame of this scene in this context");
         row_list = ctx->vis_index.as<uint32_t>();
         d_rows   = ctx->counts.as<uint32_t>(); // [0] = survivors of the last frame
-        hint     = ctx->hint_V > 0 ? std::min<int64_t>(ctx->hint_V, num_gaussians) : num_gaussians;
+        hint     = rows_hint(ctx);
     }
     const AdamArrays g = { grads->d_dL_dpos, grads->d_dL_dscale, grads->d_dL_drotq, grads->d_dL_dsh, grads->d_dL_dopacity };
     launch_adam_step(num_gaussians, (int)sh_floats(sh_degree), row_list, d_rows, hint, g, adam_arrays(raw), adam_arrays(m),

@@ -16,8 +16,7 @@ constexpr int kMaxGradSlices = 16; // splat-range slices of the dense gradient r
 // (host/comm_wire.cpp) a context that goes away before its communicator: the communicator forgets it
 void comm_forget_context(lcgs_comm* comm);
 // (host/comm_grads.cpp) sparse exchange: a dense backward flags the rows of the frame it has just differentiated
-lcgs_status comm_mark_touched(lcgs_comm* comm, const uint32_t* vis_index, const uint32_t* d_counts, int64_t P, int64_t hint_V,
-                              bool accumulate, hipStream_t stream);
+lcgs_status comm_mark_touched(lcgs_comm* comm, const KeptRows& rows, bool accumulate, hipStream_t stream);
 namespace abi
 {
 // (abi_scene.cpp) position / scale / rotation rows inside these arrays are being written: every live context drops the rows

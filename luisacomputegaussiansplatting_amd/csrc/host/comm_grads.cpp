@@ -261,9 +261,9 @@ lcgs_status compact_touched(lcgs_context* ctx, lcgs_comm* c, int64_t P, int worl
 namespace lcgs
 {
 // (abi_backward.cpp render_backward) flag the rows of the frame a dense backward has just differentiated
-lcgs_status comm_mark_touched(lcgs_comm* c, const uint32_t* vis_index, const uint32_t* d_counts, int64_t P, int64_t hint_V,
-                              bool accumulate, hipStream_t stream)
+lcgs_status comm_mark_touched(lcgs_comm* c, const KeptRows& rows, bool accumulate, hipStream_t stream)
 {
+    const int64_t P = rows.P;
     if (!c || !c->track_rows || P <= 0) return LCGS_OK;
     const size_t fb = sparse_flag_bytes(P);
     if (c->flags_P != P || !accumulate) {
@@ -271,7 +271,7 @@ lcgs_status comm_mark_touched(lcgs_comm* c, const uint32_t* vis_index, const uin
         LCGS_HIP_CHECK(hipMemsetAsync(c->flags.ptr, 0, fb, stream));
         c->flags_P = P;
     }
-    launch_mark_rows(vis_index, d_counts, c->flags.as<uint8_t>(), P, hint_V, stream);
+    launch_mark_rows(rows, c->flags.as<uint8_t>(), stream);
     return LCGS_OK;
 }
 } // namespace lcgs

@@ -19,6 +19,7 @@
 // Thresholds are constants for the derivative: near cull, alpha < 1/255 skip, T < 1e-4 stop and power > 0 gate the
 // sums; the 0.99 alpha cap, the colour clamp and a saturated cam_clamp axis pass no gradient.
 #include "adam_rows.hpp"
+#include "kept_rows.hpp"
 #include "kept_walk.hpp"
 #include "splat_backward.hpp"
 #include "stream_access.hpp"
@@ -524,31 +525,28 @@ k_preprocess_backward(int sh_deg, CamParams cp, float scale_modifier, const floa
     const bool staged = sh_deg == 3 && ((reinterpret_cast<uintptr_t>(sh) & 15) == 0) &&
                         ((reinterpret_cast<uintptr_t>(dL_dsh) & 15) == 0);
     for (uint32_t blk = blockIdx.x; v0 + blk * 256u < V; blk += gridDim.x) {
-        const uint32_t vid   = v0 + blk * 256u + threadIdx.x;
-        const bool     valid = vid < V;
-        const int      idx   = (int)vis_index[valid ? vid : V - 1];
-        const uint32_t wave_first = v0 + blk * 256u + wave * 64u;
-        const uint32_t nvalid     = wave_first < V ? ((V - wave_first) < 64u ? (V - wave_first) : 64u) : 0u;
+        const RowBlock b   = row_block(v0, V, blk, vis_index);
         float*         row = reinterpret_cast<float*>(&s_sh[wave][lane * 13]); // this lane's 48 floats (+4 pad)
-        const SplatOperands in = load_splat_operands<AA>(valid ? vid : V - 1, idx, grads2d, pos, scale, rotq, opacity); // (with the SH rows below)
+        const SplatOperands in = load_splat_operands<AA>(b.vsafe, b.idx, grads2d, pos, scale, rotq, opacity); // (with the SH rows below)
 
         // ---- stage the SH rows (coalesced), or fetch them lane-wise for other degrees
         __syncthreads();
+        // (its own copy of the 12-lane loop: through row_part_step the kernel's SGPR spills change)
         if (staged) {
 #pragma unroll
             for (int i = 0; i < 12; ++i) {
                 const uint32_t c    = (uint32_t)i * 64u + lane;
                 const uint32_t slot = c / 12u, part = c - slot * 12u;
-                const int      sidx = __shfl(idx, (int)slot, 64);
-                if (slot < nvalid) s_sh[wave][slot * 13u + part] = reinterpret_cast<const float4*>(sh + (size_t)sidx * 48)[part];
+                const int      sidx = __shfl(b.idx, (int)slot, 64);
+                if (slot < b.nvalid) s_sh[wave][slot * 13u + part] = reinterpret_cast<const float4*>(sh + (size_t)sidx * 48)[part];
             }
-        } else if (valid) {
-            const float* s = sh + (size_t)idx * feat * 3;
+        } else if (b.valid) {
+            const float* s = sh + (size_t)b.idx * feat * 3;
             for (int k = 0; k < 48; ++k) row[k] = k < feat * 3 ? s[k] : 0.0f;
         }
         __syncthreads();
 
-        if (valid) {
+        if (b.valid) {
             float gp[3] = { 0.0f, 0.0f, 0.0f };
 
             // ---- colour -> SH coefficients and position (through the view direction)
@@ -558,7 +556,7 @@ k_preprocess_backward(int sh_deg, CamParams cp, float scale_modifier, const floa
             float4 gq;
             geom_backward<AA>(cp, scale_modifier, in, gp, gs, gq, gop);
 
-            const size_t orow = compact ? (size_t)vid : (size_t)idx; // compact: row = dense id (see launch.hpp)
+            const size_t orow = compact ? (size_t)b.vid : (size_t)b.idx; // compact: row = dense id (see launch.hpp)
             store_geometry_rows(orow, accumulate, gp, gs, gq, gop, dL_dpos, dL_dscale, dL_drotq, dL_dopacity);
         }
 
@@ -566,23 +564,19 @@ k_preprocess_backward(int sh_deg, CamParams cp, float scale_modifier, const floa
         __syncthreads();
         if (staged) {
 #pragma unroll
-            for (int i = 0; i < 12; ++i) {
-                const uint32_t cidx = (uint32_t)i * 64u + lane;
-                const uint32_t slot = cidx / 12u, part = cidx - slot * 12u;
-                const int      sidx = __shfl(idx, (int)slot, 64);
-                const size_t   orow = compact ? (size_t)(wave_first + slot) : (size_t)sidx;
-                if (slot < nvalid) {
-                    float4* dst = reinterpret_cast<float4*>(dL_dsh + orow * 48) + part;
-                    float4  v   = s_sh[wave][slot * 13u + part];
+            for (int i = 0; i < 12; ++i)
+                row_part_step(b, lane, i, [&](uint32_t slot, uint32_t part, int sidx) {
+                    const size_t orow = compact ? (size_t)(b.wave_first + slot) : (size_t)sidx;
+                    float4*      dst  = reinterpret_cast<float4*>(dL_dsh + orow * 48) + part;
+                    float4       v    = s_sh[wave][slot * 13u + part];
                     if (accumulate) {
                         const float4 o = *dst;
                         v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
                     }
                     *dst = v;
-                }
-            }
-        } else if (valid) {
-            float* o = dL_dsh + (compact ? (size_t)vid : (size_t)idx) * feat * 3;
+                });
+        } else if (b.valid) {
+            float* o = dL_dsh + (compact ? (size_t)b.vid : (size_t)b.idx) * feat * 3;
             for (int k = 0; k < feat * 3; ++k) o[k] = accumulate ? o[k] + row[k] : row[k];
         }
     }
@@ -624,32 +618,24 @@ k_preprocess_backward_jac(CamParams cp, float scale_modifier, const float* __res
     const uint32_t V  = slice_bounds ? slice_bounds[slice + 1] : d_counts[0];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (uint32_t blk = blockIdx.x; v0 + blk * 256u < V; blk += gridDim.x) {
-        const uint32_t vid   = v0 + blk * 256u + threadIdx.x;
-        const bool     valid = vid < V;
-        const uint32_t vsafe = valid ? vid : V - 1;
-        const int      idx   = (int)vis_index[vsafe];
-        const uint32_t wave_first = v0 + blk * 256u + wave * 64u;
-        const uint32_t nvalid     = wave_first < V ? ((V - wave_first) < 64u ? (V - wave_first) : 64u) : 0u;
-        const SplatOperands in = load_splat_operands<AA>(vsafe, idx, grads2d, pos, scale, rotq, opacity);
-        const float4 j0 = shjac[(size_t)vsafe * 3 + 0], j1 = shjac[(size_t)vsafe * 3 + 1], j2 = shjac[(size_t)vsafe * 3 + 2];
-        if (valid) {
+        const RowBlock      b  = row_block(v0, V, blk, vis_index);
+        const SplatOperands in = load_splat_operands<AA>(b.vsafe, b.idx, grads2d, pos, scale, rotq, opacity);
+        const float4 j0 = shjac[(size_t)b.vsafe * 3 + 0], j1 = shjac[(size_t)b.vsafe * 3 + 1], j2 = shjac[(size_t)b.vsafe * 3 + 2];
+        if (b.valid) {
             float  gp[3], gs[3], gop;
             float4 gq;
             jac_colour_step(cp, in, j0, j1, j2, &s_outer[wave][lane * kJacPitch], gp);
             geom_backward<AA>(cp, scale_modifier, in, gp, gs, gq, gop);
-            const size_t orow = compact ? (size_t)vid : (size_t)idx; // compact: row = dense id (see launch.hpp)
+            const size_t orow = compact ? (size_t)b.vid : (size_t)b.idx; // compact: row = dense id (see launch.hpp)
             store_geometry_rows(orow, accumulate, gp, gs, gq, gop, dL_dpos, dL_dscale, dL_drotq, dL_dopacity);
         }
         __syncthreads();
         // ---- SH gradient rows: 12 consecutive lanes write one splat's 192 contiguous bytes
 #pragma unroll 1
-        for (int i = 0; i < 12; ++i) {
-            const uint32_t cidx = (uint32_t)i * 64u + lane;
-            const uint32_t slot = cidx / 12u, part = cidx - slot * 12u;
-            const int      sidx = __shfl(idx, (int)slot, 64);
-            if (slot < nvalid) {
+        for (int i = 0; i < 12; ++i)
+            row_part_step(b, lane, i, [=](uint32_t slot, uint32_t part, int sidx) { // (by value: by reference costs two SGPRs)
                 float4       v    = jac_outer_part(&s_outer[wave][slot * kJacPitch], part);
-                const size_t orow = compact ? (size_t)(wave_first + slot) : (size_t)sidx;
+                const size_t orow = compact ? (size_t)(b.wave_first + slot) : (size_t)sidx;
                 float4*      dst  = reinterpret_cast<float4*>(dL_dsh + orow * 48) + part;
                 if (accumulate) {
                     const float4 o = *dst;
@@ -657,8 +643,7 @@ k_preprocess_backward_jac(CamParams cp, float scale_modifier, const float* __res
                 }
                 // written once, read by the optimiser / the all-reduce a kernel later: a streaming store
                 st_stream(dst, v);
-            }
-        }
+            });
         __syncthreads(); // the slab is reused by the next iteration
     }
 }
@@ -684,16 +669,12 @@ k_preprocess_backward_adam(CamParams cp, float scale_modifier, const float* pos,
     const uint32_t V = d_counts[0];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (uint32_t blk = blockIdx.x; blk * 256u < V; blk += gridDim.x) {
-        const uint32_t vid   = blk * 256u + threadIdx.x;
-        const bool     valid = vid < V;
-        const uint32_t vsafe = valid ? vid : V - 1;
-        const int      idx   = (int)vis_index[vsafe];
-        const uint32_t wave_first = blk * 256u + wave * 64u;
-        const uint32_t nvalid     = wave_first < V ? ((V - wave_first) < 64u ? (V - wave_first) : 64u) : 0u;
+        const RowBlock b   = row_block(0u, V, blk, vis_index);
+        const int      idx = b.idx;
         // (an antialiased frame's raw opacity is read here, before this lane's update of the activated row below)
-        const SplatOperands in = load_splat_operands<AA>(vsafe, idx, grads2d, pos, scale, rotq, opacity);
-        const float4 j0 = shjac[(size_t)vsafe * 3 + 0], j1 = shjac[(size_t)vsafe * 3 + 1], j2 = shjac[(size_t)vsafe * 3 + 2];
-        if (valid) {
+        const SplatOperands in = load_splat_operands<AA>(b.vsafe, idx, grads2d, pos, scale, rotq, opacity);
+        const float4 j0 = shjac[(size_t)b.vsafe * 3 + 0], j1 = shjac[(size_t)b.vsafe * 3 + 1], j2 = shjac[(size_t)b.vsafe * 3 + 2];
+        if (b.valid) {
             float  gp[3], gs[3], gop;
             float4 gq;
             jac_colour_step(cp, in, j0, j1, j2, &s_outer[wave][lane * kJacPitch], gp);
@@ -742,11 +723,12 @@ k_preprocess_backward_adam(CamParams cp, float scale_modifier, const float* pos,
         __syncthreads();
         // ---- SH rows: 12 consecutive lanes own one splat's 192 contiguous bytes of raw / m / v (train.hip: k_adam_sh48)
 #pragma unroll 1
+        // (its own copy of the 12-lane loop: through row_part_step the kernel's register counts change)
         for (int i = 0; i < 12; ++i) {
             const uint32_t cidx = (uint32_t)i * 64u + lane;
             const uint32_t slot = cidx / 12u, part = cidx - slot * 12u;
             const int      sidx = __shfl(idx, (int)slot, 64);
-            if (slot < nvalid) {
+            if (slot < b.nvalid) {
                 const float4 g  = jac_outer_part(&s_outer[wave][slot * kJacPitch], part);
                 const size_t r4 = (size_t)sidx * 12 + part;
                 float4*      xr = reinterpret_cast<float4*>(raw.sh) + r4;
@@ -829,53 +811,44 @@ __global__ void __launch_bounds__(64) k_slice_bounds(const uint32_t* __restrict_
     bounds[k] = lo;
 }
 
-void launch_slice_bounds(const uint32_t* vis_index, const uint32_t* d_counts, int64_t P, int slices, uint32_t* bounds,
-                         hipStream_t stream)
+void launch_slice_bounds(const KeptRows& r, int slices, uint32_t* bounds, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_slice_bounds, dim3(1), dim3(64), 0, stream, vis_index, d_counts, (uint32_t)P, slices, bounds);
+    hipLaunchKernelGGL(k_slice_bounds, dim3(1), dim3(64), 0, stream, r.vis_index, r.d_counts, (uint32_t)r.P, slices, bounds);
 }
 
-void launch_preprocess_backward(int64_t v_hint, int sh_deg, const CamParams& cp, float scale_modifier, const float* pos,
-                                const float* scale, const float* rotq, const float* sh, const uint32_t* vis_index,
-                                const uint32_t* d_counts, const float* grads2d, float* dL_dpos, float* dL_dscale,
-                                float* dL_drotq, float* dL_dsh, float* dL_dopacity, hipStream_t stream,
-                                const float4* shjac, bool compact, const uint32_t* slice_bounds, int slice, int slices,
-                                bool accumulate, const float* opacity)
+void launch_preprocess_backward(const KeptRows& r, float* dL_dpos, float* dL_dscale, float* dL_drotq, float* dL_dsh,
+                                float* dL_dopacity, const RowsOut& out, hipStream_t stream)
 {
-    const int mode = (compact ? 1 : 0) | (accumulate ? 2 : 0);
+    const int mode = (out.compact ? 1 : 0) | (out.accumulate ? 2 : 0);
     // (a slice's launch is sized for its share of the hint; larger live counts are strided)
-    const unsigned blocks = grid_256(v_hint / (slice_bounds ? slices : 1));
-    const bool aa = cp.raster_mode != 0; // (one instantiation per raster mode: the classic pass carries none of the other's code)
-    if (shjac && sh_deg == 3 && (reinterpret_cast<uintptr_t>(dL_dsh) & 15) == 0) {
+    const unsigned blocks = grid_256(r.hint / (out.slice_bounds ? out.slices : 1));
+    const bool aa = r.cp.raster_mode != 0; // (one instantiation per raster mode: the classic pass carries none of the other's code)
+    if (r.shjac && r.sh_deg == 3 && (reinterpret_cast<uintptr_t>(dL_dsh) & 15) == 0) {
 #define LCGS_LAUNCH_JAC(AA_)                                                                                                   \
-    hipLaunchKernelGGL((k_preprocess_backward_jac<AA_>), dim3(blocks), dim3(256), 0, stream, cp, scale_modifier, pos, scale, rotq,  \
-                       vis_index, d_counts, grads2d, shjac, dL_dpos, dL_dscale, dL_drotq, dL_dsh, dL_dopacity, mode, slice_bounds, \
-                       slice, opacity)
+    hipLaunchKernelGGL((k_preprocess_backward_jac<AA_>), dim3(blocks), dim3(256), 0, stream, r.cp, r.scale_modifier, r.pos, r.scale, \
+                       r.rotq, r.vis_index, r.d_counts, r.grads2d, r.shjac, dL_dpos, dL_dscale, dL_drotq, dL_dsh, dL_dopacity, \
+                       mode, out.slice_bounds, out.slice, r.opacity)
         if (aa) LCGS_LAUNCH_JAC(true);
         else LCGS_LAUNCH_JAC(false);
 #undef LCGS_LAUNCH_JAC
         return;
     }
 #define LCGS_LAUNCH_ROWS(AA_)                                                                                                  \
-    hipLaunchKernelGGL((k_preprocess_backward<AA_>), dim3(blocks), dim3(256), 0, stream, sh_deg, cp, scale_modifier, pos, scale,  \
-                       rotq, sh, vis_index, d_counts, grads2d, dL_dpos, dL_dscale, dL_drotq, dL_dsh, dL_dopacity, mode,        \
-                       slice_bounds, slice, opacity)
+    hipLaunchKernelGGL((k_preprocess_backward<AA_>), dim3(blocks), dim3(256), 0, stream, r.sh_deg, r.cp, r.scale_modifier, r.pos,  \
+                       r.scale, r.rotq, r.sh, r.vis_index, r.d_counts, r.grads2d, dL_dpos, dL_dscale, dL_drotq, dL_dsh,        \
+                       dL_dopacity, mode, out.slice_bounds, out.slice, r.opacity)
     if (aa) LCGS_LAUNCH_ROWS(true);
     else LCGS_LAUNCH_ROWS(false);
 #undef LCGS_LAUNCH_ROWS
 }
 
-void launch_preprocess_backward_adam(int64_t v_hint, const CamParams& cp, float scale_modifier, const float* pos,
-                                     const float* scale, const float* rotq, const float* opacity, const uint32_t* vis_index,
-                                     const uint32_t* d_counts,
-                                     const float* grads2d, const float4* shjac, const AdamArrays& raw, const AdamArrays& m,
-                                     const AdamArrays& v, const AdamArrays& act, const AdamRates& lr, const AdamStep& a,
-                                     hipStream_t stream)
+void launch_preprocess_backward_adam(const KeptRows& r, const AdamArrays& raw, const AdamArrays& m, const AdamArrays& v,
+                                     const AdamArrays& act, const AdamRates& lr, const AdamStep& a, hipStream_t stream)
 {
 #define LCGS_LAUNCH_ADAM(AA_)                                                                                                  \
-    hipLaunchKernelGGL((k_preprocess_backward_adam<AA_>), dim3(grid_256(v_hint)), dim3(256), 0, stream, cp, scale_modifier, pos,   \
-                       scale, rotq, opacity, vis_index, d_counts, grads2d, shjac, raw, m, v, act, lr, a)
-    if (cp.raster_mode != 0) LCGS_LAUNCH_ADAM(true);
+    hipLaunchKernelGGL((k_preprocess_backward_adam<AA_>), dim3(grid_256(r.hint)), dim3(256), 0, stream, r.cp, r.scale_modifier,   \
+                       r.pos, r.scale, r.rotq, r.opacity, r.vis_index, r.d_counts, r.grads2d, r.shjac, raw, m, v, act, lr, a)
+    if (r.cp.raster_mode != 0) LCGS_LAUNCH_ADAM(true);
     else LCGS_LAUNCH_ADAM(false);
 #undef LCGS_LAUNCH_ADAM
 }

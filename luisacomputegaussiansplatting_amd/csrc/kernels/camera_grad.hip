@@ -13,6 +13,7 @@
 //                         in order) and writes the twelve floats, each rounded once.  The entry count comes from d_counts[0].
 // No atomics: the summation tree depends on the number of on-screen rows only -- not on the grid, the launch hint or timing --
 // so the same 2-D rows give the same bits.
+#include "kept_rows.hpp"
 #include "kept_walk.hpp"
 #include "splat_backward.hpp"
 
@@ -44,46 +45,38 @@ k_camera_grad(int sh_deg, CamParams cp, float scale_modifier, const float* __res
     const int feat = (sh_deg + 1) * (sh_deg + 1);
     const bool staged = sh_deg == 3 && ((reinterpret_cast<uintptr_t>(sh) & 15) == 0);
     for (uint32_t blk = blockIdx.x; (uint64_t)blk * 256u < V; blk += gridDim.x) { // (no row at all: no pass, no V - 1)
-        const uint32_t vid   = blk * 256u + threadIdx.x;
-        const bool     valid = vid < V;
-        const uint32_t vsafe = valid ? vid : V - 1;
-        const int      idx   = (int)vis_index[vsafe];
-        const SplatOperands in = load_splat_operands<AA>(vsafe, idx, grads2d, pos, scale, rotq, opacity);
+        const RowBlock      b  = row_block(0u, V, blk, vis_index);
+        const SplatOperands in = load_splat_operands<AA>(b.vsafe, b.idx, grads2d, pos, scale, rotq, opacity);
         float gdir[3] = { 0.0f, 0.0f, 0.0f };
         if constexpr (JAC) {
-            const float4 j0 = shjac[(size_t)vsafe * 3 + 0], j1 = shjac[(size_t)vsafe * 3 + 1], j2 = shjac[(size_t)vsafe * 3 + 2];
+            const float4 j0 = shjac[(size_t)b.vsafe * 3 + 0], j1 = shjac[(size_t)b.vsafe * 3 + 1], j2 = shjac[(size_t)b.vsafe * 3 + 2];
             jac_colour_step<false>(cp, in, j0, j1, j2, nullptr, gdir);
         } else {
-            // ---- stage the SH rows (coalesced), or fetch them lane-wise for other degrees: k_preprocess_backward's staging
-            const uint32_t wave_first = blk * 256u + wave * 64u;
-            const uint32_t nvalid     = wave_first < V ? ((V - wave_first) < 64u ? (V - wave_first) : 64u) : 0u;
-            float*         row = reinterpret_cast<float*>(&s_sh[wave][lane * 13]);
+            // ---- stage the SH rows (coalesced), or fetch them lane-wise for other degrees, as k_preprocess_backward does
+            float* row = reinterpret_cast<float*>(&s_sh[wave][lane * 13]);
             __syncthreads(); // the previous block's readers are done with the slab
             if (staged) {
 #pragma unroll
-                for (int i = 0; i < 12; ++i) {
-                    const uint32_t c    = (uint32_t)i * 64u + lane;
-                    const uint32_t slot = c / 12u, part = c - slot * 12u;
-                    const int      sidx = __shfl(idx, (int)slot, 64);
-                    if (slot < nvalid)
+                for (int i = 0; i < 12; ++i)
+                    row_part_step(b, lane, i, [&](uint32_t slot, uint32_t part, int sidx) {
                         s_sh[wave][slot * 13u + part] = reinterpret_cast<const float4*>(sh + (size_t)sidx * 48)[part];
-                }
-            } else if (valid) {
-                const float* s = sh + (size_t)idx * feat * 3;
+                    });
+            } else if (b.valid) {
+                const float* s = sh + (size_t)b.idx * feat * 3;
                 for (int k = 0; k < 48; ++k) row[k] = k < feat * 3 ? s[k] : 0.0f;
             }
             __syncthreads();
-            if (valid) sh_colour_step<false>(cp, in, feat, row, gdir);
+            if (b.valid) sh_colour_step<false>(cp, in, feat, row, gdir);
         }
         double t[kCamTerms];
 #pragma unroll
         for (int k = 0; k < kCamTerms; ++k) t[k] = 0.0;
-        if (valid) {
+        if (b.valid) {
             // the depth channel's dL/dvalue reaches view z directly (as in maps.hip k_maps_depth_to_pos)
             float gz = 0.0f;
             if (depth_mode >= 0) {
-                const float gv = grads2d[(size_t)vid * kG2D + kG2DValueSlot];
-                if (gv != 0.0f) gz = kept_walk::depth_value_backward(recs[vid].depth, depth_mode, gv);
+                const float gv = grads2d[(size_t)b.vid * kG2D + kG2DValueSlot];
+                if (gv != 0.0f) gz = kept_walk::depth_value_backward(recs[b.vid].depth, depth_mode, gv);
             }
             camera_terms<AA>(cp, scale_modifier, in, gdir, gz, t);
         }
@@ -126,23 +119,20 @@ __global__ void __launch_bounds__(256) k_camera_grad_finish(const uint32_t* __re
 
 size_t camera_grad_slab_bytes(int64_t P) { return (size_t)((P + 255) / 256) * kCamTerms * sizeof(double); }
 
-void launch_camera_grad(int64_t v_hint, int sh_deg, const CamParams& cp, float scale_modifier, const float* pos, const float* scale,
-                        const float* rotq, const float* sh, const uint32_t* vis_index, const uint32_t* d_counts,
-                        const float* grads2d, const float4* shjac, const SplatRecord* recs, int depth_mode, double* slab,
-                        float* dL_dcam, hipStream_t stream, const float* opacity)
+void launch_camera_grad(const KeptRows& r, int depth_mode, double* slab, float* dL_dcam, hipStream_t stream)
 {
-    const unsigned blocks = grid_256(v_hint);
+    const unsigned blocks = grid_256(r.hint);
     // (one instantiation per raster mode, like the preprocess-backward's: the classic pass carries none of the other's code)
 #define LCGS_LAUNCH_CAM(JAC_, AA_)                                                                                             \
-    hipLaunchKernelGGL((k_camera_grad<JAC_, AA_>), dim3(blocks), dim3(256), 0, stream, sh_deg, cp, scale_modifier, pos, scale,   \
-                       rotq, sh, vis_index, d_counts, grads2d, shjac, recs, depth_mode, slab, opacity)
-    const bool jac = shjac && sh_deg == 3, aa = cp.raster_mode != 0;
+    hipLaunchKernelGGL((k_camera_grad<JAC_, AA_>), dim3(blocks), dim3(256), 0, stream, r.sh_deg, r.cp, r.scale_modifier, r.pos,  \
+                       r.scale, r.rotq, r.sh, r.vis_index, r.d_counts, r.grads2d, r.shjac, r.recs, depth_mode, slab, r.opacity)
+    const bool jac = r.shjac && r.sh_deg == 3, aa = r.cp.raster_mode != 0;
     if (jac && aa) LCGS_LAUNCH_CAM(true, true);
     else if (jac) LCGS_LAUNCH_CAM(true, false);
     else if (aa) LCGS_LAUNCH_CAM(false, true);
     else LCGS_LAUNCH_CAM(false, false);
 #undef LCGS_LAUNCH_CAM
-    hipLaunchKernelGGL(k_camera_grad_finish, dim3(1), dim3(256), 0, stream, d_counts, slab, dL_dcam);
+    hipLaunchKernelGGL(k_camera_grad_finish, dim3(1), dim3(256), 0, stream, r.d_counts, slab, dL_dcam);
 }
 
 } // namespace lcgs

@@ -11,6 +11,7 @@
 //              unique: plain read-modify-write, no atomics; messages are applied in rank order -> deterministic sums)
 // No MFMA, nothing to tile: byte-moving kernels, bound by HBM (gathers of 12-192-byte rows on one side, streams on the
 // other).
+#include "kept_rows.hpp"
 #include "launch.hpp"
 
 #include "../common.hpp"
@@ -197,12 +198,11 @@ unsigned grid_words(uint64_t words)
 size_t sparse_flag_bytes(int64_t P) { return (size_t)div_up64(P, kFlagsPerChunk) * kFlagsPerChunk; }
 uint32_t sparse_flag_chunks(int64_t P) { return (uint32_t)div_up64(P, kFlagsPerChunk); }
 
-void launch_mark_rows(const uint32_t* vis_index, const uint32_t* d_counts, uint8_t* flags, int64_t P, int64_t hint_V,
-                      hipStream_t stream)
+void launch_mark_rows(const KeptRows& r, uint8_t* flags, hipStream_t stream)
 {
-    if (P <= 0) return;
-    const int64_t n = hint_V > 0 ? hint_V : P;
-    hipLaunchKernelGGL(k_mark_rows, dim3(grid_words((uint64_t)n)), dim3(256), 0, stream, vis_index, d_counts, flags, (uint32_t)P);
+    if (r.P <= 0) return;
+    hipLaunchKernelGGL(k_mark_rows, dim3(grid_words((uint64_t)r.hint)), dim3(256), 0, stream, r.vis_index, r.d_counts, flags,
+                       (uint32_t)r.P);
 }
 
 // flags (sparse_flag_bytes(P), zero beyond P) -> rows[0 .. *d_total) ascending; chunk_ws: sparse_flag_chunks(P) x u32

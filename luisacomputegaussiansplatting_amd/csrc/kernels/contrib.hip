@@ -17,6 +17,7 @@
 //                      for the rewrite, its emit count.
 // The max and the counts do not depend on the order of the atomics; the sum is a binary32 sum of non-negative terms in an order
 // that differs from run to run.
+#include "kept_rows.hpp"
 #include "kept_walk.hpp"
 
 namespace lcgs
@@ -123,9 +124,9 @@ __global__ void __launch_bounds__(256) k_contrib_classify(int64_t P, ContribRule
 
 size_t contrib_slab_bytes(int64_t rows) { return (size_t)std::max<int64_t>(rows, 1) * kSlot * sizeof(uint32_t); }
 
-void launch_contrib_zero(int64_t v_hint, const uint32_t* d_counts, uint32_t* slab, hipStream_t stream)
+void launch_contrib_zero(const KeptRows& r, uint32_t* slab, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_contrib_zero, dim3(grid_256(std::max<int64_t>(v_hint, 1) * kSlot)), dim3(256), 0, stream, d_counts, slab);
+    hipLaunchKernelGGL(k_contrib_zero, dim3(grid_256(r.hint * kSlot)), dim3(256), 0, stream, r.d_counts, slab);
 }
 
 void launch_contrib_walk(const KeptFrame& f, uint32_t* slab, hipStream_t stream)
@@ -134,11 +135,11 @@ void launch_contrib_walk(const KeptFrame& f, uint32_t* slab, hipStream_t stream)
     hipLaunchKernelGGL(k_contrib_walk, dim3(maps_grid(f.cp, f.tile_order)), dim3(256), 0, stream, f, slab);
 }
 
-void launch_contrib_fold(int64_t v_hint, int64_t P, const uint32_t* vis_index, const uint32_t* d_counts, const uint32_t* slab,
-                         float* weight_sum, float* weight_max, uint32_t* pixels, uint32_t* views, hipStream_t stream)
+void launch_contrib_fold(const KeptRows& r, const uint32_t* slab, float* weight_sum, float* weight_max, uint32_t* pixels,
+                         uint32_t* views, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_contrib_fold, dim3(grid_256(std::max<int64_t>(v_hint, 1))), dim3(256), 0, stream, vis_index, d_counts, P,
-                       slab, weight_sum, weight_max, pixels, views);
+    hipLaunchKernelGGL(k_contrib_fold, dim3(grid_256(r.hint)), dim3(256), 0, stream, r.vis_index, r.d_counts, r.P, slab, weight_sum,
+                       weight_max, pixels, views);
 }
 
 void launch_contrib_classify(int64_t P, const ContribRule& rule, const float* weight_sum, const float* weight_max,

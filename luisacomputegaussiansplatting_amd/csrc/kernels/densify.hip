@@ -11,6 +11,7 @@
 // loads of the source, destination offsets monotone in the source index (coalesced stores), the zero moments of new rows
 // written here instead of by a memset over the whole array.  64-bit element indices throughout.
 #include "activations.hpp" // train.hip's exact expression sequences (the values equal what an Adam step writes)
+#include "kept_rows.hpp"
 #include "launch.hpp"
 #include "philox.hpp"
 #include "stream_access.hpp"
@@ -215,12 +216,10 @@ void launch_rows(int64_t P, const uint8_t* action, const uint32_t* incl, const f
 
 } // namespace
 
-void launch_densify_stats(int64_t v_hint, int64_t P, const CamParams& cp, float scale_modifier, const float* pos,
-                          const float* scale, const float* rotq, const uint32_t* vis_index, const uint32_t* d_counts,
-                          const float* grads2d, float* grad_accum, uint32_t* denom, int32_t* max_radii, hipStream_t stream)
+void launch_densify_stats(const KeptRows& r, float* grad_accum, uint32_t* denom, int32_t* max_radii, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_densify_stats, dim3(grid_256(std::max<int64_t>(v_hint, 1))), dim3(256), 0, stream, vis_index, d_counts,
-                       P, cp, scale_modifier, pos, scale, rotq, grads2d, grad_accum, denom, max_radii);
+    hipLaunchKernelGGL(k_densify_stats, dim3(grid_256(r.hint)), dim3(256), 0, stream, r.vis_index, r.d_counts, r.P, r.cp,
+                       r.scale_modifier, r.pos, r.scale, r.rotq, r.grads2d, grad_accum, denom, max_radii);
 }
 
 void launch_densify_classify(int64_t P, const DensifyRule& rule, const float* raw_scale, const float* raw_opacity,

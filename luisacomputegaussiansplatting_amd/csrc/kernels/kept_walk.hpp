@@ -11,7 +11,8 @@
 
 namespace lcgs
 {
-// the last keep-state frame as the walks read it (final_T: the backwards only; strip_masks NULL: every entry is fetched)
+// the last keep-state frame as the walks read it (final_T: the backwards only; strip_masks NULL: every entry is fetched);
+// kept_rows.hpp has the counterpart for the passes with one lane per on-screen row
 struct KeptFrame {
     CamParams          cp;
     const uint32_t*    ranges;

@@ -9,6 +9,8 @@
 
 namespace lcgs
 {
+struct KeptFrame; // kept_walk.hpp: what a walk of the last keep-state frame's kept lists reads
+struct KeptRows;  // kept_rows.hpp: what a pass with one lane per on-screen row of a kept frame reads
 
 // workgroups of 256 lanes for `elements` items: one item per lane, at least one workgroup, at most 65536 (kernels stride beyond)
 inline unsigned grid_256(int64_t elements)
@@ -215,11 +217,9 @@ void launch_adam_step(int64_t P, int sh_floats, const uint32_t* row_list, const 
                       const AdamArrays& act, const AdamRates& lr, float beta1, float beta2, float eps, int step,
                       hipStream_t stream, bool grad_compact = false);
 // ---- densify.hip : adaptive density control (statistics of a step, the clone / split / prune rewrite, opacity reset) ----
-// one thread per on-screen row of the last keep-state frame (count in d_counts[0], launch sized for v_hint rows): the
-// screen-space positional gradient (grads2d rows, pixel units -> NDC), the visit count and the largest reference radius
-void launch_densify_stats(int64_t v_hint, int64_t P, const CamParams& cp, float scale_modifier, const float* pos,
-                          const float* scale, const float* rotq, const uint32_t* vis_index, const uint32_t* d_counts,
-                          const float* grads2d, float* grad_accum, uint32_t* denom, int32_t* max_radii, hipStream_t stream);
+// one thread per on-screen row of the last keep-state frame (KeptRows, kept_rows.hpp): the screen-space positional gradient
+// (grads2d rows, pixel units -> NDC), the visit count and the largest reference radius
+void launch_densify_stats(const KeptRows& r, float* grad_accum, uint32_t* denom, int32_t* max_radii, hipStream_t stream);
 struct DensifyRule {
     float   grad_threshold, dense_extent /* percent_dense x scene_extent */, huge_extent /* 0.1 x scene_extent */, min_opacity;
     int32_t max_screen_size;
@@ -292,12 +292,9 @@ void launch_photometric_finish(int W, int H, const double* partials, float lambd
                                hipStream_t stream);
 // backward.hip: the per-splat half of the backward with the on-screen-only Adam update applied where the gradients are
 // formed (degree 3, frames that kept the colour Jacobian): no gradient rows are written at all
-void launch_preprocess_backward_adam(int64_t v_hint, const CamParams& cp, float scale_modifier, const float* pos,
-                                     const float* scale, const float* rotq, const float* opacity /* read for an antialiased frame */,
-                                     const uint32_t* vis_index, const uint32_t* d_counts,
-                                     const float* grads2d, const float4* shjac, const AdamArrays& raw, const AdamArrays& m,
-                                     const AdamArrays& v, const AdamArrays& act, const AdamRates& lr, const AdamStep& a,
-                                     hipStream_t stream);
+// (r.shjac is not NULL; r.opacity is read for an antialiased frame, before the lane's update of the activated row)
+void launch_preprocess_backward_adam(const KeptRows& r, const AdamArrays& raw, const AdamArrays& m, const AdamArrays& v,
+                                     const AdamArrays& act, const AdamRates& lr, const AdamStep& a, hipStream_t stream);
 // byte offsets, inside one vertex record, of the 59 wanted float columns (pos3 dc3 rest45 opacity scale3 rot4)
 struct PlyColumns {
     uint32_t offset[59];
@@ -360,8 +357,7 @@ void launch_unpack_f16(const uint16_t* in, size_t n, const float* d_inv, float* 
 // comm_sparse.hip: the sparse gradient exchange (touched-row flags -> ascending row list -> per-owner messages)
 size_t   sparse_flag_bytes(int64_t P);
 uint32_t sparse_flag_chunks(int64_t P);
-void     launch_mark_rows(const uint32_t* vis_index, const uint32_t* d_counts, uint8_t* flags, int64_t P, int64_t hint_V,
-                          hipStream_t stream);
+void     launch_mark_rows(const KeptRows& r, uint8_t* flags, hipStream_t stream); // flags[r.vis_index[row]] = 1, rows < r.P
 void     launch_compact_flags(const uint8_t* flags, int64_t P, uint32_t* chunk_ws, uint32_t* rows, uint32_t* d_total,
                               hipStream_t stream, const uint32_t* copy_src = nullptr, uint32_t* copy_dst = nullptr,
                               const uint32_t* box_word0 = nullptr, uint32_t* host_box = nullptr, uint32_t serial = 0);
@@ -387,28 +383,24 @@ struct DenseFill {
     float *b0 = nullptr, *b1 = nullptr, *b2 = nullptr, *b3 = nullptr, *b4 = nullptr;
     uint32_t n[5] = { 0, 0, 0, 0, 0 };
 };
-struct KeptFrame; // kept_walk.hpp: what a walk of the last keep-state frame's kept lists reads
 void   launch_render_backward(const KeptFrame& f, const float bg[3], const float* dL_dimg, float* grads2d, hipStream_t stream,
                               uint32_t* work_counter = nullptr, uint32_t persistent_wgs = 0, const DenseFill* fill = nullptr);
-void   launch_preprocess_backward(int64_t v_hint, int sh_deg, const CamParams& cp, float scale_modifier, const float* pos,
-                                  const float* scale, const float* rotq, const float* sh, const uint32_t* vis_index,
-                                  const uint32_t* d_counts, const float* grads2d, float* dL_dpos, float* dL_dscale,
-                                  float* dL_drotq, float* dL_dsh, float* dL_dopacity, hipStream_t stream,
-                                  const float4* shjac = nullptr, // the forward's colour Jacobian rows, if kept
-                                  // compact: output row r belongs to the frame's r-th on-screen splat (dense id r,
-                                  // splat vis_index[r], ascending) instead of row = splat index: consecutive rows, every
-                                  // one written -- no zero-fill, no 39 %-dense store pattern
-                                  bool compact = false,
-                                  // slice_bounds != NULL: only the survivors [slice_bounds[slice], slice_bounds[slice + 1])
-                                  // (a splat-range slice, see launch_slice_bounds; `slices` sizes the launch)
-                                  const uint32_t* slice_bounds = nullptr, int slice = 0, int slices = 1,
-                                  // accumulate: ADD the rows to what the arrays hold (dense rows of a further view)
-                                  bool accumulate = false,
-                                  // the scene's opacity rows: read only for a row of an antialiased frame (cp.raster_mode)
-                                  const float* opacity = nullptr);
+// The per-splat pass of the rows r (kept_rows.hpp; r.shjac: the forward's colour Jacobian rows, if kept; r.opacity: read only
+// for a row of an antialiased frame, r.cp.raster_mode) into the five gradient arrays, laid out as `out` says:
+struct RowsOut {
+    // compact: output row k belongs to the frame's k-th on-screen splat (dense id k, splat vis_index[k], ascending) instead of
+    // row = splat index: consecutive rows, every one written -- no zero-fill, no 39 %-dense store pattern
+    // accumulate: ADD the rows to what the arrays hold (dense rows of a further view)
+    bool compact, accumulate;
+    // slice_bounds != NULL: only the survivors [slice_bounds[slice], slice_bounds[slice + 1]) (a splat-range slice, see
+    // launch_slice_bounds; `slices` sizes the launch).  NULL: all of them (slice 0 of 1)
+    const uint32_t* slice_bounds;
+    int             slice, slices;
+};
+void   launch_preprocess_backward(const KeptRows& r, float* dL_dpos, float* dL_dscale, float* dL_drotq, float* dL_dsh,
+                                  float* dL_dopacity, const RowsOut& out, hipStream_t stream);
 // bounds[0 .. slices]: dense-id boundaries of the splat-index ranges [k P / slices, (k + 1) P / slices), k < slices <= 63
-void   launch_slice_bounds(const uint32_t* vis_index, const uint32_t* d_counts, int64_t P, int slices, uint32_t* bounds,
-                           hipStream_t stream);
+void   launch_slice_bounds(const KeptRows& r, int slices, uint32_t* bounds, hipStream_t stream);
 
 // ---- maps.hip : depth and alpha maps of the last keep-state frame and their backward ----
 constexpr int kDepthZ = 0, kDepthInvZ = 1; // = LCGS_DEPTH_Z, LCGS_DEPTH_INV_Z: a splat's value is its view z, or 1 / z
@@ -422,19 +414,18 @@ void launch_render_distortion(const KeptFrame& f, int mode, float center, float*
 void launch_render_maps_backward(const KeptFrame& f, int mode, const float* dL_ddepth, const float* dL_dalpha, float* grads2d,
                                  hipStream_t stream, float center = 0.0f, const float* dL_ddist = nullptr);
 // one lane per on-screen row: dL_dpos[row] += grads2d slot kG2DValueSlot x dvalue/dz x front (behind the preprocess-backward)
-void launch_maps_depth_to_pos(int64_t v_hint, const CamParams& cp, const uint32_t* vis_index, const uint32_t* d_counts,
-                              const SplatRecord* recs, const float* grads2d, int mode, float* dL_dpos, hipStream_t stream);
+void launch_maps_depth_to_pos(const KeptRows& r, int mode, float* dL_dpos, hipStream_t stream);
 
 // ---- contrib.hip : per-splat blend-weight statistics of the last keep-state frame, and the keep / drop rule ----
 // the context-owned slab: {sum, max bits, count} per on-screen row, indexed by the lists' on-screen indices
 size_t contrib_slab_bytes(int64_t rows);
-// clears the slots of the frame's on-screen rows (count in d_counts[0], launch sized for v_hint rows)
-void launch_contrib_zero(int64_t v_hint, const uint32_t* d_counts, uint32_t* slab, hipStream_t stream);
+// clears the slots of the frame's on-screen rows
+void launch_contrib_zero(const KeptRows& r, uint32_t* slab, hipStream_t stream);
 // the walk of launch_render_maps, every entry reduced over the pixels that blend it; ATOMICALLY adds to the slab
 void launch_contrib_walk(const KeptFrame& f, uint32_t* slab, hipStream_t stream);
 // one lane per on-screen row: slots with a count fold into the caller's arrays at vis_index[row] (any of the four may be NULL)
-void launch_contrib_fold(int64_t v_hint, int64_t P, const uint32_t* vis_index, const uint32_t* d_counts, const uint32_t* slab,
-                         float* weight_sum, float* weight_max, uint32_t* pixels, uint32_t* views, hipStream_t stream);
+void launch_contrib_fold(const KeptRows& r, const uint32_t* slab, float* weight_sum, float* weight_max, uint32_t* pixels,
+                         uint32_t* views, hipStream_t stream);
 struct ContribRule { // a row is kept iff every enabled (non-zero) minimum is met
     float    min_weight_max, min_weight_sum;
     uint64_t min_pixels, min_views;
@@ -446,13 +437,9 @@ void launch_contrib_classify(int64_t P, const ContribRule& rule, const float* we
 // ---- camera_grad.hip : the camera gradient of the last backward, from the 2-D rows it left ----
 // the context-owned slab: twelve doubles per block of 256 on-screen rows
 size_t camera_grad_slab_bytes(int64_t P);
-// dL_dcam: 12 floats (position, front, up, right), overwritten.  shjac: the kept colour Jacobian or NULL (then the direction
-// part comes from the sh rows); depth_mode: the depth mode of the backward that wrote grads2d slot kG2DValueSlot, -1: none.
+// dL_dcam: 12 floats (position, front, up, right), overwritten.  r.shjac NULL: the direction part comes from the sh rows;
+// depth_mode: the depth mode of the backward that wrote grads2d slot kG2DValueSlot, -1: none.
 // Two launches (per-block sums, then one workgroup that adds them in a fixed order); no atomics
-void launch_camera_grad(int64_t v_hint, int sh_deg, const CamParams& cp, float scale_modifier, const float* pos, const float* scale,
-                        const float* rotq, const float* sh, const uint32_t* vis_index, const uint32_t* d_counts,
-                        const float* grads2d, const float4* shjac, const SplatRecord* recs, int depth_mode, double* slab,
-                        float* dL_dcam, hipStream_t stream,
-                        const float* opacity = nullptr); // the scene's opacity rows: read only for an antialiased frame (cp.raster_mode)
+void launch_camera_grad(const KeptRows& r, int depth_mode, double* slab, float* dL_dcam, hipStream_t stream);
 
 } // namespace lcgs

@@ -26,6 +26,7 @@
 //                           two-channel kernel, operation for operation.
 //   k_maps_depth_to_pos     one lane per on-screen row: dL/dpos += slot 9 x dv/dz x front.
 // Thresholds are constants for the derivative, exactly as in backward.hip: the 0.99 cap passes nothing, a saturated pixel stops.
+#include "kept_rows.hpp"
 #include "kept_walk.hpp"
 
 namespace lcgs
@@ -243,11 +244,10 @@ void launch_render_maps_backward(const KeptFrame& f, int mode, const float* dL_d
                            nullptr, grads2d);
 }
 
-void launch_maps_depth_to_pos(int64_t v_hint, const CamParams& cp, const uint32_t* vis_index, const uint32_t* d_counts,
-                              const SplatRecord* recs, const float* grads2d, int mode, float* dL_dpos, hipStream_t stream)
+void launch_maps_depth_to_pos(const KeptRows& r, int mode, float* dL_dpos, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_maps_depth_to_pos, dim3(grid_256(v_hint)), dim3(256), 0, stream, cp, vis_index, d_counts, recs,
-                       grads2d, mode, dL_dpos);
+    hipLaunchKernelGGL(k_maps_depth_to_pos, dim3(grid_256(r.hint)), dim3(256), 0, stream, r.cp, r.vis_index, r.d_counts, r.recs,
+                       r.grads2d, mode, dL_dpos);
 }
 
 } // namespace lcgs

@@ -179,6 +179,37 @@ __device__ __forceinline__ SplatOperands load_splat_operands(uint32_t vsafe, int
     return in;
 }
 
+// ---- what the per-row kernels (backward.hip's three preprocess passes, camera_grad.hip) share around those expressions
+// One lane's place in block `blk` (256 rows) of a pass over the survivors [v0, V): its dense id (lanes past V take the last
+// survivor's operands through vsafe and discard the result), its splat, and its wave's first dense id and number of live rows
+struct RowBlock {
+    uint32_t vid, vsafe, wave_first, nvalid;
+    bool     valid;
+    int      idx;
+};
+__device__ __forceinline__ RowBlock row_block(uint32_t v0, uint32_t V, uint32_t blk, const uint32_t* vis_index)
+{
+    RowBlock b;
+    b.vid        = v0 + blk * 256u + threadIdx.x;
+    b.valid      = b.vid < V;
+    b.vsafe      = b.valid ? b.vid : V - 1;
+    b.idx        = (int)vis_index[b.vsafe];
+    b.wave_first = v0 + blk * 256u + (threadIdx.x >> 6) * 64u;
+    b.nvalid     = b.wave_first < V ? ((V - b.wave_first) < 64u ? (V - b.wave_first) : 64u) : 0u;
+    return b;
+}
+// "12 consecutive lanes own one splat's 192 bytes": step i (of 12) of a wave's pass over the 12 float4 of each of its 64 rows.
+// body(slot, part, sidx) runs on the lanes of live rows: slot = the row inside the wave, part = its float4, sidx = its splat.
+// (The loop over i and its unrolling are the caller's, and so is how the body captures: these kernels' register allocation
+// follows such details, and each use is held to the registers its own copy of the loop had.)
+template <class Body>
+__device__ __forceinline__ void row_part_step(const RowBlock& b, int lane, int i, Body body)
+{
+    const uint32_t c    = (uint32_t)i * 64u + lane;
+    const uint32_t slot = c / 12u, part = c - slot * 12u;
+    const int      sidx = __shfl(b.idx, (int)slot, 64);
+    if (slot < b.nvalid) body(slot, part, sidx);
+}
 // A footprint beyond this (trace of the 2-D covariance, px^2: radius ~ 3 sqrt(lambda_max) > 64 px) takes the algebra in f64.
 constexpr float kGiantCovTrace = 455.0f;
 // (Both precisions are inlined: the kernels' register count doubles and their occupancy halves -- preprocess-backward
