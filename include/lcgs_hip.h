@@ -170,8 +170,9 @@ LCGS_API lcgs_status lcgs_set_lod(lcgs_context* ctx, int min_radius_px);
  * position / scale / rotation / camera gradients carry d rho.  lcgs_fit_views and batches follow the context's mode.
  * NOT offered: the stage-level operators (lcgs_sh_process / lcgs_project_forward / lcgs_tile_splat_forward, deferred mode
  * included) and the ownership step (lcgs_owner_*, lcgs_owner_step_*) ignore the mode and render and differentiate the classic
- * frame consistently; Mip-Splatting's 3-D smoothing filter (it needs per-splat sampling rates over the training views); a
- * per-call mode argument.  Any other value: LCGS_ERR_INVALID_ARG. */
+ * frame consistently; a per-call mode argument.  (The other half of that paper, the 3-D smoothing filter, is a set of calls of
+ * its own that work on the caller's arrays in front of the frame: lcgs_filter3d_accumulate / _finalize / _apply / _backward.)
+ * Any other value: LCGS_ERR_INVALID_ARG. */
 #define LCGS_RASTER_CLASSIC     0   /* default: the reference's frame, unchanged */
 #define LCGS_RASTER_ANTIALIASED 1
 LCGS_API lcgs_status lcgs_set_raster_mode(lcgs_context* ctx, int mode);
@@ -548,6 +549,61 @@ LCGS_API lcgs_status lcgs_mcmc_noise(lcgs_context* ctx, int num_gaussians, const
  * are not indexed by splat and must not be passed.  Only the opacity and scale members are read.  Only enqueues. */
 LCGS_API lcgs_status lcgs_mcmc_regularize(lcgs_context* ctx, int num_gaussians, float lambda_opacity, float lambda_scale,
                                           const lcgs_grads* grads);
+
+/* ---- Mip-Splatting's 3-D smoothing filter (Yu et al., CVPR 2024; no reference counterpart) -------------------- */
+/* The 2-D filter (lcgs_set_raster_mode) fixes zoom-out aliasing; this one stops zoom-in erosion: every splat's size is bounded
+ * from below by the highest rate at which any training view sampled it.  Four calls on CALLER-OWNED arrays in the caller's row
+ * order (device pointers; the bound scene is not read), all of which only enqueue on the context's stream.  Arithmetic: binary32,
+ * round to nearest, nothing contracted, IEEE division and square root; u = 2^-24 below.
+ *
+ * Training recipe.  (1) Start d_min_z at +inf and max_focal at 0, lcgs_filter3d_accumulate over ALL training views (any number of
+ * calls), lcgs_filter3d_finalize -> d_filter; repeat after every density-control rewrite (Mip-Splatting: every 100 iterations).
+ * Between recomputations a rewritten scene gathers d_filter through the rewrite's d_src_row.  (2) After every optimiser step,
+ * lcgs_filter3d_apply from the optimiser's activated scale / opacity into the arrays bound with lcgs_scene_bind: the frames render
+ * the filtered scene.  (3) Between the render backward and lcgs_adam_step, lcgs_filter3d_backward turns the gradients with respect
+ * to the filtered values into gradients with respect to the activated ones.  (4) A baked export writes log(scale_out) and
+ * logit(opacity_out) through lcgs_ply_write_raw.
+ * NOT offered: the filter inside lcgs_render_backward_adam (the fused step goes straight to the raw values); the filter inside
+ * lcgs_fit_views or the ownership step (lcgs_owner_step_*); a filter_3D PLY property; an lcgs-app flag.
+ *
+ * lcgs_filter3d_accumulate.  d_min_z [P] in/out: the caller starts it at +inf, which means "no view has seen the row";
+ * *max_focal (host) in/out: the caller starts it at 0.  For every view, cp = the frame's camera constants and
+ * v = (right . p + tx, up . p + ty, front . p + tz), each ((a0 p0 + a1 p1) + a2 p2) + t -- the frame's view transform.  The row is
+ * SEEN by the view iff  v.z > 0.2f  and  |v.x| <= (1.3f * tanfovx) * v.z  and  |v.y| <= (1.3f * tanfovy) * v.z  (Mip-Splatting's
+ * compute_3D_filter: depth beyond 0.2 and inside the screen with a 15 % margin, -0.15 W <= x_pix <= 1.15 W, stated in the tangent
+ * plane with the limit the projector clamps to); for a seen row min_z = min(min_z, v.z).  A NaN fails every comparison: such a row
+ * is never seen.  *max_focal = max(*max_focal, W / (2 tanfovx)) over the views, on the host (also when num_gaussians is 0).
+ * cameras: host array.  Reads nothing back.  Two calls with the views split between them leave what one call with all leaves. */
+LCGS_API lcgs_status lcgs_filter3d_accumulate(lcgs_context* ctx, int num_gaussians, const float* d_pos, int num_views,
+                                              const lcgs_camera* cameras, float* d_min_z, float* max_focal);
+/* d_filter[i] = ((isfinite(d_min_z[i]) ? d_min_z[i] : zmax) / max_focal) * c, zmax = the largest finite entry of d_min_z (a row
+ * no view saw gets the coarsest rate of the scene), c = the binary32 nearest to sqrt(0.2) -- Mip-Splatting's filter_3D.  No finite
+ * entry: every d_filter[i] = 0, the identity filter.  zmax is found on the device (no read-back); bit-exact whatever the order. */
+LCGS_API lcgs_status lcgs_filter3d_finalize(lcgs_context* ctx, int num_gaussians, const float* d_min_z, float max_focal, float* d_filter);
+/* Mip-Splatting's get_scaling_with_3D_filter / get_opacity_with_3D_filter from ACTIVATED d_scale [P][3] / d_opacity [P].  Per row,
+ * f = d_filter[i]: f == 0 copies the row bit for bit; otherwise f2 = f f, a_k = s_k s_k, b_k = a_k + f2,
+ *   scale_out_k = sqrt(b_k),  r_k = a_k / b_k,  coef = sqrt((r_0 r_1) r_2),  opacity_out = opacity * coef.
+ * The determinant ratio det(S^2) / det(S^2 + f2 I) is taken as a product of three ratios in [0, 1]: it cannot underflow where
+ * prod(s^2) does (scales of 1e-8).  Against exact arithmetic: scale_out within 3 u, opacity_out within 8 u, relative.
+ * Out of place: an output that overlaps an input or the other output is LCGS_ERR_INVALID_ARG.  A context whose bound scene is
+ * d_scale_out rebuilds its derived rows, as after the library's other writers. */
+LCGS_API lcgs_status lcgs_filter3d_apply(lcgs_context* ctx, int num_gaussians, const float* d_scale, const float* d_opacity,
+                                         const float* d_filter, float* d_scale_out, float* d_opacity_out);
+/* In place: d_dL_dscale / d_dL_dopacity arrive as the gradients with respect to scale_out / opacity_out and leave as those with
+ * respect to d_scale / d_opacity (what lcgs_adam_step takes).  f == 0: the row is untouched.  Otherwise, with the forward's coef,
+ * b_k and sf_k = scale_out_k re-derived from d_scale / d_filter:
+ *   g_op'  = g_op * coef
+ *   g_s_k' = g_s_k * (s_k / sf_k) + (((g_op * opacity) * coef) * f2) / (s_k * b_k)
+ * within 8 u relative and 16 u (|first term| + |second term|) of exact arithmetic.  d_rows NULL (with d_count): dense rows.
+ * Otherwise gradient row r < *d_count (device) belongs to row d_rows[r] of d_scale / d_opacity / d_filter -- the layout of
+ * lcgs_render_backward_compact with lcgs_visible_rows; rows beyond the count are untouched, the launch is sized by num_gaussians.
+ *
+ * All four: LCGS_ERR_INVALID_ARG before any device work for a NULL context or array, a negative count, num_views > 0 with NULL
+ * cameras, exactly one of d_rows / d_count NULL, max_focal not finite or <= 0.  num_gaussians == 0 or num_views == 0: LCGS_OK,
+ * no array touched (*max_focal untouched for 0 views). */
+LCGS_API lcgs_status lcgs_filter3d_backward(lcgs_context* ctx, int num_gaussians, const float* d_scale, const float* d_opacity,
+                                            const float* d_filter, const uint32_t* d_rows, const uint32_t* d_count,
+                                            float* d_dL_dscale, float* d_dL_dopacity);
 
 /* ---- a scene from a point cloud (no reference counterpart: app/gaussians.cpp only loads trained PLYs) -------- */
 /* The mean squared distance to the three nearest neighbours, of n points p_i (binary32, AoS xyz xyz ...):

@@ -33,6 +33,7 @@ from .api import (  # noqa: F401
     build_library,
     camera_grad_to_twist,
     camera_with_vectors,
+    filter3d_autograd,
     get_lookat_cam,
     image_to_rgb8,
     knn_mean_dist2,

@@ -54,6 +54,7 @@ LCGS_ERR_STATE = 8
 DEPTH_Z, DEPTH_INV_Z = 0, 1  # LCGS_DEPTH_Z, LCGS_DEPTH_INV_Z
 _DEPTH_MODES = {"z": DEPTH_Z, "inv_z": DEPTH_INV_Z}
 LCGS_KNN_CHUNK = 256  # sorted points per query workgroup of the nearest-neighbour search (sizes around its multiples are edge cases)
+LCGS_FILTER3D_VIEW_CHUNK = 64  # kFilter3dViewChunk: views per launch of filter3d_accumulate (view counts around its multiples are edge cases)
 # lcgs_set_fit_loss kinds (LCGS_LOSS_* in include/lcgs_hip.h)
 LOSS_L2, LOSS_PHOTOMETRIC = 0, 1
 # lcgs_set_raster_mode modes (LCGS_RASTER_* in include/lcgs_hip.h)
@@ -308,6 +309,11 @@ def _signatures() -> dict:
         "lcgs_mcmc_add": (st, [p, i, i, ptr["mcmc_config"], *packs, i64, i64, p, p]),
         "lcgs_mcmc_noise": (st, [p, i, ptr["mcmc_noise_config"], *packs[:2], p]),
         "lcgs_mcmc_regularize": (st, [p, i, f, f, grads]),
+        # Mip-Splatting's 3-D smoothing filter
+        "lcgs_filter3d_accumulate": (st, [p, i, p, i, cam, p, p]),
+        "lcgs_filter3d_finalize": (st, [p, i, p, f, p]),
+        "lcgs_filter3d_apply": (st, [p, i, p, p, p, p, p]),
+        "lcgs_filter3d_backward": (st, [p, i, p, p, p, p, p, p, p]),
         # a scene from a point cloud
         "lcgs_knn_mean_dist2": (st, [p, i64, p, p]),
         "lcgs_scene_init_from_points": (st, [p, i, i, p, p, ptr["init_config"], *packs[:2]]),
@@ -1141,6 +1147,39 @@ class Renderer:
         g = _Grads(None, _ptr(grads["scale"]), None, None, _ptr(grads["opacity"]))
         _check(load_library().lcgs_mcmc_regularize(self.ctx._h, P, lambda_opacity, lambda_scale, C.byref(g)))
 
+    # ---- Mip-Splatting's 3-D smoothing filter
+    def filter3d_accumulate(self, pos, cams, min_z, max_focal: float = 0.0) -> float:
+        """lcgs_filter3d_accumulate: min_z[i] = min(min_z[i], view depth of row i) over the views of `cams` (a sequence of Camera)
+        that see the row -- depth > 0.2 and inside 1.3 x the view's frustum, Mip-Splatting's rule.  pos [P, 3] and min_z [P]
+        (start it at +inf) are device tensors; returns max(max_focal, the views' focal lengths in pixels) for the next call /
+        filter3d_finalize.  Only enqueues."""
+        cams = list(cams)
+        arr = (Camera * len(cams))(*cams) if cams else None
+        focal = C.c_float(max_focal)
+        _check(load_library().lcgs_filter3d_accumulate(self.ctx._h, int(min_z.shape[0]), _ptr(pos), len(cams), arr, _ptr(min_z),
+                                                       C.byref(focal)))
+        return float(focal.value)
+
+    def filter3d_finalize(self, min_z, max_focal: float, filt):
+        """lcgs_filter3d_finalize: filt[i] = (min_z[i] / max_focal) * sqrt(0.2), a row no view saw taking the largest finite
+        min_z; all zeros (the identity filter) when no row was seen.  Only enqueues, no read-back."""
+        _check(load_library().lcgs_filter3d_finalize(self.ctx._h, int(min_z.shape[0]), _ptr(min_z), max_focal, _ptr(filt)))
+
+    def filter3d_apply(self, scale, opacity, filt, scale_out, opacity_out):
+        """lcgs_filter3d_apply: scale_out = sqrt(scale^2 + filt^2), opacity_out = opacity * sqrt(prod_k scale_k^2 / (scale_k^2 +
+        filt^2)) from ACTIVATED scale [P, 3] / opacity [P]; rows with filt == 0 are copied.  Out of place (aliased outputs are
+        refused); a context bound to scale_out rebuilds its derived rows.  Only enqueues."""
+        _check(load_library().lcgs_filter3d_apply(self.ctx._h, int(opacity.shape[0]), _ptr(scale), _ptr(opacity), _ptr(filt),
+                                                  _ptr(scale_out), _ptr(opacity_out)))
+
+    def filter3d_backward(self, scale, opacity, filt, dscale, dopacity, rows=None, count=None):
+        """lcgs_filter3d_backward: dscale / dopacity, gradients w.r.t. the FILTERED scale and opacity, become gradients w.r.t. the
+        unfiltered activated values (what adam_step takes), in place.  rows / count (device int32 tensors or addresses, as
+        lcgs_visible_rows gives them): gradient row r < count[0] belongs to row rows[r] -- the compact rows of
+        backward(compact=True); None: dense rows.  Only enqueues."""
+        _check(load_library().lcgs_filter3d_backward(self.ctx._h, int(opacity.shape[0]), _ptr(scale), _ptr(opacity), _ptr(filt),
+                                                     _ptr(rows), _ptr(count), _ptr(dscale), _ptr(dopacity)))
+
 
     # ---- a scene from a point cloud (DESIGN.md 9)
     def init_from_points(self, pos, rgb, sh_degree: int = 3, initial_opacity: float = 0.1, min_dist2: float = 1e-7):
@@ -1503,6 +1542,35 @@ def render_autograd_distortion(renderer: "Renderer", cam: Camera, pos, scale, ro
     the loss does not use arrives as None (or zero-shaped) and is passed as NULL.  Like render_autograd it re-renders its own
     view when the renderer's generation has moved."""
     return _autograd_frame(renderer, cam, (pos, scale, rotq, sh, opacity), bg, scale_modifier, "distortion", depth_mode, center)
+
+
+def filter3d_autograd(renderer: "Renderer", scale, opacity, filt):
+    """Differentiable 3-D smoothing filter for torch: `scale_f, opacity_f = filter3d_autograd(r, scale, opacity, filt)` from
+    ACTIVATED scale [P, 3] and opacity [P] and the per-splat filter of Renderer.filter3d_finalize (a constant: no gradient).
+    Forward is lcgs_filter3d_apply into fresh tensors, backward lcgs_filter3d_backward on dense rows.  Composes with the
+    frames: `render_autograd(r, cam, pos, scale_f, rotq, sh, opacity_f)`."""
+    import torch
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, scale, opacity, filt):
+            args = [t.detach().contiguous() for t in (scale, opacity, filt)]
+            scale_f, opacity_f = torch.empty_like(args[0]), torch.empty_like(args[1])
+            renderer.filter3d_apply(*args, scale_f, opacity_f)
+            ctx.save_for_backward(*args)
+            ctx.shapes = (scale.shape, opacity.shape)
+            return scale_f, opacity_f
+
+        @staticmethod
+        def backward(ctx, g_scale, g_opacity):
+            args = ctx.saved_tensors
+            # (the call works in place: on copies, the incoming gradients are autograd's)
+            g_scale = torch.zeros_like(args[0]) if g_scale is None else g_scale.contiguous().clone()
+            g_opacity = torch.zeros_like(args[1]) if g_opacity is None else g_opacity.contiguous().clone()
+            renderer.filter3d_backward(*args, g_scale, g_opacity)
+            return g_scale.view(ctx.shapes[0]), g_opacity.view(ctx.shapes[1]), None
+
+    return _Fn.apply(scale, opacity, filt)
 
 
 CAM12_FIELDS = ("position", "front", "up", "right")  # the camera gradient's order: Camera's first four members

@@ -197,6 +197,8 @@ struct lcgs_context {
     // the weights and the draws that landed on the row; per draw the dead row it fills and its source; the u64 scan's block
     // sums; one status word (kernels/launch.hpp launch_mcmc_draw)
     DeviceBuffer mc_w, mc_dead, mc_dead_incl, mc_cdf, mc_count, mc_dead_list, mc_draw, mc_scan_temp, mc_status;
+    // lcgs_filter3d_finalize (abi_filter3d.cpp): the word its reduction leaves the largest finite min_z in
+    DeviceBuffer f3_word;
     // lcgs_knn_mean_dist2 / lcgs_scene_init_from_points (abi_init.cpp): Morton keys and original indices (the sort's ping-pong),
     // the sort's workspace, the sorted points, the per-chunk boxes, the box partials + grid, the init call's dist2
     DeviceBuffer knn_keys[2], knn_vals[2], knn_sort_ws, knn_sorted, knn_boxes, knn_grid, knn_dist2;

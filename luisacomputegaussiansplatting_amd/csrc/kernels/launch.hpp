@@ -276,6 +276,27 @@ void launch_mcmc_noise(int64_t P, float gain, float k, float x0, const float* ra
                        hipStream_t stream);
 // d_opacity[i] += add_opacity, d_scale[i][c] += add_scale
 void launch_mcmc_regularize(int64_t P, float add_opacity, float add_scale, float* d_opacity, float* d_scale, hipStream_t stream);
+// ---- filter3d.hip : Mip-Splatting's 3-D smoothing filter (sampling rates over the training views, apply, backward) ----
+constexpr int kFilter3dViewChunk = 64; // views per launch of the accumulate pass: its table travels in the kernel's arguments
+struct Filter3dView {                  // what the pass reads of a view: gs_math.hpp view_transform's rows, cam_clamp's limits
+    float right[3], tx, up[3], ty, front[3], tz;
+    float limx, limy; // 1.3f * tanfovx, 1.3f * tanfovy
+};
+struct Filter3dViews {
+    Filter3dView v[kFilter3dViewChunk];
+};
+static_assert(sizeof(Filter3dViews) <= 3840, "the table and the pass's other arguments must fit the 4 KiB of kernel arguments");
+// min_z[i] = min(min_z[i], view z of row i) over the first num_views (<= kFilter3dViewChunk) views that see the row
+void launch_filter3d_accumulate(int64_t P, const float* pos, int num_views, const Filter3dViews& views, float* min_z,
+                                hipStream_t stream);
+// word (one u32, zeroed by the caller on the stream): receives the largest finite min_z as an ordered key; then
+// filter[i] = ((finite min_z[i] ? min_z[i] : zmax) / max_focal) * sqrt(0.2), all 0 when nothing is finite
+void launch_filter3d_finalize(int64_t P, const float* min_z, float max_focal, uint32_t* word, float* filter, hipStream_t stream);
+void launch_filter3d_apply(int64_t P, const float* scale, const float* opacity, const float* filter, float* scale_out,
+                           float* opacity_out, hipStream_t stream);
+// in place on the gradient rows; rows != NULL: gradient row r < *d_count belongs to row rows[r], the launch is sized by P
+void launch_filter3d_backward(int64_t P, const float* scale, const float* opacity, const float* filter, const uint32_t* rows,
+                              const uint32_t* d_count, float* g_scale, float* g_opacity, hipStream_t stream);
 // ---- loss.hip : the 3DGS photometric loss, (1 - lambda) L1 + lambda (1 - SSIM), and its gradient ----
 // Both passes tile a channel into 32 x 16 outputs, one workgroup each; partial sums are indexed by workgroup.
 int64_t photometric_workgroups(int W, int H);
