@@ -301,6 +301,51 @@ LCGS_API lcgs_status lcgs_render_backward_distortion(lcgs_context* ctx, const fl
                                                      const float* d_dL_ddepth, const float* d_dL_dalpha, const float* d_dL_ddist,
                                                      int accumulate, const lcgs_grads* grads);
 
+/* ---- normal map of the last lcgs_render_forward(keep_state = 1), and its backward ---- */
+/* The blended per-splat normal of every ray, in VIEW space: the other half of the regulariser pair 2DGS, GOF, RaDe-GS and PGSR
+ * train with (normal consistency against the normal of the rendered depth surface; the stencil and the loss stay with the
+ * caller, who has depth, alpha and normal differentiable).
+ * The per-splat normal, per on-screen row, from the BOUND arrays (activated scale s, rotq as stored, pos) and the frame's
+ * camera, every operation binary32 and uncontracted; scale_modifier plays no part:
+ *     axis         k = 0; if (s[1] < s[k]) k = 1; if (s[2] < s[k]) k = 2;          (the shortest axis, ties to the lower index)
+ *     world normal c = column k of the rotation matrix of rotq, (w, x, y, z) as stored, NOT renormalised:
+ *                      k = 0: (1 - 2yy - 2zz, 2xy + 2zw, 2xz - 2yw)     every term as ((2 a) b), a difference or sum of two
+ *                      k = 1: (2xy - 2zw, 1 - 2xx - 2zz, 2yz + 2xw)     terms as such, the diagonal as ((1 - 2aa) - 2bb);
+ *                      k = 2: (2xz + 2yw, 2yz - 2xw, 1 - 2xx - 2yy)     a unit vector for a unit quaternion
+ *     facing       d = pos - camera position (componentwise), t = (c0 d0 + c1 d1) + c2 d2;  if (t > 0) c = -c
+ *                  (t == 0 and NaN leave c as it is)
+ *     view space   n = (right . c, up . c, front . c), each dot product as (a0 b0 + a1 b1) + a2 b2
+ * The map, with the entries i, the weights w_i and the list order of the maps above:
+ *     normal[c][p] = sum_i fl(w_i n_i,c)          (binary32, list order, from 0;  c = 0, 1, 2;  3*H*W floats, CHW)
+ * which a CPU restatement of the frame composites bit for bit as the per-splat colour n.  The map is NOT normalised (divide by
+ * alpha, or normalise the vector), NO background is blended in and it is NOT clamped.  A pixel outside every list, and every
+ * pixel of a frame that drew nothing, is 0 in all three channels (such a frame leaves the colour image untouched).
+ * The backward treats thresholds, the 0.99 cap and saturation as lcgs_render_backward does; the axis k and the flip are
+ * constants too.  n_i . dL/dnormal[p] is taken through the blend like a per-pixel value of entry i (to pos, scale, rotq and
+ * opacity through the weights, as in every other channel), and dL/dn_i = sum_p w_i dL/dnormal[.][p] reaches rotq alone, through
+ * dL/dc = +-(right gn0 + up gn1 + front gn2) and the closed-form derivative of column k: nothing goes to scale or pos from the
+ * normal's own value.
+ * Like lcgs_camera_backward both calls re-read the BOUND arrays: call them before anything rewrites those.  Both compute the
+ * rows' normals themselves: the backward needs no preceding lcgs_render_normals and no map as input.
+ * Not offered: world-space output; a normal channel in lcgs_render_backward_camera, lcgs_render_backward_compact, lcgs_fit_views
+ * or the ownership step; a fused normal-consistency loss; an lcgs-app flag. */
+/* d_normal: 3*H*W floats, CHW.  Enqueues on the context's stream, reads nothing back.  Stages under lcgs_set_profiling:
+ * splat_normals, render_normals. */
+LCGS_API lcgs_status lcgs_render_normals(lcgs_context* ctx, float* d_normal);
+/* lcgs_render_backward_distortion with a fifth channel: the gradient of <dL_dimg, img> + <dL_ddepth, depth> + <dL_dalpha, alpha>
+ * + <dL_ddist, dist> + <dL_dnormal, normal>, dense rows overwritten (accumulate = 0) or added to.  d_dL_dnormal: 3*H*W floats,
+ * CHW.  Any of the five incoming gradients may be NULL, not all five; all map channels share one walk of the lists.  With
+ * d_dL_dnormal NULL the call is lcgs_render_backward_distortion.  lcgs_densify_accumulate works behind it and sees the combined
+ * 2-D gradient.  lcgs_camera_backward behind a call that passed a non-NULL d_dL_dnormal returns LCGS_ERR_STATE: the view-space
+ * normal depends on the camera's rotation directly, that term is not built, and a silently incomplete gradient is worse than a
+ * refusal; behind any later backward of the frame it works as before.
+ * Both calls: LCGS_ERR_STATE without a keep_state frame, or after a frame of lcgs_owner_render.  LCGS_ERR_INVALID_ARG (before
+ * any device work): NULL ctx, output or grads, a NULL gradient buffer, a mode that is neither constant, a non-finite center,
+ * all five gradients NULL.  Stages under lcgs_set_profiling: splat_normals, render_maps_backward, normals_to_rot. */
+LCGS_API lcgs_status lcgs_render_backward_normals(lcgs_context* ctx, const float* d_dL_dimg, int mode, float center,
+                                                  const float* d_dL_ddepth, const float* d_dL_dalpha, const float* d_dL_ddist,
+                                                  const float* d_dL_dnormal, int accumulate, const lcgs_grads* grads);
+
 /* ---- per-splat blend-weight statistics of the last lcgs_render_forward(keep_state = 1) ---- */
 /* Which splats a set of views actually uses.  w is the w_i = T_i alpha_i above: the weight pixel p gives entry i of its list, for
  * the entries p blended (positions up to n_contrib[p] that pass the renderer's power and 1/255 tests, the 0.99 cap and the

@@ -285,6 +285,9 @@ def _signatures() -> dict:
         # depth-distortion map
         "lcgs_render_distortion": (st, [p, i, f, p]),
         "lcgs_render_backward_distortion": (st, [p, p, i, f, p, p, p, i, grads]),
+        # normal map
+        "lcgs_render_normals": (st, [p, p]),
+        "lcgs_render_backward_normals": (st, [p, p, i, f, p, p, p, p, i, grads]),
         # per-splat blend-weight statistics
         "lcgs_contrib_accumulate": (st, [p, i, cstats]),
         # camera gradient
@@ -858,6 +861,22 @@ class Renderer:
         _check(load_library().lcgs_render_backward_distortion(self.ctx._h, _ptr(dL_dimg), _DEPTH_MODES[mode], float(center),
                                                               _ptr(dL_ddepth), _ptr(dL_dalpha), _ptr(dL_ddist),
                                                               bool(accumulate), C.byref(g)))
+
+    def render_normals(self, normal):
+        """lcgs_render_normals: the view-space normal map of the last keep_state frame, 3 x H x W floats (CHW) -- per pixel the
+        sum of w_i n_i over the blended entries, n_i the splat's shortest axis turned to face the camera (include/lcgs_hip.h has
+        the definition).  Not normalised, not clamped, no background.  Enqueues only."""
+        _check(load_library().lcgs_render_normals(self.ctx._h, _ptr(normal)))
+
+    def backward_normals(self, dL_dimg, dL_ddepth, dL_dalpha, dL_ddist, dL_dnormal, dpos, dscale, drotq, dsh, dopacity,
+                         mode: str = "z", center: float = 0.0, accumulate: bool = False):
+        """lcgs_render_backward_normals: backward_distortion with the normal map's incoming gradient (3 x H x W) as a fifth
+        channel; any of the five may be None (not all).  With dL_dnormal None it is backward_distortion.  camera_backward is
+        refused behind a call that passed dL_dnormal."""
+        g = _grads((dpos, dscale, drotq, dsh, dopacity))
+        _check(load_library().lcgs_render_backward_normals(self.ctx._h, _ptr(dL_dimg), _DEPTH_MODES[mode], float(center),
+                                                           _ptr(dL_ddepth), _ptr(dL_dalpha), _ptr(dL_ddist), _ptr(dL_dnormal),
+                                                           bool(accumulate), C.byref(g)))
 
     def camera_backward(self, out12):
         """lcgs_camera_backward: the camera gradient of the last backward of the kept frame -- 12 floats on the device in the
@@ -1443,12 +1462,12 @@ def _autograd_frame(renderer: "Renderer", view: Camera, scene, bg, scale_modifie
                     depth_mode: str = "z", center: float = 0.0, cam12=None):
     """The one differentiable frame behind render_autograd and its variants: binds the scene, renders `view` with keep_state,
     renders the maps `outputs` asks for ("image": the image alone; "maps": plus depth and alpha; "distortion": plus the
-    distortion map about `center`) and, on backward, differentiates that frame -- after binding its saved scene and rendering
+    distortion map about `center`; "normals": plus the normal map) and, on backward, differentiates that frame -- after binding its saved scene and rendering
     its view again when the renderer's generation has moved -- through the one Renderer backward that fits.  cam12 (a tensor
     or None): the pose is an input too, in front of the five scene tensors, and gets the camera gradient."""
     import torch
 
-    maps, dist, pose = outputs != "image", outputs == "distortion", cam12 is not None
+    maps, dist, nrm, pose = outputs != "image", outputs in ("distortion", "normals"), outputs == "normals", cam12 is not None
 
     class _Fn(torch.autograd.Function):
         @staticmethod
@@ -1466,6 +1485,9 @@ def _autograd_frame(renderer: "Renderer", view: Camera, scene, bg, scale_modifie
                 renderer.render_maps(extra[0], extra[1], mode=depth_mode)
             if dist:
                 renderer.render_distortion(extra[2], mode=depth_mode, center=center)
+            if nrm:
+                extra.append(torch.empty(3, view.height, view.width, device=dev, dtype=torch.float32))
+                renderer.render_normals(extra[3])
             ctx.shapes = [t.shape for t in params]
             if pose:
                 ctx.cam_like = (inputs[0].shape, inputs[0].device)
@@ -1493,6 +1515,8 @@ def _autograd_frame(renderer: "Renderer", view: Camera, scene, bg, scale_modifie
                     ctx.generation = renderer._generation
                 if not want_scene:
                     renderer.backward_camera(*incoming, g12, mode=depth_mode)
+                elif nrm:
+                    renderer.backward_normals(*incoming, *grads, mode=depth_mode, center=center)
                 elif dist:
                     renderer.backward_distortion(*incoming, *grads, mode=depth_mode, center=center)
                 elif maps:
@@ -1542,6 +1566,17 @@ def render_autograd_distortion(renderer: "Renderer", cam: Camera, pos, scale, ro
     the loss does not use arrives as None (or zero-shaped) and is passed as NULL.  Like render_autograd it re-renders its own
     view when the renderer's generation has moved."""
     return _autograd_frame(renderer, cam, (pos, scale, rotq, sh, opacity), bg, scale_modifier, "distortion", depth_mode, center)
+
+
+def render_autograd_normals(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh, opacity, bg=(0.0, 0.0, 0.0),
+                            depth_mode: str = "z", center: float = 0.0, scale_modifier: float = 1.0):
+    """render_autograd_distortion with the frame's view-space normal map: returns (img [3, H, W], depth [H, W], alpha [H, W],
+    dist [H, W], normal [3, H, W]) as include/lcgs_hip.h defines them (normal = sum_i w_i n_i, n_i the splat's shortest axis
+    facing the camera; not normalised, not clamped).  The backward runs lcgs_render_backward_normals with the five incoming
+    gradients; an output the loss does not use arrives as None (or zero-shaped) and is passed as NULL.  Like render_autograd it
+    re-renders its own view when the renderer's generation has moved.  The pose is not an input: the camera gradient of the
+    normal channel is not offered."""
+    return _autograd_frame(renderer, cam, (pos, scale, rotq, sh, opacity), bg, scale_modifier, "normals", depth_mode, center)
 
 
 def filter3d_autograd(renderer: "Renderer", scale, opacity, filt):

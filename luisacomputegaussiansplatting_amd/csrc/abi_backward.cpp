@@ -1,6 +1,6 @@
 // abi_backward.cpp -- the C ABI, part 5: the backward of the fused frame -- dense per-splat rows, compact
 // rows, accumulation over views, and the variant with the optimiser folded into the per-splat pass -- and the frame's depth
-// alpha and depth-distortion maps with their backward (kernels/maps.hip), the per-splat blend-weight statistics of the same kept
+// alpha, depth-distortion and normal maps with their backward (kernels/maps.hip), the per-splat blend-weight statistics of the same kept
 // lists (kernels/contrib.hip), and the camera gradient (kernels/camera_grad.hip).
 #include <math.h>
 #include <stdio.h>
@@ -21,6 +21,7 @@ struct BackwardRequest {
     // the incoming gradients of the image, of the depth and alpha maps (about depth mode `mode`) and of the distortion map
     // (about `center`): any may be NULL, not all
     const float *d_dL_dimg = nullptr, *d_dL_ddepth = nullptr, *d_dL_dalpha = nullptr, *d_dL_ddist = nullptr;
+    const float *d_dL_dnormal = nullptr; // ... and of the normal map (dense rows only)
     int          mode   = kDepthZ;
     float        center = 0.0f;
     // exactly one destination: per-splat rows in `grads` (dense, dense added to what the arrays hold, or compact), the
@@ -32,7 +33,7 @@ struct BackwardRequest {
     AdamStep          step{};
     float*            d_dL_dcam = nullptr; // CameraOnly
 
-    bool maps() const { return d_dL_ddepth || d_dL_dalpha || d_dL_ddist; }
+    bool maps() const { return d_dL_ddepth || d_dL_dalpha || d_dL_ddist || d_dL_dnormal; }
     bool value_channel() const { return d_dL_ddepth || d_dL_ddist; } // something arrives in the rows' value slot
     bool rows() const { return dest == Dense || dest == DenseAccumulate || dest == Compact; }
 };
@@ -215,6 +216,44 @@ lcgs_status lcgs_render_backward_distortion(lcgs_context* ctx, const float* d_dL
     return render_backward(ctx, req);
 }
 
+lcgs_status lcgs_render_normals(lcgs_context* ctx, float* d_normal)
+{
+    LCGS_REQUIRE(ctx && d_normal, "NULL argument");
+    LCGS_ENTRY(ctx);
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    LCGS_TRY(check_own_kept_frame(ctx, "lcgs_render_normals"));
+    LCGS_TRY(ctx->splat_normals.ensure(splat_normals_bytes((int64_t)ctx->P)));
+    ctx->n_marks = 0;
+    LCGS_TRY(mark(ctx, "begin"));
+    launch_splat_normals(kept_rows(ctx), ctx->splat_normals.as<float4>(), nullptr, ctx->stream);
+    LCGS_TRY(mark(ctx, "splat_normals"));
+    launch_render_normals(kept_frame(ctx), ctx->splat_normals.as<float4>(), d_normal, ctx->stream);
+    LCGS_TRY(mark(ctx, "render_normals"));
+    LCGS_HIP_CHECK(hipGetLastError());
+    if (ctx->profiling) {
+        LCGS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        LCGS_TRY(collect_marks(ctx));
+    }
+    return LCGS_OK;
+}
+
+lcgs_status lcgs_render_backward_normals(lcgs_context* ctx, const float* d_dL_dimg, int mode, float center,
+                                         const float* d_dL_ddepth, const float* d_dL_dalpha, const float* d_dL_ddist,
+                                         const float* d_dL_dnormal, int accumulate, const lcgs_grads* grads)
+{
+    LCGS_REQUIRE(ctx && grads, "NULL argument");
+    LCGS_REQUIRE(mode == LCGS_DEPTH_Z || mode == LCGS_DEPTH_INV_Z, "mode must be LCGS_DEPTH_Z or LCGS_DEPTH_INV_Z");
+    LCGS_REQUIRE(isfinite(center), "center must be finite");
+    LCGS_REQUIRE(d_dL_dimg || d_dL_ddepth || d_dL_dalpha || d_dL_ddist || d_dL_dnormal, "all five incoming gradients are NULL");
+    LCGS_REQUIRE(grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh && grads->d_dL_dopacity,
+                 "NULL gradient buffer");
+    BackwardRequest req = rows_request(d_dL_dimg, grads, accumulate ? BackwardRequest::DenseAccumulate : BackwardRequest::Dense);
+    req.mode = mode, req.center = center;
+    req.d_dL_ddepth = d_dL_ddepth, req.d_dL_dalpha = d_dL_dalpha, req.d_dL_ddist = d_dL_ddist, req.d_dL_dnormal = d_dL_dnormal;
+    LCGS_ENTRY(ctx);
+    return render_backward(ctx, req);
+}
+
 lcgs_status lcgs_camera_backward(lcgs_context* ctx, float* d_dL_dcam)
 {
     LCGS_REQUIRE(ctx && d_dL_dcam, "NULL argument");
@@ -222,6 +261,11 @@ lcgs_status lcgs_camera_backward(lcgs_context* ctx, float* d_dL_dcam)
     LCGS_TRY(check_own_kept_frame(ctx, "lcgs_camera_backward"));
     if (!ctx->g2d_backward_done) {
         set_last_error("lcgs_camera_backward needs a backward of the last frame (its 2-D gradient rows are only zeros until then)");
+        return LCGS_ERR_STATE;
+    }
+    if (ctx->g2d_normal_channel) { // the view-space normal depends on the camera's rotation directly: that term is not built
+        set_last_error("lcgs_camera_backward: the last backward passed a normal gradient (lcgs_render_backward_normals); the camera "
+                       "gradient of the normal channel is not offered");
         return LCGS_ERR_STATE;
     }
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
@@ -292,6 +336,12 @@ lcgs_status render_backward(lcgs_context* ctx, const BackwardRequest& req)
                               "the last frame was drawn from received records (lcgs_owner_render): use lcgs_owner_render_backward"));
     LCGS_REQUIRE(!rows_out || (reinterpret_cast<uintptr_t>(grads->d_dL_drotq) & 15) == 0, "dL_drotq must be 16-byte aligned");
     if (camera_only) LCGS_TRY(ctx->cam_slab.ensure(camera_grad_slab_bytes((int64_t)ctx->P))); // (before any device work)
+    const bool normals = req.d_dL_dnormal != nullptr;
+    LCGS_REQUIRE(!normals || (rows_out && !compact), "the normal channel writes dense rows only");
+    if (normals) {
+        LCGS_TRY(ctx->splat_normals.ensure(splat_normals_bytes((int64_t)ctx->P)));
+        LCGS_TRY(ctx->splat_normal_grads.ensure(splat_normals_bytes((int64_t)ctx->P)));
+    }
     hipStream_t  st   = ctx->stream;
     const size_t P    = (size_t)ctx->P;
     ctx->n_marks      = 0;
@@ -346,9 +396,14 @@ lcgs_status render_backward(lcgs_context* ctx, const BackwardRequest& req)
                                fill_in_kernel ? &fill : nullptr);
         LCGS_TRY(mark(ctx, "render_backward"));
     }
+    NormalChannel nrm{ req.d_dL_dnormal, ctx->splat_normals.as<float4>(), ctx->splat_normal_grads.as<float>() };
+    if (normals) { // the rows' normals, as the forward's own pass forms them, and their cleared dL/dn slots
+        launch_splat_normals(rows, ctx->splat_normals.as<float4>(), ctx->splat_normal_grads.as<float4>(), st);
+        LCGS_TRY(mark(ctx, "splat_normals"));
+    }
     if (maps) { // the map channels add to the rows the colour walk (or the zeroing alone) left: one walk for all of them
         launch_render_maps_backward(kept, req.mode, req.d_dL_ddepth, req.d_dL_dalpha, ctx->grads2d.as<float>(), st, req.center,
-                                    req.d_dL_ddist);
+                                    req.d_dL_ddist, normals ? &nrm : nullptr);
         LCGS_TRY(mark(ctx, "render_maps_backward"));
     }
     if (overlap) LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_join, 0));
@@ -370,8 +425,13 @@ lcgs_status render_backward(lcgs_context* ctx, const BackwardRequest& req)
         LCGS_TRY(lcgs::comm_mark_touched(ctx->comm, rows, accumulate, st));
     ctx->g2d_backward_done = true; // the frame's 2-D gradient rows now hold a backward's sums (lcgs_densify_accumulate)
     ctx->g2d_value_mode    = req.value_channel() ? req.mode : -1; // (every backward starts from zeroed rows)
+    ctx->g2d_normal_channel = normals;
     if (camera_only) LCGS_TRY(camera_pass(ctx, req.d_dL_dcam));
     LCGS_TRY(mark(ctx, "preprocess_backward"));
+    if (normals) { // dL/dn reaches the rotation rows through the closed form of the axis' column
+        launch_normals_to_rot(rows, ctx->splat_normals.as<float4>(), ctx->splat_normal_grads.as<float4>(), grads->d_dL_drotq, st);
+        LCGS_TRY(mark(ctx, "normals_to_rot"));
+    }
     LCGS_HIP_CHECK(hipGetLastError());
     if (ctx->profiling) {
         LCGS_HIP_CHECK(hipStreamSynchronize(st));

@@ -480,6 +480,7 @@ lcgs_status lcgs_render_forward(lcgs_context* ctx, const lcgs_camera* camera, co
     ctx->owner_recs   = nullptr; // (an ordinary frame: its backward is lcgs_render_backward again)
     ctx->g2d_backward_done = false; // (a new frame: nothing for lcgs_densify_accumulate to read until its backward ran)
     ctx->g2d_value_mode    = -1;
+    ctx->g2d_normal_channel = false;
     uint32_t        earlier_truncated = 0; // asynchronous frames before this one that overflowed the pair workspace
     for (int attempt = 0; attempt < 4; ++attempt) {
         LCGS_TRY(ensure_fused_workspace(ctx, cp, keep_state != 0));

@@ -189,6 +189,10 @@ struct lcgs_context {
     bool        g2d_backward_done = false;
     // ... and the depth mode of the backward that wrote their value slot (kG2DValueSlot), -1: none did (lcgs_camera_backward)
     int         g2d_value_mode = -1;
+    // ... and whether it passed a normal gradient: the camera gradient lacks that channel's direct term (lcgs_camera_backward refuses)
+    bool        g2d_normal_channel = false;
+    // lcgs_render_normals / lcgs_render_backward_normals: the on-screen rows' normals and dL/dn (splat_normals_bytes each)
+    DeviceBuffer splat_normals, splat_normal_grads;
     DeviceBuffer cam_slab; // lcgs_camera_backward: per-block partial sums (camera_grad_slab_bytes)
     DeviceBuffer contrib_slab; // lcgs_contrib_accumulate: {sum, max bits, count} per on-screen row (contrib_slab_bytes)
     // lcgs_densify: emit counts, their inclusive sums, actions (one entry per source row)

@@ -432,10 +432,27 @@ void launch_render_distortion(const KeptFrame& f, int mode, float center, float*
 // ADDS the sums of the map channels to grads2d slots 0-5 and kG2DValueSlot (dL_ddepth / dL_dalpha / dL_ddist: any may be NULL).
 // dL_ddist != NULL: the distortion channel about `center`, its three per-pixel sums re-derived by a pre-walk inside the kernel;
 // NULL: the two-channel kernel
+// nrm != NULL: the normal channel as well -- n_i . dL_dnormal[p] joins the per-entry scalar, the three sums w_i dL_dnormal_c[p]
+// are ADDED to dL_dn (4 floats per on-screen row, cleared by launch_splat_normals), not to grads2d
+struct NormalChannel {
+    const float* dL_dnormal; // 3 H W, CHW
+    const float4* normals;   // launch_splat_normals' rows
+    float*       dL_dn;
+};
 void launch_render_maps_backward(const KeptFrame& f, int mode, const float* dL_ddepth, const float* dL_dalpha, float* grads2d,
-                                 hipStream_t stream, float center = 0.0f, const float* dL_ddist = nullptr);
+                                 hipStream_t stream, float center = 0.0f, const float* dL_ddist = nullptr,
+                                 const NormalChannel* nrm = nullptr);
 // one lane per on-screen row: dL_dpos[row] += grads2d slot kG2DValueSlot x dvalue/dz x front (behind the preprocess-backward)
 void launch_maps_depth_to_pos(const KeptRows& r, int mode, float* dL_dpos, hipStream_t stream);
+// ---- the normal map (maps.hip): the per-splat normal is defined in include/lcgs_hip.h ----
+// the two context-owned workspaces, each: 16 bytes per on-screen row (n0, n1, n2, axis | flip << 2; dL/dn0..2, unused)
+size_t splat_normals_bytes(int64_t rows);
+// one lane per on-screen row: writes the row's normal; dL_dn != NULL: clears the row's dL/dn slot too
+void launch_splat_normals(const KeptRows& r, float4* normals, float4* dL_dn, hipStream_t stream);
+// k_render_maps' walk with three accumulators: normal_map 3 H W floats, CHW
+void launch_render_normals(const KeptFrame& f, const float4* normals, float* normal_map, hipStream_t stream);
+// one lane per on-screen row: dL_drotq[row] += (dc/dq)^T dL/dc from dL_dn (behind the preprocess-backward)
+void launch_normals_to_rot(const KeptRows& r, const float4* normals, const float4* dL_dn, float* dL_drotq, hipStream_t stream);
 
 // ---- contrib.hip : per-splat blend-weight statistics of the last keep-state frame, and the keep / drop rule ----
 // the context-owned slab: {sum, max bits, count} per on-screen row, indexed by the lists' on-screen indices

@@ -24,7 +24,17 @@
 //                           the per-entry scalar as a third per-pixel "value" and 2 w_i (A u_i - M1) dL/ddist joins the
 //                           w dL/dD sum.  Still seven sums per (tile, splat) and the same flush.  DIST = false is the
 //                           two-channel kernel, operation for operation.
+//                           NRM = true adds the normal channel: n_i . dL/dN[p] joins the per-entry scalar as one more
+//                           per-pixel value, and three more sums w_i dL/dN_c[p] join the seven -- ten per (tile, splat), the
+//                           same butterfly, LDS accumulator and flush (sixteen lanes per entry instead of eight); the three
+//                           leave as float atomics into the per-row dL/dn workspace, not into grads2d.
 //   k_maps_depth_to_pos     one lane per on-screen row: dL/dpos += slot 9 x dv/dz x front.
+//   k_splat_normals         one lane per on-screen row: the row's view-space normal (include/lcgs_hip.h: the shortest axis'
+//                           column of rot_from_quat, turned to face the camera, taken to view space), the axis and the flip in
+//                           the fourth word; clears the row's dL/dn slot when the backward asks.  Every row a walk reads is written.
+//   k_render_normals        k_render_maps' walk with three accumulators N_c = sum fl(w n_c); the entry's normal is staged into
+//                           LDS in the round's `before` hook.
+//   k_normals_to_rot        one lane per on-screen row: dL/drotq += (dc/dq)^T (+-)(right gn0 + up gn1 + front gn2).
 // Thresholds are constants for the derivative, exactly as in backward.hip: the 0.99 cap passes nothing, a saturated pixel stops.
 #include "kept_rows.hpp"
 #include "kept_walk.hpp"
@@ -97,16 +107,88 @@ __global__ void __launch_bounds__(256) k_render_distortion(KeptFrame f, int mode
     if (t.inside) dist_map[t.pix] = A * M2 - M1 * M1;
 }
 
-template <bool DIST>
+// the fourth word of a row's normal: bits 0-1 the axis k, bit 2 the flip
+constexpr uint32_t kNrmFlipBit = 4u;
+
+__global__ void __launch_bounds__(256) k_splat_normals(CamParams cp, const uint32_t* __restrict__ vis_index,
+                                                       const uint32_t* __restrict__ d_counts, const float* __restrict__ pos,
+                                                       const float* __restrict__ scale, const float* __restrict__ rotq,
+                                                       float4* __restrict__ normals, float4* __restrict__ dL_dn)
+{
+    const uint32_t V = d_counts[0];
+    for (uint32_t vid = blockIdx.x * 256u + threadIdx.x; vid < V; vid += gridDim.x * 256u) {
+        const size_t i = vis_index[vid];
+        const float  s[3] = { scale[3 * i + 0], scale[3 * i + 1], scale[3 * i + 2] };
+        uint32_t     k = 0u;
+        if (s[1] < s[k]) k = 1u;
+        if (s[2] < s[k]) k = 2u;
+        float R[3][3];
+        rot_from_quat(rotq[4 * i + 1], rotq[4 * i + 2], rotq[4 * i + 3], rotq[4 * i + 0], R); // stored (w, x, y, z)
+        float       c0 = R[k][0], c1 = R[k][1], c2 = R[k][2];
+        const float d0 = pos[3 * i + 0] - cp.campos[0], d1 = pos[3 * i + 1] - cp.campos[1], d2 = pos[3 * i + 2] - cp.campos[2];
+        const float t  = (c0 * d0 + c1 * d1) + c2 * d2;
+        const bool  flip = t > 0.0f; // (0 and NaN: unflipped)
+        if (flip) c0 = -c0, c1 = -c1, c2 = -c2;
+        float4 n;
+        n.x = (cp.right[0] * c0 + cp.right[1] * c1) + cp.right[2] * c2;
+        n.y = (cp.up[0] * c0 + cp.up[1] * c1) + cp.up[2] * c2;
+        n.z = (cp.front[0] * c0 + cp.front[1] * c1) + cp.front[2] * c2;
+        n.w = __uint_as_float(k | (flip ? kNrmFlipBit : 0u));
+        normals[vid] = n;
+        if (dL_dn) dL_dn[vid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_render_normals(KeptFrame f, const float4* __restrict__ normals,
+                                                        float* __restrict__ normal_map)
+{
+    __shared__ WalkShared s_walk;
+    __shared__ float4     s_nrm[256]; // the round's staged entries' normals
+    TileWalk              t;
+    if (!tile_prologue(f, s_walk, t)) return; // (a frame that drew nothing walks nothing: the map is zero)
+
+    float T = 1.0f, N0 = 0.0f, N1 = 0.0f, N2 = 0.0f;
+    walk_rounds<false>(
+        f, s_walk, t, kDepthZ,
+        [&](uint32_t vid) {
+            if (vid != 0xFFFFFFFFu) s_nrm[t.tid] = normals[vid];
+        },
+        [&](uint32_t idx, uint32_t pos, const float4& ea, const float4& eb) {
+            const EntryEval v = eval_entry(ea, eb, t.pxf, t.pyf, pos, t.last);
+            if (__builtin_amdgcn_ballot_w64(v.cand) == 0ull) return;
+            const EntryBlend b = blend_entry(eb, v);
+            if (b.blended) {
+                const float4 n   = s_nrm[idx];
+                const float  wgt = T * b.alpha;
+                N0               = N0 + wgt * n.x;
+                N1               = N1 + wgt * n.y;
+                N2               = N2 + wgt * n.z;
+                T                = T * (1.0f - b.alpha);
+            }
+        },
+        [] {});
+    if (t.inside) {
+        const size_t plane = (size_t)f.cp.width * f.cp.height;
+        normal_map[t.pix]             = N0;
+        normal_map[plane + t.pix]     = N1;
+        normal_map[2 * plane + t.pix] = N2;
+    }
+}
+
+template <bool DIST, bool NRM>
 __global__ void __launch_bounds__(256) k_render_maps_backward(KeptFrame f, int mode, float center,
                                                               const float* __restrict__ dL_ddepth,
                                                               const float* __restrict__ dL_dalpha,
-                                                              const float* __restrict__ dL_ddist, float* __restrict__ grads2d)
+                                                              const float* __restrict__ dL_ddist, float* __restrict__ grads2d,
+                                                              const float* __restrict__ dL_dnormal,
+                                                              const float4* __restrict__ normals, float* __restrict__ dL_dn)
 {
-    constexpr int         kSums = 7;
+    constexpr int         kSums  = NRM ? 10 : 7;
+    constexpr uint32_t    kLanes = NRM ? 16u : 8u; // the flush's lanes per entry
     __shared__ WalkShared s_walk;
     __shared__ float      s_acc[kSums][256]; // the round's sums over the tile's pixels, per entry
     __shared__ uint32_t   s_vid[256];        // the entry's splat (dense id); ~0: nothing staged
+    __shared__ float4     s_nrm[NRM ? 256 : 1]; // NRM: the entry's normal
 
     if (f.d_counts[1] == 0u) return; // nothing drawn: final_T / n_contrib are not this frame's, every gradient is zero
     TileWalk t;
@@ -119,6 +201,13 @@ __global__ void __launch_bounds__(256) k_render_maps_backward(KeptFrame f, int m
     if constexpr (DIST) {
         gq = (t.inside && dL_ddist) ? dL_ddist[t.pix] : 0.0f;
         walk_distortion_sums(f, s_walk, t, mode, center, dA, dM1, dM2);
+    }
+    float gn0 = 0.0f, gn1 = 0.0f, gn2 = 0.0f;
+    if constexpr (NRM) {
+        if (t.inside) {
+            const size_t plane = (size_t)f.cp.width * f.cp.height;
+            gn0 = dL_dnormal[t.pix], gn1 = dL_dnormal[plane + t.pix], gn2 = dL_dnormal[2 * plane + t.pix];
+        }
     }
 
     // per-pixel recurrences, back to front (backward.hip): Qr = prod (1 - alpha) over the entries walked so far, over T_final;
@@ -133,6 +222,9 @@ __global__ void __launch_bounds__(256) k_render_maps_backward(KeptFrame f, int m
             s_vid[t.tid] = vid;
 #pragma unroll
             for (int g = 0; g < kSums; ++g) s_acc[g][t.tid] = 0.0f;
+            if constexpr (NRM) {
+                if (vid != 0xFFFFFFFFu) s_nrm[t.tid] = normals[vid];
+            }
         },
         [&](uint32_t idx, uint32_t pos, const float4& ea, const float4& eb) {
             const EntryEval v = eval_entry(ea, eb, t.pxf, t.pyf, pos, t.last);
@@ -149,6 +241,10 @@ __global__ void __launch_bounds__(256) k_render_maps_backward(KeptFrame f, int m
                 val = val + gq * (dM2 + u * (au - 2.0f * dM1));
                 gv  = gv + (2.0f * gq) * (wgt * (au - dM1));
             }
+            if constexpr (NRM) { // n_i . dL/dN[p] as one more per-pixel value
+                const float4 n = s_nrm[idx];
+                val            = val + ((n.x * gn0 + n.y * gn1) + n.z * gn2);
+            }
             const float d   = val - Bd; // (value - what lies behind) . dL/dpixel
             const float dLa = d * Tn;
             Bd              = __builtin_fmaf(a, d, Bd);
@@ -162,6 +258,7 @@ __global__ void __launch_bounds__(256) k_render_maps_backward(KeptFrame f, int m
             s[4] = s[1] * v.dy;
             s[5] = q;
             s[6] = gv;
+            if constexpr (NRM) s[7] = wgt * gn0, s[8] = wgt * gn1, s[9] = wgt * gn2; // dL/dn_i
 #pragma unroll
             for (int g = 0; g < kSums; ++g) s[g] = row16_sum(s[g]);
             if (row_head) {
@@ -177,8 +274,8 @@ __global__ void __launch_bounds__(256) k_render_maps_backward(KeptFrame f, int m
             __syncthreads();
             // ---- flush the round: eight consecutive lanes own one entry's row (seven of them add), so a wave instruction covers
             // contiguous bytes of a few rows instead of 64 different rows
-            for (uint32_t cidx = t.tid; cidx < 256u * 8u; cidx += 256u) {
-                const uint32_t g = cidx & 7u, idx = cidx >> 3;
+            for (uint32_t cidx = t.tid; cidx < 256u * kLanes; cidx += 256u) {
+                const uint32_t g = cidx & (kLanes - 1u), idx = cidx / kLanes;
                 const uint32_t vid = s_vid[idx];
                 if (g < (uint32_t)kSums && vid != 0xFFFFFFFFu) {
                     // sums -> gradients: d/dmean = -opacity conic (S q dx, S q dy), d/dconic = opacity (-1/2, -1, -1/2) (S q dx dx, ...)
@@ -192,6 +289,10 @@ __global__ void __launch_bounds__(256) k_render_maps_backward(KeptFrame f, int m
                             s *= (g == 3u) ? -1.0f : -0.5f;
                         }
                         s *= eb.z;
+                    }
+                    if (NRM && g >= 7u) { // the normal channel's sums: the per-row dL/dn workspace, not a grads2d slot
+                        if (s != 0.0f) atomicAdd(&dL_dn[(size_t)vid * 4u + (g - 7u)], s);
+                        continue;
                     }
                     if (s != 0.0f) atomicAdd(&grads2d[(size_t)vid * kG2D + (g < 6u ? g : (uint32_t)kG2DValueSlot)], s);
                 }
@@ -217,6 +318,47 @@ __global__ void __launch_bounds__(256) k_maps_depth_to_pos(CamParams cp, const u
     }
 }
 
+__global__ void __launch_bounds__(256) k_normals_to_rot(CamParams cp, const uint32_t* __restrict__ vis_index,
+                                                        const uint32_t* __restrict__ d_counts, const float* __restrict__ rotq,
+                                                        const float4* __restrict__ normals, const float4* __restrict__ dL_dn,
+                                                        float* __restrict__ dL_drotq)
+{
+    const uint32_t V = d_counts[0];
+    for (uint32_t vid = blockIdx.x * 256u + threadIdx.x; vid < V; vid += gridDim.x * 256u) {
+        const float4 gn = dL_dn[vid];
+        if (gn.x == 0.0f && gn.y == 0.0f && gn.z == 0.0f) continue;
+        const uint32_t bits = __float_as_uint(normals[vid].w), k = bits & 3u;
+        const float    sg   = (bits & kNrmFlipBit) ? -1.0f : 1.0f;
+        // dL/dc = +-(right gn0 + up gn1 + front gn2): the view rotation's transpose, the flip a constant
+        const float g0 = sg * ((cp.right[0] * gn.x + cp.up[0] * gn.y) + cp.front[0] * gn.z);
+        const float g1 = sg * ((cp.right[1] * gn.x + cp.up[1] * gn.y) + cp.front[1] * gn.z);
+        const float g2 = sg * ((cp.right[2] * gn.x + cp.up[2] * gn.y) + cp.front[2] * gn.z);
+        const size_t o = 4 * (size_t)vis_index[vid];
+        const float  w = rotq[o + 0], x = rotq[o + 1], y = rotq[o + 2], z = rotq[o + 3];
+        float        gw, gx, gy, gz; // (dc/dq)^T dL/dc from column k of rot_from_quat
+        if (k == 0u) {      // (1 - 2yy - 2zz, 2xy + 2zw, 2xz - 2yw)
+            gx = 2.0f * (y * g1 + z * g2);
+            gy = 2.0f * ((x * g1 - w * g2) - 2.0f * y * g0);
+            gz = 2.0f * ((w * g1 + x * g2) - 2.0f * z * g0);
+            gw = 2.0f * (z * g1 - y * g2);
+        } else if (k == 1u) { // (2xy - 2zw, 1 - 2xx - 2zz, 2yz + 2xw)
+            gx = 2.0f * ((y * g0 + w * g2) - 2.0f * x * g1);
+            gy = 2.0f * (x * g0 + z * g2);
+            gz = 2.0f * ((y * g2 - w * g0) - 2.0f * z * g1);
+            gw = 2.0f * (x * g2 - z * g0);
+        } else {              // (2xz + 2yw, 2yz - 2xw, 1 - 2xx - 2yy)
+            gx = 2.0f * ((z * g0 - w * g1) - 2.0f * x * g2);
+            gy = 2.0f * ((w * g0 + z * g1) - 2.0f * y * g2);
+            gz = 2.0f * (x * g0 + y * g1);
+            gw = 2.0f * (y * g0 - x * g1);
+        }
+        dL_drotq[o + 0] += gw;
+        dL_drotq[o + 1] += gx;
+        dL_drotq[o + 2] += gy;
+        dL_drotq[o + 3] += gz;
+    }
+}
+
 } // namespace
 
 void launch_render_maps(const KeptFrame& f, int mode, float* depth, float* alpha, hipStream_t stream)
@@ -232,16 +374,44 @@ void launch_render_distortion(const KeptFrame& f, int mode, float center, float*
 }
 
 void launch_render_maps_backward(const KeptFrame& f, int mode, const float* dL_ddepth, const float* dL_dalpha, float* grads2d,
-                                 hipStream_t stream, float center, const float* dL_ddist)
+                                 hipStream_t stream, float center, const float* dL_ddist, const NormalChannel* nrm)
 {
     if (f.cp.grid_x * f.cp.grid_y == 0) return;
     const dim3 grid(maps_grid(f.cp, f.tile_order));
-    if (dL_ddist)
-        hipLaunchKernelGGL(k_render_maps_backward<true>, grid, dim3(256), 0, stream, f, mode, center, dL_ddepth, dL_dalpha,
-                           dL_ddist, grads2d);
+    if (nrm) { // the normal channel: ten sums per (tile, splat)
+        if (dL_ddist)
+            hipLaunchKernelGGL((k_render_maps_backward<true, true>), grid, dim3(256), 0, stream, f, mode, center, dL_ddepth,
+                               dL_dalpha, dL_ddist, grads2d, nrm->dL_dnormal, nrm->normals, nrm->dL_dn);
+        else
+            hipLaunchKernelGGL((k_render_maps_backward<false, true>), grid, dim3(256), 0, stream, f, mode, 0.0f, dL_ddepth,
+                               dL_dalpha, nullptr, grads2d, nrm->dL_dnormal, nrm->normals, nrm->dL_dn);
+    } else if (dL_ddist)
+        hipLaunchKernelGGL((k_render_maps_backward<true, false>), grid, dim3(256), 0, stream, f, mode, center, dL_ddepth,
+                           dL_dalpha, dL_ddist, grads2d, nullptr, nullptr, nullptr);
     else // (the two-channel kernel: no pre-walk, lcgs_render_backward_maps' arithmetic)
-        hipLaunchKernelGGL(k_render_maps_backward<false>, grid, dim3(256), 0, stream, f, mode, 0.0f, dL_ddepth, dL_dalpha,
-                           nullptr, grads2d);
+        hipLaunchKernelGGL((k_render_maps_backward<false, false>), grid, dim3(256), 0, stream, f, mode, 0.0f, dL_ddepth,
+                           dL_dalpha, nullptr, grads2d, nullptr, nullptr, nullptr);
+}
+
+size_t splat_normals_bytes(int64_t rows) { return (size_t)(rows > 1 ? rows : 1) * sizeof(float4); }
+
+void launch_splat_normals(const KeptRows& r, float4* normals, float4* dL_dn, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_splat_normals, dim3(grid_256(r.hint)), dim3(256), 0, stream, r.cp, r.vis_index, r.d_counts, r.pos,
+                       r.scale, r.rotq, normals, dL_dn);
+}
+
+void launch_render_normals(const KeptFrame& f, const float4* normals, float* normal_map, hipStream_t stream)
+{
+    if (f.cp.grid_x * f.cp.grid_y == 0) return;
+    hipLaunchKernelGGL(k_render_normals, dim3(maps_grid(f.cp, f.tile_order)), dim3(256), 0, stream, f,
+                       normals, normal_map);
+}
+
+void launch_normals_to_rot(const KeptRows& r, const float4* normals, const float4* dL_dn, float* dL_drotq, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_normals_to_rot, dim3(grid_256(r.hint)), dim3(256), 0, stream, r.cp, r.vis_index, r.d_counts, r.rotq,
+                       normals, dL_dn, dL_drotq);
 }
 
 void launch_maps_depth_to_pos(const KeptRows& r, int mode, float* dL_dpos, hipStream_t stream)
