@@ -328,7 +328,8 @@ LCGS_API lcgs_status lcgs_render_backward_distortion(lcgs_context* ctx, const fl
  * Like lcgs_camera_backward both calls re-read the BOUND arrays: call them before anything rewrites those.  Both compute the
  * rows' normals themselves: the backward needs no preceding lcgs_render_normals and no map as input.
  * Not offered: world-space output; a normal channel in lcgs_render_backward_camera, lcgs_render_backward_compact, lcgs_fit_views
- * or the ownership step; a fused normal-consistency loss; an lcgs-app flag. */
+ * or the ownership step; a fused normal-consistency loss; an lcgs-app flag.  (That loss has since been added as a call of
+ * its own on the three maps, outside these two: lcgs_normal_consistency_loss_backward, below.) */
 /* d_normal: 3*H*W floats, CHW.  Enqueues on the context's stream, reads nothing back.  Stages under lcgs_set_profiling:
  * splat_normals, render_normals. */
 LCGS_API lcgs_status lcgs_render_normals(lcgs_context* ctx, float* d_normal);
@@ -445,6 +446,46 @@ LCGS_API lcgs_status lcgs_l2_loss_backward(lcgs_context* ctx, int width, int hei
 LCGS_API lcgs_status lcgs_photometric_loss_backward(lcgs_context* ctx, int width, int height, const float* d_img_chw,
                                                     const float* d_target_chw, float lambda_dssim, float* d_dL_dimg,
                                                     float* d_loss, float* d_terms);
+/* The normal-consistency loss of a frame's maps, the other half of the regulariser pair 2DGS, GOF, RaDe-GS and PGSR train with
+ * (the distortion term is a map, its loss a mean): the rendered normal against the normal of the rendered depth surface.
+ * Inputs of a W x H frame, binary32 device arrays as the library writes them: depth[H*W], the accumulated view z of
+ * LCGS_DEPTH_Z mode (lcgs_render_maps); alpha[H*W]; normal[3*H*W], CHW, view space (lcgs_render_normals).  `camera` supplies
+ * width, height, fov and aspect_ratio ONLY: the pose plays no part.  All per-pixel algebra is binary64, uncontracted, the
+ * inputs widened exactly, each output rounded to binary32 once (the edge vectors are differences of neighbouring points whose
+ * z agree to three or four digits on a smooth surface, and the result is divided by the length of their cross product):
+ *     tany = tan((double)fov / 180 * pi * 0.5)      tanx = tany * (double)aspect_ratio
+ *     rx(x) = ((x + 0.5) / W * 2 - 1) * tanx        ry(y) = ((y + 0.5) / H * 2 - 1) * tany       (pixel centres)
+ *     z_q   = depth_q / max(alpha_q, alpha_min)      P_q = (rx z_q, ry z_q, z_q)                 (view space)
+ *     for every INTERIOR pixel p = (x, y), 1 <= x <= W-2, 1 <= y <= H-2:
+ *       ex = P(x+1,y) - P(x-1,y)     ey = P(x,y+1) - P(x,y-1)
+ *       m  = ey x ex                 (faces the camera: a fronto-parallel plane gives (0, 0, -1), the sign convention of the
+ *                                     rendered normals' facing rule)
+ *       s  = sqrt(m.m + 1e-20)       nt = m / s
+ *       term_p = alpha_p - normal_p . nt
+ *     loss = weight / ((W-2)(H-2)) * sum_p term_p     (binary64 sum in a fixed order; same inputs -> same bits)
+ * Gradients, with c = weight / ((W-2)(H-2)); zero where nothing below reaches, the border included:
+ *     dL/dnormal_p = -c nt                                   (interior p)
+ *     g_m  = -c (normal_p / s - m (m . normal_p) / s^3)      g_ey = ex x g_m       g_ex = g_m x ey      (interior p, else 0)
+ *     G_q  = g_ex(q - x^) - g_ex(q + x^) + g_ey(q - y^) - g_ey(q + y^)           (a GATHER over q's four neighbours)
+ *     g_z  = G_q . (rx, ry, 1)
+ *     dL/ddepth_q = g_z / max(alpha_q, alpha_min)
+ *     dL/dalpha_q = [q interior] c  +  (alpha_q >= alpha_min ? -g_z depth_q / alpha_q^2 : 0)
+ * alpha_q is differentiated both in the leading alpha_p and through z: nothing is detached.  The clamp passes its gradient at
+ * equality, as torch.clamp_min does.
+ * The three gradients (d_dL_ddepth[H*W], d_dL_dalpha[H*W], d_dL_dnormal[3*H*W]: what lcgs_render_backward_normals takes) are
+ * either all non-NULL or all NULL.  All NULL is evaluation only: the call writes the loss, and its bits equal the gradient
+ * call's loss.  Gradients are overwritten, never accumulated, and the whole array is written, zeros at the border included.
+ * The call needs no kept frame: it is a function of its arguments, like the photometric loss.  It enqueues on the context's
+ * stream, reads nothing back and uses no atomics.
+ * LCGS_ERR_INVALID_ARG (before any device work): a NULL ctx, camera, input or loss pointer; width or height below 3; a weight
+ * that is not finite or is negative; an alpha_min that is not finite or is <= 0; gradient pointers of which some but not all
+ * are NULL; a gradient buffer that overlaps any input or another gradient buffer (the gather reads neighbours).
+ * Not offered: the term inside lcgs_fit_views; LCGS_DEPTH_INV_Z input; world-space normals; a median-depth surface; an
+ * lcgs-app flag for it; a camera gradient. */
+LCGS_API lcgs_status lcgs_normal_consistency_loss_backward(lcgs_context* ctx, const lcgs_camera* camera, const float* d_depth,
+                                                           const float* d_alpha, const float* d_normal, float weight,
+                                                           float alpha_min, float* d_dL_ddepth, float* d_dL_dalpha,
+                                                           float* d_dL_dnormal, float* d_loss);
 #define LCGS_LOSS_L2 0
 #define LCGS_LOSS_PHOTOMETRIC 1
 /* The loss lcgs_fit_views applies (default LCGS_LOSS_L2: unchanged behaviour). */

@@ -41,6 +41,7 @@ from .api import (  # noqa: F401
     load_library,
     local_to_world_matrix,
     mcmc_num_new,
+    normal_consistency_autograd,
     ply_filter_rows,
     projection_matrix,
     read_gs_ply,

@@ -299,6 +299,7 @@ def _signatures() -> dict:
         "lcgs_render_backward_adam": (st, [p, p, i, i, adam, *packs]),
         "lcgs_l2_loss_backward": (st, [p, i, i, p, p, p, p]),
         "lcgs_photometric_loss_backward": (st, [p, i, i, p, p, f, p, p, p]),
+        "lcgs_normal_consistency_loss_backward": (st, [p, cam, p, p, p, f, f, p, p, p, p]),
         "lcgs_set_fit_loss": (st, [p, i, f]),
         "lcgs_fit_views": (st, [p, i, cam, p, f, pp, grads, p]),
         # adaptive density control
@@ -971,6 +972,18 @@ class Renderer:
         _check(load_library().lcgs_photometric_loss_backward(self.ctx._h, W, H, _ptr(img), _ptr(target), lambda_dssim,
                                                              _ptr(dL_dimg), _ptr(loss), _ptr(terms)))
 
+    def normal_consistency_loss_backward(self, cam: Camera, depth, alpha, normal, dL_ddepth, dL_dalpha, dL_dnormal, loss,
+                                         weight: float = 0.05, alpha_min: float = 1e-3):
+        """lcgs_normal_consistency_loss_backward: loss[0] = weight x the mean over the interior pixels of alpha - normal . nt,
+        nt the unit normal of the rendered depth surface z = depth / max(alpha, alpha_min) (central differences of the
+        back-projected points, facing the camera), from a frame's depth [H, W] (mode "z"), alpha [H, W] and normal [3, H, W] maps;
+        cam supplies width, height, fov and aspect ratio only.  dL_ddepth, dL_dalpha, dL_dnormal (all three, or all None:
+        evaluation only) = its gradients, what backward_normals takes, written whole.  Device tensors, float32; binary64
+        inside; the same inputs give the same bits."""
+        _check(load_library().lcgs_normal_consistency_loss_backward(self.ctx._h, C.byref(cam), _ptr(depth), _ptr(alpha), _ptr(normal),
+                                                                    weight, alpha_min, _ptr(dL_ddepth), _ptr(dL_dalpha),
+                                                                    _ptr(dL_dnormal), _ptr(loss)))
+
     def set_fit_loss(self, kind: int, lambda_dssim: float = 0.2):
         """lcgs_set_fit_loss: the loss fit_views applies from now on -- LOSS_L2 (default) or LOSS_PHOTOMETRIC"""
         _check(load_library().lcgs_set_fit_loss(self.ctx._h, kind, lambda_dssim))
@@ -1577,6 +1590,33 @@ def render_autograd_normals(renderer: "Renderer", cam: Camera, pos, scale, rotq,
     re-renders its own view when the renderer's generation has moved.  The pose is not an input: the camera gradient of the
     normal channel is not offered."""
     return _autograd_frame(renderer, cam, (pos, scale, rotq, sh, opacity), bg, scale_modifier, "normals", depth_mode, center)
+
+
+def normal_consistency_autograd(renderer: "Renderer", cam: Camera, depth, alpha, normal, weight: float = 0.05,
+                                alpha_min: float = 1e-3):
+    """Differentiable normal-consistency loss for torch: `loss = normal_consistency_autograd(r, cam, depth, alpha, normal)`, a
+    scalar tensor, from a frame's depth (mode "z"), alpha and normal maps.  The forward is ONE
+    lcgs_normal_consistency_loss_backward call that also stores the three gradients; the backward hands them out scaled by
+    the incoming scalar.  Composes with the frame: `_, depth, alpha, _, normal = render_autograd_normals(r, cam, ...)`."""
+    import torch
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, depth, alpha, normal):
+            args = [t.detach().contiguous() for t in (depth, alpha, normal)]
+            grads = [torch.empty_like(t) for t in args]
+            loss = torch.empty(1, device=args[0].device, dtype=torch.float32)
+            renderer.normal_consistency_loss_backward(cam, *args, *grads, loss, weight, alpha_min)
+            ctx.save_for_backward(*grads)
+            ctx.shapes = (depth.shape, alpha.shape, normal.shape)
+            return loss[0]
+
+        @staticmethod
+        def backward(ctx, g_loss):
+            return tuple((g * g_loss).view(s) if need else None
+                         for g, s, need in zip(ctx.saved_tensors, ctx.shapes, ctx.needs_input_grad))
+
+    return _Fn.apply(depth, alpha, normal)
 
 
 def filter3d_autograd(renderer: "Renderer", scale, opacity, filt):

@@ -311,6 +311,14 @@ void launch_photometric_grad(int W, int H, const float* img, const float* target
 // the partials summed in index order -> loss[0]; terms (nullable) = { L1, SSIM }
 void launch_photometric_finish(int W, int H, const double* partials, float lambda, float* loss, float* terms,
                                hipStream_t stream);
+// the normal-consistency loss of a W x H frame's maps (include/lcgs_hip.h has the definition): one workgroup per 32 x 16 tile,
+// one binary64 partial each (normal_consistency_workgroups of them), summed in index order by the photometric loss's finish
+// step -> loss[0] = scale * sum of the interior pixels' terms, scale = weight / ((W - 2)(H - 2)).  The three gradients are all
+// NULL (evaluation only: the same loss bits) or all written whole, zeros at the border included.
+int64_t normal_consistency_workgroups(int W, int H);
+void launch_normal_consistency(int W, int H, double tanx, double tany, double scale, double alpha_min, const float* depth,
+                               const float* alpha, const float* normal, float* dL_ddepth, float* dL_dalpha, float* dL_dnormal,
+                               double* partials, float* loss, hipStream_t stream);
 // backward.hip: the per-splat half of the backward with the on-screen-only Adam update applied where the gradients are
 // formed (degree 3, frames that kept the colour Jacobian): no gradient rows are written at all
 // (r.shjac is not NULL; r.opacity is read for an antialiased frame, before the lane's update of the activated row)

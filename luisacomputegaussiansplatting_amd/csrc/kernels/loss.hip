@@ -19,6 +19,8 @@
 //   rows, is conflict free.
 //   staged inputs: the planes of one row sit side by side at a 48-word spacing (42 used) and the row pitch is 32 mod 64 words
 //   (96 for x | y, 160 for a | b | c), so the row pass is conflict free for the same reason.
+// Below it, on the same tiles and the same finish step: the normal-consistency loss of a frame's depth, alpha and normal maps
+// and its three gradients in one kernel (k_normal_consistency; its comment has the phases and the LDS reasoning).
 #include "launch.hpp"
 #include "stream_access.hpp"
 
@@ -204,38 +206,188 @@ __global__ void __launch_bounds__(kThreads) k_photometric_grad(int W, int H, con
     }
 }
 
-// ---- finish: the workgroups' pairs in index order (each thread a contiguous run, then the 256 run sums in order)
+// ---- finish: the workgroups' partials (N per workgroup) in index order -- each thread a contiguous run, then thread 0 the
+// 256 run sums in order.  Returns true on thread 0, whose `out` holds the N sums.
+template <int N>
+__device__ __forceinline__ bool sum_partials_in_order(int64_t num, const double* __restrict__ partials, double (&out)[N])
+{
+    __shared__ double s_sum[N][kThreads];
+    const int64_t     run = (num + kThreads - 1) / kThreads;
+    const int64_t     lo = (int64_t)threadIdx.x * run, hi = lo + run < num ? lo + run : num;
+#pragma unroll
+    for (int k = 0; k < N; ++k) out[k] = 0.0;
+    for (int64_t i = lo; i < hi; ++i) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) out[k] += partials[N * i + k];
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) s_sum[k][threadIdx.x] = out[k];
+    __syncthreads();
+    if (threadIdx.x != 0) return false;
+#pragma unroll
+    for (int k = 0; k < N; ++k) out[k] = 0.0;
+    for (int t = 0; t < kThreads; ++t) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) out[k] += s_sum[k][t];
+    }
+    return true;
+}
+
 __global__ void __launch_bounds__(kThreads) k_photometric_finish(int64_t num, double n, const double* __restrict__ partials,
                                                                  float lambda, float* __restrict__ loss, float* __restrict__ terms)
 {
-    __shared__ double s_sum[2][kThreads];
-    const int64_t     run = (num + kThreads - 1) / kThreads;
-    const int64_t     lo = (int64_t)threadIdx.x * run, hi = lo + run < num ? lo + run : num;
-    double            a = 0.0, b = 0.0;
-    for (int64_t i = lo; i < hi; ++i) {
-        a += partials[2 * i + 0];
-        b += partials[2 * i + 1];
+    double sums[2];
+    if (!sum_partials_in_order<2>(num, partials, sums)) return;
+    const double ssim = sums[0] / n, l1 = sums[1] / n, lam = (double)lambda;
+    loss[0] = (float)((1.0 - lam) * l1 + lam * (1.0 - ssim));
+    if (terms) {
+        terms[0] = (float)l1;
+        terms[1] = (float)ssim;
     }
-    s_sum[0][threadIdx.x] = a;
-    s_sum[1][threadIdx.x] = b;
+}
+
+// ---- the normal-consistency loss (the contract in include/lcgs_hip.h): one workgroup per 32 x 16 tile, three phases
+//   stage   z = depth / max(alpha, alpha_min) of the tile + a 2-pixel halo (0 outside the image: only cells that are not interior
+//           would read it, and those read nothing) and the ray slopes rx, ry of its columns and rows -> LDS
+//   cells   every cell of the tile + a 1-pixel halo (34 x 18, a flat index over the threads): ex, ey, m, s, nt from the staged z,
+//           the rendered normal from global memory -> g_ex, g_ey (0 for a cell that is not interior) into LDS, six planes;
+//           a cell of the tile proper also adds its term to the thread's sum and writes dL/dnormal
+//   gather  every pixel of the tile: G from its four neighbours' cells, g_z -> dL/ddepth, dL/dalpha, written once
+// All binary64, uncontracted; each output rounded once.  The evaluation-only kernel runs stage and the tile's own cells in the
+// same order with the same operations, so its partial is the gradient kernel's bit for bit.
+// LDS (34.5 KB: four workgroups a CU): every array holds doubles at consecutive indices for consecutive lanes.  The gather
+// reads four cells of a plane per pixel, and the 32 lanes that one ds_read_b64 serves together are one tile row: 32 consecutive
+// doubles = the 64 banks once each, whatever the pitch (34).  The cell phase writes plane[i] for lane i (ds_write_b64 serves 16
+// lanes together: 32 consecutive words, the 32 banks once each) and reads z at (row, column) of a flat cell index: 32
+// consecutive cells span at most two rows of pitch 36, i.e. 32 of 34 consecutive doubles with a hole of two -- at most two
+// 2-way conflicts per read, on five reads a cell beside some 150 binary64 operations.
+// The planes were measured against every pixel recomputing its own and its four neighbours' cells (no planes, 6 KB of LDS, twice
+// the waves a SIMD): 47.7 us against 63.7 us at 1920 x 1080 (profiles/normal_consistency_bench.txt), so the planes stay.
+constexpr int kZW = kTW + 4, kZH = kTH + 4; // staged z: 36 x 20
+constexpr int kGW = kTW + 2, kGH = kTH + 2; // cells: 34 x 18
+
+template <bool GRAD>
+__global__ void __launch_bounds__(kThreads) k_normal_consistency(int W, int H, double tanx, double tany, double scale,
+                                                                 double alpha_min, const float* __restrict__ depth,
+                                                                 const float* __restrict__ alpha, const float* __restrict__ normal,
+                                                                 float* __restrict__ dL_ddepth, float* __restrict__ dL_dalpha,
+                                                                 float* __restrict__ dL_dnormal, double* __restrict__ partials)
+{
+    __shared__ double s_z[kZH][kZW];
+    __shared__ double s_rx[kZW], s_ry[kZH];
+    __shared__ double s_g[6][GRAD ? kGH * kGW : 1]; // g_ex at planes 0..2, g_ey at 3..5
+    __shared__ double s_red[kThreads / 64];
+    const int     tid = threadIdx.x;
+    const int     x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+    const int64_t plane = (int64_t)W * H;
+    for (int i = tid; i < kZH * kZW; i += kThreads) {
+        const int  r = i / kZW, c = i - r * kZW;
+        const int  gy = y0 - 2 + r, gx = x0 - 2 + c;
+        double     z = 0.0;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const int64_t o = (int64_t)gy * W + gx;
+            const double  a = (double)alpha[o];
+            z = (double)depth[o] / (a < alpha_min ? alpha_min : a);
+        }
+        s_z[r][c] = z;
+    }
+    if (tid < kZW) s_rx[tid] = (((double)(x0 - 2 + tid) + 0.5) / (double)W * 2.0 - 1.0) * tanx;
+    if (tid >= 64 && tid < 64 + kZH) s_ry[tid - 64] = (((double)(y0 - 2 + tid - 64) + 0.5) / (double)H * 2.0 - 1.0) * tany;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        a = 0.0, b = 0.0;
-        for (int t = 0; t < kThreads; ++t) {
-            a += s_sum[0][t];
-            b += s_sum[1][t];
-        }
-        const double ssim = a / n, l1 = b / n, lam = (double)lambda;
-        loss[0] = (float)((1.0 - lam) * l1 + lam * (1.0 - ssim));
-        if (terms) {
-            terms[0] = (float)l1;
-            terms[1] = (float)ssim;
+    double sum = 0.0;
+    for (int i = tid; i < kGH * kGW; i += kThreads) {
+        const int  r = i / kGW, c = i - r * kGW; // cell (r, c) is pixel (x0 - 1 + c, y0 - 1 + r): z at s_z[r + 1][c + 1]
+        const int  gy = y0 - 1 + r, gx = x0 - 1 + c;
+        const bool own = r >= 1 && r <= kTH && c >= 1 && c <= kTW; // a cell of the tile proper
+        if (!GRAD && !own) continue;
+        const int64_t o = (int64_t)gy * W + gx;
+        if (gx >= 1 && gx <= W - 2 && gy >= 1 && gy <= H - 2) { // interior: its four neighbours are pixels
+            const double zxm = s_z[r + 1][c], zxp = s_z[r + 1][c + 2], zym = s_z[r][c + 1], zyp = s_z[r + 2][c + 1];
+            const double rxm = s_rx[c], rx = s_rx[c + 1], rxp = s_rx[c + 2], rym = s_ry[r], ry = s_ry[r + 1], ryp = s_ry[r + 2];
+            const double ex0 = rxp * zxp - rxm * zxm, ex1 = ry * zxp - ry * zxm, ex2 = zxp - zxm;
+            const double ey0 = rx * zyp - rx * zym, ey1 = ryp * zyp - rym * zym, ey2 = zyp - zym;
+            const double m0 = ey1 * ex2 - ey2 * ex1, m1 = ey2 * ex0 - ey0 * ex2, m2 = ey0 * ex1 - ey1 * ex0; // ey x ex
+            const double inv = 1.0 / sqrt((m0 * m0 + m1 * m1 + m2 * m2) + 1e-20);
+            const double nt0 = m0 * inv, nt1 = m1 * inv, nt2 = m2 * inv;
+            const double n0 = (double)normal[o], n1 = (double)normal[plane + o], n2 = (double)normal[2 * plane + o];
+            if (own) sum += (double)alpha[o] - (n0 * nt0 + n1 * nt1 + n2 * nt2);
+            if (GRAD) {
+                if (own) {
+                    dL_dnormal[o]             = (float)(-scale * nt0);
+                    dL_dnormal[plane + o]     = (float)(-scale * nt1);
+                    dL_dnormal[2 * plane + o] = (float)(-scale * nt2);
+                }
+                // g_m = -c (n / s - m (m . n) / s^3), g_ey = ex x g_m, g_ex = g_m x ey
+                const double t   = (m0 * n0 + m1 * n1 + m2 * n2) * (inv * inv * inv);
+                const double gm0 = -scale * (n0 * inv - m0 * t), gm1 = -scale * (n1 * inv - m1 * t), gm2 = -scale * (n2 * inv - m2 * t);
+                s_g[0][i] = gm1 * ey2 - gm2 * ey1;
+                s_g[1][i] = gm2 * ey0 - gm0 * ey2;
+                s_g[2][i] = gm0 * ey1 - gm1 * ey0;
+                s_g[3][i] = ex1 * gm2 - ex2 * gm1;
+                s_g[4][i] = ex2 * gm0 - ex0 * gm2;
+                s_g[5][i] = ex0 * gm1 - ex1 * gm0;
+            }
+        } else if (GRAD) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) s_g[k][i] = 0.0;
+            if (own && gx < W && gy < H) { // a border pixel (an own cell has gx, gy >= 0)
+                dL_dnormal[o]             = 0.0f;
+                dL_dnormal[plane + o]     = 0.0f;
+                dL_dnormal[2 * plane + o] = 0.0f;
+            }
         }
     }
+    sum = wave_sum(sum);
+    if ((tid & 63) == 0) s_red[tid >> 6] = sum;
+    __syncthreads(); // (the planes of s_g too)
+    if (tid == 0) partials[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+    if (!GRAD) return;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int r = (tid >> 5) + half * (kTH / 2), c = tid & 31;
+        const int gx = x0 + c, gy = y0 + r;
+        if (gx >= W || gy >= H) continue;
+        const int i = (r + 1) * kGW + (c + 1); // the pixel's own cell
+        // G = g_ex(q - x^) - g_ex(q + x^) + g_ey(q - y^) - g_ey(q + y^)
+        const double G0 = ((s_g[0][i - 1] - s_g[0][i + 1]) + s_g[3][i - kGW]) - s_g[3][i + kGW];
+        const double G1 = ((s_g[1][i - 1] - s_g[1][i + 1]) + s_g[4][i - kGW]) - s_g[4][i + kGW];
+        const double G2 = ((s_g[2][i - 1] - s_g[2][i + 1]) + s_g[5][i - kGW]) - s_g[5][i + kGW];
+        const double gz = (G0 * s_rx[c + 2] + G1 * s_ry[r + 2]) + G2;
+        const int64_t o = (int64_t)gy * W + gx;
+        const double  a = (double)alpha[o], d = (double)depth[o];
+        double        ga = gx >= 1 && gx <= W - 2 && gy >= 1 && gy <= H - 2 ? scale : 0.0;
+        if (a >= alpha_min) ga += -gz * d / (a * a); // (the clamp passes its gradient at equality)
+        st_stream(dL_ddepth + o, (float)(gz / (a < alpha_min ? alpha_min : a)));
+        st_stream(dL_dalpha + o, (float)ga);
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) k_normal_consistency_finish(int64_t num, double scale, const double* __restrict__ partials,
+                                                                        float* __restrict__ loss)
+{
+    double sum[1];
+    if (sum_partials_in_order<1>(num, partials, sum)) loss[0] = (float)(scale * sum[0]);
 }
 
 inline dim3 tile_grid(int W, int H) { return dim3((unsigned)((W + kTW - 1) / kTW), (unsigned)((H + kTH - 1) / kTH), 3u); }
 } // namespace
+
+int64_t normal_consistency_workgroups(int W, int H) { return (int64_t)((W + kTW - 1) / kTW) * ((H + kTH - 1) / kTH); }
+
+void launch_normal_consistency(int W, int H, double tanx, double tany, double scale, double alpha_min, const float* depth,
+                               const float* alpha, const float* normal, float* dL_ddepth, float* dL_dalpha, float* dL_dnormal,
+                               double* partials, float* loss, hipStream_t stream)
+{
+    const dim3 grid((unsigned)((W + kTW - 1) / kTW), (unsigned)((H + kTH - 1) / kTH));
+    if (dL_ddepth)
+        hipLaunchKernelGGL(k_normal_consistency<true>, grid, dim3(kThreads), 0, stream, W, H, tanx, tany, scale, alpha_min, depth,
+                           alpha, normal, dL_ddepth, dL_dalpha, dL_dnormal, partials);
+    else
+        hipLaunchKernelGGL(k_normal_consistency<false>, grid, dim3(kThreads), 0, stream, W, H, tanx, tany, scale, alpha_min, depth,
+                           alpha, normal, dL_ddepth, dL_dalpha, dL_dnormal, partials);
+    hipLaunchKernelGGL(k_normal_consistency_finish, dim3(1), dim3(kThreads), 0, stream, normal_consistency_workgroups(W, H), scale,
+                       partials, loss);
+}
 
 int64_t photometric_workgroups(int W, int H)
 {

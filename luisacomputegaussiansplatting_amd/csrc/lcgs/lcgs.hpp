@@ -105,6 +105,16 @@ public:
     {
         check(lcgs_photometric_loss_backward(m_ctx, width, height, d_img, d_target, lambda_dssim, d_dL_dimg, d_loss, d_terms));
     }
+    // the normal-consistency loss of a frame's depth (LCGS_DEPTH_Z), alpha and normal maps and its three gradients, what
+    // lcgs_render_backward_normals takes (device pointers; the gradients all three or all NULL: evaluation only; cam supplies
+    // width, height, fov and aspect ratio only)
+    void normal_consistency_loss_backward(const Camera& cam, const float* d_depth, const float* d_alpha, const float* d_normal,
+                                          float* d_dL_ddepth, float* d_dL_dalpha, float* d_dL_dnormal, float* d_loss,
+                                          float weight = 0.05f, float alpha_min = 1e-3f)
+    {
+        check(lcgs_normal_consistency_loss_backward(m_ctx, &cam, d_depth, d_alpha, d_normal, weight, alpha_min, d_dL_ddepth,
+                                                    d_dL_dalpha, d_dL_dnormal, d_loss));
+    }
     // the loss Scene::fit_views applies: LCGS_LOSS_L2 (default) or LCGS_LOSS_PHOTOMETRIC
     void set_fit_loss(int kind, float lambda_dssim = 0.2f) { check(lcgs_set_fit_loss(m_ctx, kind, lambda_dssim)); }
     // LCGS_RASTER_CLASSIC (default) or LCGS_RASTER_ANTIALIASED: the fused frame's opacity compensation (lcgs_set_raster_mode)
