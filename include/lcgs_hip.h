@@ -728,6 +728,75 @@ LCGS_API lcgs_status lcgs_scene_extent(int num_cameras, const lcgs_camera* camer
 LCGS_API lcgs_status lcgs_points_read_ply(const char* path, int64_t* num_points, float** pos, float** rgb);
 LCGS_API void        lcgs_points_free(float* pos, float* rgb);
 
+/* ---- a surface out of the trained scene: TSDF fusion of depth maps, marching tetrahedra (no reference counterpart) - */
+/* The last step of 2DGS, GOF, RaDe-GS and PGSR: the rendered depth maps of the training views (lcgs_render_maps, LCGS_DEPTH_Z)
+ * are fused into a truncated signed distance volume -- Curless & Levoy's running mean with projective distance and nearest-pixel
+ * lookup, what Open3D's fusion does -- and the volume's zero level set is extracted as a welded, indexed, consistently oriented
+ * triangle mesh.
+ * The volume is the caller's: samples on an nx x ny x nz lattice, sample (i, j, k) at linear index s = (k ny + j) nx + i and at
+ * world position X_c = fl(origin_c + fl(voxel_size * (float)i_c)); the caller zeroes d_tsdf and d_weight (and d_rgb) before the
+ * first view. */
+typedef struct lcgs_tsdf_volume {
+    float  origin[3], voxel_size; /* voxel_size finite, > 0 */
+    int    nx, ny, nz;            /* each >= 1; nx ny nz <= 2^31 - 1 */
+    float *d_tsdf, *d_weight;     /* nx ny nz floats each */
+    float *d_rgb;                 /* 3 floats per sample (sample-major), or NULL: no colour */
+} lcgs_tsdf_volume;
+typedef struct lcgs_tsdf_config {
+    float trunc, depth_max, alpha_min; /* each finite and > 0 */
+} lcgs_tsdf_config;
+/* Integrates num_views views, in call order, into every sample.  Per view the constants are the frame's own (right, up, front,
+ * tx, ty, tz, inv_tanx, inv_tany, W, H of the camera); d_depths[v] is W H floats in the library's layout, pixel (x, y) being the
+ * ray rx(x), ry(y) of lcgs_normal_consistency_loss_backward (no row flip).  Every operation binary32, uncontracted, `/` one IEEE
+ * division.  For sample X and each view:
+ *     v_c = fl(fl(fl(r0 X0 + r1 X1) + r2 X2) + t_c) for the rows right / up / front;  z = v_2;  skip unless z > 0 (a NaN skips)
+ *     ux = fl(fl(fl(fl(v_0 / z) * inv_tanx) + 1) * fl(0.5f * W)), uy likewise with v_1, inv_tany, H
+ *     skip unless 0 <= ux < W and 0 <= uy < H (compared as floats);  px = (int)floorf(ux), py = (int)floorf(uy)
+ *     d = depth[py W + px];  with an alpha map: a = alpha[py W + px], skip unless a >= alpha_min, d = fl(d / a)
+ *     skip unless d is finite, d > 0, d <= depth_max;  sdf = fl(d - z);  skip if sdf < -trunc;  t = fminf(1.0f, fl(sdf / trunc))
+ *     w = weight[s];  tsdf[s] = fl(fl(fl(tsdf[s] * w) + t) / fl(w + 1));  rgb[s][c] likewise from image[c H W + py W + px] where
+ *     the volume and the view both have colour;  weight[s] = fl(w + 1)
+ * A batch of views leaves the bits the same views leave passed one call at a time, in order.  d_alphas and d_images may be NULL
+ * (no view has one) or hold NULL entries.  Only enqueues; needs no kept frame; num_views == 0: LCGS_OK, nothing touched.
+ * LCGS_ERR_INVALID_ARG before any device work: a NULL context, volume, config, d_tsdf, d_weight, cameras, d_depths or depth map;
+ * a lattice dimension < 1 or more than 2^31 - 1 samples; a voxel size, origin or config value that is not finite, or not > 0 where
+ * required; num_views < 0; a camera with width or height < 1; a volume array that overlaps another volume array or an input map. */
+#define LCGS_TSDF_VIEW_CHUNK 42 /* views per launch: view counts around its multiples are the kernel's edge cases */
+LCGS_API lcgs_status lcgs_tsdf_integrate(lcgs_context* ctx, const lcgs_tsdf_volume* volume, const lcgs_tsdf_config* cfg, int num_views,
+                                         const lcgs_camera* cameras, const float* const* d_depths, const float* const* d_alphas,
+                                         const float* const* d_images);
+/* The mesh, by marching tetrahedra on the 6-tetrahedron Kuhn split: no case table, no ambiguous case, a closed 2-manifold wherever
+ * the volume is valid, and vertices welded by rank instead of by sorting or hashing.
+ *   cells      cell (i, j, k), i < nx - 1 etc., is VALID iff all 8 corner samples have weight >= weight_min (finite, > 0); a sample is
+ *              INSIDE iff tsdf < 0 (neither -0.0f nor a NaN is inside)
+ *   split      tetrahedron q = 0 .. 5 of a cell belongs to the q-th permutation (a, b, c) of the axes in lexicographic order:
+ *              corners c0 = (0,0,0), c1 = c0 + e_a, c2 = c1 + e_b, c3 = (1,1,1)
+ *   edges      a tetrahedron's edge runs from a lower sample lo to lo + dir, dir in {0,1}^3 \ {0}, coded dx + 2 dy + 4 dz; it CROSSES
+ *              iff exactly one endpoint is inside; its key is (s_lo, dir), ordered by s_lo, then dir
+ *   vertices   one per crossing edge of at least one valid cell, numbered in ascending key order; with a = lo, b = lo + dir:
+ *              lambda = fl(t_a / fl(t_a - t_b)), p_c = fl(X_a,c + fl(lambda * fl(X_b,c - X_a,c))); the colour by the same formula
+ *   triangles  one corner against three: one triangle; two against two: a quad, split along the diagonal through its lowest vertex
+ *              id.  Order: by cell linear index ((k (ny-1) + j) (nx-1) + i), then tetrahedron, then a quad's two triangles by their
+ *              other two vertex ids, each pair sorted, compared lexicographically.  Each triangle is wound so that in exact
+ *              arithmetic (v1 - v0) x (v2 - v0) points from the inside corners to the outside corners -- decided from the sign
+ *              case, not from computed geometry -- and rotated so that its first index is its lowest vertex id.
+ * Same inputs, same bits.  lcgs_tsdf_mesh_count reads the two counts back (one synchronisation).  lcgs_tsdf_mesh_extract writes
+ * d_vertices (3 floats per vertex), d_vertex_rgb (nullable; needs volume->d_rgb) and d_triangles (3 indices per triangle) and
+ * returns the counts; LCGS_ERR_CAPACITY with the needed counts in the two outputs and nothing written when either capacity is
+ * too small, or when either count is 2^32 or more.  An empty mesh (any of nx, ny, nz equal to 1 included) is LCGS_OK with zeros.
+ * Scratch is the context's: 12 bytes per sample, grown on demand.
+ * Not offered: sparse or hashed volumes; weight caps; trilinear depth lookup; median depth; mesh decimation or smoothing; an
+ * lcgs-app flag; any gradient. */
+LCGS_API lcgs_status lcgs_tsdf_mesh_count(lcgs_context* ctx, const lcgs_tsdf_volume* volume, float weight_min, uint64_t* num_vertices,
+                                          uint64_t* num_triangles);
+LCGS_API lcgs_status lcgs_tsdf_mesh_extract(lcgs_context* ctx, const lcgs_tsdf_volume* volume, float weight_min, uint64_t cap_vertices,
+                                            uint64_t cap_triangles, float* d_vertices, float* d_vertex_rgb, uint32_t* d_triangles,
+                                            uint64_t* num_vertices, uint64_t* num_triangles);
+/* Host: a binary little-endian PLY of nv vertices (float x y z; with h_rgb also uchar red green blue, clamp(rgb, 0, 1) * 255
+ * rounded to nearest) and nt triangular faces (uchar 3, int indices).  LCGS_ERR_IO: the file cannot be opened or written. */
+LCGS_API lcgs_status lcgs_mesh_write_ply(const char* path, uint64_t nv, const float* h_vertices, const float* h_rgb, uint64_t nt,
+                                         const uint32_t* h_triangles);
+
 /* ---- multi-GPU (no reference counterpart: one device, app/main.cpp:162-163) ------------------------ */
 /* One process per GPU, scene replicated, one view per GPU; RCCL is bound at run time (absent: LCGS_ERR_NO_DEVICE). */
 typedef struct lcgs_comm lcgs_comm;

@@ -30,6 +30,7 @@ from .api import (  # noqa: F401
     RASTER_CLASSIC,
     Renderer,
     SHProcessor,
+    TsdfVolume,
     build_library,
     camera_grad_to_twist,
     camera_with_vectors,
@@ -55,6 +56,7 @@ from .api import (  # noqa: F401
     shard_rows,
     synth_scene,
     world_to_local_matrix,
+    write_mesh_ply,
     write_png,
     write_ply_raw,
 )

@@ -54,6 +54,8 @@ LCGS_ERR_STATE = 8
 DEPTH_Z, DEPTH_INV_Z = 0, 1  # LCGS_DEPTH_Z, LCGS_DEPTH_INV_Z
 _DEPTH_MODES = {"z": DEPTH_Z, "inv_z": DEPTH_INV_Z}
 LCGS_KNN_CHUNK = 256  # sorted points per query workgroup of the nearest-neighbour search (sizes around its multiples are edge cases)
+LCGS_TSDF_VIEW_CHUNK = 42  # kTsdfViewChunk: views per launch of tsdf_integrate (view counts around its multiples are edge cases)
+LCGS_ERR_CAPACITY = 5
 LCGS_FILTER3D_VIEW_CHUNK = 64  # kFilter3dViewChunk: views per launch of filter3d_accumulate (view counts around its multiples are edge cases)
 # lcgs_set_fit_loss kinds (LCGS_LOSS_* in include/lcgs_hip.h)
 LOSS_L2, LOSS_PHOTOMETRIC = 0, 1
@@ -178,6 +180,15 @@ class _InitConfig(C.Structure):
     _fields_ = [("initial_opacity", C.c_float), ("min_dist2", C.c_float)]
 
 
+class _TsdfVolume(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("voxel_size", C.c_float), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
+                ("d_tsdf", C.c_void_p), ("d_weight", C.c_void_p), ("d_rgb", C.c_void_p)]
+
+
+class _TsdfConfig(C.Structure):
+    _fields_ = [("trunc", C.c_float), ("depth_max", C.c_float), ("alpha_min", C.c_float)]
+
+
 class _SparseRows(C.Structure):
     _fields_ = [("d_rows", C.c_void_p), ("num_rows", C.c_int64), ("owner_first", C.c_int64 * (LCGS_MAX_RANKS + 2))]
 
@@ -206,7 +217,7 @@ STRUCTS = {
     "lcgs_stage_times": _StageTimes, "lcgs_frame_stats": _FrameStats, "lcgs_grads": _Grads, "lcgs_params": _Params,
     "lcgs_adam_config": _AdamConfig, "lcgs_densify_stats": _DensifyStats, "lcgs_densify_config": _DensifyConfig,
     "lcgs_mcmc_config": _McmcConfig, "lcgs_mcmc_noise_config": _McmcNoiseConfig,
-    "lcgs_init_config": _InitConfig, "lcgs_contrib_stats": _ContribStats, "lcgs_prune_config": _PruneConfig,
+    "lcgs_init_config": _InitConfig, "lcgs_tsdf_volume": _TsdfVolume, "lcgs_tsdf_config": _TsdfConfig, "lcgs_contrib_stats": _ContribStats, "lcgs_prune_config": _PruneConfig,
     "lcgs_sparse_rows": _SparseRows, "lcgs_comm_stats": _CommStats, "lcgs_comm_selftest_report": _SelftestReport,
     "lcgs_scene_host": _SceneHost,
 }
@@ -324,6 +335,11 @@ def _signatures() -> dict:
         "lcgs_scene_extent": (st, [i, cam, p, p]),
         "lcgs_points_read_ply": (st, [s, pi64, pp, pp]),
         "lcgs_points_free": (None, [p, p]),
+        # TSDF fusion, marching tetrahedra
+        "lcgs_tsdf_integrate": (st, [p, ptr["tsdf_volume"], ptr["tsdf_config"], i, cam, pp, pp, pp]),
+        "lcgs_tsdf_mesh_count": (st, [p, ptr["tsdf_volume"], f, p, p]),
+        "lcgs_tsdf_mesh_extract": (st, [p, ptr["tsdf_volume"], f, u64, u64, p, p, p, p, p]),
+        "lcgs_mesh_write_ply": (st, [s, u64, p, p, u64, p]),
         # multi-GPU
         "lcgs_comm_unique_id": (st, [p]),
         "lcgs_comm_create": (st, [p, p, i, i, pp]),
@@ -1212,6 +1228,52 @@ class Renderer:
         _check(load_library().lcgs_filter3d_backward(self.ctx._h, int(opacity.shape[0]), _ptr(scale), _ptr(opacity), _ptr(filt),
                                                      _ptr(rows), _ptr(count), _ptr(dscale), _ptr(dopacity)))
 
+    # ---- a surface out of the scene: TSDF fusion of depth maps, marching tetrahedra
+    def tsdf_integrate(self, volume: "TsdfVolume", cams, depths, alphas=None, images=None, trunc: Optional[float] = None,
+                       depth_max: float = 1e4, alpha_min: float = 0.5):
+        """lcgs_tsdf_integrate: fuses the views `cams` (a sequence of Camera) into `volume`, in order -- depths[v] [H, W] the
+        accumulated view z of render_maps (divided by alphas[v] where given; pixels with alpha < alpha_min are skipped), images[v]
+        [3, H, W] the colours of a volume with rgb.  alphas / images: None, or sequences that may hold None.  trunc: the truncation
+        distance (default: 4 voxels).  Curless & Levoy's running mean, nearest-pixel lookup; a batch leaves the bits of the same
+        views passed one call at a time.  Only enqueues."""
+        cams, n = list(cams), len(cams)
+        assert len(depths) == n and (alphas is None or len(alphas) == n) and (images is None or len(images) == n)
+        for k, c in enumerate(cams):
+            assert int(depths[k].numel()) == c.width * c.height, f"depth map {k} is not {c.height} x {c.width}"
+
+        def table(maps):
+            return None if maps is None else (C.c_void_p * max(n, 1))(*[_ptr(m) for m in maps])
+
+        cfg = _TsdfConfig(4.0 * volume.voxel_size if trunc is None else trunc, depth_max, alpha_min)
+        vol = volume._struct()
+        _check(load_library().lcgs_tsdf_integrate(self.ctx._h, C.byref(vol), C.byref(cfg), n, (Camera * max(n, 1))(*cams), table(depths),
+                                                  table(alphas), table(images)))
+
+    def tsdf_mesh_count(self, volume: "TsdfVolume", weight_min: float = 1.0):
+        """lcgs_tsdf_mesh_count: (vertices, triangles) of the mesh tsdf_mesh would return.  Synchronises once."""
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        vol = volume._struct()
+        _check(load_library().lcgs_tsdf_mesh_count(self.ctx._h, C.byref(vol), weight_min, C.addressof(nv), C.addressof(nt)))
+        return int(nv.value), int(nt.value)
+
+    def tsdf_mesh(self, volume: "TsdfVolume", weight_min: float = 1.0):
+        """lcgs_tsdf_mesh_count + lcgs_tsdf_mesh_extract: the zero level set of `volume` over the cells whose 8 samples all have
+        weight >= weight_min, by marching tetrahedra -- (vertices [V, 3] float32, rgb [V, 3] float32 or None, triangles [T, 3]
+        int64 holding the 32-bit indices), device tensors; welded, consistently oriented (normals point from inside to outside),
+        deterministic."""
+        import torch
+
+        nv, nt = self.tsdf_mesh_count(volume, weight_min)
+        dev = volume.tsdf.device
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        rgb = torch.empty((nv, 3), dtype=torch.float32, device=dev) if volume.rgb is not None else None
+        tri = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        got_v, got_t = C.c_uint64(0), C.c_uint64(0)
+        vol = volume._struct()
+        _check(load_library().lcgs_tsdf_mesh_extract(self.ctx._h, C.byref(vol), weight_min, nv, nt, _ptr(vertices), _ptr(rgb), _ptr(tri),
+                                                     C.addressof(got_v), C.addressof(got_t)))
+        assert (got_v.value, got_t.value) == (nv, nt)
+        return vertices, rgb, tri.to(torch.int64) & 0xFFFFFFFF
 
     # ---- a scene from a point cloud (DESIGN.md 9)
     def init_from_points(self, pos, rgb, sh_degree: int = 3, initial_opacity: float = 0.1, min_dist2: float = 1e-7):
@@ -1234,6 +1296,52 @@ class Renderer:
         packs = _params(raw, activated)
         _check(load_library().lcgs_scene_init_from_points(self.ctx._h, int(pos.shape[0]), sh_degree, _ptr(pos), _ptr(rgb),
                                                           C.byref(cfg), *map(C.byref, packs)))
+
+
+class TsdfVolume:
+    """lcgs_tsdf_volume: a dense TSDF lattice of dims = (nx, ny, nz) samples, sample (i, j, k) at origin + voxel_size * (i, j, k);
+    device tensors tsdf / weight [nz, ny, nx] and rgb [nz, ny, nx, 3] (or None), zeroed."""
+
+    def __init__(self, origin, voxel_size: float, dims, rgb: bool = False, device="cuda:0"):
+        import torch
+
+        self.origin = tuple(float(x) for x in origin)
+        self.voxel_size = float(voxel_size)
+        self.dims = tuple(int(x) for x in dims)
+        nx, ny, nz = self.dims
+        self.tsdf = torch.zeros((nz, ny, nx), dtype=torch.float32, device=device)
+        self.weight = torch.zeros((nz, ny, nx), dtype=torch.float32, device=device)
+        self.rgb = torch.zeros((nz, ny, nx, 3), dtype=torch.float32, device=device) if rgb else None
+
+    @classmethod
+    def from_tensors(cls, origin, voxel_size: float, dims, tsdf, weight, rgb=None) -> "TsdfVolume":
+        """a volume over the caller's contiguous device tensors (nx ny nz floats each, rgb three per sample), left as they are"""
+        self = cls.__new__(cls)
+        self.origin, self.voxel_size, self.dims = tuple(float(x) for x in origin), float(voxel_size), tuple(int(x) for x in dims)
+        n = self.dims[0] * self.dims[1] * self.dims[2]
+        assert tsdf.numel() == n and weight.numel() == n and (rgb is None or rgb.numel() == 3 * n)
+        self.tsdf, self.weight, self.rgb = tsdf, weight, rgb
+        return self
+
+    def zero_(self):
+        for t in (self.tsdf, self.weight, self.rgb):
+            if t is not None:
+                t.zero_()
+        return self
+
+    def _struct(self) -> _TsdfVolume:
+        return _TsdfVolume(_f3(self.origin), self.voxel_size, *self.dims, _ptr(self.tsdf).value, _ptr(self.weight).value,
+                           _ptr(self.rgb).value)
+
+
+def write_mesh_ply(path: str, vertices, triangles, rgb=None):
+    """lcgs_mesh_write_ply: a binary PLY of vertices [V, 3], optional rgb [V, 3] in [0, 1] (written as uchar) and triangles
+    [T, 3]; tensors (copied to the host) or arrays"""
+    host = lambda a, dt: np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=dt)
+    v, t = host(vertices, np.float32).reshape(-1, 3), host(triangles, np.uint32).reshape(-1, 3)
+    c = None if rgb is None else host(rgb, np.float32).reshape(-1, 3)
+    assert c is None or c.shape == v.shape
+    _check(load_library().lcgs_mesh_write_ply(os.fsencode(path), v.shape[0], _ptr(v), _ptr(c), t.shape[0], _ptr(t)))
 
 
 def knn_mean_dist2(ctx: Context, pos):

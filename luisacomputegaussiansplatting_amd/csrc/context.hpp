@@ -203,6 +203,9 @@ struct lcgs_context {
     DeviceBuffer mc_w, mc_dead, mc_dead_incl, mc_cdf, mc_count, mc_dead_list, mc_draw, mc_scan_temp, mc_status;
     // lcgs_filter3d_finalize (abi_filter3d.cpp): the word its reduction leaves the largest finite min_z in
     DeviceBuffer f3_word;
+    // lcgs_tsdf_mesh_count / _extract (abi_tsdf.cpp): per sample the edge-mask / triangle-count word, the vertex counts and the
+    // triangle counts (scanned in place); the scan's block sums; the two u64 totals
+    DeviceBuffer ts_word, ts_vcount, ts_tcount, ts_scan_temp, ts_totals;
     // lcgs_knn_mean_dist2 / lcgs_scene_init_from_points (abi_init.cpp): Morton keys and original indices (the sort's ping-pong),
     // the sort's workspace, the sorted points, the per-chunk boxes, the box partials + grid, the init call's dist2
     DeviceBuffer knn_keys[2], knn_vals[2], knn_sort_ws, knn_sorted, knn_boxes, knn_grid, knn_dist2;

@@ -469,6 +469,42 @@ lcgs_status lcgs_ply_filter_rows(const char* in_path, const char* out_path, int6
     return LCGS_OK;
 }
 
+// A triangle mesh (lcgs_tsdf_mesh_extract's arrays, on the host): vertices x y z [+ uchar red green blue], faces as uchar 3 + int x 3.
+lcgs_status lcgs_mesh_write_ply(const char* path, uint64_t nv, const float* h_vertices, const float* h_rgb, uint64_t nt,
+                                const uint32_t* h_triangles)
+{
+    if (!path || (nv > 0 && !h_vertices) || (nt > 0 && !h_triangles)) return fail(LCGS_ERR_INVALID_ARG, "lcgs_mesh_write_ply: NULL argument");
+    if (nv > 0x7FFFFFFFull) return fail(LCGS_ERR_INVALID_ARG, "lcgs_mesh_write_ply: the face indices of a PLY are 32-bit ints");
+    FILE* fp = fopen(path, "wb");
+    if (!fp) return fail(LCGS_ERR_IO, std::string("cannot open ") + path + " for writing");
+    fprintf(fp, "ply\nformat binary_little_endian 1.0\nelement vertex %llu\nproperty float x\nproperty float y\nproperty float z\n",
+            (unsigned long long)nv);
+    if (h_rgb) fprintf(fp, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
+    fprintf(fp, "element face %llu\nproperty list uchar int vertex_indices\nend_header\n", (unsigned long long)nt);
+    bool ok = true;
+    for (uint64_t j = 0; j < nv && ok; ++j) {
+        unsigned char rec[15];
+        memcpy(rec, h_vertices + 3 * j, 12);
+        for (int c = 0; c < 3 && h_rgb; ++c) {
+            const float x = h_rgb[3 * j + c];
+            rec[12 + c]   = (unsigned char)(x > 0.0f ? (x < 1.0f ? x * 255.0f + 0.5f : 255.0f) : 0.0f); // (a NaN: 0)
+        }
+        const size_t len = h_rgb ? 15 : 12;
+        ok               = fwrite(rec, 1, len, fp) == len;
+    }
+    for (uint64_t j = 0; j < nt && ok; ++j) {
+        unsigned char rec[13] = { 3 };
+        memcpy(rec + 1, h_triangles + 3 * j, 12);
+        ok = fwrite(rec, 1, 13, fp) == 13;
+    }
+    ok = (fclose(fp) == 0) && ok;
+    if (!ok) {
+        remove(path);
+        return fail(LCGS_ERR_IO, "short write");
+    }
+    return LCGS_OK;
+}
+
 } // extern "C"
 
 namespace lcgs

@@ -297,6 +297,38 @@ void launch_filter3d_apply(int64_t P, const float* scale, const float* opacity, 
 // in place on the gradient rows; rows != NULL: gradient row r < *d_count belongs to row rows[r], the launch is sized by P
 void launch_filter3d_backward(int64_t P, const float* scale, const float* opacity, const float* filter, const uint32_t* rows,
                               const uint32_t* d_count, float* g_scale, float* g_opacity, hipStream_t stream);
+// ---- tsdf.hip : TSDF fusion of depth maps into a dense volume, marching tetrahedra on the Kuhn split ----
+constexpr int kTsdfViewChunk = 42; // = LCGS_TSDF_VIEW_CHUNK: views per launch of the integrate pass, their table in the kernel's arguments
+struct TsdfView {                  // what the pass reads of a view: gs_math.hpp view_transform's rows, the projection, the maps
+    float        right[3], tx, up[3], ty, front[3], tz;
+    float        inv_tanx, inv_tany;
+    int          W, H;
+    const float *depth, *alpha, *image; // alpha / image: NULL = the view has none
+};
+struct TsdfViews {
+    TsdfView v[kTsdfViewChunk];
+};
+static_assert(sizeof(TsdfViews) <= 3840, "the table and the pass's other arguments must fit the 4 KiB of kernel arguments");
+struct TsdfGrid { // the lattice of include/lcgs_hip.h's lcgs_tsdf_volume
+    float origin[3], voxel;
+    int   nx, ny, nz;
+};
+// every sample through the first num_views (<= kTsdfViewChunk) views of the table, in order; rgb may be NULL
+void launch_tsdf_integrate(const TsdfGrid& g, float* tsdf, float* weight, float* rgb, float trunc, float depth_max, float alpha_min,
+                           int num_views, const TsdfViews& views, hipStream_t stream);
+// The mesh passes.  word[s] (zeroed by the caller): bits 0-6 the crossing edges whose lower sample is s (bit dir - 1), bits 8-11
+// the triangle count of the cell whose lowest corner is s.  The cell pass ORs into it (integer OR: order-free).
+void launch_tsdf_mesh_cells(const TsdfGrid& g, const float* tsdf, const float* weight, float weight_min, uint32_t* word,
+                            hipStream_t stream);
+// vcount[s] = popcount of the edge bits, tcount[s] = the triangle count; totals[0] += sum vcount, totals[1] += sum tcount (u64,
+// zeroed by the caller; integer adds: order-free)
+void launch_tsdf_mesh_counts(int64_t n, const uint32_t* word, uint32_t* vcount, uint32_t* tcount, unsigned long long* totals,
+                             hipStream_t stream);
+// vincl / tincl: the inclusive sums of vcount / tcount.  vertices 3 floats each (vertex_rgb nullable), triangles 3 indices each
+void launch_tsdf_mesh_vertices(const TsdfGrid& g, const float* tsdf, const float* rgb, const uint32_t* word, const uint32_t* vincl,
+                               float* vertices, float* vertex_rgb, hipStream_t stream);
+void launch_tsdf_mesh_triangles(const TsdfGrid& g, const float* tsdf, const uint32_t* word, const uint32_t* vincl,
+                                const uint32_t* tincl, uint32_t* triangles, hipStream_t stream);
 // ---- loss.hip : the 3DGS photometric loss, (1 - lambda) L1 + lambda (1 - SSIM), and its gradient ----
 // Both passes tile a channel into 32 x 16 outputs, one workgroup each; partial sums are indexed by workgroup.
 int64_t photometric_workgroups(int W, int H);
