@@ -486,6 +486,59 @@ LCGS_API lcgs_status lcgs_normal_consistency_loss_backward(lcgs_context* ctx, co
                                                            const float* d_alpha, const float* d_normal, float weight,
                                                            float alpha_min, float* d_dL_ddepth, float* d_dL_dalpha,
                                                            float* d_dL_dnormal, float* d_loss);
+/* Per-view bilateral-grid colour correction ("Bilateral Guided Radiance Field Processing"; gsplat's use_bilateral_grid): what
+ * absorbs the exposure, white balance and tone curve that change from photograph to photograph, so that the scene does not.
+ * Each training view owns a small 3-D grid of 3 x 4 affine colour transforms; the grid is sliced at (pixel x, pixel y,
+ * luminance of the rendered pixel), the transform is applied to the rendered colour in front of the photometric loss, and a
+ * total-variation term keeps each grid smooth.
+ * One view's grid is float32 [12][L][GH][GW], contiguous: the layout of a torch (12, L, GH, GW) tensor.  Channel c = 4 r + k is
+ * entry (row r, column k) of the 3 x 4 matrix: columns 0..2 multiply r, g, b, column 3 is the offset.  A training set's grids
+ * are [N][12][L][GH][GW]; a slice or backward call takes one view's slab.  (gw, gh, gl) = (GW, GH, L); the usual choice is
+ * (16, 16, 8); accepted: 2 <= gw, gh <= 256 and 2 <= gl <= 16.  Images are float32 [3][H][W] as everywhere else, W, H >= 1.
+ * For pixel (px, py) with input colour c = (r, g, b), in binary32, uncontracted:
+ *     x = ((float)px + 0.5f) / W * (GW-1)      x0 = min(floor(x), GW-2)      fx = x - x0      (the same for y with H and GH;
+ *                                                                                              x and y never reach the border)
+ *     gray = 0.299f*r + 0.587f*g + 0.114f*b     (the three products summed in that order)
+ *     zr = gray*(L-1)      z = clamp(zr, 0, L-1)      z0 = min((int)z, L-2)      fz = z - z0
+ *     A[c] = the trilinear sample of channel c at (x, y, z), written as nested lerps a + t*(b - a): along x, then y, then z
+ *     out_r = A[4r]*r + A[4r+1]*g + A[4r+2]*b + A[4r+3]
+ * With the nested-lerp form an identity grid returns a finite image bit for bit (every lerp is a + t*0), the sign of a zero
+ * aside: a channel that is -0 comes back as +0 when the sum of the other products is +0.
+ * This is torch.nn.functional.grid_sample(grid[None], coords, mode="bilinear", padding_mode="border", align_corners=True) with
+ * coords = 2 (x/(GW-1), y/(GH-1), gray) - 1, followed by the affine apply (tests/bilagrid_ref.py).
+ * Backward, given g = dL/dout, with hat(t) = max(0, 1 - |t|):
+ *     dL/dgrid[c=4r+k][l][j][i] = sum over pixels of hat(x-i) hat(y-j) hat(z-l) g_r (k<3 ? c_k : 1)
+ *     dL/dc_k = sum_r A[4r+k] g_r + w_k (L-1) inside sum_r g_r (dA[4r..4r+3]/dz . (r,g,b,1))
+ *     dA/dz = the xy-bilinear sample at level z0+1 minus the one at z0         w = (0.299f, 0.587f, 0.114f)
+ *     inside = (zr > 0 && zr < L-1)
+ * The guidance passes no gradient where it is clamped, exactly 0 included: black background pixels pass none.  At an interior
+ * integer z the cell is the one above (floor).  Both rules are grid_sample's.
+ * dL/dgrid is a gather, not a scatter: every vertex sums the pixels in its reach in a fixed order (a lane's run of pixels in
+ * binary32 for gl <= 8, everything across lanes and row slices in binary64, rounded to binary32 once); no float atomics.
+ * Vertices that no pixel reaches are written as exact zeros (more vertices than pixels is a legal call).
+ * lcgs_bilagrid_backward: d_dL_dimg_chw (3*H*W floats) and d_dL_dgrid (12*L*GH*GW floats) are each optional (NULL: not wanted,
+ * nothing is computed for it and the other's bits do not change), not both NULL.
+ * The TV term over N grids:
+ *     loss = weight/N * sum over axis in {x,y,z} of sum (grid[v+e_axis] - grid[v])^2 / count_axis
+ * count_axis = the number of differences along that axis in ONE grid, times 12: for x, 12 L GH (GW-1).  The per-element algebra
+ * is binary64, the sum is binary64 in a fixed order, the loss and each gradient element are rounded to binary32 once.
+ * d_dL_dgrids NULL is evaluation only: *d_loss has the gradient call's bits.  weight = 0 gives exact zeros.
+ * All outputs are overwritten, never accumulated.  The same inputs give the same bits, across calls and across contexts.  No
+ * call needs a kept frame or reads anything back; each enqueues on the context's stream.  Workspace: the buffer the photometric
+ * loss uses, grown on demand.  The grids are ordinary caller-owned arrays: the caller's optimiser steps them.
+ * LCGS_ERR_INVALID_ARG (before any device work): a NULL ctx or required pointer; a non-positive width or height; grid
+ * dimensions outside the accepted ranges; a weight that is not finite or is negative; num_grids <= 0; both gradient pointers
+ * NULL in lcgs_bilagrid_backward; any output that overlaps any input or another output (in-place slicing is not offered);
+ * in lcgs_bilagrid_tv_loss_backward, more than 2^31 - 1 workgroups of 256 grid elements (num_grids is too large for one call).
+ * Not offered: the grid inside lcgs_fit_views or lcgs-app; a library optimiser for grids; interpolation between views' grids;
+ * slicing fused into the photometric loss; guidance other than the input's luminance. */
+LCGS_API lcgs_status lcgs_bilagrid_slice(lcgs_context* ctx, int width, int height, const float* d_grid, int gw, int gh, int gl,
+                                         const float* d_img_chw, float* d_out_chw);
+LCGS_API lcgs_status lcgs_bilagrid_backward(lcgs_context* ctx, int width, int height, const float* d_grid, int gw, int gh, int gl,
+                                            const float* d_img_chw, const float* d_dL_dout_chw, float* d_dL_dimg_chw,
+                                            float* d_dL_dgrid);
+LCGS_API lcgs_status lcgs_bilagrid_tv_loss_backward(lcgs_context* ctx, const float* d_grids, int num_grids, int gw, int gh, int gl,
+                                                    float weight, float* d_dL_dgrids, float* d_loss);
 #define LCGS_LOSS_L2 0
 #define LCGS_LOSS_PHOTOMETRIC 1
 /* The loss lcgs_fit_views applies (default LCGS_LOSS_L2: unchanged behaviour). */

@@ -31,6 +31,9 @@ from .api import (  # noqa: F401
     Renderer,
     SHProcessor,
     TsdfVolume,
+    bilagrid_autograd,
+    bilagrid_identity,
+    bilagrid_tv_autograd,
     build_library,
     camera_grad_to_twist,
     camera_with_vectors,

@@ -311,6 +311,10 @@ def _signatures() -> dict:
         "lcgs_l2_loss_backward": (st, [p, i, i, p, p, p, p]),
         "lcgs_photometric_loss_backward": (st, [p, i, i, p, p, f, p, p, p]),
         "lcgs_normal_consistency_loss_backward": (st, [p, cam, p, p, p, f, f, p, p, p, p]),
+        # per-view bilateral-grid colour correction
+        "lcgs_bilagrid_slice": (st, [p, i, i, p, i, i, i, p, p]),
+        "lcgs_bilagrid_backward": (st, [p, i, i, p, i, i, i, p, p, p, p]),
+        "lcgs_bilagrid_tv_loss_backward": (st, [p, p, i, i, i, i, f, p, p]),
         "lcgs_set_fit_loss": (st, [p, i, f]),
         "lcgs_fit_views": (st, [p, i, cam, p, f, pp, grads, p]),
         # adaptive density control
@@ -999,6 +1003,50 @@ class Renderer:
         _check(load_library().lcgs_normal_consistency_loss_backward(self.ctx._h, C.byref(cam), _ptr(depth), _ptr(alpha), _ptr(normal),
                                                                     weight, alpha_min, _ptr(dL_ddepth), _ptr(dL_dalpha),
                                                                     _ptr(dL_dnormal), _ptr(loss)))
+
+    @staticmethod
+    def _bilagrid_buffers(first, **named):
+        """every named tensor (name -> (tensor or None, shape)) is float32, on `first`'s device and of its shape: a mismatched
+        buffer would be an out-of-bounds device access behind the C ABI, which sees pointers only"""
+        import torch
+
+        for name, (t, shape) in named.items():
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or t.device != first.device or tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{name}: expected float32 {tuple(shape)} on {first.device}, got {t.dtype} {tuple(t.shape)} "
+                                 f"on {t.device}")
+
+    def bilagrid_slice(self, grid, img, out):
+        """lcgs_bilagrid_slice: out [3, H, W] = one view's bilateral grid [12, L, GH, GW] (3 x 4 affine colour transforms; channel
+        4 r + k = row r, column k, column 3 the offset) sliced at (pixel x, pixel y, luminance of img's pixel) and applied to img
+        [3, H, W].  Device tensors, float32 (shapes, dtype and device are checked: ValueError); out must not overlap img or grid.  An identity
+        grid returns img bit for bit."""
+        _, L, GH, GW = grid.shape
+        _, H, W = img.shape
+        self._bilagrid_buffers(img, grid=(grid, (12, L, GH, GW)), img=(img, (3, H, W)), out=(out, (3, H, W)))
+        _check(load_library().lcgs_bilagrid_slice(self.ctx._h, W, H, _ptr(grid), GW, GH, L, _ptr(img), _ptr(out)))
+
+    def bilagrid_backward(self, grid, img, dL_dout, dL_dimg=None, dL_dgrid=None):
+        """lcgs_bilagrid_backward: from dL_dout [3, H, W], dL_dimg [3, H, W] and / or dL_dgrid [12, L, GH, GW] (None: not wanted;
+        not both) of bilagrid_slice(grid, img).  Both are written whole, never accumulated: vertices no pixel reaches get exact
+        zeros.  dL/dgrid is a fixed-order gather (no atomics): the same inputs give the same bits."""
+        _, L, GH, GW = grid.shape
+        _, H, W = img.shape
+        self._bilagrid_buffers(img, grid=(grid, (12, L, GH, GW)), img=(img, (3, H, W)), dL_dout=(dL_dout, (3, H, W)),
+                               dL_dimg=(dL_dimg, (3, H, W)), dL_dgrid=(dL_dgrid, (12, L, GH, GW)))
+        _check(load_library().lcgs_bilagrid_backward(self.ctx._h, W, H, _ptr(grid), GW, GH, L, _ptr(img), _ptr(dL_dout),
+                                                     _ptr(dL_dimg), _ptr(dL_dgrid)))
+
+    def bilagrid_tv_loss_backward(self, grids, dL_dgrids, loss, weight: float = 10.0):
+        """lcgs_bilagrid_tv_loss_backward: loss[0] = weight / N x the total variation of grids [N, 12, L, GH, GW] (the mean squared
+        forward difference along x, y and z, summed over the three axes); dL_dgrids (None: evaluation only, the same loss bits)
+        = its gradient, written whole.  Device tensors, float32; binary64 inside."""
+        N, _, L, GH, GW = grids.shape
+        self._bilagrid_buffers(grids, grids=(grids, (N, 12, L, GH, GW)), dL_dgrids=(dL_dgrids, (N, 12, L, GH, GW)),
+                               loss=(loss, (1,)))
+        _check(load_library().lcgs_bilagrid_tv_loss_backward(self.ctx._h, _ptr(grids), N, GW, GH, L, weight, _ptr(dL_dgrids),
+                                                             _ptr(loss)))
 
     def set_fit_loss(self, kind: int, lambda_dssim: float = 0.2):
         """lcgs_set_fit_loss: the loss fit_views applies from now on -- LOSS_L2 (default) or LOSS_PHOTOMETRIC"""
@@ -1725,6 +1773,70 @@ def normal_consistency_autograd(renderer: "Renderer", cam: Camera, depth, alpha,
                          for g, s, need in zip(ctx.saved_tensors, ctx.shapes, ctx.needs_input_grad))
 
     return _Fn.apply(depth, alpha, normal)
+
+
+def bilagrid_identity(num: int, dims=(16, 16, 8), device="cuda:0"):
+    """`num` bilateral grids [num, 12, L, GH, GW], dims = (GW, GH, L), every cell the identity transform: channels 0, 5 and 10
+    (the diagonal of the 3 x 4 matrix) are 1, the rest 0.  An ordinary float32 tensor: make it a parameter and step it with
+    torch's optimiser."""
+    import torch
+
+    GW, GH, L = dims
+    grids = torch.zeros(num, 12, L, GH, GW, dtype=torch.float32, device=device)
+    grids[:, (0, 5, 10)] = 1.0
+    return grids
+
+
+def bilagrid_autograd(renderer: "Renderer", grid, img):
+    """Differentiable bilateral-grid slice for torch: `out = bilagrid_autograd(r, grid, img)`, grid [12, L, GH, GW] one view's
+    slab (e.g. `grids[v]`), img [3, H, W] the rendered frame (render_autograd's output).  The backward is ONE
+    lcgs_bilagrid_backward call that computes only the gradients autograd asks for."""
+    import torch
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, grid, img):
+            grid, img = grid.detach().contiguous(), img.detach().contiguous()
+            out = torch.empty_like(img)
+            renderer.bilagrid_slice(grid, img, out)
+            ctx.save_for_backward(grid, img)
+            return out
+
+        @staticmethod
+        def backward(ctx, g_out):
+            grid, img = ctx.saved_tensors
+            g_grid = torch.empty_like(grid) if ctx.needs_input_grad[0] else None
+            g_img = torch.empty_like(img) if ctx.needs_input_grad[1] else None
+            if g_grid is not None or g_img is not None:
+                renderer.bilagrid_backward(grid, img, g_out.contiguous(), g_img, g_grid)
+            return g_grid, g_img
+
+    return _Fn.apply(grid, img)
+
+
+def bilagrid_tv_autograd(renderer: "Renderer", grids, weight: float = 10.0):
+    """Differentiable total-variation term of bilateral grids for torch: `loss = bilagrid_tv_autograd(r, grids)`, a scalar
+    tensor, grids [N, 12, L, GH, GW] (or one grid [12, L, GH, GW]).  The forward is ONE lcgs_bilagrid_tv_loss_backward call that
+    also stores the gradient; the backward hands it out scaled by the incoming scalar."""
+    import torch
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, grids):
+            g = grids.detach().contiguous()
+            g = g[None] if g.dim() == 4 else g
+            grad = torch.empty_like(g)
+            loss = torch.empty(1, device=g.device, dtype=torch.float32)
+            renderer.bilagrid_tv_loss_backward(g, grad, loss, weight)
+            ctx.save_for_backward(grad)
+            ctx.shape = grids.shape
+            return loss[0]
+
+        @staticmethod
+        def backward(ctx, g_loss):
+            return (ctx.saved_tensors[0] * g_loss).view(ctx.shape)
+
+    return _Fn.apply(grids)
 
 
 def filter3d_autograd(renderer: "Renderer", scale, opacity, filt):

@@ -351,6 +351,27 @@ int64_t normal_consistency_workgroups(int W, int H);
 void launch_normal_consistency(int W, int H, double tanx, double tany, double scale, double alpha_min, const float* depth,
                                const float* alpha, const float* normal, float* dL_ddepth, float* dL_dalpha, float* dL_dnormal,
                                double* partials, float* loss, hipStream_t stream);
+// ---- bilagrid.hip : per-view bilateral-grid colour correction -- slice, its two gradients, total variation ----
+// A view's grid is [12][gl][gh][gw] floats (include/lcgs_hip.h has the definition); images are CHW.
+constexpr int kBilagridTileW = 32, kBilagridTileH = 16; // the pixel tile of a workgroup of the per-pixel passes
+struct BilagridDims {
+    int gw, gh, gl;
+};
+// the per-pixel pass, one workgroup per tile: dL_dout == NULL -> out = the sliced image; else out = dL/dimg
+void launch_bilagrid_pixels(int W, int H, const float* grid, const BilagridDims& d, const float* img, const float* dL_dout,
+                            float* out, hipStream_t stream);
+// dL/dgrid as a gather, one workgroup per (vertex column, row slice) for gl <= 8 and per (vertex, row slice) for deeper grids;
+// the slice count depends on the dimensions only.  More than one slice: `partials` holds bilagrid_grid_partial_doubles(d)
+// doubles, summed in slice order by a second launch.  Every element of dL_dgrid is written.
+int    bilagrid_grid_slices(const BilagridDims& d);
+size_t bilagrid_grid_partial_doubles(const BilagridDims& d);
+void   launch_bilagrid_grid_grad(int W, int H, const BilagridDims& d, const float* img, const float* dL_dout, float* dL_dgrid,
+                                 double* partials, hipStream_t stream);
+// the TV term of num_grids grids: one binary64 partial per workgroup (bilagrid_tv_workgroups of them), summed in index order
+// -> loss[0]; dL_dgrids NULL: evaluation only, the same loss bits
+int64_t bilagrid_tv_workgroups(int64_t num_grids, const BilagridDims& d);
+void    launch_bilagrid_tv(const float* grids, int64_t num_grids, const BilagridDims& d, double weight, float* dL_dgrids,
+                           double* partials, float* loss, hipStream_t stream);
 // backward.hip: the per-splat half of the backward with the on-screen-only Adam update applied where the gradients are
 // formed (degree 3, frames that kept the colour Jacobian): no gradient rows are written at all
 // (r.shjac is not NULL; r.opacity is read for an antialiased frame, before the lane's update of the activated row)

@@ -22,6 +22,7 @@
 // Below it, on the same tiles and the same finish step: the normal-consistency loss of a frame's depth, alpha and normal maps
 // and its three gradients in one kernel (k_normal_consistency; its comment has the phases and the LDS reasoning).
 #include "launch.hpp"
+#include "ordered_sum.hpp"
 #include "stream_access.hpp"
 
 namespace lcgs
@@ -33,7 +34,7 @@ constexpr int kTW = 32, kTH = 16;         // outputs of a workgroup
 constexpr int kInW = kTW + 2 * kR, kInH = kTH + 2 * kR; // ... and what they read: 42 x 26
 constexpr int kSlot = 48;                 // spacing of the planes inside a staged row
 constexpr int kPitchA = 96, kPitchB = 160;
-constexpr int kThreads = 256;
+constexpr int kThreads = kOrderedSumThreads;
 static_assert(kInW <= kSlot && kSlot + kInW <= kPitchA && 2 * kSlot + kInW <= kPitchB, "staged planes overlap");
 static_assert(kPitchA % 64 == 32 && kPitchB % 64 == 32, "row pitch must be 32 mod 64 banks");
 
@@ -41,13 +42,6 @@ static_assert(kPitchA % 64 == 32 && kPitchB % 64 == 32, "row pitch must be 32 mo
 __device__ const float kGauss[kTaps] = { 0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c4p-3f, 0x1.10656p-2f,
                                          0x1.b43c4p-3f,   0x1.bff0fep-4f, 0x1.26eb18p-5f, 0x1.f1fe02p-8f, 0x1.0d956cp-10f };
 constexpr double kC1 = 0.01 * 0.01, kC2 = 0.03 * 0.03;
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // ---- pass A
 template <bool STORE>
@@ -206,33 +200,7 @@ __global__ void __launch_bounds__(kThreads) k_photometric_grad(int W, int H, con
     }
 }
 
-// ---- finish: the workgroups' partials (N per workgroup) in index order -- each thread a contiguous run, then thread 0 the
-// 256 run sums in order.  Returns true on thread 0, whose `out` holds the N sums.
-template <int N>
-__device__ __forceinline__ bool sum_partials_in_order(int64_t num, const double* __restrict__ partials, double (&out)[N])
-{
-    __shared__ double s_sum[N][kThreads];
-    const int64_t     run = (num + kThreads - 1) / kThreads;
-    const int64_t     lo = (int64_t)threadIdx.x * run, hi = lo + run < num ? lo + run : num;
-#pragma unroll
-    for (int k = 0; k < N; ++k) out[k] = 0.0;
-    for (int64_t i = lo; i < hi; ++i) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) out[k] += partials[N * i + k];
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) s_sum[k][threadIdx.x] = out[k];
-    __syncthreads();
-    if (threadIdx.x != 0) return false;
-#pragma unroll
-    for (int k = 0; k < N; ++k) out[k] = 0.0;
-    for (int t = 0; t < kThreads; ++t) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) out[k] += s_sum[k][t];
-    }
-    return true;
-}
-
+// ---- finish: the workgroups' partials in index order (ordered_sum.hpp)
 __global__ void __launch_bounds__(kThreads) k_photometric_finish(int64_t num, double n, const double* __restrict__ partials,
                                                                  float lambda, float* __restrict__ loss, float* __restrict__ terms)
 {

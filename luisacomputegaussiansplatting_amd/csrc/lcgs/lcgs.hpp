@@ -115,6 +115,23 @@ public:
         check(lcgs_normal_consistency_loss_backward(m_ctx, &cam, d_depth, d_alpha, d_normal, weight, alpha_min, d_dL_ddepth,
                                                     d_dL_dalpha, d_dL_dnormal, d_loss));
     }
+    // per-view bilateral-grid colour correction (device pointers; one view's grid is [12][gl][gh][gw]): the slice of the grid at
+    // (pixel x, pixel y, luminance of the input pixel) applied to the image; its backward (either gradient may be NULL, not
+    // both); the total-variation term of num_grids grids (d_dL_dgrids NULL: evaluation only)
+    void bilagrid_slice(int width, int height, const float* d_grid, int gw, int gh, int gl, const float* d_img, float* d_out)
+    {
+        check(lcgs_bilagrid_slice(m_ctx, width, height, d_grid, gw, gh, gl, d_img, d_out));
+    }
+    void bilagrid_backward(int width, int height, const float* d_grid, int gw, int gh, int gl, const float* d_img,
+                           const float* d_dL_dout, float* d_dL_dimg, float* d_dL_dgrid)
+    {
+        check(lcgs_bilagrid_backward(m_ctx, width, height, d_grid, gw, gh, gl, d_img, d_dL_dout, d_dL_dimg, d_dL_dgrid));
+    }
+    void bilagrid_tv_loss_backward(const float* d_grids, int num_grids, int gw, int gh, int gl, float* d_dL_dgrids, float* d_loss,
+                                   float weight = 10.0f)
+    {
+        check(lcgs_bilagrid_tv_loss_backward(m_ctx, d_grids, num_grids, gw, gh, gl, weight, d_dL_dgrids, d_loss));
+    }
     // the loss Scene::fit_views applies: LCGS_LOSS_L2 (default) or LCGS_LOSS_PHOTOMETRIC
     void set_fit_loss(int kind, float lambda_dssim = 0.2f) { check(lcgs_set_fit_loss(m_ctx, kind, lambda_dssim)); }
     // LCGS_RASTER_CLASSIC (default) or LCGS_RASTER_ANTIALIASED: the fused frame's opacity compensation (lcgs_set_raster_mode)
