@@ -98,9 +98,7 @@ lcgs_status lcgs_render_backward_adam(lcgs_context* ctx, const float* d_dL_dimg,
     LCGS_ENTRY(ctx);
     LCGS_REQUIRE(num_gaussians == ctx->P && sh_degree == ctx->sh_deg, "num_gaussians / sh_degree must be the bound scene's");
     LCGS_TRY(check_adam_config(cfg));
-    const lcgs_params* packs[4] = { raw, m, v, activated };
-    for (const lcgs_params* p : packs)
-        LCGS_REQUIRE(p->pos && p->scale && p->rotq && p->sh && p->opacity, "NULL device pointer in a parameter pack");
+    LCGS_TRY(check_param_packs({ raw, m, v, activated }, false));
     auto aligned16 = [](const lcgs_params* p) {
         return ((reinterpret_cast<uintptr_t>(p->rotq) | reinterpret_cast<uintptr_t>(p->sh)) & 15) == 0;
     };

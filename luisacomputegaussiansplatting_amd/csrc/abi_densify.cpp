@@ -27,6 +27,47 @@ ContribRule prune_rule(const lcgs_prune_config* cfg)
 {
     return { cfg->min_weight_max, cfg->min_weight_sum, cfg->min_pixels, cfg->min_views };
 }
+
+// The out-of-place rewrite of lcgs_densify and lcgs_prune, behind their argument checks.  classify(emit, action, stream) fills
+// the rows each source row emits and what becomes of it; the inclusive sums of `emit` are every row's place, and their last
+// the new count: the call's one read-back, known before anything is scattered.  `who`: the call's name; `verb`: needs | keeps.
+struct RowRewrite {
+    int                sh_degree;
+    const lcgs_params *raw, *m, *v, *out_raw, *out_m, *out_v, *out_activated;
+    int64_t            capacity;
+    float              split_drop; // the scatter's last arguments: lcgs_prune splits no row and has none of them
+    const float*       noise;
+    uint64_t           seed;
+    uint32_t*          src_row;
+};
+template <class Classify>
+lcgs_status rewrite_rows(lcgs_context* ctx, const char* who, const char* verb, int64_t P, const RowRewrite& r, Classify classify,
+                         int64_t* new_count)
+{
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    LCGS_TRY(ctx->dn_emit.ensure((size_t)P * 4));
+    LCGS_TRY(ctx->dn_incl.ensure((size_t)P * 4));
+    LCGS_TRY(ctx->dn_action.ensure((size_t)P));
+    LCGS_TRY(ctx->st_scan_temp.ensure(scan_temp_bytes(P)));
+    classify(ctx->dn_emit.as<uint32_t>(), ctx->dn_action.as<uint8_t>(), st);
+    launch_inclusive_sum_u32(ctx->dn_emit.as<uint32_t>(), ctx->dn_incl.as<uint32_t>(), P, ctx->st_scan_temp.ptr, st);
+    uint32_t total = 0;
+    LCGS_HIP_CHECK(hipMemcpyAsync(&total, ctx->dn_incl.as<uint32_t>() + (P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    LCGS_HIP_CHECK(hipStreamSynchronize(st));
+    *new_count = (int64_t)total;
+    if ((int64_t)total > r.capacity) {
+        set_last_error(std::string(who) + ": the rewrite " + verb + " " + std::to_string(total) +
+                       " rows, the destination arrays hold " + std::to_string((long long)r.capacity));
+        return LCGS_ERR_CAPACITY;
+    }
+    if (total == 0) return LCGS_OK;
+    scene_arrays_written(ctx, r.out_activated->pos, r.out_activated->scale, r.out_activated->rotq); // (destinations a context renders)
+    launch_densify_scatter(P, (int)sh_floats(r.sh_degree), ctx->dn_action.as<uint8_t>(), ctx->dn_incl.as<uint32_t>(),
+                           adam_arrays(r.raw), adam_arrays(r.m), adam_arrays(r.v), adam_arrays(r.out_raw), adam_arrays(r.out_m),
+                           adam_arrays(r.out_v), adam_arrays(r.out_activated), r.split_drop, r.noise, r.seed, r.src_row, st);
+    return LCGS_OK;
+}
 } // namespace
 
 extern "C" {
@@ -65,54 +106,35 @@ lcgs_status lcgs_densify(lcgs_context* ctx, int num_gaussians, int sh_degree, co
     LCGS_REQUIRE(capacity >= 0, "capacity is negative");
     *new_num_gaussians = 0;
     if (num_gaussians == 0) return LCGS_OK;
-    const lcgs_params* packs[7] = { raw, m, v, out_raw, out_m, out_v, out_activated };
-    for (const lcgs_params* p : packs)
-        LCGS_REQUIRE(p->pos && p->scale && p->rotq && p->sh && p->opacity, "NULL device pointer in a parameter pack");
-    for (const lcgs_params* p : packs)
-        LCGS_REQUIRE((reinterpret_cast<uintptr_t>(p->rotq) & 15) == 0, "rotq arrays must be 16-byte aligned");
+    LCGS_TRY(check_param_packs({ raw, m, v, out_raw, out_m, out_v, out_activated }, true));
     LCGS_REQUIRE(stats->grad_accum && stats->denom && stats->max_radii && out_stats->grad_accum && out_stats->denom &&
                      out_stats->max_radii,
                  "NULL device pointer in the statistics");
     LCGS_REQUIRE(out_raw->pos != raw->pos && out_m->pos != m->pos && out_v->pos != v->pos && out_stats->denom != stats->denom,
                  "the rewrite is out of place: destinations must not alias sources");
     LCGS_ENTRY(ctx);
-    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t   st = ctx->stream;
-    const int64_t P  = num_gaussians;
-    LCGS_TRY(ctx->dn_emit.ensure((size_t)P * 4));
-    LCGS_TRY(ctx->dn_incl.ensure((size_t)P * 4));
-    LCGS_TRY(ctx->dn_action.ensure((size_t)P));
-    LCGS_TRY(ctx->st_scan_temp.ensure(scan_temp_bytes(P)));
     DensifyRule rule;
     rule.grad_threshold  = cfg->grad_threshold;
     rule.dense_extent    = cfg->percent_dense * cfg->scene_extent;
     rule.huge_extent     = 0.1f * cfg->scene_extent;
     rule.min_opacity     = cfg->min_opacity;
     rule.max_screen_size = cfg->max_screen_size;
-    launch_densify_classify(P, rule, raw->scale, raw->opacity, stats->grad_accum, stats->denom, stats->max_radii,
-                            ctx->dn_emit.as<uint32_t>(), ctx->dn_action.as<uint8_t>(), st);
-    launch_inclusive_sum_u32(ctx->dn_emit.as<uint32_t>(), ctx->dn_incl.as<uint32_t>(), P, ctx->st_scan_temp.ptr, st);
-    // the call's one read-back: the new count, known before anything is scattered
-    uint32_t total = 0;
-    LCGS_HIP_CHECK(hipMemcpyAsync(&total, ctx->dn_incl.as<uint32_t>() + (P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    LCGS_HIP_CHECK(hipStreamSynchronize(st));
-    *new_num_gaussians = (int64_t)total;
-    if ((int64_t)total > capacity) {
-        set_last_error("lcgs_densify: the rewrite needs " + std::to_string(total) + " rows, the destination arrays hold " +
-                       std::to_string((long long)capacity));
-        return LCGS_ERR_CAPACITY;
-    }
-    if (total == 0) return LCGS_OK;
-    scene_arrays_written(ctx, out_activated->pos, out_activated->scale, out_activated->rotq); // (destinations a context renders)
+    const int64_t P = num_gaussians;
     // ln 1.6 to binary32 (children are 1.6 x smaller: raw scale - ln 1.6), rounded once from the double value
-    const float split_drop = (float)log((double)1.6f);
-    launch_densify_scatter(P, (int)sh_floats(sh_degree), ctx->dn_action.as<uint8_t>(), ctx->dn_incl.as<uint32_t>(),
-                           adam_arrays(raw), adam_arrays(m), adam_arrays(v), adam_arrays(out_raw), adam_arrays(out_m), adam_arrays(out_v),
-                           adam_arrays(out_activated),
-                           split_drop, d_noise, cfg->seed, d_src_row, st);
-    LCGS_HIP_CHECK(hipMemsetAsync(out_stats->grad_accum, 0, (size_t)total * 4, st));
-    LCGS_HIP_CHECK(hipMemsetAsync(out_stats->denom, 0, (size_t)total * 4, st));
-    LCGS_HIP_CHECK(hipMemsetAsync(out_stats->max_radii, 0, (size_t)total * 4, st));
+    const float      split_drop = (float)log((double)1.6f);
+    const RowRewrite rw = { sh_degree, raw, m, v, out_raw, out_m, out_v, out_activated, capacity, split_drop, d_noise, cfg->seed,
+                            d_src_row };
+    LCGS_TRY(rewrite_rows(ctx, "lcgs_densify", "needs", P, rw,
+                          [&](uint32_t* emit, uint8_t* action, hipStream_t st) {
+                              launch_densify_classify(P, rule, raw->scale, raw->opacity, stats->grad_accum, stats->denom,
+                                                      stats->max_radii, emit, action, st);
+                          },
+                          new_num_gaussians));
+    const size_t total = (size_t)*new_num_gaussians;
+    if (total == 0) return LCGS_OK;
+    LCGS_HIP_CHECK(hipMemsetAsync(out_stats->grad_accum, 0, total * 4, ctx->stream));
+    LCGS_HIP_CHECK(hipMemsetAsync(out_stats->denom, 0, total * 4, ctx->stream));
+    LCGS_HIP_CHECK(hipMemsetAsync(out_stats->max_radii, 0, total * 4, ctx->stream));
     LCGS_HIP_CHECK(hipGetLastError());
     return LCGS_OK;
 }
@@ -145,40 +167,18 @@ lcgs_status lcgs_prune(lcgs_context* ctx, int num_gaussians, int sh_degree, cons
     LCGS_TRY(check_prune_rule(cfg, stats));
     *new_num_gaussians = 0;
     if (num_gaussians == 0) return LCGS_OK;
-    const lcgs_params* packs[7] = { raw, m, v, out_raw, out_m, out_v, out_activated };
-    for (const lcgs_params* p : packs)
-        LCGS_REQUIRE(p->pos && p->scale && p->rotq && p->sh && p->opacity, "NULL device pointer in a parameter pack");
-    for (const lcgs_params* p : packs)
-        LCGS_REQUIRE((reinterpret_cast<uintptr_t>(p->rotq) & 15) == 0, "rotq arrays must be 16-byte aligned");
+    LCGS_TRY(check_param_packs({ raw, m, v, out_raw, out_m, out_v, out_activated }, true));
     LCGS_REQUIRE(out_raw->pos != raw->pos && out_m->pos != m->pos && out_v->pos != v->pos,
                  "the rewrite is out of place: destinations must not alias sources");
     LCGS_ENTRY(ctx);
-    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t   st = ctx->stream;
-    const int64_t P  = num_gaussians;
-    LCGS_TRY(ctx->dn_emit.ensure((size_t)P * 4));
-    LCGS_TRY(ctx->dn_incl.ensure((size_t)P * 4));
-    LCGS_TRY(ctx->dn_action.ensure((size_t)P));
-    LCGS_TRY(ctx->st_scan_temp.ensure(scan_temp_bytes(P)));
-    launch_contrib_classify(P, prune_rule(cfg), stats->weight_sum, stats->weight_max, stats->pixels, stats->views,
-                            ctx->dn_emit.as<uint32_t>(), ctx->dn_action.as<uint8_t>(), st);
-    launch_inclusive_sum_u32(ctx->dn_emit.as<uint32_t>(), ctx->dn_incl.as<uint32_t>(), P, ctx->st_scan_temp.ptr, st);
-    // the call's one read-back: the new count, known before anything is scattered
-    uint32_t total = 0;
-    LCGS_HIP_CHECK(hipMemcpyAsync(&total, ctx->dn_incl.as<uint32_t>() + (P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    LCGS_HIP_CHECK(hipStreamSynchronize(st));
-    *new_num_gaussians = (int64_t)total;
-    if ((int64_t)total > capacity) {
-        set_last_error("lcgs_prune: the rewrite keeps " + std::to_string(total) + " rows, the destination arrays hold " +
-                       std::to_string((long long)capacity));
-        return LCGS_ERR_CAPACITY;
-    }
-    if (total == 0) return LCGS_OK;
-    scene_arrays_written(ctx, out_activated->pos, out_activated->scale, out_activated->rotq); // (destinations a context renders)
     // (actions 0 and 1 only: no row splits, so neither the split's scale drop nor the sampler is reached)
-    launch_densify_scatter(P, (int)sh_floats(sh_degree), ctx->dn_action.as<uint8_t>(), ctx->dn_incl.as<uint32_t>(),
-                           adam_arrays(raw), adam_arrays(m), adam_arrays(v), adam_arrays(out_raw), adam_arrays(out_m), adam_arrays(out_v),
-                           adam_arrays(out_activated), 0.0f, nullptr, 0, d_src_row, st);
+    const RowRewrite rw = { sh_degree, raw, m, v, out_raw, out_m, out_v, out_activated, capacity, 0.0f, nullptr, 0, d_src_row };
+    LCGS_TRY(rewrite_rows(ctx, "lcgs_prune", "keeps", num_gaussians, rw,
+                          [&](uint32_t* emit, uint8_t* action, hipStream_t st) {
+                              launch_contrib_classify(num_gaussians, prune_rule(cfg), stats->weight_sum, stats->weight_max,
+                                                      stats->pixels, stats->views, emit, action, st);
+                          },
+                          new_num_gaussians));
     LCGS_HIP_CHECK(hipGetLastError());
     return LCGS_OK;
 }

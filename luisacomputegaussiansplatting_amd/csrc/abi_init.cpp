@@ -74,10 +74,7 @@ lcgs_status lcgs_scene_init_from_points(lcgs_context* ctx, int num_points, int s
     LCGS_REQUIRE(cfg->min_dist2 > 0.0f, "min_dist2 must be > 0");
     if (num_points == 0) return LCGS_OK;
     LCGS_REQUIRE(d_pos && d_rgb, "NULL device pointer");
-    for (const lcgs_params* p : { out_raw, out_activated }) {
-        LCGS_REQUIRE(p->pos && p->scale && p->rotq && p->sh && p->opacity, "NULL device pointer in a parameter pack");
-        LCGS_REQUIRE((reinterpret_cast<uintptr_t>(p->rotq) & 15) == 0, "rotq arrays must be 16-byte aligned");
-    }
+    LCGS_TRY(check_param_packs({ out_raw, out_activated }, true));
     LCGS_ENTRY(ctx);
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     const int64_t n = num_points;

@@ -20,6 +20,7 @@
 #pragma once
 
 #include <algorithm>
+#include <initializer_list>
 
 #include "common.hpp"
 #include "context.hpp"
@@ -87,6 +88,16 @@ inline AdamRates  adam_rates(const lcgs_adam_config* c)
     return { c->lr_pos, c->lr_sh_dc, c->lr_sh_rest, c->lr_opacity, c->lr_scale, c->lr_rot };
 }
 lcgs_status check_adam_config(const lcgs_adam_config* cfg); // abi_train.cpp
+// every member of every pack is a pointer; rotq_aligned: ... and the rotq arrays can be read as float4
+inline lcgs_status check_param_packs(std::initializer_list<const lcgs_params*> packs, bool rotq_aligned)
+{
+    for (const lcgs_params* p : packs)
+        LCGS_REQUIRE(p->pos && p->scale && p->rotq && p->sh && p->opacity, "NULL device pointer in a parameter pack");
+    if (rotq_aligned)
+        for (const lcgs_params* p : packs)
+            LCGS_REQUIRE((reinterpret_cast<uintptr_t>(p->rotq) & 15) == 0, "rotq arrays must be 16-byte aligned");
+    return LCGS_OK;
+}
 
 // abi_core.cpp
 lcgs_status mark(lcgs_context* ctx, const char* name);          // per-stage timing mark (+ LCGS_DEBUG_SYNC)

@@ -12,15 +12,6 @@ using namespace lcgs::abi;
 
 namespace
 {
-lcgs_status check_mcmc_packs(const lcgs_params* raw, const lcgs_params* m, const lcgs_params* v, const lcgs_params* activated)
-{
-    const lcgs_params* packs[4] = { raw, m, v, activated };
-    for (const lcgs_params* p : packs)
-        LCGS_REQUIRE(p->pos && p->scale && p->rotq && p->sh && p->opacity, "NULL device pointer in a parameter pack");
-    for (const lcgs_params* p : packs)
-        LCGS_REQUIRE((reinterpret_cast<uintptr_t>(p->rotq) & 15) == 0, "rotq arrays must be 16-byte aligned");
-    return LCGS_OK;
-}
 lcgs_status check_mcmc_config(const lcgs_mcmc_config* cfg)
 {
     LCGS_REQUIRE(cfg->n_max >= 1 && cfg->n_max <= kMcmcMaxN, "n_max must be in [1,51]");
@@ -33,18 +24,17 @@ lcgs_status enqueue_weights(lcgs_context* ctx, int64_t P, float min_opacity, con
     LCGS_TRY(ctx->mc_w.ensure((size_t)P * 4));
     LCGS_TRY(ctx->mc_cdf.ensure((size_t)P * 8));
     LCGS_TRY(ctx->mc_count.ensure((size_t)P * 4));
-    LCGS_TRY(ctx->mc_scan_temp.ensure(mcmc_scan_temp_bytes(P)));
+    LCGS_TRY(ctx->st_scan_temp.ensure(scan_temp_bytes(P))); // (also the dead-row scan's, behind this one on the stream)
     LCGS_TRY(ctx->mc_status.ensure(16));
     if (dead) {
         LCGS_TRY(ctx->mc_dead.ensure((size_t)P * 4));
         LCGS_TRY(ctx->mc_dead_incl.ensure((size_t)P * 4));
         LCGS_TRY(ctx->mc_dead_list.ensure((size_t)P * 4));
-        LCGS_TRY(ctx->st_scan_temp.ensure(scan_temp_bytes(P)));
     }
     hipStream_t st = ctx->stream;
     launch_mcmc_weights(P, min_opacity, raw_opacity, ctx->mc_w.as<uint32_t>(), dead ? ctx->mc_dead.as<uint32_t>() : nullptr, src_row,
                         st);
-    launch_mcmc_inclusive_sum_u64(ctx->mc_w.as<uint32_t>(), ctx->mc_cdf.as<uint64_t>(), P, ctx->mc_scan_temp.ptr, st);
+    launch_inclusive_sum_u64(ctx->mc_w.as<uint32_t>(), ctx->mc_cdf.as<uint64_t>(), P, ctx->st_scan_temp.ptr, st);
     LCGS_HIP_CHECK(hipMemsetAsync(ctx->mc_count.ptr, 0, (size_t)P * 4, st));
     LCGS_HIP_CHECK(hipMemsetAsync(ctx->mc_status.ptr, 0, 16, st));
     return LCGS_OK;
@@ -64,7 +54,7 @@ lcgs_status lcgs_mcmc_relocate(lcgs_context* ctx, int num_gaussians, int sh_degr
     *num_relocated = 0;
     LCGS_ENTRY(ctx);
     if (num_gaussians == 0) return LCGS_OK;
-    LCGS_TRY(check_mcmc_packs(raw, m, v, activated));
+    LCGS_TRY(check_param_packs({ raw, m, v, activated }, true));
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t   st = ctx->stream;
     const int64_t P  = num_gaussians;
@@ -122,7 +112,7 @@ lcgs_status lcgs_mcmc_add(lcgs_context* ctx, int num_gaussians, int sh_degree, c
         set_last_error("lcgs_mcmc_add: no live row to grow from");
         return LCGS_ERR_STATE;
     }
-    LCGS_TRY(check_mcmc_packs(raw, m, v, activated));
+    LCGS_TRY(check_param_packs({ raw, m, v, activated }, true));
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     LCGS_TRY(ctx->mc_draw.ensure((size_t)num_new * 4));

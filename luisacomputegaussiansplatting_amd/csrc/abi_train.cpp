@@ -34,9 +34,7 @@ lcgs_status lcgs_adam_step(lcgs_context* ctx, int num_gaussians, int sh_degree, 
     LCGS_ENTRY(ctx);
     scene_arrays_written(ctx, activated->pos, activated->scale, activated->rotq); // (a context-owned scene trained in place)
     if (num_gaussians == 0) return LCGS_OK;
-    const lcgs_params* packs[4] = { raw, m, v, activated };
-    for (const lcgs_params* p : packs)
-        LCGS_REQUIRE(p->pos && p->scale && p->rotq && p->sh && p->opacity, "NULL device pointer in a parameter pack");
+    LCGS_TRY(check_param_packs({ raw, m, v, activated }, false));
     LCGS_REQUIRE(grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh && grads->d_dL_dopacity,
                  "NULL gradient pointer");
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));

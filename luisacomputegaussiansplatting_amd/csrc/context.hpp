@@ -200,7 +200,7 @@ struct lcgs_context {
     // lcgs_mcmc_relocate / lcgs_mcmc_add (abi_mcmc.cpp): per row the weight, the dead flag, its inclusive sums, the u64 sums of
     // the weights and the draws that landed on the row; per draw the dead row it fills and its source; the u64 scan's block
     // sums; one status word (kernels/launch.hpp launch_mcmc_draw)
-    DeviceBuffer mc_w, mc_dead, mc_dead_incl, mc_cdf, mc_count, mc_dead_list, mc_draw, mc_scan_temp, mc_status;
+    DeviceBuffer mc_w, mc_dead, mc_dead_incl, mc_cdf, mc_count, mc_dead_list, mc_draw, mc_status;
     // lcgs_filter3d_finalize (abi_filter3d.cpp): the word its reduction leaves the largest finite min_z in
     DeviceBuffer f3_word;
     // lcgs_tsdf_mesh_count / _extract (abi_tsdf.cpp): per sample the edge-mask / triangle-count word, the vertex counts and the

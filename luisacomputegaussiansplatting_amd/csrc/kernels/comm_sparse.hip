@@ -13,6 +13,7 @@
 // other).
 #include "kept_rows.hpp"
 #include "launch.hpp"
+#include "wave_scan.hpp"
 
 #include "../common.hpp"
 
@@ -68,22 +69,14 @@ __global__ void __launch_bounds__(1024) k_flag_scan(uint32_t* __restrict__ chunk
 {
     __shared__ uint32_t s_w[16];
     __shared__ uint32_t s_carry;
-    const uint32_t      tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t      tid = threadIdx.x;
     if (tid == 0) s_carry = 0;
     __syncthreads();
     for (uint32_t base = 0; base < chunks; base += 1024u) {
-        const uint32_t i   = base + tid;
-        const uint32_t own = i < chunks ? chunk_count[i] : 0u;
-        uint32_t       inc = own;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, 64);
-            if (lane >= (uint32_t)off) inc += o;
-        }
-        if (lane == 63u) s_w[wave] = inc;
-        __syncthreads();
-        uint32_t before = s_carry;
-        for (uint32_t w = 0; w < wave; ++w) before += s_w[w];
+        const uint32_t i      = base + tid;
+        const uint32_t own    = i < chunks ? chunk_count[i] : 0u;
+        const uint32_t inc    = wave_inclusive_scan(own);
+        const uint32_t before = block_carry<16>(inc, s_w) + s_carry;
         if (i < chunks) chunk_count[i] = before + inc - own;
         __syncthreads();
         if (tid == 1023u) s_carry = before + inc;
@@ -110,17 +103,8 @@ __global__ void __launch_bounds__(256) k_flag_scatter(const uint8_t* __restrict_
     uint32_t            f[4];
     const uint32_t      first = blockIdx.x * (uint32_t)kFlagsPerChunk + threadIdx.x * 16u;
     const uint32_t      own   = load_flags16(flags, first, P, f);
-    const uint32_t      lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t            inc = own;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= (uint32_t)off) inc += o;
-    }
-    if (lane == 63u) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t at = chunk_base[blockIdx.x] + inc - own;
-    for (uint32_t w = 0; w < wave; ++w) at += s_w[w];
+    const uint32_t      inc   = wave_inclusive_scan(own);
+    uint32_t            at    = chunk_base[blockIdx.x] + inc - own + block_carry<4>(inc, s_w);
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll

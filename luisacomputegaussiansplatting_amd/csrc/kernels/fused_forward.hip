@@ -32,6 +32,7 @@
 #include "launch.hpp"
 #include "stream_access.hpp"
 #include "tie_order.hpp"
+#include "wave_scan.hpp"
 
 namespace lcgs
 {
@@ -39,19 +40,6 @@ namespace
 {
 
 constexpr int kThreads = 256;
-
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t& total)
-{
-    const int lane = threadIdx.x & 63;
-    uint32_t  inc  = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    total = __shfl(inc, 63, 64);
-    return inc - v;
-}
 
 // Everything the projector + allocate_tiles compute for one splat (gs_projector/shader.cpp:107-137,
 // gs_tile_splatter/shader.cpp:117-157), plus the pruned rect of gs_math.hpp tight_rect.
@@ -677,12 +665,8 @@ __global__ void __launch_bounds__(1024) k_expand_offsets(uint32_t* __restrict__ 
             e[j] = tot;
             tot += v[j];
         }
-        uint32_t inc = tot;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
+        const uint32_t inc = wave_inclusive_scan(tot);
+        // (the carry is written out: through block_carry the compiler no longer peels the first round and takes 12 more VGPRs)
         if (lane == 63) s_wave[wave] = inc;
         __syncthreads();
         uint32_t carry = carry_in, round_total = 0;

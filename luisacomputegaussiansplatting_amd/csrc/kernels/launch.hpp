@@ -55,8 +55,10 @@ size_t copy_with_keys_windows_bytes(uint32_t L);
 void launch_get_ranges_u64(int64_t L, const uint64_t* keys, uint32_t* ranges, hipStream_t stream);
 
 // ---- scan.hip : DeviceScan::InclusiveSum<uint> ----
-size_t scan_temp_bytes(int64_t n);
+size_t scan_temp_bytes(int64_t n); // of `temp`, for either sum type
 void   launch_inclusive_sum_u32(const uint32_t* in, uint32_t* out, int64_t n, void* temp, hipStream_t stream);
+// out[i] = in[0] + ... + in[i] in u64
+void   launch_inclusive_sum_u64(const uint32_t* in, uint64_t* out, int64_t n, void* temp, hipStream_t stream);
 // element count read from device memory (*d_n <= n_cap)
 void   launch_inclusive_sum_u32_dyn(const uint32_t* in, uint32_t* out, int64_t n_cap, const uint32_t* d_n, void* temp,
                                     hipStream_t stream);
@@ -236,7 +238,6 @@ void launch_densify_scatter(int64_t P, int sh_floats, const uint8_t* action, con
 // raw = min(raw, ceiling), m = v = 0, act = sigmoid(raw)
 void launch_opacity_reset(int64_t P, float ceiling, float* raw, float* m, float* v, float* act, hipStream_t stream);
 // ---- mcmc.hip : 3DGS-MCMC density control (relocation, growth, SGLD noise, the L1 regulariser) ----
-constexpr int      kMcmcScanTile    = 512;         // elements per workgroup of the u64 scan (256 lanes x 2), and its block-sums step
 constexpr int      kMcmcMaxN        = 51;          // the binomial table's rows: n_max <= 51
 constexpr uint32_t kMcmcTagRelocate = 0x4D430001u; // word 2 of the Philox counters (philox.hpp)
 constexpr uint32_t kMcmcTagAdd      = 0x4D430002u;
@@ -246,13 +247,10 @@ constexpr uint32_t kMcmcTagNoise    = 0x4D430003u;
 void launch_mcmc_weights(int64_t P, float min_opacity, const float* raw_opacity, uint32_t* w, uint32_t* dead, uint32_t* src_row,
                          hipStream_t stream);
 // dead_list[dead_incl[i] - 1] = i for every dead row (dead_incl: inclusive sums of dead)
-void   launch_mcmc_dead_list(int64_t P, const uint32_t* dead, const uint32_t* dead_incl, uint32_t* dead_list, hipStream_t stream);
-size_t mcmc_scan_temp_bytes(int64_t n);
-// cdf[i] = w[0] + ... + w[i] in u64 (reduce / block sums / final, like scan.hip)
-void launch_mcmc_inclusive_sum_u64(const uint32_t* w, uint64_t* cdf, int64_t n, void* temp, hipStream_t stream);
+void launch_mcmc_dead_list(int64_t P, const uint32_t* dead, const uint32_t* dead_incl, uint32_t* dead_list, hipStream_t stream);
 // draws 0 .. D - 1 (D = *d_n if d_n, else n_host; the launch is sized for n_launch): draw_src[j] = src_in ? src_in[j] : the
-// smallest i with cdf[i] > mulhi64(u_j, T), u_j = Philox(seed; j low, j high, tag, 0) words 0 | 1 << 32, T = cdf[P - 1];
-// count[draw_src[j]] += 1.  status[0] |= 1: an entry of src_in is >= P or has weight 0 (the draw is skipped); |= 2: T == 0
+// smallest i with cdf[i] > mulhi64(u_j, T), u_j = Philox(seed; j low, j high, tag, 0) words 0 | 1 << 32, T = cdf[P - 1]
+// (cdf: the u64 inclusive sums of w, launch_inclusive_sum_u64); count[draw_src[j]] += 1.  status[0] |= 1: an entry of src_in is >= P or has weight 0 (the draw is skipped); |= 2: T == 0
 // (no draw is made)
 void launch_mcmc_draw(int64_t P, int64_t n_launch, int64_t n_host, const uint32_t* d_n, const uint64_t* cdf, const uint32_t* w,
                       const uint32_t* src_in, uint64_t seed, uint32_t tag, uint32_t* draw_src, uint32_t* count, uint32_t* status,

@@ -11,7 +11,7 @@
 //   K1 / K2     the update is IN PLACE: K1 (per draw) reads a source's original scale / opacity and writes a dead or appended
 //               row; K2 (per source) then rewrites the source itself.  Dead and appended rows have weight 0 and are never
 //               sources, so K1's reads and writes never meet.
-// The u64 scan has scan.hip's shape (per-block sums -> their exclusive scan by one block -> per-block scan with carry-in).
+// The u64 inclusive sum of the weights is scan.hip's (launch_inclusive_sum_u64).
 #include "activations.hpp"
 #include "launch.hpp"
 #include "philox.hpp"
@@ -41,100 +41,6 @@ __global__ void __launch_bounds__(256) k_mcmc_dead_list(int64_t P, const uint32_
 {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < P; i += (int64_t)gridDim.x * 256)
         if (dead[i]) dead_list[dead_incl[i] - 1u] = (uint32_t)i; // (dead_incl[i] >= 1 here and <= P)
-}
-
-// ---- the u64 inclusive sum of u32 weights
-constexpr int kThreads = 256;
-constexpr int kItems   = kMcmcScanTile / kThreads; // 2: one uint2 per lane
-static_assert(kItems == 2 && kMcmcScanTile == 512, "the block-sums step below is one 512-thread workgroup");
-
-__device__ __forceinline__ uint64_t wave_inclusive_scan_u64(uint64_t v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t o = (uint64_t)__shfl_up((unsigned long long)v, off, 64);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
-// inclusive scan of one value per thread across a 256-thread block; the block total in `total`
-__device__ __forceinline__ uint64_t block_inclusive_scan_u64(uint64_t v, uint64_t* s_wave /*[4]*/, uint64_t& total)
-{
-    const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t inc  = wave_inclusive_scan_u64(v);
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    uint64_t carry = 0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) {
-        const uint64_t s = s_wave[w];
-        if (w < wave) carry += s;
-    }
-    total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    __syncthreads();
-    return inc + carry;
-}
-__device__ __forceinline__ void load_pair(const uint32_t* __restrict__ in, int64_t base, int64_t n, uint32_t v[2])
-{
-    const int64_t i = base + (int64_t)threadIdx.x * kItems;
-    if (i + 1 < n && ((reinterpret_cast<uintptr_t>(in + i) & 7) == 0)) {
-        const uint2 q = *reinterpret_cast<const uint2*>(in + i);
-        v[0] = q.x, v[1] = q.y;
-    } else {
-        v[0] = i < n ? in[i] : 0u;
-        v[1] = i + 1 < n ? in[i + 1] : 0u;
-    }
-}
-__global__ void __launch_bounds__(kThreads) k_mcmc_scan_reduce(const uint32_t* __restrict__ in, int64_t n,
-                                                               uint64_t* __restrict__ block_sums)
-{
-    __shared__ uint64_t s_wave[4];
-    const int64_t       base = (int64_t)blockIdx.x * kMcmcScanTile;
-    if (base >= n) return;
-    uint32_t v[2];
-    load_pair(in, base, n, v);
-    uint64_t total;
-    block_inclusive_scan_u64((uint64_t)v[0] + v[1], s_wave, total);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
-// exclusive scan of the block sums, in place, by one workgroup of kMcmcScanTile threads (passes of kMcmcScanTile sums)
-__global__ void __launch_bounds__(kMcmcScanTile) k_mcmc_scan_block_sums(uint64_t* __restrict__ block_sums, int64_t nb)
-{
-    __shared__ uint64_t s_wave[kMcmcScanTile / 64];
-    __shared__ uint64_t s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nb; base += kMcmcScanTile) {
-        const int64_t  i   = base + threadIdx.x;
-        const uint64_t v   = i < nb ? block_sums[i] : 0ull;
-        const uint64_t inc = wave_inclusive_scan_u64(v);
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint64_t carry = s_carry;
-        for (int w = 0; w < wave; ++w) carry += s_wave[w];
-        if (i < nb) block_sums[i] = carry + inc - v; // exclusive
-        __syncthreads();
-        if (threadIdx.x == kMcmcScanTile - 1) s_carry = carry + inc;
-        __syncthreads();
-    }
-}
-__global__ void __launch_bounds__(kThreads) k_mcmc_scan_final(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, int64_t n,
-                                                              const uint64_t* __restrict__ block_sums)
-{
-    __shared__ uint64_t s_wave[4];
-    const int64_t       base = (int64_t)blockIdx.x * kMcmcScanTile;
-    if (base >= n) return;
-    uint32_t v[2];
-    load_pair(in, base, n, v);
-    const uint64_t a = v[0], b = (uint64_t)v[0] + v[1];
-    uint64_t       total;
-    const uint64_t inc   = block_inclusive_scan_u64(b, s_wave, total);
-    const uint64_t carry = block_sums[blockIdx.x] + (inc - b);
-    const int64_t  i     = base + (int64_t)threadIdx.x * kItems;
-    if (i < n) out[i] = a + carry;
-    if (i + 1 < n) out[i + 1] = b + carry;
 }
 
 // ---- the sampler: one thread per draw
@@ -371,22 +277,6 @@ void launch_mcmc_weights(int64_t P, float min_opacity, const float* raw_opacity,
 void launch_mcmc_dead_list(int64_t P, const uint32_t* dead, const uint32_t* dead_incl, uint32_t* dead_list, hipStream_t stream)
 {
     hipLaunchKernelGGL(k_mcmc_dead_list, dim3(grid_256(P)), dim3(256), 0, stream, P, dead, dead_incl, dead_list);
-}
-
-size_t mcmc_scan_temp_bytes(int64_t n)
-{
-    const int64_t nb = (n + kMcmcScanTile - 1) / kMcmcScanTile;
-    return (size_t)(nb + 1) * sizeof(uint64_t);
-}
-
-void launch_mcmc_inclusive_sum_u64(const uint32_t* w, uint64_t* cdf, int64_t n, void* temp, hipStream_t stream)
-{
-    if (n <= 0) return;
-    uint64_t*     block_sums = reinterpret_cast<uint64_t*>(temp);
-    const int64_t nb         = (n + kMcmcScanTile - 1) / kMcmcScanTile;
-    hipLaunchKernelGGL(k_mcmc_scan_reduce, dim3((unsigned)nb), dim3(kThreads), 0, stream, w, n, block_sums);
-    hipLaunchKernelGGL(k_mcmc_scan_block_sums, dim3(1), dim3(kMcmcScanTile), 0, stream, block_sums, nb);
-    hipLaunchKernelGGL(k_mcmc_scan_final, dim3((unsigned)nb), dim3(kThreads), 0, stream, w, cdf, n, block_sums);
 }
 
 void launch_mcmc_draw(int64_t P, int64_t n_launch, int64_t n_host, const uint32_t* d_n, const uint64_t* cdf, const uint32_t* w,

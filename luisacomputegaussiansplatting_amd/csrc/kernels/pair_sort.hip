@@ -15,6 +15,7 @@
 
 #include "launch.hpp"
 #include "tie_order.hpp"
+#include "wave_scan.hpp"
 
 namespace lcgs
 {
@@ -24,6 +25,9 @@ namespace
 constexpr int kThreads = 256;
 constexpr int kWaves   = kThreads / 64;
 constexpr int kRadix   = 256;
+// The two scatter kernels and k_rowscan_first take wave_scan.hpp's wave step and write the carry across the waves out:
+// through block_carry the compiler schedules the scatters differently (other register counts), and k_rowscan_first shares
+// the barrier with a second reduced value.  The other kernels here use both steps.
 
 // Layout of the count table: counts[digit * row_stride + chunk], row_stride = the chunk CAPACITY rounded up to 8 --
 // host-known, so every address is known before the live element count (*d_n) has been read, and each kernel issues
@@ -79,8 +83,7 @@ __global__ void __launch_bounds__(kThreads) k_rowscan(uint32_t* __restrict__ cou
     constexpr int kKPB = kThreads * kItems;
     constexpr int kPer = 8;
     __shared__ uint32_t s_wave[kWaves];
-    uint32_t*      row  = counts + (size_t)blockIdx.x * row_stride;
-    const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t*      row = counts + (size_t)blockIdx.x * row_stride;
     uint4          a = make_uint4(0, 0, 0, 0), b = a;
     uint32_t       i0 = threadIdx.x * kPer;
     if (i0 < row_stride) { // row_stride is a multiple of 8: the whole group is inside the row
@@ -107,21 +110,9 @@ __global__ void __launch_bounds__(kThreads) k_rowscan(uint32_t* __restrict__ cou
             e[j] = tot;
             tot += v[j];
         }
-        uint32_t inc = tot;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t carry = carry_in, block_total = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            if (w < wave) carry += s_wave[w];
-            block_total += s_wave[w];
-        }
-        const uint32_t ex = carry + inc - tot;
+        const uint32_t inc = wave_inclusive_scan(tot);
+        uint32_t       block_total;
+        const uint32_t ex = carry_in + block_carry<kWaves>(inc, s_wave, block_total) + inc - tot;
         if (i0 < row_stride) {
             *reinterpret_cast<uint4*>(row + i0)     = make_uint4(ex + e[0], ex + e[1], ex + e[2], ex + e[3]);
             *reinterpret_cast<uint4*>(row + i0 + 4) = make_uint4(ex + e[4], ex + e[5], ex + e[6], ex + e[7]);
@@ -176,12 +167,7 @@ __global__ void __launch_bounds__(kThreads) k_scatter_first(const uint4* __restr
     }
 
     {
-        uint32_t inc = own;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
+        const uint32_t inc = wave_inclusive_scan(own);
         if (lane == 63) s_scan[wave] = inc;
         __syncthreads();
         uint32_t carry = 0;
@@ -233,12 +219,7 @@ __global__ void __launch_bounds__(kThreads) k_scatter_first(const uint4* __restr
         wave_off[w] = total;
         total += s_wave_hist[w][tid];
     }
-    uint32_t inc = total;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
+    const uint32_t inc = wave_inclusive_scan(total);
     if (lane == 63) s_scan[wave] = inc;
     __syncthreads();
     uint32_t carry = 0;
@@ -312,12 +293,7 @@ __global__ void __launch_bounds__(kThreads) k_rowscan_first(uint32_t* __restrict
             tot += v[j];
             tot2 += w2[j];
         }
-        uint32_t inc = tot;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
+        const uint32_t inc = wave_inclusive_scan(tot);
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) tot2 += __shfl_xor(tot2, off, 64);
         if (lane == 63) s_wave[wave] = inc;
@@ -392,12 +368,7 @@ __global__ void __launch_bounds__(kThreads) k_scatter(const K* __restrict__ keys
 
     // global exclusive base of each digit from the 256 row totals
     {
-        uint32_t inc = own;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
+        const uint32_t inc = wave_inclusive_scan(own);
         if (lane == 63) s_scan[wave] = inc;
         __syncthreads();
         uint32_t carry = 0;
@@ -450,12 +421,7 @@ __global__ void __launch_bounds__(kThreads) k_scatter(const K* __restrict__ keys
             wave_off[w] = total;
             total += s_wave_hist[w][tid];
         }
-        uint32_t inc = total;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
+        const uint32_t inc = wave_inclusive_scan(total);
         if (lane == 63) s_scan[wave] = inc;
         __syncthreads();
         uint32_t carry = 0;
@@ -544,17 +510,8 @@ __device__ void sort_long_run_by_file_index(uint32_t* vals, uint32_t lo, uint32_
         __syncthreads();
         { // exclusive scan of the 256 digit counts: thread d owns digit d
             const uint32_t own = s_hist[tid];
-            uint32_t       inc = own;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t o = __shfl_up(inc, off, 64);
-                if (lane >= (uint32_t)off) inc += o;
-            }
-            if (lane == 63u) s_scan[wave] = inc;
-            __syncthreads();
-            uint32_t carry = 0;
-            for (uint32_t w = 0; w < wave; ++w) carry += s_scan[w];
-            s_base[tid] = carry + inc - own;
+            const uint32_t inc = wave_inclusive_scan(own);
+            s_base[tid]        = block_carry<kWaves>(inc, s_scan) + inc - own;
         }
         __syncthreads();
         for (uint32_t base = 0; base < m; base += kThreads) { // members in order, 256 at a time: a STABLE scatter

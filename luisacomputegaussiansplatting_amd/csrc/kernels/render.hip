@@ -26,6 +26,7 @@
 
 #include "launch.hpp"
 #include "tile_common.hpp"
+#include "wave_scan.hpp"
 
 namespace lcgs
 {
@@ -409,16 +410,8 @@ __global__ void __launch_bounds__(1024) k_tile_order(const uint32_t* __restrict_
     }
     __syncthreads();
     const uint32_t own = s_bucket[tid];
-    uint32_t       inc = own;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= (uint32_t)off) inc += o;
-    }
-    if (lane == 63u) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t carry = 0;
-    for (uint32_t w = 0; w < wave; ++w) carry += s_wave[w];
+    const uint32_t inc   = wave_inclusive_scan(own);
+    const uint32_t carry = block_carry<16>(inc, s_wave);
     __syncthreads();
     s_bucket[tid] = carry + inc - own; // exclusive start of the bucket
     __syncthreads();

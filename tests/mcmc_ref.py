@@ -4,7 +4,7 @@ CPU; tests/test_gpu_mcmc.py holds the kernels to it."""
 import numpy as np
 
 F32, F64, U64 = np.float32, np.float64, np.uint64
-SCAN_TILE = 512  # kMcmcScanTile (csrc/kernels/launch.hpp): rows per workgroup of the u64 scan, and sums per pass of its middle step
+SCAN_TILE = 1024  # kScanTile (csrc/kernels/scan.hip): rows per workgroup of the u64 scan, and sums per pass of its middle step
 TAG_RELOCATE, TAG_ADD, TAG_NOISE = 0x4D430001, 0x4D430002, 0x4D430003
 N_MAX = 51
 _MASK = U64(0xFFFFFFFF)

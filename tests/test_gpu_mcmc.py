@@ -3,8 +3,9 @@ in tests/mcmc_ref.py: the built-in sampler bit for bit, the binary64 relocation 
 update's untouched rows, the edges, the SGLD noise, the regulariser, the image invariance the formulas exist for, and a short
 end-to-end fit with a growing splat count.
 
-The u64 scan of the weights works in blocks of SCAN_TILE = 512 rows (kMcmcScanTile, csrc/kernels/launch.hpp), its middle step
-in passes of 512 block sums: the sampler's sizes sit on both edges (512 +- 1, and 512^2 + 1 = 262 145 rows for the second pass).
+The u64 scan of the weights works in blocks of SCAN_TILE = 1024 rows (kScanTile, csrc/kernels/scan.hip), its middle step
+in passes of 1024 block sums: the sampler's sizes sit on both edges (1024 +- 1, and 1024^2 + 1 = 1 048 577 rows for the second
+pass).
 
 The weights are a function of the binary32 sigmoid as the DEVICE evaluates it (its expf may differ from NumPy's in the last
 place), so the model takes that value from the library's own activation kernel: lcgs_opacity_reset with a ceiling above every
@@ -24,7 +25,7 @@ LR = {"pos": 1.6e-4, "sh_dc": 2.5e-3, "sh_rest": 1.25e-4, "opacity": 5e-2, "scal
 F32, F64 = np.float32, np.float64
 SCAN_TILE = ref.SCAN_TILE
 MIN_OP = 0.005
-assert SCAN_TILE == 512
+assert SCAN_TILE == 1024
 
 
 def _activate(raw):
@@ -118,7 +119,7 @@ def _sampler_scene(P, seed):
 
 @pytest.mark.parametrize("P", [1, 2, SCAN_TILE - 1, SCAN_TILE, SCAN_TILE + 1, 100_003, SCAN_TILE * SCAN_TILE + 1])
 def test_built_in_sampler_matches_the_model_bit_for_bit(lcgs, P):
-    assert SCAN_TILE * SCAN_TILE + 1 < 300_000
+    assert SCAN_TILE * SCAN_TILE + 1 < 1_100_000
     raw = _sampler_scene(P, 100 + P % 97)
     o = _device_sigmoid(lcgs, raw["opacity"])
     w, dead = ref.weights(o, MIN_OP)

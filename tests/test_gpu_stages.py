@@ -176,7 +176,8 @@ def test_tile_splatter_all_culled_and_capacity(lcgs, oracle, ops):
     assert e.value.status == 5  # LCGS_ERR_CAPACITY (the reference silently overruns, app/main.cpp:245)
 
 
-@pytest.mark.parametrize("n", [0, 1, 63, 1024, 1025, 4097, 1_000_003])
+# (1024 * 1024 elements are 1024 block sums, one more puts the block-sums step into its second pass)
+@pytest.mark.parametrize("n", [0, 1, 63, 1024, 1025, 4097, 1_000_003, 1024 * 1024, 1024 * 1024 + 1])
 def test_inclusive_sum(lcgs, oracle, ops, n):
     ctx = ops[0]
     rng = np.random.default_rng(n)
