@@ -486,6 +486,66 @@ LCGS_API lcgs_status lcgs_normal_consistency_loss_backward(lcgs_context* ctx, co
                                                            const float* d_alpha, const float* d_normal, float weight,
                                                            float alpha_min, float* d_dL_ddepth, float* d_dL_dalpha,
                                                            float* d_dL_dnormal, float* d_loss);
+/* Depth-prior supervision: the rendered depth of a frame against a depth the caller brings (a monocular estimate, a sensor, a
+ * COLMAP-scaled map), the term sparse-view and indoor recipes add first.  Two kinds: the Pearson-correlation loss of FSGS,
+ * SparseGS and DNGaussian (per patch in the last two: a monocular prior is only locally affine-correct), and 3DGS's "depth
+ * regularisation", an L1 against the prior aligned by a scale and a shift.
+ * Inputs of a W x H frame, binary32 device arrays: depth[H*W] and alpha[H*W] as lcgs_render_maps writes them, prior[H*W], and
+ * mask[H*W] bytes (nullable).  The call does not care which map mode produced depth: render LCGS_DEPTH_INV_Z for a disparity
+ * prior and LCGS_DEPTH_Z for a metric one.
+ * Arithmetic: all per-pixel and per-group algebra is binary64, uncontracted, the inputs widened exactly; every output is
+ * rounded to binary32 once; all sums run in a fixed order with no float atomics: same inputs -> same bits, across calls and
+ * contexts.
+ *     value    v_p = depth_p / max(alpha_p, alpha_min)           m_p = prior_p
+ *     valid    (d_mask == NULL or mask_p != 0) and isfinite(prior_p)
+ *     group    patch == 0: the whole image.  Otherwise the patch x patch blocks of the grid anchored at pixel
+ *              (-patch_x, -patch_y), cut at the image border (the offsets let a trainer jitter the grid per step)
+ *     counted  a group that holds at least 2 valid pixels; under LCGS_DEPTH_ALIGN_GIVEN there is one group and 1 valid pixel
+ *              suffices.  G = the number of counted groups, N_c = the number of valid pixels in counted groups
+ * Per-group statistics over the n valid pixels of a counted group, the means first, then centred sums (two passes, not raw
+ * moments); eps = 1e-12:
+ *     mu_v = sum v / n      mu_m = sum m / n
+ *     var_v = sum (v - mu_v)^2 / n      var_m = sum (m - mu_m)^2 / n      cov = sum (v - mu_v)(m - mu_m) / n
+ *     r = cov / sqrt((var_v + eps)(var_m + eps))      s = cov / (var_m + eps)      t = mu_v - s mu_m
+ * (a constant prior gives m - mu_m = 0 exactly, so r = 0 and s = 0).
+ * LCGS_DEPTH_PRIOR_PEARSON:
+ *     loss = weight / G * sum_g (1 - r_g)             (0 if G == 0)
+ *     g_v(p) = -weight / (G n) * [ (m_p - mu_m) - cov (v_p - mu_v) / (var_v + eps) ] / sqrt((var_v + eps)(var_m + eps))
+ * LCGS_DEPTH_PRIOR_L1:
+ *     res_p = v_p - (s_g m_p + t_g)      loss = weight / N_c * sum |res_p|      (0 if N_c == 0)
+ *     g_v(p) = weight / N_c * sign(res_p), sign(0) = 0
+ *   s and t are constants of the gradient: they are detached, as in a fit done under no_grad or taken from COLMAP.
+ *   LCGS_DEPTH_ALIGN_GIVEN uses cfg->scale and cfg->shift for s and t and computes no statistics.
+ * The chain to the maps, for the valid pixels of counted groups; every other pixel gets an exact zero:
+ *     dL/ddepth_p = g_v / max(alpha_p, alpha_min)
+ *     dL/dalpha_p = (alpha_p >= alpha_min ? -g_v depth_p / alpha_p^2 : 0)          (the clamp passes its gradient at equality)
+ * d_dL_ddepth[H*W] and d_dL_dalpha[H*W] (what lcgs_render_backward_maps takes) are both non-NULL or both NULL.  Both NULL is
+ * evaluation only: the call writes the loss, and its bits equal the gradient call's loss.  Both arrays are written whole,
+ * overwritten, never accumulated.
+ * d_stats (nullable, 4 floats) = { N_c, G, s, t }: the group's fit when patch == 0, the given pair under
+ * LCGS_DEPTH_ALIGN_GIVEN, zeros for s and t in patch mode.
+ * The call needs no kept frame: it is a function of its arguments.  It enqueues on the context's stream and reads nothing back.
+ * LCGS_ERR_INVALID_ARG (before any device work): a NULL ctx, cfg, input or loss pointer; a width or height that is not
+ * positive; an unknown kind or align; LCGS_DEPTH_ALIGN_GIVEN with the Pearson kind or with patch != 0; a scale or shift that
+ * is not finite under LCGS_DEPTH_ALIGN_GIVEN; a weight that is not finite or is negative; an alpha_min that is not finite or
+ * is <= 0; a patch that is not 0, 32, 64 or 128, or an offset outside [0, patch); exactly one gradient pointer NULL; any
+ * output (gradients, loss, stats) that overlaps any input or another output.
+ * Not offered: FSGS's min over two depth transforms; random or overlapping patches; a non-detached alignment; the term inside
+ * lcgs_fit_views; an lcgs-app flag for it; a camera gradient. */
+#define LCGS_DEPTH_PRIOR_PEARSON 0
+#define LCGS_DEPTH_PRIOR_L1      1
+#define LCGS_DEPTH_ALIGN_FIT     0   /* per-group least-squares scale and shift of the prior, detached */
+#define LCGS_DEPTH_ALIGN_GIVEN   1   /* L1 only: the caller's scale and shift (3DGS: from COLMAP) */
+typedef struct lcgs_depth_prior_config {
+    int   kind, align;
+    float scale, shift;               /* ALIGN_GIVEN */
+    float weight, alpha_min;
+    int   patch, patch_x, patch_y;    /* 0 = one group (the image); else 32, 64 or 128 with 0 <= patch_x, patch_y < patch */
+} lcgs_depth_prior_config;
+LCGS_API lcgs_status lcgs_depth_prior_loss_backward(lcgs_context* ctx, int width, int height, const float* d_depth,
+                                                    const float* d_alpha, const float* d_prior, const uint8_t* d_mask,
+                                                    const lcgs_depth_prior_config* cfg, float* d_dL_ddepth, float* d_dL_dalpha,
+                                                    float* d_loss, float* d_stats);
 /* Per-view bilateral-grid colour correction ("Bilateral Guided Radiance Field Processing"; gsplat's use_bilateral_grid): what
  * absorbs the exposure, white balance and tone curve that change from photograph to photograph, so that the scene does not.
  * Each training view owns a small 3-D grid of 3 x 4 affine colour transforms; the grid is sliced at (pixel x, pixel y,

@@ -37,6 +37,7 @@ from .api import (  # noqa: F401
     build_library,
     camera_grad_to_twist,
     camera_with_vectors,
+    depth_prior_autograd,
     filter3d_autograd,
     get_lookat_cam,
     image_to_rgb8,

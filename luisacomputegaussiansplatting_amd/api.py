@@ -189,6 +189,11 @@ class _TsdfConfig(C.Structure):
     _fields_ = [("trunc", C.c_float), ("depth_max", C.c_float), ("alpha_min", C.c_float)]
 
 
+class _DepthPriorConfig(C.Structure):
+    _fields_ = [("kind", C.c_int), ("align", C.c_int), ("scale", C.c_float), ("shift", C.c_float), ("weight", C.c_float),
+                ("alpha_min", C.c_float), ("patch", C.c_int), ("patch_x", C.c_int), ("patch_y", C.c_int)]
+
+
 class _SparseRows(C.Structure):
     _fields_ = [("d_rows", C.c_void_p), ("num_rows", C.c_int64), ("owner_first", C.c_int64 * (LCGS_MAX_RANKS + 2))]
 
@@ -217,7 +222,7 @@ STRUCTS = {
     "lcgs_stage_times": _StageTimes, "lcgs_frame_stats": _FrameStats, "lcgs_grads": _Grads, "lcgs_params": _Params,
     "lcgs_adam_config": _AdamConfig, "lcgs_densify_stats": _DensifyStats, "lcgs_densify_config": _DensifyConfig,
     "lcgs_mcmc_config": _McmcConfig, "lcgs_mcmc_noise_config": _McmcNoiseConfig,
-    "lcgs_init_config": _InitConfig, "lcgs_tsdf_volume": _TsdfVolume, "lcgs_tsdf_config": _TsdfConfig, "lcgs_contrib_stats": _ContribStats, "lcgs_prune_config": _PruneConfig,
+    "lcgs_init_config": _InitConfig, "lcgs_tsdf_volume": _TsdfVolume, "lcgs_tsdf_config": _TsdfConfig, "lcgs_depth_prior_config": _DepthPriorConfig, "lcgs_contrib_stats": _ContribStats, "lcgs_prune_config": _PruneConfig,
     "lcgs_sparse_rows": _SparseRows, "lcgs_comm_stats": _CommStats, "lcgs_comm_selftest_report": _SelftestReport,
     "lcgs_scene_host": _SceneHost,
 }
@@ -311,6 +316,7 @@ def _signatures() -> dict:
         "lcgs_l2_loss_backward": (st, [p, i, i, p, p, p, p]),
         "lcgs_photometric_loss_backward": (st, [p, i, i, p, p, f, p, p, p]),
         "lcgs_normal_consistency_loss_backward": (st, [p, cam, p, p, p, f, f, p, p, p, p]),
+        "lcgs_depth_prior_loss_backward": (st, [p, i, i, p, p, p, p, ptr["depth_prior_config"], p, p, p, p]),
         # per-view bilateral-grid colour correction
         "lcgs_bilagrid_slice": (st, [p, i, i, p, i, i, i, p, p]),
         "lcgs_bilagrid_backward": (st, [p, i, i, p, i, i, i, p, p, p, p]),
@@ -1003,6 +1009,41 @@ class Renderer:
         _check(load_library().lcgs_normal_consistency_loss_backward(self.ctx._h, C.byref(cam), _ptr(depth), _ptr(alpha), _ptr(normal),
                                                                     weight, alpha_min, _ptr(dL_ddepth), _ptr(dL_dalpha),
                                                                     _ptr(dL_dnormal), _ptr(loss)))
+
+    def depth_prior_loss_backward(self, depth, alpha, prior, dL_ddepth, dL_dalpha, loss, mask=None, kind: str = "pearson",
+                                  align: str = "fit", scale: float = 1.0, shift: float = 0.0, weight: float = 1.0,
+                                  alpha_min: float = 1e-3, patch: int = 0, patch_offset=(0, 0), stats=None):
+        """lcgs_depth_prior_loss_backward: the rendered depth v = depth / max(alpha, alpha_min) of a frame's maps [H, W] against
+        a depth the caller brings, prior [H, W], over the pixels where mask (optional, uint8 / bool [H, W]) is set and the prior
+        is finite.  kind "pearson": loss[0] = weight x the mean over the groups of 1 - corr(v, prior); kind "l1": weight x the
+        mean of |v - (s prior + t)|, (s, t) the group's least-squares fit (align "fit", detached) or (scale, shift) (align
+        "given").  A group is the image (patch 0) or a patch x patch block (32, 64, 128) of the grid anchored at
+        -patch_offset.  dL_ddepth, dL_dalpha (both, or both None: evaluation only) = its gradients, what backward_maps takes,
+        written whole; stats (optional, 4 floats) = (N_c, G, s, t).  Device tensors, float32; binary64 inside; the same
+        inputs give the same bits."""
+        import torch
+
+        H, W = depth.shape
+        for name, t, dtypes in (("depth", depth, (torch.float32,)), ("alpha", alpha, (torch.float32,)),
+                                ("prior", prior, (torch.float32,)), ("mask", mask, (torch.uint8, torch.bool)),
+                                ("dL_ddepth", dL_ddepth, (torch.float32,)), ("dL_dalpha", dL_dalpha, (torch.float32,))):
+            # (a mismatched buffer would be an out-of-bounds device access behind the C ABI, which sees pointers only)
+            if t is not None and (t.dtype not in dtypes or tuple(t.shape) != (H, W) or t.device != depth.device or not t.is_contiguous()):
+                raise ValueError(f"{name}: expected a contiguous {dtypes[0]} ({H}, {W}) tensor on {depth.device}, got {t.dtype} "
+                                 f"{tuple(t.shape)} on {t.device}")
+        for name, t, numel in (("loss", loss, 1), ("stats", stats, 4)):  # ... and so would a short or misplaced output
+            if t is None and name == "loss":
+                raise ValueError("loss: expected a float32 tensor of 1 element, got None")
+            if t is not None and (t.dtype != torch.float32 or t.numel() != numel or t.device != depth.device or not t.is_contiguous()):
+                raise ValueError(f"{name}: expected a contiguous float32 tensor of {numel} element(s) on {depth.device}, got {t.dtype} "
+                                 f"{tuple(t.shape)} on {t.device}")
+        kinds, aligns = {"pearson": 0, "l1": 1}, {"fit": 0, "given": 1}
+        if kind not in kinds or align not in aligns:
+            raise ValueError(f"kind must be one of {sorted(kinds)} and align one of {sorted(aligns)}, got {kind!r}, {align!r}")
+        cfg = _DepthPriorConfig(kinds[kind], aligns[align], scale, shift, weight, alpha_min, int(patch), int(patch_offset[0]),
+                                int(patch_offset[1]))
+        _check(load_library().lcgs_depth_prior_loss_backward(self.ctx._h, W, H, _ptr(depth), _ptr(alpha), _ptr(prior), _ptr(mask),
+                                                             C.byref(cfg), _ptr(dL_ddepth), _ptr(dL_dalpha), _ptr(loss), _ptr(stats)))
 
     @staticmethod
     def _bilagrid_buffers(first, **named):
@@ -1773,6 +1814,37 @@ def normal_consistency_autograd(renderer: "Renderer", cam: Camera, depth, alpha,
                          for g, s, need in zip(ctx.saved_tensors, ctx.shapes, ctx.needs_input_grad))
 
     return _Fn.apply(depth, alpha, normal)
+
+
+def depth_prior_autograd(renderer: "Renderer", depth, alpha, prior, mask=None, kind: str = "pearson", align: str = "fit",
+                         scale: float = 1.0, shift: float = 0.0, weight: float = 1.0, alpha_min: float = 1e-3, patch: int = 0,
+                         patch_offset=(0, 0), stats=None):
+    """Differentiable depth-prior loss for torch: `loss = depth_prior_autograd(r, depth, alpha, prior)`, a scalar tensor
+    differentiable in depth and alpha (the prior and the mask are data).  The forward is ONE lcgs_depth_prior_loss_backward call
+    that also stores the two gradients; the backward hands them out scaled by the incoming scalar.  Composes with the frame:
+    `_, depth, alpha = render_autograd_maps(r, cam, ..., depth_mode="inv_z")`.  The other arguments are
+    Renderer.depth_prior_loss_backward's."""
+    import torch
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, depth, alpha):
+            args = [t.detach().contiguous() for t in (depth, alpha)]
+            grads = [torch.empty_like(t) for t in args]
+            loss = torch.empty(1, device=args[0].device, dtype=torch.float32)
+            renderer.depth_prior_loss_backward(*args, prior.detach().contiguous(), *grads, loss,
+                                               None if mask is None else mask.detach().contiguous(), kind, align, scale, shift,
+                                               weight, alpha_min, patch, patch_offset, stats)
+            ctx.save_for_backward(*grads)
+            ctx.shapes = (depth.shape, alpha.shape)
+            return loss[0]
+
+        @staticmethod
+        def backward(ctx, g_loss):
+            return tuple((g * g_loss).view(s) if need else None
+                         for g, s, need in zip(ctx.saved_tensors, ctx.shapes, ctx.needs_input_grad))
+
+    return _Fn.apply(depth, alpha)
 
 
 def bilagrid_identity(num: int, dims=(16, 16, 8), device="cuda:0"):

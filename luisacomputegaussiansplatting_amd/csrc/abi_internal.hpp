@@ -14,6 +14,7 @@
 //   abi_filter3d.cpp  Mip-Splatting's 3-D smoothing filter: lcgs_filter3d_accumulate / _finalize / _apply / _backward
 //   abi_tsdf.cpp      a surface out of the scene: lcgs_tsdf_integrate, lcgs_tsdf_mesh_count / _extract
 //   abi_loss.cpp      lcgs_photometric_loss_backward, lcgs_normal_consistency_loss_backward, lcgs_set_fit_loss
+//   abi_depth_prior.cpp  depth-prior supervision (Pearson, aligned L1): lcgs_depth_prior_loss_backward
 //   abi_bilagrid.cpp  per-view bilateral-grid colour correction: lcgs_bilagrid_slice / _backward / _tv_loss_backward
 //   abi_init.cpp      a scene from a point cloud: lcgs_knn_mean_dist2, lcgs_scene_init_from_points, lcgs_scene_extent
 //   abi_owner.cpp     the frame in two halves (splat ownership): lcgs_owner_project / _render / _render_backward / _backward

@@ -219,6 +219,7 @@ struct lcgs_context {
     // lcgs_photometric_loss_backward: per-workgroup partial sums, then the planes a, b, c (loss.hip); the loss lcgs_fit_views
     // applies (lcgs_set_fit_loss; handed to the sibling in prepare_twin)
     // (lcgs_normal_consistency_loss_backward: its per-workgroup partial sums)
+    // (lcgs_depth_prior_loss_backward: the tiles' and groups' sums and the groups' coefficients, kernels/launch.hpp)
     // (lcgs_bilagrid_backward: the row slices' partial sums of dL/dgrid; lcgs_bilagrid_tv_loss_backward: per-workgroup partials)
     DeviceBuffer loss_ws;
     int          fit_loss   = LCGS_LOSS_L2;

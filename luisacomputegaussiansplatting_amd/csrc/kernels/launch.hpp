@@ -349,6 +349,36 @@ int64_t normal_consistency_workgroups(int W, int H);
 void launch_normal_consistency(int W, int H, double tanx, double tany, double scale, double alpha_min, const float* depth,
                                const float* alpha, const float* normal, float* dL_ddepth, float* dL_dalpha, float* dL_dnormal,
                                double* partials, float* loss, hipStream_t stream);
+// ---- depth_prior.hip : the Pearson and aligned-L1 losses of a depth map against a prior, with their gradients ----
+// (include/lcgs_hip.h has the definition.)  32 x 16 tiles anchored at the patch grid's anchor, every tile inside one group.
+constexpr int kDepthPriorTileW = 32, kDepthPriorTileH = 16;
+constexpr int kDepthPriorRec = 8; // doubles of a group's record (means, coefficients, counted flag)
+struct DepthPriorGrid {
+    int W, H;
+    int ox, oy;             // the grid's anchor is pixel (-ox, -oy); 0 for the whole image
+    int gtx, gty;           // tiles of a group along x and y
+    int groups_x, groups_y; // groups; every tile of every group is launched
+};
+// patch 0: one group, the image; else 32, 64 or 128 with 0 <= patch_x, patch_y < patch (checked by the caller)
+DepthPriorGrid depth_prior_grid(int W, int H, int patch, int patch_x, int patch_y);
+inline int64_t depth_prior_groups(const DepthPriorGrid& g) { return (int64_t)g.groups_x * g.groups_y; }
+inline int64_t depth_prior_tiles(const DepthPriorGrid& g) { return depth_prior_groups(g) * g.gtx * g.gty; }
+struct DepthPriorTerm {
+    int    kind;  // LCGS_DEPTH_PRIOR_PEARSON / _L1
+    bool   given; // LCGS_DEPTH_ALIGN_GIVEN: (scale, shift) are the caller's, no statistics
+    bool   patch; // patch mode, however many groups the grid has on this image: d_stats reports no fit
+    double scale, shift, weight, alpha_min;
+};
+// the call's arrays inside one block of `doubles` binary64 numbers at `base` (base NULL: only the size is wanted)
+struct DepthPriorWorkspace {
+    double *hdr, *rec, *gsum, *tile1, *tile2, *l1_part;
+    size_t  doubles;
+};
+DepthPriorWorkspace depth_prior_workspace(const DepthPriorGrid& g, double* base);
+// mask nullable; dL_ddepth and dL_dalpha both NULL: evaluation only (the same loss bits); stats nullable, 4 floats
+void launch_depth_prior(const DepthPriorGrid& g, const DepthPriorTerm& term, const float* depth, const float* alpha, const float* prior,
+                        const uint8_t* mask, float* dL_ddepth, float* dL_dalpha, float* loss, float* stats, const DepthPriorWorkspace& w,
+                        hipStream_t stream);
 // ---- bilagrid.hip : per-view bilateral-grid colour correction -- slice, its two gradients, total variation ----
 // A view's grid is [12][gl][gh][gw] floats (include/lcgs_hip.h has the definition); images are CHW.
 constexpr int kBilagridTileW = 32, kBilagridTileH = 16; // the pixel tile of a workgroup of the per-pixel passes

@@ -1,4 +1,4 @@
-// ordered_sum.hpp -- the fixed-order binary64 sums the loss kernels share (loss.hip, bilagrid.hip): a wave's butterfly and the
+// ordered_sum.hpp -- the fixed-order binary64 sums the loss kernels share (loss.hip, depth_prior.hip, bilagrid.hip): a wave's butterfly and the
 // one-workgroup finish over per-workgroup partials.  No atomics: the same inputs give the same bits.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -115,6 +115,16 @@ public:
         check(lcgs_normal_consistency_loss_backward(m_ctx, &cam, d_depth, d_alpha, d_normal, weight, alpha_min, d_dL_ddepth,
                                                     d_dL_dalpha, d_dL_dnormal, d_loss));
     }
+    // depth-prior supervision: the Pearson (cfg.kind = LCGS_DEPTH_PRIOR_PEARSON) or aligned-L1 loss of a frame's depth and alpha
+    // maps against a depth the caller brings, and its two gradients, what lcgs_render_backward_maps takes (device pointers; the
+    // gradients both or both NULL: evaluation only; d_mask and d_stats, { N_c, G, s, t }, nullable)
+    void depth_prior_loss_backward(int width, int height, const float* d_depth, const float* d_alpha, const float* d_prior,
+                                   const uint8_t* d_mask, const lcgs_depth_prior_config& cfg, float* d_dL_ddepth,
+                                   float* d_dL_dalpha, float* d_loss, float* d_stats = nullptr)
+    {
+        check(lcgs_depth_prior_loss_backward(m_ctx, width, height, d_depth, d_alpha, d_prior, d_mask, &cfg, d_dL_ddepth,
+                                             d_dL_dalpha, d_loss, d_stats));
+    }
     // per-view bilateral-grid colour correction (device pointers; one view's grid is [12][gl][gh][gw]): the slice of the grid at
     // (pixel x, pixel y, luminance of the input pixel) applied to the image; its backward (either gradient may be NULL, not
     // both); the total-variation term of num_grids grids (d_dL_dgrids NULL: evaluation only)
