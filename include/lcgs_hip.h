@@ -347,6 +347,59 @@ LCGS_API lcgs_status lcgs_render_backward_normals(lcgs_context* ctx, const float
                                                   const float* d_dL_ddepth, const float* d_dL_dalpha, const float* d_dL_ddist,
                                                   const float* d_dL_dnormal, int accumulate, const lcgs_grads* grads);
 
+/* ---- caller-supplied per-splat feature channels of the last lcgs_render_forward(keep_state = 1), and their backward ---- */
+/* Per-splat vectors the CALLER brings, blended like colour: semantic logits, distilled CLIP / DINO / SAM features (Feature-3DGS,
+ * LangSplat, LEGaussians), instance ids as one-hot rows, per-splat uncertainty.  The general case of the normal channel: the
+ * vector f_i has K components, comes from the caller and its gradient goes back to the caller.
+ * d_features: P x K floats, row-major, row r the features of row r of the context's scene arrays -- the context's row order,
+ * as lcgs_grads' arrays: after lcgs_scene_upload that is the spatial (Morton) order of lcgs_scene_permutation.  num_gaussians
+ * must be the bound scene's P.  A row of odd K need not be 16-byte aligned.
+ * The map, with the entries i, the weights w_i and the list order of lcgs_render_maps:
+ *     feature_map[c][p] = sum_i fl(w_i f_i,c)          (binary32, list order, from 0;  c = 0 .. K-1;  K*H*W floats, CHW)
+ * the multiply and the add separate operations (the build does not contract, and no matrix instruction is used: an f32 MFMA
+ * is an fmaf chain), which a CPU restatement of the frame composites bit for bit, three columns at a time, as the per-splat
+ * colour.  The map is NOT normalised (divide by alpha), NO background is blended in and it is NOT clamped.  A pixel outside
+ * every list, and every pixel of a frame that drew nothing, is 0 in all K channels (such a frame leaves the colour image
+ * untouched).  The call reads the kept state, so it works on antialiased and LOD frames unchanged.
+ * The backward treats thresholds, the 0.99 cap and saturation as lcgs_render_backward does.  f_i . dL/dfeature_map[.][p] is
+ * taken through the blend like a per-pixel value of entry i (to pos, scale, rotq and opacity through the weights, as in every
+ * other channel), and dL/df_i,c = sum_p w_i dL/dfeature_map[c][p] goes to d_dL_dfeatures.  Nothing reaches sh, and nothing
+ * reaches pos, scale or rotq from the feature's own value.  d_dL_dfeatures is summed by float atomics in unspecified order: the
+ * last bits of a row that several tiles blend vary from run to run, as weight_sum's do.
+ * Not offered: compact rows; a feature channel in lcgs_render_backward_camera, lcgs_fit_views or the ownership step; an
+ * lcgs-app flag; f16 features. */
+#define LCGS_FEATURES_MAX 256
+typedef struct lcgs_feature_channel {
+    int          channels;           /* K, 1 .. LCGS_FEATURES_MAX */
+    const float* d_features;         /* P x K, row-major, the context's row order (as lcgs_grads' arrays) */
+    const float* d_dL_dfeature_map;  /* K x H x W (CHW); backward only */
+    float*       d_dL_dfeatures;     /* P x K; backward only; may be NULL (features frozen) */
+} lcgs_feature_channel;
+/* d_feature_map: K*H*W floats, CHW.  Enqueues on the context's stream, reads nothing back.  K channels are walked in chunks of
+ * 4, 8 or 16 (the smallest that holds K, 16 beyond): ceil(K / 16) walks of the lists for a large K.  Stage under
+ * lcgs_set_profiling: render_features. */
+LCGS_API lcgs_status lcgs_render_features(lcgs_context* ctx, int num_gaussians, int channels, const float* d_features,
+                                          float* d_feature_map);
+/* lcgs_render_backward_normals with one more channel group: the gradient of <dL_dimg, img> + <dL_ddepth, depth> +
+ * <dL_dalpha, alpha> + <dL_ddist, dist> + <dL_dnormal, normal> + <dL_dfeature_map, feature_map>, dense rows overwritten
+ * (accumulate = 0) or added to; `accumulate` holds for the rows of `grads` and for d_dL_dfeatures alike, and with
+ * accumulate = 0 the rows that nothing blends are exact zeros in both.  With feat NULL the call is
+ * lcgs_render_backward_normals.  feat->d_dL_dfeatures NULL with grads given: the features are frozen, only the geometry rows
+ * are written.  grads NULL is allowed when every other incoming gradient is NULL and feat->d_dL_dfeatures is not: the
+ * frozen-geometry mode (LangSplat's) -- the walk then forms no geometry sums, and the frame's 2-D gradient rows are left as they
+ * were, so lcgs_camera_backward and lcgs_densify_accumulate behind it give what they gave before the call.  Both NULL is an
+ * argument error.  Otherwise lcgs_densify_accumulate and lcgs_camera_backward work behind the call and see the combined 2-D
+ * gradient: a caller-supplied feature has no direct camera term, so nothing is refused on its account (the refusal behind a
+ * non-NULL d_dL_dnormal stays).
+ * Both calls: LCGS_ERR_STATE without a keep_state frame, or after a frame of lcgs_owner_render.  LCGS_ERR_INVALID_ARG (before
+ * any device work): NULL ctx, rows, map or map gradient, channels outside 1 .. LCGS_FEATURES_MAX, a num_gaussians that is not
+ * the bound scene's, every gradient NULL, a NULL gradient buffer, a mode that is neither constant, a non-finite center.
+ * Stages under lcgs_set_profiling: those of lcgs_render_backward_normals, zero_features (accumulate = 0), render_features_backward. */
+LCGS_API lcgs_status lcgs_render_backward_features(lcgs_context* ctx, const float* d_dL_dimg, int mode, float center,
+                                                   const float* d_dL_ddepth, const float* d_dL_dalpha, const float* d_dL_ddist,
+                                                   const float* d_dL_dnormal, const lcgs_feature_channel* feat, int accumulate,
+                                                   const lcgs_grads* grads);
+
 /* ---- per-splat blend-weight statistics of the last lcgs_render_forward(keep_state = 1) ---- */
 /* Which splats a set of views actually uses.  w is the w_i = T_i alpha_i above: the weight pixel p gives entry i of its list, for
  * the entries p blended (positions up to n_contrib[p] that pass the renderer's power and 1/255 tests, the 0.99 cap and the

@@ -54,6 +54,7 @@ from .api import (  # noqa: F401
     render_autograd,
     render_autograd_camera,
     render_autograd_distortion,
+    render_autograd_features,
     render_autograd_normals,
     render_autograd_maps,
     scene_extent,

@@ -56,6 +56,7 @@ _DEPTH_MODES = {"z": DEPTH_Z, "inv_z": DEPTH_INV_Z}
 LCGS_KNN_CHUNK = 256  # sorted points per query workgroup of the nearest-neighbour search (sizes around its multiples are edge cases)
 LCGS_TSDF_VIEW_CHUNK = 42  # kTsdfViewChunk: views per launch of tsdf_integrate (view counts around its multiples are edge cases)
 LCGS_ERR_CAPACITY = 5
+LCGS_FEATURES_MAX = 256  # the most channels lcgs_render_features / lcgs_render_backward_features take
 LCGS_FILTER3D_VIEW_CHUNK = 64  # kFilter3dViewChunk: views per launch of filter3d_accumulate (view counts around its multiples are edge cases)
 # lcgs_set_fit_loss kinds (LCGS_LOSS_* in include/lcgs_hip.h)
 LOSS_L2, LOSS_PHOTOMETRIC = 0, 1
@@ -171,6 +172,11 @@ class _ContribStats(C.Structure):
     _fields_ = [("weight_sum", C.c_void_p), ("weight_max", C.c_void_p), ("pixels", C.c_void_p), ("views", C.c_void_p)]
 
 
+class _FeatureChannel(C.Structure):
+    _fields_ = [("channels", C.c_int), ("d_features", C.c_void_p), ("d_dL_dfeature_map", C.c_void_p),
+                ("d_dL_dfeatures", C.c_void_p)]
+
+
 class _PruneConfig(C.Structure):
     _fields_ = [("min_weight_max", C.c_float), ("min_weight_sum", C.c_float), ("min_pixels", C.c_uint64),
                 ("min_views", C.c_uint64)]
@@ -223,6 +229,7 @@ STRUCTS = {
     "lcgs_adam_config": _AdamConfig, "lcgs_densify_stats": _DensifyStats, "lcgs_densify_config": _DensifyConfig,
     "lcgs_mcmc_config": _McmcConfig, "lcgs_mcmc_noise_config": _McmcNoiseConfig,
     "lcgs_init_config": _InitConfig, "lcgs_tsdf_volume": _TsdfVolume, "lcgs_tsdf_config": _TsdfConfig, "lcgs_depth_prior_config": _DepthPriorConfig, "lcgs_contrib_stats": _ContribStats, "lcgs_prune_config": _PruneConfig,
+    "lcgs_feature_channel": _FeatureChannel,
     "lcgs_sparse_rows": _SparseRows, "lcgs_comm_stats": _CommStats, "lcgs_comm_selftest_report": _SelftestReport,
     "lcgs_scene_host": _SceneHost,
 }
@@ -304,6 +311,9 @@ def _signatures() -> dict:
         # normal map
         "lcgs_render_normals": (st, [p, p]),
         "lcgs_render_backward_normals": (st, [p, p, i, f, p, p, p, p, i, grads]),
+        # caller-supplied feature channels
+        "lcgs_render_features": (st, [p, i, i, p, p]),
+        "lcgs_render_backward_features": (st, [p, p, i, f, p, p, p, p, ptr["feature_channel"], i, grads]),
         # per-splat blend-weight statistics
         "lcgs_contrib_accumulate": (st, [p, i, cstats]),
         # camera gradient
@@ -904,6 +914,29 @@ class Renderer:
         _check(load_library().lcgs_render_backward_normals(self.ctx._h, _ptr(dL_dimg), _DEPTH_MODES[mode], float(center),
                                                            _ptr(dL_ddepth), _ptr(dL_dalpha), _ptr(dL_ddist), _ptr(dL_dnormal),
                                                            bool(accumulate), C.byref(g)))
+
+    def render_features(self, features, out):
+        """lcgs_render_features: the caller's per-splat vectors blended like colour over the last keep_state frame.  features:
+        [P, K] float32 rows in the context's row order (after upload_scene: features[permutation()]); out: K x H x W floats
+        (CHW), per pixel the sum of w_i f_i over the blended entries.  Not normalised, not clamped, no background.  Enqueues only."""
+        P, K = int(features.shape[0]), int(features.shape[1])
+        _check(load_library().lcgs_render_features(self.ctx._h, P, K, _ptr(features), _ptr(out)))
+
+    def backward_features(self, dL_dimg, dL_ddepth, dL_dalpha, dL_ddist, dL_dnormal, features, dL_dfeature_map, dL_dfeatures,
+                          dpos=None, dscale=None, drotq=None, dsh=None, dopacity=None, mode: str = "z", center: float = 0.0,
+                          accumulate: bool = False):
+        """lcgs_render_backward_features: backward_normals with the feature map's incoming gradient (K x H x W) as one more
+        channel group; dL_dfeatures ([P, K], overwritten or, accumulate, added to) may be None (the features are frozen).  With
+        features None it is backward_normals.  All five gradient arrays None: the frozen-geometry mode -- dL_dfeatures alone,
+        every other incoming gradient must then be None, and the frame's 2-D gradient rows are left as they were."""
+        rows = (dpos, dscale, drotq, dsh, dopacity)
+        g = None if all(t is None for t in rows) else _grads(rows)
+        feat = None
+        if features is not None:
+            feat = _FeatureChannel(int(features.shape[1]), _ptr(features), _ptr(dL_dfeature_map), _ptr(dL_dfeatures))
+        _check(load_library().lcgs_render_backward_features(
+            self.ctx._h, _ptr(dL_dimg), _DEPTH_MODES[mode], float(center), _ptr(dL_ddepth), _ptr(dL_dalpha), _ptr(dL_ddist),
+            _ptr(dL_dnormal), None if feat is None else C.byref(feat), bool(accumulate), None if g is None else C.byref(g)))
 
     def camera_backward(self, out12):
         """lcgs_camera_backward: the camera gradient of the last backward of the kept frame -- 12 floats on the device in the
@@ -1669,22 +1702,24 @@ def sparse_message_words(count: int, sh_degree: int = 3) -> int:
 
 
 def _autograd_frame(renderer: "Renderer", view: Camera, scene, bg, scale_modifier: float, outputs: str = "image",
-                    depth_mode: str = "z", center: float = 0.0, cam12=None):
+                    depth_mode: str = "z", center: float = 0.0, cam12=None, features=None):
     """The one differentiable frame behind render_autograd and its variants: binds the scene, renders `view` with keep_state,
     renders the maps `outputs` asks for ("image": the image alone; "maps": plus depth and alpha; "distortion": plus the
-    distortion map about `center`; "normals": plus the normal map) and, on backward, differentiates that frame -- after binding its saved scene and rendering
+    distortion map about `center`; "normals": plus the normal map; "features": the image, alpha and the blended map of the
+    caller's `features` rows, a sixth differentiable input behind the five scene tensors) and, on backward, differentiates that frame -- after binding its saved scene and rendering
     its view again when the renderer's generation has moved -- through the one Renderer backward that fits.  cam12 (a tensor
     or None): the pose is an input too, in front of the five scene tensors, and gets the camera gradient."""
     import torch
 
-    maps, dist, nrm, pose = outputs != "image", outputs in ("distortion", "normals"), outputs == "normals", cam12 is not None
+    feats = outputs == "features"
+    maps, dist, nrm, pose = outputs not in ("image", "features"), outputs in ("distortion", "normals"), outputs == "normals", cam12 is not None
 
     class _Fn(torch.autograd.Function):
         @staticmethod
         def forward(ctx, *inputs):
             params = inputs[1:] if pose else inputs
             args = [t.detach().contiguous() for t in params]
-            renderer.bind_scene(*args)
+            renderer.bind_scene(*args[:5])
             dev = args[0].device
             img = torch.empty(3, view.height, view.width, device=dev, dtype=torch.float32)
             extra = [torch.empty(view.height, view.width, device=dev, dtype=torch.float32) for _ in range(3 if dist else 2 if maps else 0)]
@@ -1698,13 +1733,18 @@ def _autograd_frame(renderer: "Renderer", view: Camera, scene, bg, scale_modifie
             if nrm:
                 extra.append(torch.empty(3, view.height, view.width, device=dev, dtype=torch.float32))
                 renderer.render_normals(extra[3])
+            if feats:
+                extra = [torch.empty(view.height, view.width, device=dev, dtype=torch.float32),
+                         torch.empty(args[5].shape[1], view.height, view.width, device=dev, dtype=torch.float32)]
+                renderer.render_maps(None, extra[0])
+                renderer.render_features(args[5], extra[1])
             ctx.shapes = [t.shape for t in params]
             if pose:
                 ctx.cam_like = (inputs[0].shape, inputs[0].device)
             ctx.empty = n == 0
             ctx.generation = renderer._generation
             ctx.save_for_backward(*args)
-            if not maps:
+            if not maps and not feats:
                 return img  # (its single gradient arrives materialised)
             ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None and is passed as NULL
             return (img, *extra)
@@ -1719,11 +1759,17 @@ def _autograd_frame(renderer: "Renderer", view: Camera, scene, bg, scale_modifie
             incoming = [None if g is None or g.numel() == 0 else g.contiguous() for g in incoming]
             if not ctx.empty and any(g is not None for g in incoming):
                 if renderer._generation != ctx.generation:  # the renderer's frame state is no longer this frame's
-                    renderer.bind_scene(*args)
+                    renderer.bind_scene(*args[:5])
                     scratch = torch.empty(3, view.height, view.width, device=args[0].device, dtype=torch.float32)
                     renderer.forward(view, scratch, bg=bg, scale_modifier=scale_modifier, keep_state=True, sync=True)
                     ctx.generation = renderer._generation
-                if not want_scene:
+                if feats:
+                    gi, ga, gf = incoming
+                    if gf is None:  # the feature map is not in the loss: no feature channel, dL/dfeatures stays zero
+                        renderer.backward_maps(gi, None, ga, *grads[:5])
+                    else:
+                        renderer.backward_features(gi, None, ga, None, None, args[5], gf, grads[5], *grads[:5])
+                elif not want_scene:
                     renderer.backward_camera(*incoming, g12, mode=depth_mode)
                 elif nrm:
                     renderer.backward_normals(*incoming, *grads, mode=depth_mode, center=center)
@@ -1741,7 +1787,7 @@ def _autograd_frame(renderer: "Renderer", view: Camera, scene, bg, scale_modifie
                 out = (g12.to(dev).view(shape) if want_cam else None,) + out
             return out
 
-    return _Fn.apply(*((cam12,) if pose else ()), *scene)
+    return _Fn.apply(*((cam12,) if pose else ()), *scene, *((features,) if feats else ()))
 
 
 def render_autograd(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh, opacity, bg=(0.0, 0.0, 0.0),
@@ -1787,6 +1833,17 @@ def render_autograd_normals(renderer: "Renderer", cam: Camera, pos, scale, rotq,
     re-renders its own view when the renderer's generation has moved.  The pose is not an input: the camera gradient of the
     normal channel is not offered."""
     return _autograd_frame(renderer, cam, (pos, scale, rotq, sh, opacity), bg, scale_modifier, "normals", depth_mode, center)
+
+
+def render_autograd_features(renderer: "Renderer", cam: Camera, pos, scale, rotq, sh, opacity, features, bg=(0.0, 0.0, 0.0),
+                             scale_modifier: float = 1.0):
+    """render_autograd with the caller's per-splat feature rows blended like colour: returns (img [3, H, W], alpha [H, W],
+    feature_map [K, H, W]) as include/lcgs_hip.h defines them (feature_map = sum_i w_i f_i; not normalised, not clamped, no
+    background).  features: [P, K] float32 in the order of the five scene tensors (a bound scene keeps the caller's order).  The
+    backward runs lcgs_render_backward_features and the gradient goes to all six inputs; an output the loss does not use
+    arrives as None (or zero-shaped) and is passed as NULL.  Like render_autograd it re-renders its own view when the
+    renderer's generation has moved."""
+    return _autograd_frame(renderer, cam, (pos, scale, rotq, sh, opacity), bg, scale_modifier, "features", features=features)
 
 
 def normal_consistency_autograd(renderer: "Renderer", cam: Camera, depth, alpha, normal, weight: float = 0.05,

@@ -1,6 +1,6 @@
 // abi_backward.cpp -- the C ABI, part 5: the backward of the fused frame -- dense per-splat rows, compact
 // rows, accumulation over views, and the variant with the optimiser folded into the per-splat pass -- and the frame's depth
-// alpha, depth-distortion and normal maps with their backward (kernels/maps.hip), the per-splat blend-weight statistics of the same kept
+// alpha, depth-distortion and normal maps with their backward (kernels/maps.hip), the caller's feature channels with theirs (kernels/features.hip), the per-splat blend-weight statistics of the same kept
 // lists (kernels/contrib.hip), and the camera gradient (kernels/camera_grad.hip).
 #include <math.h>
 #include <stdio.h>
@@ -22,6 +22,8 @@ struct BackwardRequest {
     // (about `center`): any may be NULL, not all
     const float *d_dL_dimg = nullptr, *d_dL_ddepth = nullptr, *d_dL_dalpha = nullptr, *d_dL_ddist = nullptr;
     const float *d_dL_dnormal = nullptr; // ... and of the normal map (dense rows only)
+    // ... and the caller's feature channel (dense rows only): its rows, the map's incoming gradient, where dL/dfeatures goes
+    const lcgs_feature_channel* feat = nullptr;
     int          mode   = kDepthZ;
     float        center = 0.0f;
     // exactly one destination: per-splat rows in `grads` (dense, dense added to what the arrays hold, or compact), the
@@ -38,6 +40,7 @@ struct BackwardRequest {
     bool rows() const { return dest == Dense || dest == DenseAccumulate || dest == Compact; }
 };
 lcgs_status render_backward(lcgs_context* ctx, const BackwardRequest& req);
+lcgs_status features_only_backward(lcgs_context* ctx, const lcgs_feature_channel& feat, bool accumulate);
 // the camera pass over the 2-D rows the context holds (kernels/camera_grad.hip)
 lcgs_status camera_pass(lcgs_context* ctx, float* d_dL_dcam)
 {
@@ -252,6 +255,53 @@ lcgs_status lcgs_render_backward_normals(lcgs_context* ctx, const float* d_dL_di
     return render_backward(ctx, req);
 }
 
+lcgs_status lcgs_render_features(lcgs_context* ctx, int num_gaussians, int channels, const float* d_features, float* d_feature_map)
+{
+    LCGS_REQUIRE(ctx && d_features && d_feature_map, "NULL argument");
+    LCGS_REQUIRE(channels >= 1 && channels <= LCGS_FEATURES_MAX, "channels must be 1 .. LCGS_FEATURES_MAX");
+    LCGS_ENTRY(ctx);
+    LCGS_REQUIRE(num_gaussians == ctx->P, "num_gaussians must be the bound scene's");
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    LCGS_TRY(check_own_kept_frame(ctx, "lcgs_render_features"));
+    const FeatureChannel fc{ channels, ctx->vis_index.as<uint32_t>(), d_features, nullptr, nullptr };
+    ctx->n_marks = 0;
+    LCGS_TRY(mark(ctx, "begin"));
+    launch_render_features(kept_frame(ctx), fc, d_feature_map, features_chunk_width(channels, ctx->features_ch_forced), ctx->stream);
+    LCGS_TRY(mark(ctx, "render_features"));
+    LCGS_HIP_CHECK(hipGetLastError());
+    if (ctx->profiling) {
+        LCGS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        LCGS_TRY(collect_marks(ctx));
+    }
+    return LCGS_OK;
+}
+
+lcgs_status lcgs_render_backward_features(lcgs_context* ctx, const float* d_dL_dimg, int mode, float center,
+                                          const float* d_dL_ddepth, const float* d_dL_dalpha, const float* d_dL_ddist,
+                                          const float* d_dL_dnormal, const lcgs_feature_channel* feat, int accumulate,
+                                          const lcgs_grads* grads)
+{
+    LCGS_REQUIRE(ctx && (grads || feat), "NULL argument");
+    LCGS_REQUIRE(mode == LCGS_DEPTH_Z || mode == LCGS_DEPTH_INV_Z, "mode must be LCGS_DEPTH_Z or LCGS_DEPTH_INV_Z");
+    LCGS_REQUIRE(isfinite(center), "center must be finite");
+    const bool others = d_dL_dimg || d_dL_ddepth || d_dL_dalpha || d_dL_ddist || d_dL_dnormal;
+    LCGS_REQUIRE(others || feat, "all five incoming gradients are NULL and there is no feature channel");
+    if (feat) {
+        LCGS_REQUIRE(feat->channels >= 1 && feat->channels <= LCGS_FEATURES_MAX, "channels must be 1 .. LCGS_FEATURES_MAX");
+        LCGS_REQUIRE(feat->d_features && feat->d_dL_dfeature_map, "NULL feature rows or NULL feature-map gradient");
+        LCGS_REQUIRE(grads || feat->d_dL_dfeatures, "grads and d_dL_dfeatures are both NULL: nothing to write");
+        LCGS_REQUIRE(grads || !others, "grads may be NULL only when every other incoming gradient is NULL (frozen geometry)");
+    }
+    LCGS_REQUIRE(!grads || (grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh && grads->d_dL_dopacity),
+                 "NULL gradient buffer");
+    LCGS_ENTRY(ctx);
+    if (!grads) return features_only_backward(ctx, *feat, accumulate != 0);
+    BackwardRequest req = rows_request(d_dL_dimg, grads, accumulate ? BackwardRequest::DenseAccumulate : BackwardRequest::Dense);
+    req.mode = mode, req.center = center, req.feat = feat;
+    req.d_dL_ddepth = d_dL_ddepth, req.d_dL_dalpha = d_dL_dalpha, req.d_dL_ddist = d_dL_ddist, req.d_dL_dnormal = d_dL_dnormal;
+    return render_backward(ctx, req);
+}
+
 lcgs_status lcgs_camera_backward(lcgs_context* ctx, float* d_dL_dcam)
 {
     LCGS_REQUIRE(ctx && d_dL_dcam, "NULL argument");
@@ -325,7 +375,8 @@ lcgs_status render_backward(lcgs_context* ctx, const BackwardRequest& req)
     const bool maps = req.maps(), rows_out = req.rows(); // (rows_out: gradient arrays are written; else the optimiser's or the camera's)
     const bool camera_only = req.dest == Dest::CameraOnly; // (lcgs_render_backward_camera: the walks and the camera pass, no per-splat pass)
     const bool accumulate = req.dest == Dest::DenseAccumulate, compact = !accumulate && req.dest != Dest::Dense;
-    LCGS_REQUIRE(ctx && (d_dL_dimg || maps) && (grads || !rows_out), "NULL argument");
+    const lcgs_feature_channel* const feat = req.feat;
+    LCGS_REQUIRE(ctx && (d_dL_dimg || maps || feat) && (grads || !rows_out), "NULL argument");
     LCGS_HIP_CHECK(hipSetDevice(ctx->device)); // multi-GPU processes: every entry point selects its device
     LCGS_REQUIRE(!rows_out || (grads->d_dL_dpos && grads->d_dL_dscale && grads->d_dL_drotq && grads->d_dL_dsh &&
                                grads->d_dL_dopacity),
@@ -336,6 +387,7 @@ lcgs_status render_backward(lcgs_context* ctx, const BackwardRequest& req)
     if (camera_only) LCGS_TRY(ctx->cam_slab.ensure(camera_grad_slab_bytes((int64_t)ctx->P))); // (before any device work)
     const bool normals = req.d_dL_dnormal != nullptr;
     LCGS_REQUIRE(!normals || (rows_out && !compact), "the normal channel writes dense rows only");
+    LCGS_REQUIRE(!feat || (rows_out && !compact), "the feature channel writes dense rows only");
     if (normals) {
         LCGS_TRY(ctx->splat_normals.ensure(splat_normals_bytes((int64_t)ctx->P)));
         LCGS_TRY(ctx->splat_normal_grads.ensure(splat_normals_bytes((int64_t)ctx->P)));
@@ -366,7 +418,7 @@ lcgs_status render_backward(lcgs_context* ctx, const BackwardRequest& req)
     // dense rows with a communicator attached: the preprocess pass runs as splat-range slices so that the gradient
     // all-reduce (lcgs_grads_allreduce) can start on the first rows while the later ones are still being computed
     // (the maps backward adds to dL_dpos behind the preprocess pass: unsliced, so that no all-reduce starts on rows it has yet to finish)
-    const bool sliced = !compact && !maps && ctx->grad_slices > 1 && P >= 4096;
+    const bool sliced = !compact && !maps && !feat && ctx->grad_slices > 1 && P >= 4096;
     if (sliced) {
         LCGS_TRY(ctx->slice_bounds.ensure((lcgs::kMaxGradSlices + 1) * sizeof(uint32_t)));
         for (int k = 0; k < ctx->grad_slices; ++k)
@@ -404,6 +456,15 @@ lcgs_status render_backward(lcgs_context* ctx, const BackwardRequest& req)
                                     req.d_dL_ddist, normals ? &nrm : nullptr);
         LCGS_TRY(mark(ctx, "render_maps_backward"));
     }
+    if (feat) { // the caller's channels: one walk per chunk of them, adding to the same 2-D rows; their own sums go to the caller
+        if (feat->d_dL_dfeatures && !accumulate) { // rows nothing blends: exact zeros (P K floats: a stage of its own under profiling)
+            LCGS_HIP_CHECK(hipMemsetAsync(feat->d_dL_dfeatures, 0, P * (size_t)feat->channels * sizeof(float), st));
+            LCGS_TRY(mark(ctx, "zero_features"));
+        }
+        const FeatureChannel fc{ feat->channels, rows.vis_index, feat->d_features, feat->d_dL_dfeature_map, feat->d_dL_dfeatures };
+        launch_render_features_backward(kept, fc, ctx->grads2d.as<float>(), features_chunk_width(feat->channels, ctx->features_ch_forced), st);
+        LCGS_TRY(mark(ctx, "render_features_backward"));
+    }
     if (overlap) LCGS_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_join, 0));
     const int slices = rows_out ? (sliced ? ctx->grad_slices : 1) : 0;
     if (req.dest == Dest::FusedAdam) // (compact, unsliced: the update is applied where the gradients are formed; nothing is written out)
@@ -430,6 +491,30 @@ lcgs_status render_backward(lcgs_context* ctx, const BackwardRequest& req)
         launch_normals_to_rot(rows, ctx->splat_normals.as<float4>(), ctx->splat_normal_grads.as<float4>(), grads->d_dL_drotq, st);
         LCGS_TRY(mark(ctx, "normals_to_rot"));
     }
+    LCGS_HIP_CHECK(hipGetLastError());
+    if (ctx->profiling) {
+        LCGS_HIP_CHECK(hipStreamSynchronize(st));
+        LCGS_TRY(collect_marks(ctx));
+    }
+    return LCGS_OK;
+}
+
+// lcgs_render_backward_features without gradient arrays: the geometry is frozen, dL/dfeatures alone.  A short path of its own:
+// the walk forms no geometry sums, and the frame's 2-D gradient rows and the flags behind them are left as they were
+lcgs_status features_only_backward(lcgs_context* ctx, const lcgs_feature_channel& feat, bool accumulate)
+{
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    LCGS_TRY(check_own_kept_frame(ctx, "lcgs_render_backward_features"));
+    hipStream_t st = ctx->stream;
+    ctx->n_marks   = 0;
+    LCGS_TRY(mark(ctx, "begin"));
+    if (!accumulate) {
+        LCGS_HIP_CHECK(hipMemsetAsync(feat.d_dL_dfeatures, 0, (size_t)ctx->P * (size_t)feat.channels * sizeof(float), st));
+        LCGS_TRY(mark(ctx, "zero_features"));
+    }
+    const FeatureChannel fc{ feat.channels, ctx->vis_index.as<uint32_t>(), feat.d_features, feat.d_dL_dfeature_map, feat.d_dL_dfeatures };
+    launch_render_features_backward(kept_frame(ctx), fc, nullptr, features_chunk_width(feat.channels, ctx->features_ch_forced), st);
+    LCGS_TRY(mark(ctx, "render_features_backward"));
     LCGS_HIP_CHECK(hipGetLastError());
     if (ctx->profiling) {
         LCGS_HIP_CHECK(hipStreamSynchronize(st));

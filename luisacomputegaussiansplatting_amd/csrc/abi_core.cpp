@@ -170,6 +170,7 @@ lcgs_status lcgs::abi::create_context(int device_id, void* stream, hipStream_t b
     if (const char* e = getenv("LCGS_RENDER_WGS_IN_FLIGHT")) ctx->persist_in_flight = atoi(e);
     if (const char* e = getenv("LCGS_BWD_WGS_PER_CU")) ctx->persist_bwd_forced = atoi(e);
     if (const char* e = getenv("LCGS_BWD_WGS_IN_FLIGHT")) ctx->persist_bwd_in_flight = atoi(e);
+    if (const char* e = getenv("LCGS_FEATURES_CH")) ctx->features_ch_forced = atoi(e); // measurement hook (tools/features_bench.py)
     if (const char* e = getenv("LCGS_GRAPH")) ctx->use_graph = (e[0] == '1'); // tuning hook
     if (const char* e = getenv("LCGS_STAGE_SIDE_COPY")) ctx->stage_side_copy = e[0] != '0'; // A/B hook
     if (const char* e = getenv("LCGS_STAGE_MAILBOX")) ctx->stage_mailbox = e[0] != '0';      // A/B hook

@@ -193,6 +193,8 @@ struct lcgs_context {
     bool        g2d_normal_channel = false;
     // lcgs_render_normals / lcgs_render_backward_normals: the on-screen rows' normals and dL/dn (splat_normals_bytes each)
     DeviceBuffer splat_normals, splat_normal_grads;
+    // lcgs_render_features / lcgs_render_backward_features: measurement hook LCGS_FEATURES_CH (4, 8, 16: that chunk width for every K)
+    int         features_ch_forced = 0;
     DeviceBuffer cam_slab; // lcgs_camera_backward: per-block partial sums (camera_grad_slab_bytes)
     DeviceBuffer contrib_slab; // lcgs_contrib_accumulate: {sum, max bits, count} per on-screen row (contrib_slab_bytes)
     // lcgs_densify: emit counts, their inclusive sums, actions (one entry per source row)

@@ -543,6 +543,23 @@ void launch_render_normals(const KeptFrame& f, const float4* normals, float* nor
 // one lane per on-screen row: dL_drotq[row] += (dc/dq)^T dL/dc from dL_dn (behind the preprocess-backward)
 void launch_normals_to_rot(const KeptRows& r, const float4* normals, const float4* dL_dn, float* dL_drotq, hipStream_t stream);
 
+// ---- features.hip : caller-supplied per-splat feature channels of the last keep-state frame and their backward ----
+// the caller's rows as the walks read them: K floats per scene row, found through the frame's on-screen row -> scene row table
+struct FeatureChannel {
+    int             K;               // 1 .. LCGS_FEATURES_MAX
+    const uint32_t* vis_index;       // on-screen row -> scene row (KeptRows::vis_index)
+    const float*    features;        // P x K, row-major
+    const float*    dL_dfeature_map; // K H W, CHW (the backward only)
+    float*          dL_dfeatures;    // P x K, ADDED to by float atomics (the backward only; NULL: the features are frozen)
+};
+// the channels a walk takes at a time: the smallest of 4 / 8 / 16 that holds K, 16 beyond; forced (4, 8, 16): that width (measurement)
+int features_chunk_width(int K, int forced = 0);
+// k_render_maps' walk with `ch` accumulators per chunk of channels (grid.y: the chunks): feature_map K H W floats, CHW
+void launch_render_features(const KeptFrame& f, const FeatureChannel& fc, float* feature_map, int ch, hipStream_t stream);
+// grads2d != NULL: ADDS the channel's six geometry sums to grads2d slots 0-5 (no value slot); fc.dL_dfeatures != NULL: ADDS
+// sum_p w_i dL_dfeature_map[c][p] to it.  grads2d NULL: the frozen-geometry walk, which forms no geometry sums at all
+void launch_render_features_backward(const KeptFrame& f, const FeatureChannel& fc, float* grads2d, int ch, hipStream_t stream);
+
 // ---- contrib.hip : per-splat blend-weight statistics of the last keep-state frame, and the keep / drop rule ----
 // the context-owned slab: {sum, max bits, count} per on-screen row, indexed by the lists' on-screen indices
 size_t contrib_slab_bytes(int64_t rows);
