@@ -676,6 +676,36 @@ typedef struct lcgs_densify_stats {
  * backward on it yet, or a frame of lcgs_owner_render.  Only enqueues.  Behind lcgs_render_backward_maps or
  * lcgs_render_backward_distortion the mean gradient is the combined one of every channel that call was given. */
 LCGS_API lcgs_status lcgs_densify_accumulate(lcgs_context* ctx, int num_gaussians, const lcgs_densify_stats* stats);
+/* AbsGS densification statistics (Ye et al. 2024; GOF's criterion, gsplat's absgrad): the sum over PIXELS of the absolute per-pixel
+ * gradient of the pixel-space mean, where lcgs_densify_accumulate takes the norm of the summed one -- a large splat that is wrong
+ * in opposite directions on its two sides sums to almost nothing there and is never split.
+ * The frame is the context's last lcgs_render_forward(keep_state = 1), classic or antialiased (the frame remembers its mode), and
+ *     L = <dL_dimg, img> + <dL_ddepth, depth> + <dL_dalpha, alpha>
+ * with depth and alpha as lcgs_render_maps(mode) defines them; any of the three gradients may be NULL, not all three.  For pixel p
+ * and on-screen row i, g(p, i) is the gradient of the part of L that belongs to pixel p with respect to the pixel-space mean of i,
+ * by the conventions of lcgs_render_backward and lcgs_render_backward_maps: thresholds are constants, the 0.99 cap passes nothing,
+ * a saturated pixel stops, the kept frame's background colour is the last layer behind the colour channels and nothing lies behind
+ * the map channels.  The channels are summed per pixel FIRST, then the absolute value is taken, then the pixels are summed:
+ *     a_i = ( sum_p |g_x(p, i)| , sum_p |g_y(p, i)| ).
+ * Two outputs, each nullable, at least one given:
+ *   d_absgrad[2 P]: (a_x, a_y) of row i is ADDED at [2 i, 2 i + 1], in pixel units, the context's row order (gsplat's
+ *                   means2d.absgrad); rows not on screen are untouched.
+ *   stats:          grad_accum[i] += sqrt((a_x W/2)^2 + (a_y H/2)^2), denom[i] += 1, max_radii[i] = max(., reference radius) --
+ *                   the last two exactly what lcgs_densify_accumulate does for the same frame (the same code), bit for bit.
+ * A caller calls ONE of the two accumulate calls per step and then lcgs_densify unchanged; the threshold is the caller's (AbsGS
+ * uses about twice the 3DGS value).
+ * State: this context's own kept frame (LCGS_ERR_STATE otherwise; a frame of lcgs_owner_render is refused).  NO preceding backward
+ * is needed.  Reads nothing back, only enqueues on the context's stream.  It leaves the frame's 2-D gradient rows and everything
+ * else a later backward, lcgs_densify_accumulate or lcgs_camera_backward reads as it was.  A frame that drew nothing returns
+ * LCGS_OK and writes nothing.  The sums are binary32 sums of non-negative terms in an UNSPECIFIED order (float atomics across tiles).
+ * LCGS_ERR_INVALID_ARG (before any device work): NULL ctx, all three gradients NULL, both outputs NULL, a stats with a NULL member,
+ * a mode that is neither constant, num_gaussians not the bound scene's.
+ * Not offered: the distortion, normal and feature channels, compact rows, frames of the ownership step, the statistic inside
+ * lcgs_fit_views, an lcgs-app flag, the sums fused into the render-backward (a second walk of the lists is what the call costs,
+ * on the steps that collect statistics).  Stages under lcgs_set_profiling: absgrad_walk, absgrad_rows. */
+LCGS_API lcgs_status lcgs_absgrad_accumulate(lcgs_context* ctx, int num_gaussians, const float* d_dL_dimg, int mode,
+                                             const float* d_dL_ddepth, const float* d_dL_dalpha,
+                                             const lcgs_densify_stats* stats, float* d_absgrad);
 typedef struct lcgs_densify_config {
     float    grad_threshold;  /* 3DGS: 2e-4 */
     float    percent_dense;   /* 3DGS: 0.01 */

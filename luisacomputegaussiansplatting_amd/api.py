@@ -335,6 +335,7 @@ def _signatures() -> dict:
         "lcgs_fit_views": (st, [p, i, cam, p, f, pp, grads, p]),
         # adaptive density control
         "lcgs_densify_accumulate": (st, [p, i, dstats]),
+        "lcgs_absgrad_accumulate": (st, [p, i, p, i, p, p, dstats, p]),
         "lcgs_densify": (st, [p, i, i, ptr["densify_config"], dstats, *packs, *packs[:3], dstats, i64, p, p, pi64]),
         "lcgs_contrib_keep_mask": (st, [p, i, prune, cstats, p]),
         "lcgs_prune": (st, [p, i, i, prune, cstats, *packs, *packs[:3], i64, p, pi64]),
@@ -1210,6 +1211,18 @@ class Renderer:
         (int32 bits of a uint32 count), ["max_radii"] (int32), device tensors of P entries, on-screen rows only."""
         st = _densify_stats(stats)
         _check(load_library().lcgs_densify_accumulate(self.ctx._h, int(stats["denom"].shape[0]), C.byref(st)))
+
+    def absgrad_accumulate(self, dL_dimg=None, dL_ddepth=None, dL_dalpha=None, mode: str = "z", stats: Optional[dict] = None,
+                           absgrad=None):
+        """lcgs_absgrad_accumulate: the AbsGS statistic of the last keep_state frame -- per on-screen row the sum over pixels of
+        the absolute per-pixel gradient of the pixel-space mean of <dL_dimg, img> + <dL_ddepth, depth> + <dL_dalpha, alpha> (any
+        gradient may be None, not all; mode as in render_maps).  stats: densify_accumulate's dict, grad_accum += the norm of the
+        sums in NDC units, denom and max_radii as densify_accumulate; absgrad: float32 [P, 2], the sums ADDED in pixel units
+        (gsplat's means2d.absgrad).  Either output may be None, not both.  Needs no backward and disturbs none; only enqueues."""
+        st = None if stats is None else _densify_stats(stats)
+        rows = int(stats["denom"].shape[0]) if stats is not None else (int(absgrad.numel()) // 2 if absgrad is not None else 0)
+        _check(load_library().lcgs_absgrad_accumulate(self.ctx._h, rows, _ptr(dL_dimg), _DEPTH_MODES[mode], _ptr(dL_ddepth),
+                                                      _ptr(dL_dalpha), None if st is None else C.byref(st), _ptr(absgrad)))
 
     def densify(self, stats: dict, raw: dict, m: dict, v: dict, out_raw: dict, out_m: dict, out_v: dict, out_activated: dict,
                 out_stats: dict, grad_threshold: float = 2e-4, percent_dense: float = 0.01, scene_extent: float = 1.0,

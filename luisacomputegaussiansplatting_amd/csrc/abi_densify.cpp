@@ -1,4 +1,5 @@
-// abi_densify.cpp -- the C ABI, part 7: adaptive density control (csrc/kernels/densify.hip) -- the statistics of a step, the
+// abi_densify.cpp -- the C ABI, part 7: adaptive density control (csrc/kernels/densify.hip) -- the statistics of a step (and
+// their AbsGS form, lcgs_absgrad_accumulate: kernels/absgrad.hip, a walk of the kept frame's lists of its own), the
 // out-of-place clone / split / prune rewrite of raw parameters and Adam moments, the opacity reset, and contribution-based
 // pruning on the statistics of lcgs_contrib_accumulate (kernels/contrib.hip: the keep mask, and the rewrite restricted to it).
 #include <math.h>
@@ -89,6 +90,43 @@ lcgs_status lcgs_densify_accumulate(lcgs_context* ctx, int num_gaussians, const 
     LCGS_HIP_CHECK(hipSetDevice(ctx->device));
     launch_densify_stats(kept_rows(ctx), stats->grad_accum, stats->denom, stats->max_radii, ctx->stream);
     LCGS_HIP_CHECK(hipGetLastError());
+    return LCGS_OK;
+}
+
+lcgs_status lcgs_absgrad_accumulate(lcgs_context* ctx, int num_gaussians, const float* d_dL_dimg, int mode,
+                                    const float* d_dL_ddepth, const float* d_dL_dalpha, const lcgs_densify_stats* stats,
+                                    float* d_absgrad)
+{
+    LCGS_REQUIRE(ctx, "NULL argument");
+    LCGS_REQUIRE(d_dL_dimg || d_dL_ddepth || d_dL_dalpha, "all three gradients are NULL");
+    LCGS_REQUIRE(stats || d_absgrad, "both outputs are NULL");
+    LCGS_REQUIRE(!stats || (stats->grad_accum && stats->denom && stats->max_radii), "NULL device pointer in the statistics");
+    LCGS_REQUIRE(mode == LCGS_DEPTH_Z || mode == LCGS_DEPTH_INV_Z, "mode must be LCGS_DEPTH_Z or LCGS_DEPTH_INV_Z");
+    LCGS_ENTRY(ctx);
+    LCGS_REQUIRE(num_gaussians == ctx->P, "num_gaussians must be the bound scene's");
+    // (no backward is needed, and none is disturbed: the walk reads the kept lists and the caller's gradients, its sums go to a
+    //  workspace of their own -- the frame's 2-D gradient rows and the flags behind them stay as they are)
+    LCGS_TRY(check_own_kept_frame(ctx, "lcgs_absgrad_accumulate",
+                                  "the last frame was drawn from received records (lcgs_owner_render): no statistics for it"));
+    LCGS_HIP_CHECK(hipSetDevice(ctx->device));
+    // one slot per on-screen row; sized for the scene's rows like the frame's other per-row buffers (the count stays on the device)
+    LCGS_TRY(ctx->absgrad_ws.ensure(absgrad_ws_bytes((int64_t)ctx->P)));
+    hipStream_t    st   = ctx->stream;
+    const KeptRows rows = kept_rows(ctx);
+    float*         ws   = ctx->absgrad_ws.as<float>();
+    ctx->n_marks        = 0;
+    LCGS_TRY(mark(ctx, "begin"));
+    launch_absgrad_zero(rows, ws, st);
+    launch_absgrad_walk(kept_frame(ctx), mode, ctx->last.bg, d_dL_dimg, d_dL_ddepth, d_dL_dalpha, ws, st);
+    LCGS_TRY(mark(ctx, "absgrad_walk"));
+    launch_absgrad_rows(rows, ws, d_absgrad, stats ? stats->grad_accum : nullptr, stats ? stats->denom : nullptr,
+                        stats ? stats->max_radii : nullptr, st);
+    LCGS_TRY(mark(ctx, "absgrad_rows"));
+    LCGS_HIP_CHECK(hipGetLastError());
+    if (ctx->profiling) {
+        LCGS_HIP_CHECK(hipStreamSynchronize(st));
+        LCGS_TRY(collect_marks(ctx));
+    }
     return LCGS_OK;
 }
 

@@ -197,6 +197,7 @@ struct lcgs_context {
     int         features_ch_forced = 0;
     DeviceBuffer cam_slab; // lcgs_camera_backward: per-block partial sums (camera_grad_slab_bytes)
     DeviceBuffer contrib_slab; // lcgs_contrib_accumulate: {sum, max bits, count} per on-screen row (contrib_slab_bytes)
+    DeviceBuffer absgrad_ws;   // lcgs_absgrad_accumulate: (sum |g_x|, sum |g_y|) per on-screen row (absgrad_ws_bytes)
     // lcgs_densify: emit counts, their inclusive sums, actions (one entry per source row)
     DeviceBuffer dn_emit, dn_incl, dn_action;
     // lcgs_mcmc_relocate / lcgs_mcmc_add (abi_mcmc.cpp): per row the weight, the dead flag, its inclusive sums, the u64 sums of

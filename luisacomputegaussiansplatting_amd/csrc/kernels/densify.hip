@@ -11,6 +11,7 @@
 // loads of the source, destination offsets monotone in the source index (coalesced stores), the zero moments of new rows
 // written here instead of by a memset over the whole array.  64-bit element indices throughout.
 #include "activations.hpp" // train.hip's exact expression sequences (the values equal what an Adam step writes)
+#include "densify_row.hpp"
 #include "kept_rows.hpp"
 #include "launch.hpp"
 #include "philox.hpp"
@@ -35,19 +36,8 @@ __global__ void __launch_bounds__(256) k_densify_stats(const uint32_t* __restric
         const int64_t i = (int64_t)vis_index[r];
         if (i >= P) continue;
         const float gx = grads2d[r * 12 + 0] * hw, gy = grads2d[r * 12 + 1] * hh;
-        // the reference radius (gs_tile_splatter/shader.cpp:145-148) as the frame's cull pass evaluates it
-        float v[3], t[3], Sig[3][3], cov2d[3], conic[3];
-        view_transform(cp, pos[3 * i + 0], pos[3 * i + 1], pos[3 * i + 2], v);
-        const float  s[3] = { scale_modifier * scale[3 * i + 0], scale_modifier * scale[3 * i + 1], scale_modifier * scale[3 * i + 2] };
-        const float4 q    = *reinterpret_cast<const float4*>(rotq + 4 * i);
-        cov3d_from_scale_rot(s, q.y, q.z, q.w, q.x, Sig);
-        cam_clamp(cp, v, t);
-        ewa_cov2d(cp, Sig, t, true, cov2d);
-        int32_t radius = 0;
-        conic_and_radius(cov2d[0], cov2d[1], cov2d[2], true, cp.width, cp.height, conic, radius);
         grad_accum[i] += sqrtf(gx * gx + gy * gy);
-        denom[i] += 1u;
-        max_radii[i] = max(max_radii[i], radius);
+        densify_count_row(cp, scale_modifier, pos, scale, rotq, i, denom, max_radii); // (shared with absgrad.hip)
     }
 }
 

@@ -578,6 +578,21 @@ struct ContribRule { // a row is kept iff every enabled (non-zero) minimum is me
 void launch_contrib_classify(int64_t P, const ContribRule& rule, const float* weight_sum, const float* weight_max,
                              const uint32_t* pixels, const uint32_t* views, uint32_t* emit, uint8_t* action, hipStream_t stream);
 
+// ---- absgrad.hip : AbsGS densification statistics of the last keep-state frame ----
+// the context-owned workspace: (sum_p |g_x|, sum_p |g_y|) per on-screen row, indexed by the lists' on-screen indices
+size_t absgrad_ws_bytes(int64_t rows);
+// clears the slots of the frame's on-screen rows
+void launch_absgrad_zero(const KeptRows& r, float* ws, hipStream_t stream);
+// the walk of launch_render_maps_backward with the frame's colours and background beside the map channels (any of the three
+// gradients may be NULL, not all): per (pixel, entry) the mean gradient of all given channels, its absolute value, summed over
+// the pixels; ATOMICALLY adds to the workspace.  Reads no 2-D gradient row and writes none
+void launch_absgrad_walk(const KeptFrame& f, int mode, const float bg[3], const float* dL_dimg, const float* dL_ddepth,
+                         const float* dL_dalpha, float* ws, hipStream_t stream);
+// one lane per on-screen row: absgrad[2 i ..] += the slot (NULL: skipped); grad_accum != NULL: grad_accum[i] += its norm in NDC
+// units, denom and max_radii as launch_densify_stats
+void launch_absgrad_rows(const KeptRows& r, const float* ws, float* absgrad, float* grad_accum, uint32_t* denom, int32_t* max_radii,
+                         hipStream_t stream);
+
 // ---- camera_grad.hip : the camera gradient of the last backward, from the 2-D rows it left ----
 // the context-owned slab: twelve doubles per block of 256 on-screen rows
 size_t camera_grad_slab_bytes(int64_t P);

@@ -321,6 +321,13 @@ public:
     {
         check(lcgs_densify_accumulate(m_dev->ctx(), num_gaussians, &stats));
     }
+    // AbsGS statistics of the last keep-state frame (no backward needed): the sum over pixels of the absolute per-pixel mean
+    // gradient of <dL_dimg, img> + <dL_ddepth, depth> + <dL_dalpha, alpha> -> stats and / or d_absgrad [2 P] (either may be NULL)
+    void absgrad_accumulate(int num_gaussians, const float* d_dL_dimg, const lcgs_densify_stats* stats, float* d_absgrad = nullptr,
+                            const float* d_dL_ddepth = nullptr, const float* d_dL_dalpha = nullptr, int mode = LCGS_DEPTH_Z)
+    {
+        check(lcgs_absgrad_accumulate(m_dev->ctx(), num_gaussians, d_dL_dimg, mode, d_dL_ddepth, d_dL_dalpha, stats, d_absgrad));
+    }
     int64_t densify(int num_gaussians, const lcgs_densify_config& cfg, const lcgs_densify_stats& stats, const lcgs_params& raw,
                     const lcgs_params& m, const lcgs_params& v, const lcgs_params& out_raw, const lcgs_params& out_m,
                     const lcgs_params& out_v, const lcgs_params& out_activated, const lcgs_densify_stats& out_stats,
