@@ -887,6 +887,76 @@ LCGS_API lcgs_status lcgs_filter3d_backward(lcgs_context* ctx, int num_gaussians
                                             const float* d_filter, const uint32_t* d_rows, const uint32_t* d_count,
                                             float* d_dL_dscale, float* d_dL_dopacity);
 
+/* ---- scene similarity transforms: rotate the SH bands, move, scale, crop (no reference counterpart) ------------ */
+/* new = scale * rot * old + trans moves a whole scene: a COLMAP frame onto the axis-aligned volume lcgs_tsdf_integrate fuses into,
+ * a second capture into the first one's frame, a scene normalised before training, a region of interest cropped out.  The
+ * view-dependent colour rotates with the scene: band l = 1, 2, 3 of the coefficients is multiplied by the rotation's matrix D_l
+ * ((2l+1) x (2l+1), orthogonal) in THIS library's basis -- gs_math.hpp's LCGS_SH_TERMS with its signs and constants -- for which
+ * B_l(R d) = D_l B_l(d) for every unit direction d, so that sum_k c'_k B_k(R d) = sum_k c_k B_k(d) with c'_l = D_l c_l per
+ * colour channel.  A transform that skips this renders highlights that stay nailed to the old axes.
+ * Not offered: non-uniform scale (it needs an eigendecomposition per splat) and reflections (they have no quaternion); raw
+ * (pre-activation) arrays and optimiser moments -- the second moment has no exact image under a rotation, so a caller who
+ * transforms mid-training transforms the activated arrays, recovers the raw ones (log, logit) and resets the moments; an
+ * lcgs-app flag (tools/transform_ply.py is the tool); gradients with respect to the transform; the ownership step's sharded
+ * scenes (each rank transforms its own rows with the same lcgs_similarity). */
+typedef struct lcgs_similarity {
+    float rot[9];   /* row-major: new = scale * rot * old + trans */
+    float scale;
+    float trans[3];
+} lcgs_similarity;
+typedef struct lcgs_similarity_plan {
+    float M[9];     /* row-major, fl32(scale * Rhat) */
+    float t[3];
+    float s;
+    float q[4];     /* (w, x, y, z), the stored order */
+    float D1[9], D2[25], D3[49];   /* row-major, D_l[k][j] */
+} lcgs_similarity_plan;
+/* The plan, host only, no context, entirely in binary64: q = the unit quaternion of rot by Shepperd's method (the largest of the
+ * trace and the three diagonal entries picks the component taken by a square root), normalised, w >= 0; Rhat = the matrix rebuilt
+ * from q with rot_from_quat's expressions -- EVERYTHING downstream uses Rhat, so positions, orientations and colours see exactly
+ * the same rotation; M = scale * Rhat; D_1, D_2, D_3 for Rhat (the basis functions as symmetric tensors, rotated index by index
+ * and contracted with the unrotated ones: no solve, nothing sampled; the constants are gs_math.hpp's literals read as binary64).
+ * M, q and every D_l entry are rounded to binary32 once (t and s are the caller's values); D64 (nullable, [83]) receives the
+ * unrounded D1 then D2 then D3.  LCGS_ERR_INVALID_ARG for a NULL xf or out, a non-finite value, scale <= 0,
+ * max |rot rot^T - I| > 1e-4 (an input check, not a measurement: a binary32 rotation composed a few times stays far inside it),
+ * det rot <= 0. */
+LCGS_API lcgs_status lcgs_similarity_plan_make(const lcgs_similarity* xf, lcgs_similarity_plan* out, double* D64 /* nullable [83] */);
+/* The camera that sees the transformed scene as `in` saw the original: position' = scale Rhat position + trans, front' = Rhat
+ * front, up' = Rhat up, right' = Rhat right, in binary64 from the plan's Rhat with one rounding; fov, aspect_ratio, width, height
+ * copied.  (The frame is the original's up to rounding for scale 1; for another scale up to the projector's 1 / (v.z + 1e-6),
+ * which is not scale-invariant: a few 1e-6.)  out may be in.  The plan's refusals, and NULL in / out. */
+LCGS_API lcgs_status lcgs_camera_transform(const lcgs_camera* in, const lcgs_similarity* xf, lcgs_camera* out);
+/* The ACTIVATED arrays of a scene, in the layouts of lcgs_params (pos [P][3], scale [P][3], rotq [P][4] stored (w, x, y, z),
+ * sh [P][(deg+1)^2][3], opacity [P]; device pointers), from `in` to `out`.  Binary32, round to nearest, nothing contracted: every
+ * product and every sum is rounded, sums run left to right as written -- one defined bit pattern, the same bits for the same
+ * inputs, equal bit for bit to tests/transform_ref.py's restatement.  With the plan of xf:
+ *   pos'_i   = ((M[i][0]*x + M[i][1]*y) + M[i][2]*z) + t[i]
+ *   scale'_i = s * scale_i
+ *   with (W, X, Y, Z) = plan q and (w, x, y, z) = the row's stored quaternion:
+ *     w' = ((W*w - X*x) - Y*y) - Z*z      x' = ((W*x + X*w) + Y*z) - Z*y
+ *     y' = ((W*y - X*z) + Y*w) + Z*x      z' = ((W*z + X*y) - Y*x) + Z*w
+ *   sh'[0][c]    = sh[0][c]                                    (bit copy)
+ *   sh'[lo+k][c] = sum over j = 0..2l of D_l[k][j] * sh[lo+j][c], j ascending, the sum started from its first product,
+ *                  lo = l*l, for every l <= sh_degree
+ *   opacity'     = opacity                                     (bit copy)
+ * The quaternion is not renormalised: the product of two unit quaternions is a unit quaternion to rounding, and a caller's
+ * non-unit input keeps its norm.  Non-finite values propagate as IEEE arithmetic says (0 * inf = NaN inside a band).
+ * Every member pair (in->X, out->X) is the same pointer (in place) or disjoint; partial overlap, and overlap of an output with a
+ * different input or another output, is refused (alias).  Each out member may be NULL to skip that array, its in member is then
+ * not read: out->pos NULL with out->sh given rotates the colours only.  Only enqueues on the context's stream, reads nothing
+ * back, no atomics.  If a written array is one of the context's bound scene arrays, what lcgs_scene_modified does happens:
+ * derived rows, the f16 coefficient copy and the kept state of the last frame are dropped (a context-owned scene gets its rows
+ * rebuilt behind the transform).  LCGS_ERR_INVALID_ARG before any device work: NULL ctx, xf, in or out; a negative count;
+ * sh_degree outside 0..3; an output whose input is NULL; the plan's refusals; alias.  num_gaussians == 0: LCGS_OK, no launch. */
+LCGS_API lcgs_status lcgs_scene_transform(lcgs_context* ctx, int num_gaussians, int sh_degree, const lcgs_similarity* xf,
+                                          const lcgs_params* in, const lcgs_params* out);
+/* The crop: b = pos' by the expression above with the plan of world_to_box; d_keep[i] = 1 iff |b_k| <= half_extent[k] for
+ * k = 0, 1, 2, compared in binary32 (a row exactly on a face is kept), else 0; a NaN position is dropped.  The bytes are what
+ * lcgs_ply_filter_rows takes after a copy to the host.  Only enqueues.  LCGS_ERR_INVALID_ARG: a NULL pointer, a negative count, a
+ * half extent that is negative or NaN (+inf is legal: unbounded on this axis), the plan's refusals. */
+LCGS_API lcgs_status lcgs_scene_box_keep_mask(lcgs_context* ctx, int num_gaussians, const float* d_pos,
+                                              const lcgs_similarity* world_to_box, const float half_extent[3], uint8_t* d_keep);
+
 /* ---- a scene from a point cloud (no reference counterpart: app/gaussians.cpp only loads trained PLYs) -------- */
 /* The mean squared distance to the three nearest neighbours, of n points p_i (binary32, AoS xyz xyz ...):
  *   valid       a point is valid if all three coordinates are finite; an invalid point is nobody's neighbour

@@ -30,12 +30,15 @@ from .api import (  # noqa: F401
     RASTER_CLASSIC,
     Renderer,
     SHProcessor,
+    Similarity,
+    SimilarityPlan,
     TsdfVolume,
     bilagrid_autograd,
     bilagrid_identity,
     bilagrid_tv_autograd,
     build_library,
     camera_grad_to_twist,
+    camera_transform,
     camera_with_vectors,
     depth_prior_autograd,
     filter3d_autograd,
@@ -59,6 +62,8 @@ from .api import (  # noqa: F401
     render_autograd_maps,
     scene_extent,
     shard_rows,
+    similarity,
+    similarity_plan,
     synth_scene,
     world_to_local_matrix,
     write_mesh_ply,

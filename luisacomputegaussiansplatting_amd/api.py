@@ -200,6 +200,19 @@ class _DepthPriorConfig(C.Structure):
                 ("alpha_min", C.c_float), ("patch", C.c_int), ("patch_x", C.c_int), ("patch_y", C.c_int)]
 
 
+class Similarity(C.Structure):
+    """lcgs_similarity: new = scale * rot * old + trans (rot row-major)"""
+
+    _fields_ = [("rot", C.c_float * 9), ("scale", C.c_float), ("trans", C.c_float * 3)]
+
+
+class SimilarityPlan(C.Structure):
+    """lcgs_similarity_plan: what the transform kernels read (q stored (w, x, y, z); D_l row-major)"""
+
+    _fields_ = [("M", C.c_float * 9), ("t", C.c_float * 3), ("s", C.c_float), ("q", C.c_float * 4), ("D1", C.c_float * 9),
+                ("D2", C.c_float * 25), ("D3", C.c_float * 49)]
+
+
 class _SparseRows(C.Structure):
     _fields_ = [("d_rows", C.c_void_p), ("num_rows", C.c_int64), ("owner_first", C.c_int64 * (LCGS_MAX_RANKS + 2))]
 
@@ -229,7 +242,7 @@ STRUCTS = {
     "lcgs_adam_config": _AdamConfig, "lcgs_densify_stats": _DensifyStats, "lcgs_densify_config": _DensifyConfig,
     "lcgs_mcmc_config": _McmcConfig, "lcgs_mcmc_noise_config": _McmcNoiseConfig,
     "lcgs_init_config": _InitConfig, "lcgs_tsdf_volume": _TsdfVolume, "lcgs_tsdf_config": _TsdfConfig, "lcgs_depth_prior_config": _DepthPriorConfig, "lcgs_contrib_stats": _ContribStats, "lcgs_prune_config": _PruneConfig,
-    "lcgs_feature_channel": _FeatureChannel,
+    "lcgs_feature_channel": _FeatureChannel, "lcgs_similarity": Similarity, "lcgs_similarity_plan": SimilarityPlan,
     "lcgs_sparse_rows": _SparseRows, "lcgs_comm_stats": _CommStats, "lcgs_comm_selftest_report": _SelftestReport,
     "lcgs_scene_host": _SceneHost,
 }
@@ -350,6 +363,11 @@ def _signatures() -> dict:
         "lcgs_filter3d_finalize": (st, [p, i, p, f, p]),
         "lcgs_filter3d_apply": (st, [p, i, p, p, p, p, p]),
         "lcgs_filter3d_backward": (st, [p, i, p, p, p, p, p, p, p]),
+        # scene similarity transforms
+        "lcgs_similarity_plan_make": (st, [ptr["similarity"], ptr["similarity_plan"], p]),
+        "lcgs_camera_transform": (st, [cam, ptr["similarity"], cam]),
+        "lcgs_scene_transform": (st, [p, i, i, ptr["similarity"], *packs[:2]]),
+        "lcgs_scene_box_keep_mask": (st, [p, i, p, ptr["similarity"], p, p]),
         # a scene from a point cloud
         "lcgs_knn_mean_dist2": (st, [p, i64, p, p]),
         "lcgs_scene_init_from_points": (st, [p, i, i, p, p, ptr["init_config"], *packs[:2]]),
@@ -505,6 +523,27 @@ def get_lookat_cam(pos, target, world_up, width: Optional[int] = None, height: O
     if fov is not None:
         cam.fov = float(fov)
     return cam
+
+
+def similarity(rot=None, scale: float = 1.0, trans=(0.0, 0.0, 0.0)) -> Similarity:
+    """lcgs_similarity of a 3 x 3 rotation (None: the identity), a uniform scale and a translation: new = scale rot old + trans"""
+    r = np.eye(3) if rot is None else np.asarray(rot, np.float64).reshape(3, 3)
+    return Similarity((C.c_float * 9)(*[float(x) for x in r.reshape(9)]), float(scale), _f3(trans))
+
+
+def similarity_plan(xf: Similarity):
+    """lcgs_similarity_plan_make: (SimilarityPlan, D64) -- the binary32 plan the kernels read and the unrounded band matrices as
+    three binary64 arrays D_1 [3, 3], D_2 [5, 5], D_3 [7, 7] (B_l(R d) = D_l B_l(d) in the basis of the library's SH terms)."""
+    plan, d64 = SimilarityPlan(), np.zeros(83, np.float64)
+    _check(load_library().lcgs_similarity_plan_make(C.byref(xf), C.byref(plan), _ptr(d64)))
+    return plan, (d64[:9].reshape(3, 3).copy(), d64[9:34].reshape(5, 5).copy(), d64[34:].reshape(7, 7).copy())
+
+
+def camera_transform(cam: Camera, xf: Similarity) -> Camera:
+    """lcgs_camera_transform: the camera that sees the scene transformed by xf as `cam` saw the original"""
+    out = Camera()
+    _check(load_library().lcgs_camera_transform(C.byref(cam), C.byref(xf), C.byref(out)))
+    return out
 
 
 def _mat(fn, *args) -> np.ndarray:
@@ -1362,6 +1401,28 @@ class Renderer:
         backward(compact=True); None: dense rows.  Only enqueues."""
         _check(load_library().lcgs_filter3d_backward(self.ctx._h, int(opacity.shape[0]), _ptr(scale), _ptr(opacity), _ptr(filt),
                                                      _ptr(rows), _ptr(count), _ptr(dscale), _ptr(dopacity)))
+
+    # ---- scene similarity transforms (DESIGN.md 9)
+    def scene_transform(self, xf: Similarity, src: dict, dst: Optional[dict] = None, sh_degree: Optional[int] = None):
+        """lcgs_scene_transform: the ACTIVATED arrays of `src` (device tensors under pos / scale / rotq / sh / opacity) moved by
+        new = scale rot old + trans into `dst` -- positions, scales, orientations, and the SH bands rotated with the scene.  dst
+        None: in place on every array src holds; otherwise every array dst holds is written (the same tensor as in src, or a
+        disjoint one) and the others are skipped -- {"sh": t} rotates the colours only.  One defined bit pattern per output.  A
+        context whose bound scene is written drops its derived rows, its f16 coefficients and its kept frame.  Only enqueues."""
+        dst = src if dst is None else dst
+        ref = src.get("opacity", src.get("pos", src.get("rotq")))
+        P = int(ref.shape[0]) if ref is not None else int(next(iter(src.values())).shape[0])
+        if sh_degree is None:
+            sh_degree = {3: 0, 12: 1, 27: 2, 48: 3}[int(src["sh"].numel()) // max(P, 1)] if "sh" in src and P else 3
+        i, o = _params(src, dst, partial=True)
+        _check(load_library().lcgs_scene_transform(self.ctx._h, P, sh_degree, C.byref(xf), C.byref(i), C.byref(o)))
+
+    def scene_box_keep_mask(self, pos, world_to_box: Similarity, half_extent, keep):
+        """lcgs_scene_box_keep_mask: keep[i] (uint8 device tensor [P]) = 1 iff row i of pos [P, 3], taken into the box's frame by
+        world_to_box, lies within half_extent on all three axes (faces included; +inf: unbounded; NaN positions dropped) -- the
+        bytes ply_filter_rows takes after a copy to the host.  Only enqueues."""
+        _check(load_library().lcgs_scene_box_keep_mask(self.ctx._h, int(pos.shape[0]), _ptr(pos), C.byref(world_to_box),
+                                                       _f3(half_extent), _ptr(keep)))
 
     # ---- a surface out of the scene: TSDF fusion of depth maps, marching tetrahedra (DESIGN.md 9)
     def tsdf_integrate(self, volume: "TsdfVolume", cams, depths, alphas=None, images=None, trunc: Optional[float] = None,

@@ -12,6 +12,8 @@
 //   abi_densify.cpp   adaptive density control: lcgs_densify_accumulate, lcgs_densify, lcgs_opacity_reset; lcgs_contrib_keep_mask, lcgs_prune
 //   abi_mcmc.cpp      3DGS-MCMC density control: lcgs_mcmc_relocate, lcgs_mcmc_add, lcgs_mcmc_noise, lcgs_mcmc_regularize
 //   abi_filter3d.cpp  Mip-Splatting's 3-D smoothing filter: lcgs_filter3d_accumulate / _finalize / _apply / _backward
+//   abi_transform.cpp a similarity transform of a scene: lcgs_similarity_plan_make, lcgs_camera_transform, lcgs_scene_transform,
+//                     lcgs_scene_box_keep_mask
 //   abi_tsdf.cpp      a surface out of the scene: lcgs_tsdf_integrate, lcgs_tsdf_mesh_count / _extract
 //   abi_loss.cpp      lcgs_photometric_loss_backward, lcgs_normal_consistency_loss_backward, lcgs_set_fit_loss
 //   abi_depth_prior.cpp  depth-prior supervision (Pearson, aligned L1): lcgs_depth_prior_loss_backward
@@ -116,6 +118,9 @@ lcgs_status build_cull_bound(lcgs_context* ctx, int P, const float* pos, const f
 // fall back to reading position + scale + rotation until the arrays are bound again
 // (EVERY live context of the process is looked at -- a second context that renders the same arrays keeps rows of its own)
 void scene_arrays_written(lcgs_context* ctx, const float* pos, const float* scale, const float* rotq);
+// ... and every OTHER thread family's context that has any of ctx's bound arrays bound is told that they changed (its f16
+// coefficient copy and the kept state of its last frame are stale); ctx and its siblings are the caller's to handle
+void scene_modified_elsewhere(lcgs_context* ctx);
 // abi_owner.cpp: lcgs_owner_render, and its variant for the ownership step that reads nothing back (comm.cpp)
 struct OwnerAsyncFrame {
     OwnerSegs       segs;            // padded per-owner segments of the received rows / records

@@ -295,6 +295,21 @@ void launch_filter3d_apply(int64_t P, const float* scale, const float* opacity, 
 // in place on the gradient rows; rows != NULL: gradient row r < *d_count belongs to row rows[r], the launch is sized by P
 void launch_filter3d_backward(int64_t P, const float* scale, const float* opacity, const float* filter, const uint32_t* rows,
                               const uint32_t* d_count, float* g_scale, float* g_opacity, hipStream_t stream);
+// ---- transform.hip : a similarity transform of a scene's activated arrays, SH bands rotated; the crop box's keep mask ----
+// include/lcgs_hip.h's lcgs_similarity_plan, member for member (abi_transform.cpp asserts the sizes): it travels in the kernels' arguments
+struct TransformPlan {
+    float M[9], t[3], s, q[4], D1[9], D2[25], D3[49];
+};
+static_assert(sizeof(TransformPlan) == 400, "100 floats");
+constexpr int kTransformTileRows = 64; // rows of coefficients a workgroup of the SH pass stages: counts around its multiples are edge cases
+// every `out` that is not NULL from its `in` (the same pointer, or disjoint from it); an opacity or a degree-0 coefficient array
+// is a plain copy, and none at all in place
+void launch_scene_transform(int64_t P, int sh_degree, const TransformPlan& plan, const float* pos, const float* scale,
+                            const float* rotq, const float* sh, float* pos_out, float* scale_out, float* rotq_out, float* sh_out,
+                            hipStream_t stream);
+// keep[i] = every |(M pos_i + t)_k| <= half[k]
+void launch_box_keep_mask(int64_t P, const TransformPlan& plan, const float* pos, const float half[3], uint8_t* keep,
+                          hipStream_t stream);
 // ---- tsdf.hip : TSDF fusion of depth maps into a dense volume, marching tetrahedra on the Kuhn split ----
 constexpr int kTsdfViewChunk = 42; // = LCGS_TSDF_VIEW_CHUNK: views per launch of the integrate pass, their table in the kernel's arguments
 struct TsdfView {                  // what the pass reads of a view: gs_math.hpp view_transform's rows, the projection, the maps

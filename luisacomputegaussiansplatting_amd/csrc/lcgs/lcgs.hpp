@@ -164,6 +164,22 @@ inline void camera_grad_to_twist(const lcgs_camera& cam, const float dL_dcam[12]
     check(lcgs_camera_grad_to_twist(&cam, dL_dcam, dL_dxi));
 }
 
+// host only: the plan of a similarity transform new = scale * rot * old + trans (the rotation's quaternion, and its matrix on each
+// SH band in the library's basis; D64, nullable [83]: the unrounded band matrices), and the camera that sees the transformed scene
+// as `cam` saw the original
+inline lcgs_similarity_plan similarity_plan(const lcgs_similarity& xf, double* D64 = nullptr)
+{
+    lcgs_similarity_plan plan;
+    check(lcgs_similarity_plan_make(&xf, &plan, D64));
+    return plan;
+}
+inline Camera camera_transform(const Camera& cam, const lcgs_similarity& xf)
+{
+    Camera out;
+    check(lcgs_camera_transform(&cam, &xf, &out));
+    return out;
+}
+
 // ---- proxies: lcgs/include/lcgs/sh_preprocessor.h:16-20, gs_projector.h:16-28, proxy.h:43-71 ----
 struct GPUPointsProxy {
     int               N      = 0;
@@ -362,6 +378,18 @@ public:
                        const lcgs_params& activated, float max_opacity = 0.01f)
     {
         check(lcgs_opacity_reset(m_dev->ctx(), num_gaussians, max_opacity, &raw, &m, &v, &activated));
+    }
+    // a similarity transform of ACTIVATED arrays (no reference counterpart): positions, scales, orientations moved and the SH bands
+    // rotated with the scene, from `in` to `out` (the same pointer per member: in place; a NULL out member skips that array); the
+    // keep mask of a crop box (d_keep[i] = 1 iff row i, taken into the box's frame, lies within half_extent on all three axes)
+    void transform(int num_gaussians, const lcgs_similarity& xf, const lcgs_params& in, const lcgs_params& out, int sh_degree = 3)
+    {
+        check(lcgs_scene_transform(m_dev->ctx(), num_gaussians, sh_degree, &xf, &in, &out));
+    }
+    void box_keep_mask(int num_gaussians, const float* d_pos, const lcgs_similarity& world_to_box, const float half_extent[3],
+                       uint8_t* d_keep)
+    {
+        check(lcgs_scene_box_keep_mask(m_dev->ctx(), num_gaussians, d_pos, &world_to_box, half_extent, d_keep));
     }
     // 3DGS-MCMC density control (no reference counterpart), all in place: dead rows relocated onto live ones -> rows relocated;
     // num_new rows appended behind num_gaussians (throws Error(LCGS_ERR_CAPACITY) when they do not fit); SGLD noise on the
